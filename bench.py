@@ -12,6 +12,8 @@ Adam, batch 2048 per GPU; weak scaling, one RCCL all-reduce of the flat 96 KB gr
 
 `--workload c5` times configs[4] (stress: VQ_VAE(num_inputs=4, num_embeddings=4096) on 4x256x256 patches, training step).
 
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (dump_outputs), for comparing two builds.
+
 Rank 0 prints ONE JSON line.  It also carries
   roofline     -- the dominant kernel of the step, timed live with events on the launch stream
   cpu_baseline -- the CPU oracle (oracle/vqvae_oracle.py, "port") timed on this host's cores on a bounded
@@ -36,7 +38,7 @@ MFMA_BF16_PEAK_TFLOPS = 2500.0  # MI355X_MICROARCH.md: bf16 MFMA ~2.5 PFLOP/s de
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=0, help="timed steps (default 200; 50 for c5 / z32ex)")
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 200; 50 for c5 / z32ex)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", choices=["c3", "c2", "c5", "z32ex"], default="c3")
     ap.add_argument("--batch", type=int, default=0,
@@ -46,9 +48,13 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-targets", action="store_true", help="skip the north-star target measurements and the C2 sub-record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
-    if args.steps <= 0:
+    if args.steps is None:
         args.steps = 50 if args.workload in ("c5", "z32ex") else 200
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     return args
 
 
@@ -466,6 +472,46 @@ def north_star_targets(model, x):
     return {"vq": vq, "enc_convs": convs, "enc_convs_total": total}
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, out, model, train):
+    """--dump-outputs: what the last timed step handed its caller, as float32 / float64 .npy files, so that two builds of
+    the project can be compared output for output (the inputs and the initial model come from fixed seeds).
+      training workloads (c3, c5, z32ex): losses.npy (the step's returned vector: recon, commitment, total, perplexity[, time
+        matching]) and the model the step left behind, param.<name>.npy for every parameter and buffer.<name>.npy for every
+        buffer (BatchNorm running statistics; num_batches_tracked as float64);
+      c2: latents.npy, the quantised latents (B, D, H, W).
+    When the arrays exceed the 64 MB budget together, each one with more than one row is cut to the same share of its rows
+    (a seeded, sorted choice along the first dimension), the same rows in every run.  Returns {name: shape written}."""
+    import numpy as np
+    arrays = {}
+    if train:
+        arrays["losses"] = out.detach().float().cpu().numpy()
+        for k, p in model.named_parameters():
+            arrays["param." + k] = p.detach().float().cpu().numpy()
+        for k, b in model.named_buffers():
+            t = b.detach().cpu()
+            arrays["buffer." + k] = (t.float() if t.is_floating_point() else t.double()).numpy()
+    else:
+        arrays["latents"] = out.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        share = DUMP_LIMIT_BYTES / total
+        for k, a in arrays.items():
+            if a.ndim and a.shape[0] > 1:
+                rows = max(1, int(a.shape[0] * share))
+                pick = np.sort(np.random.default_rng(0).choice(a.shape[0], rows, replace=False))
+                arrays[k] = a[pick]
+        total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes would exceed the {DUMP_LIMIT_BYTES}-byte budget")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def graphed(step_fn):
     """step_fn recorded once into a HIP graph (after a warm-up on a side stream) -> a function that replays it and
     returns the recorded call's output.  Same kernels in the same order; what goes away is the per-launch host work, which
@@ -860,6 +906,10 @@ def main():
     # every rank's own wall time of the timed region (after the closing barrier they differ only by launch skew)
     rank_ms = D.gather_rank_values(1e3 * elapsed / args.steps, device=dev)
     elapsed = D.max_over_ranks(elapsed, device=dev)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before anything below steps the trainer again: the arrays of the last TIMED step
+        dumped = dump_outputs(args.dump_outputs, out, model, train=args.workload != "c2")
 
     losses = out.tolist() if args.workload in ("c3", "c5", "z32ex") else None
     # evidence of the gradient exchange (after the timed region, every rank takes part): backend, world size and the
@@ -943,6 +993,8 @@ def main():
             line["z32ex"] = z32
         if losses is not None:
             line["final_losses"] = dict(zip(("recon", "commitment", "total", "perplexity"), [round(v, 6) for v in losses]))
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": len(dumped)}
         print(json.dumps(line), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

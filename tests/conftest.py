@@ -30,6 +30,28 @@ def load_golden(name):
         return {k: f[k] for k in f.files}
 
 
+# (biases of convolutions that feed a train-mode BatchNorm have an identically zero gradient: rounding noise there becomes
+# +-lr Adam steps whose signs depend on the summation order; they do not reach any output)
+NOISE = ("enc.1.bias", "enc.4.bias", "enc.7.bias", "enc.10.bias", ".1.bias", ".4.bias")
+# (... except the running mean of the BatchNorm behind them, which tracks the mean of conv + bias)
+NOISE_MEAN = ("enc.2.running_mean", "enc.5.running_mean", "enc.8.running_mean", "enc.11.running_mean", ".2.running_mean",
+              ".5.running_mean")
+
+GOLDEN_THREADS = 8      # tests/golden/make_golden*.py: torch.set_num_threads(8)
+
+
+@pytest.fixture
+def golden_threads():
+    """The CPU oracle with the thread count the golden vectors were captured with: oneDNN splits fp32 reductions (weight
+    gradients, BatchNorm statistics) by thread, so another count sums in another order and the bit-for-bit / 1e-5
+    comparisons against the vectors would measure the host instead of the oracle."""
+    import torch
+    saved = torch.get_num_threads()
+    torch.set_num_threads(GOLDEN_THREADS)
+    yield
+    torch.set_num_threads(saved)
+
+
 @pytest.fixture(scope="session")
 def golden():
     cache = {}

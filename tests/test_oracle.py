@@ -11,8 +11,10 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
+from conftest import NOISE, NOISE_MEAN, ROOT
 from oracle import vqvae_oracle as O
+
+pytestmark = pytest.mark.usefixtures("golden_threads")
 
 
 def _p(a):
@@ -154,14 +156,48 @@ def test_gradients_and_adam(golden):
 
     m = fresh(golden)
     opt = O.make_adam(m, 1e-4)
+    # run_training.py:485's optimiser, exactly: after three steps beta2 = .99 instead of .999 moves the state by 3.4e-7, below
+    # what another CPU's summation order moves it by (_adam_states_close), so the step-3 state cannot be what pins them
+    d = opt.defaults
+    assert type(opt) is torch.optim.Adam and (d["lr"], d["betas"], d["eps"], d["weight_decay"], d["amsgrad"]) == (
+        1e-4, (.9, .999), 1e-8, 0, False), d
     m.zero_grad()
     for step in range(3):
         ld = O.train_step(m, opt, x)
         got = [float(ld[k]) for k in ("recon_loss", "commitment_loss", "total_loss", "perplexity")]
         np.testing.assert_allclose(got, g7["losses"][step], rtol=2e-6)
-        if step in (0, 2):
+        if step == 0:
             for k, v in m.state_dict().items():
                 np.testing.assert_allclose(v.numpy(), g7[f"step{step + 1}/{k}"], rtol=1e-5, atol=2e-7, err_msg=k)
+        elif step == 2:
+            _adam_states_close(m.state_dict(), g7, "step3/", lr=1e-4, steps=3)
+
+
+def _adam_states_close(sd, want, prefix, lr, steps, rtol=1e-5, atol=2e-7, order_atol_lr=0.5):
+    """A state dict `steps` Adam steps in, against the reference's.  Every element within the strict gate (rtol, atol),
+    with two measured exceptions:
+      * NOISE / NOISE_MEAN (zero-gradient biases and the running means behind them): within 2.5 * lr * steps, as in
+        tests/test_train_loop_golden.py::_check_states;
+      * parameters on a CPU whose oneDNN blocks the fp32 sums differently from the capture CPU's, even at the capture's
+        thread count: on an AMD Zen 5 host the state after step 2 agreed to 1.3e-9 and no VQ code differed, but the
+        step-3 encoder gradients differed by up to 1.6 % of a tensor's scale, so up to 14 % of a weight tensor's elements
+        left the strict gate, by at most 1.8e-5 = 0.18 * lr.  A parameter element may leave it by up to order_atol_lr *
+        lr, less than the one Adam step (~lr) a wrong update would move it.
+    Running statistics other than NOISE_MEAN get no exception; num_batches_tracked is equal."""
+    for k, v in sd.items():
+        w_ = torch.from_numpy(np.asarray(want[prefix + k]))
+        assert v.shape == w_.shape and v.dtype == w_.dtype, k
+        if k.endswith("num_batches_tracked"):
+            assert torch.equal(v, w_), k
+            continue
+        diff = (v - w_).abs()
+        if k.endswith(NOISE + NOISE_MEAN) and "enc" in k:
+            assert diff.max() <= 2.5 * lr * steps, (k, float(diff.max()))
+        else:
+            tol = atol + rtol * w_.abs()
+            if "running" not in k:
+                tol = tol.clamp(min=order_atol_lr * lr)
+            assert bool((diff <= tol).all()), (k, float(diff.max()), int((diff > atol + rtol * w_.abs()).sum()))
 
 
 def test_time_matching_variants(golden):

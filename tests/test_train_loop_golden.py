@@ -11,12 +11,9 @@ import numpy as np
 import pytest
 import torch
 
-# (biases of convolutions that feed a train-mode BatchNorm have an identically zero gradient: rounding noise there becomes
-# +-lr Adam steps whose signs depend on the summation order; they do not reach any output)
-NOISE = ("enc.1.bias", "enc.4.bias", "enc.7.bias", "enc.10.bias", ".1.bias", ".4.bias")
-# (... except the running mean of the BatchNorm behind them, which tracks the mean of conv + bias)
-NOISE_MEAN = ("enc.2.running_mean", "enc.5.running_mean", "enc.8.running_mean", "enc.11.running_mean", ".2.running_mean",
-              ".5.running_mean")
+pytestmark = pytest.mark.usefixtures("golden_threads")
+
+from conftest import NOISE, NOISE_MEAN
 W = torch.arange(1, 2 * 128 * 128 + 1, dtype=torch.float64).reshape(1, 2, 128, 128) / (2 * 128 * 128)
 
 
