@@ -176,21 +176,14 @@ __global__ __launch_bounds__(256) void tm_count_kernel(const float *__restrict__
     if (threadIdx.x == 0) atomicAdd(state, (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]));      // (integers: any order)
 }
 
-// P[ks][i][j] = sum_{d in split ks} z[i][d] z[j][d] for the tiles ON AND ABOVE the diagonal: G is symmetric and the epilogue
-// reads one orientation of every entry (P[min][max]), so the nt (nt - 1) / 2 tiles below the diagonal are never formed --
-// at B = 2048 that is 496 of 1024 workgroups (blockIdx.x walks the upper triangle row by row)
-__global__ __launch_bounds__(256) void tm_gram_kernel(const float *__restrict__ z, float *__restrict__ P, int B, int n, int klen,
-                                                      int nt, const int *__restrict__ state)
+// One 64 x 64 tile of Gram partials: acc = sum_{k in [k_lo, k_hi)} z[i] z[j] for the rows i0 .. i0 + 63 (< ilim) against
+// the rows j0 .. j0 + 63 (< jlim), in the wave layout of tm_gram_kernel.  Every entry is the same sequence of MFMA steps
+// whatever the tile's origin, and a product does not care which of its factors is the A operand: the rectangular form
+// (tm_gram_rows_kernel) therefore forms the very values of the square one.
+__device__ __forceinline__ void tm_gram_tile(const float *__restrict__ z, int n, int i0, int ilim, int j0, int jlim, int k_lo,
+                                             int k_hi, float *sA, float *sB, f32x4 (&acc)[2][2])
 {
-    __shared__ float sA[TM_T * TM_LDA], sB[TM_T * TM_LDA];
-    if (tm_sparse(state, B)) return;                       // (uniform) the epilogue will not read P
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wr = wave >> 1, wc = wave & 1;
-    int tcol = blockIdx.x, trow = 0;
-    for (int len = nt; tcol >= len; --len) { tcol -= len; ++trow; }    // (uniform: at most nt scalar steps)
-    tcol += trow;
-    const int i0 = trow * TM_T, j0 = tcol * TM_T;
-    const int k_lo = blockIdx.z * klen, k_hi = min(n, k_lo + klen);
-    f32x4 acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -204,8 +197,8 @@ __global__ __launch_bounds__(256) void tm_gram_kernel(const float *__restrict__ 
         for (int pass = 0; pass < 2; ++pass) {
             const int r = lr + 32 * pass;
             va[pass] = (f32x4){0.f, 0.f, 0.f, 0.f}; vb[pass] = va[pass];
-            if (k0 < k_hi && i0 + r < B) va[pass] = *reinterpret_cast<const f32x4 *>(z + (long long)(i0 + r) * n + k0 + 4 * lq);
-            if (k0 < k_hi && j0 + r < B) vb[pass] = *reinterpret_cast<const f32x4 *>(z + (long long)(j0 + r) * n + k0 + 4 * lq);
+            if (k0 < k_hi && i0 + r < ilim) va[pass] = *reinterpret_cast<const f32x4 *>(z + (long long)(i0 + r) * n + k0 + 4 * lq);
+            if (k0 < k_hi && j0 + r < jlim) vb[pass] = *reinterpret_cast<const f32x4 *>(z + (long long)(j0 + r) * n + k0 + 4 * lq);
         }
     };
     issue(k_lo);
@@ -232,6 +225,24 @@ __global__ __launch_bounds__(256) void tm_gram_kernel(const float *__restrict__ 
             acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
         }
     }
+}
+
+// P[ks][i][j] = sum_{d in split ks} z[i][d] z[j][d] for the tiles ON AND ABOVE the diagonal: G is symmetric and the epilogue
+// reads one orientation of every entry (P[min][max]), so the nt (nt - 1) / 2 tiles below the diagonal are never formed --
+// at B = 2048 that is 496 of 1024 workgroups (blockIdx.x walks the upper triangle row by row)
+__global__ __launch_bounds__(256) void tm_gram_kernel(const float *__restrict__ z, float *__restrict__ P, int B, int n, int klen,
+                                                      int nt, const int *__restrict__ state)
+{
+    __shared__ float sA[TM_T * TM_LDA], sB[TM_T * TM_LDA];
+    if (tm_sparse(state, B)) return;                       // (uniform) the epilogue will not read P
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wr = wave >> 1, wc = wave & 1;
+    int tcol = blockIdx.x, trow = 0;
+    for (int len = nt; tcol >= len; --len) { tcol -= len; ++trow; }    // (uniform: at most nt scalar steps)
+    tcol += trow;
+    const int i0 = trow * TM_T, j0 = tcol * TM_T;
+    const int k_lo = blockIdx.z * klen, k_hi = min(n, k_lo + klen);
+    f32x4 acc[2][2];
+    tm_gram_tile(z, n, i0, B, j0, B, k_lo, k_hi, sA, sB, acc);
     float *__restrict__ Pk = P + (long long)blockIdx.z * B * B;
 #pragma unroll
     for (int a = 0; a < 2; ++a)
@@ -261,6 +272,42 @@ __device__ __forceinline__ void tm_value(const TmParams &p, float sim, float tm,
 }
 
 constexpr float TM_NEAR = 1.f / 16.f;   // Gram distance below this share of |z_i|^2 + |z_j|^2: re-evaluate from differences
+
+// The near pairs (i, j0 + l) of a wave's lanes l (`near` set), one at a time, by the whole wave: sum of squared differences,
+// 16 bytes per lane and step; lane l's `sim` receives its pair's value.  (z_i - z_j)^2 and (z_j - z_i)^2 are the same
+// number: either orientation of a pair gives the same bits.
+__device__ __forceinline__ void tm_near_sims(const float *__restrict__ z, int n, int i, int j0, bool near, int lane, float &sim)
+{
+    unsigned long long todo = __ballot(near);
+    while (todo) {
+        const int l = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        const int pj = j0 + l;                             // (the wave shares i: lane l's pair is (i, j0 + l))
+        const float *__restrict__ zi = z + (long long)i * n, *__restrict__ zj = z + (long long)pj * n;
+        double acc = 0.0;
+        int d = 4 * lane;
+        for (; d + 768 < n; d += 1024) {                    // four steps' loads in flight together (the sparse form lives here)
+            f32x4 a[4], b[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                a[u] = *reinterpret_cast<const f32x4 *>(zi + d + 256 * u);
+                b[u] = *reinterpret_cast<const f32x4 *>(zj + d + 256 * u);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {                   // (the same terms in the same order as the single steps below)
+                const f32x4 df = a[u] - b[u];
+                acc += (double)((df.x * df.x + df.y * df.y) + (df.z * df.z + df.w * df.w));
+            }
+        }
+        for (; d < n; d += 256) {                          // n % 32 == 0: whole float4s
+            const f32x4 a = *reinterpret_cast<const f32x4 *>(zi + d), b = *reinterpret_cast<const f32x4 *>(zj + d);
+            const f32x4 df = a - b;
+            acc += (double)((df.x * df.x + df.y * df.y) + (df.z * df.z + df.w * df.w));
+        }
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+        if (lane == l) sim = (float)(acc / (double)n);
+    }
+}
 
 // The 64 x 64 tiles ON OR ABOVE the diagonal (the tiles tm_gram_kernel forms), TM_EP workgroups per tile (16 rows i each),
 // one thread per 4 of its pairs (i, j), i <= j: sim from the Gram slabs (near pairs: from differences, by the wave), BOTH
@@ -323,36 +370,7 @@ __global__ __launch_bounds__(256) void tm_epilogue_kernel(const float *__restric
             sim = i == j ? 0.f : (float)(d2 / (double)n);
             near = i != j && !(d2 >= (double)TM_NEAR * (gii + gjj));    // (also when the Gram value is not finite)
         }
-        // near pairs, one at a time, by the whole wave: sum of squared differences, 16 bytes per lane and step
-        unsigned long long todo = __ballot(near);
-        while (todo) {
-            const int l = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            const int pj = j0 + l;                         // (the wave shares i: lane l's pair is (i, j0 + l))
-            const float *__restrict__ zi = z + (long long)i * n, *__restrict__ zj = z + (long long)pj * n;
-            double acc = 0.0;
-            int d = 4 * lane;
-            for (; d + 768 < n; d += 1024) {                // four steps' loads in flight together (the sparse form lives here)
-                f32x4 a[4], b[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    a[u] = *reinterpret_cast<const f32x4 *>(zi + d + 256 * u);
-                    b[u] = *reinterpret_cast<const f32x4 *>(zj + d + 256 * u);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {               // (the same terms in the same order as the single steps below)
-                    const f32x4 df = a[u] - b[u];
-                    acc += (double)((df.x * df.x + df.y * df.y) + (df.z * df.z + df.w * df.w));
-                }
-            }
-            for (; d < n; d += 256) {                      // n % 32 == 0: whole float4s
-                const f32x4 a = *reinterpret_cast<const f32x4 *>(zi + d), b = *reinterpret_cast<const f32x4 *>(zj + d);
-                const f32x4 df = a - b;
-                acc += (double)((df.x * df.x + df.y * df.y) + (df.z * df.z + df.w * df.w));
-            }
-            for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-            if (lane == l) sim = (float)(acc / (double)n);
-        }
+        tm_near_sims(z, n, i, j0, near, lane, sim);
         float sij = 0.f;
         if (have) {
             float d_ij, d_ji;
@@ -399,9 +417,11 @@ __global__ __launch_bounds__(256) void tm_epilogue_kernel(const float *__restric
 // The row's nonzero columns are compacted first (thread t owns the columns [t c, (t + 1) c): counts, a scan, the list in
 // ascending j -- a fixed order), so the sum walks the row's pairs, not its B columns (in the sparse form EVERY related pair
 // comes through here).  Dynamic LDS: B floats (the row) + B 16-bit column numbers.
+// Rows of Snear and dz are the rows r0 .. r0 + gridDim.x - 1 of the batch (the square form: r0 = 0, all B of them); z is the
+// whole batch.
 __global__ __launch_bounds__(256) void tm_near_backward_kernel(const float *__restrict__ z, const float *__restrict__ Snear,
                                                                const float *__restrict__ g_dev, float scale,
-                                                               float *__restrict__ dz, int B, int n)
+                                                               float *__restrict__ dz, int B, int n, int r0)
 {
     extern __shared__ float s_row[];                       // S_near[i][0..B)
     unsigned short *s_col = reinterpret_cast<unsigned short *>(s_row + B);
@@ -436,7 +456,7 @@ __global__ __launch_bounds__(256) void tm_near_backward_kernel(const float *__re
         if (s_row[j] != 0.f) s_col[at++] = (unsigned short)j;
     __syncthreads();
     const float sc = scale * (g_dev ? g_dev[0] : 1.f);
-    const float *__restrict__ zi = z + (long long)i * n;
+    const float *__restrict__ zi = z + (long long)(r0 + i) * n;
     for (int d = 4 * threadIdx.x; d < n; d += 1024) {
         const f32x4 a = *reinterpret_cast<const f32x4 *>(zi + d);
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -455,11 +475,12 @@ __global__ __launch_bounds__(256) void tm_near_backward_kernel(const float *__re
 
 // dz[i][d] = scale * g * (rowsum(S)_i z[i][d] - sum_j S_ij z[j][d]);  64 rows x 64 columns per workgroup, K = B
 constexpr int TM_LDZ = TM_T + 16;  // LDS row stride of the [j][d] tile: == 16 (mod 32), conflict-free B-operand reads
-// add (optional): another gradient of the same latents (the quantiser's), added here instead of in a pass of its own
+// add (optional): another gradient of the same latents (the quantiser's), added here instead of in a pass of its own.
+// Rows i of S, dz and add are the R rows r0 .. r0 + R - 1 of the batch (the square form: r0 = 0, R = B); z is the whole batch.
 __global__ __launch_bounds__(256) void tm_backward_kernel(const float *__restrict__ z, const float *__restrict__ S,
                                                           const float *__restrict__ g_dev, float scale,
                                                           float *__restrict__ dz, int B, int n, const float *__restrict__ add,
-                                                          const int *__restrict__ state)
+                                                          const int *__restrict__ state, int r0, int R)
 {
     __shared__ float sS[TM_T * TM_LDA], sZ[TM_KC * TM_LDZ], s_rs[TM_T], s_part[256];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wr = wave >> 1, wc = wave & 1;
@@ -492,7 +513,7 @@ __global__ __launch_bounds__(256) void tm_backward_kernel(const float *__restric
     {   // row sums of S for the tile's 64 rows: 4 threads per row, fixed order (a skipped chunk would have added zeros)
         const int r = threadIdx.x >> 2, q = threadIdx.x & 3;
         float a = 0.f;
-        if (i0 + r < B) {
+        if (i0 + r < R) {
             const float *__restrict__ row = S + (long long)(i0 + r) * B;
             for (int li = 0; li < nl; ++li) {
                 const int k0 = TM_KC * s_list[li];
@@ -520,7 +541,7 @@ __global__ __launch_bounds__(256) void tm_backward_kernel(const float *__restric
         // value the general path below would store (a zero row sum times a finite latent), 16 bytes per lane, z not read
         for (int e = threadIdx.x; e < TM_T * (TM_T / 4); e += 256) {
             const int i = i0 + e / (TM_T / 4), d = d0 + 4 * (e % (TM_T / 4));
-            if (i < B && d < n) {
+            if (i < R && d < n) {
                 const long long o = (long long)i * n + d;
                 f32x4 v = {0.f, 0.f, 0.f, 0.f};
                 if (add) {
@@ -549,13 +570,13 @@ __global__ __launch_bounds__(256) void tm_backward_kernel(const float *__restric
             const int r = lr + 32 * pass;
             if (s_vec) {
                 f32x4 t = {0.f, 0.f, 0.f, 0.f};
-                if (i0 + r < B && k0 + 4 * lq < B) t = *reinterpret_cast<const f32x4 *>(S + (long long)(i0 + r) * B + k0 + 4 * lq);
+                if (i0 + r < R && k0 + 4 * lq < B) t = *reinterpret_cast<const f32x4 *>(S + (long long)(i0 + r) * B + k0 + 4 * lq);
                 sv[pass][0] = t.x; sv[pass][1] = t.y; sv[pass][2] = t.z; sv[pass][3] = t.w;
             } else {
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int j = k0 + 4 * lq + u;
-                    sv[pass][u] = (i0 + r < B && j < B) ? S[(long long)(i0 + r) * B + j] : 0.f;
+                    sv[pass][u] = (i0 + r < R && j < B) ? S[(long long)(i0 + r) * B + j] : 0.f;
                 }
             }
             const int jr = zr + 16 * pass;
@@ -594,12 +615,130 @@ __global__ __launch_bounds__(256) void tm_backward_kernel(const float *__restric
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int il = wr * 32 + a * 16 + (lane >> 4) * 4 + r, i = i0 + il, d = d0 + wc * 32 + b * 16 + (lane & 15);
-                if (i < B && d < n) {
+                if (i < R && d < n) {
                     const long long o = (long long)i * n + d;
-                    const float t = sc * (s_rs[il] * z[o] - acc[a][b][r]);
+                    const float t = sc * (s_rs[il] * z[(long long)(r0 + i) * n + d] - acc[a][b][r]);
                     dz[o] = add ? __fadd_rn(add[o], t) : t;            // (rounded like the separate elementwise add it replaces)
                 }
             }
+}
+
+// ---- the row-range form (data parallel: one rank's rows r0 .. r0 + R - 1 of a global batch of B).  Every pair (i, j) with i
+// among the rows is formed from exactly the operands the square kernels use -- Gram partials with the same K split, the
+// Gram diagonal, differences for the near pairs, S_ij = d_ij + d_ji -- so S and dz are rows r0 .. r0 + R - 1 of the square
+// call's, to the bit.  The loss slabs hold the rows' own share, sum_{i in rows, j} v_ij (mode 1 normalised by B * B).
+
+// P[ks][i - r0][j] for the R rows against all B columns (tiles of 64 rows from r0, of 64 columns from 0), and behind them
+// one workgroup per 64 x 64 diagonal tile of the whole batch for the Gram diagonal D[ks][g] (the epilogue needs G_jj of
+// every column; only the diagonal of those tiles is stored)
+__global__ __launch_bounds__(256) void tm_gram_rows_kernel(const float *__restrict__ z, float *__restrict__ P, float *__restrict__ D,
+                                                           int B, int n, int klen, int r0, int R, int ntr, int nt,
+                                                           const int *__restrict__ state)
+{
+    __shared__ float sA[TM_T * TM_LDA], sB[TM_T * TM_LDA];
+    if (tm_sparse(state, B)) return;                       // (uniform) the epilogue will not read P or D
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wr = wave >> 1, wc = wave & 1;
+    const int k_lo = blockIdx.z * klen, k_hi = min(n, k_lo + klen);
+    const bool diag = (int)blockIdx.x >= ntr * nt;
+    const int i0 = diag ? (blockIdx.x - ntr * nt) * TM_T : r0 + (blockIdx.x / nt) * TM_T;
+    const int j0 = diag ? i0 : (blockIdx.x % nt) * TM_T;
+    f32x4 acc[2][2];
+    tm_gram_tile(z, n, i0, diag ? B : r0 + R, j0, B, k_lo, k_hi, sA, sB, acc);
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = i0 + wr * 32 + a * 16 + (lane >> 4) * 4 + r, j = j0 + wc * 32 + b * 16 + (lane & 15);
+                if (diag) {
+                    if (i == j && i < B) D[(long long)blockIdx.z * B + i] = acc[a][b][r];
+                } else if (i < r0 + R && j < B) {
+                    P[((long long)blockIdx.z * R + (i - r0)) * B + j] = acc[a][b][r];
+                }
+            }
+}
+
+// One workgroup per (tile of 64 rows i among the R, tile of 64 columns j) and TM_ER rows of it: thread = column j, 4 of the
+// rows.  Both entries of the pair's relation (tm[i][j], and tm[j][i] through LDS: tm need not be symmetric), S (2, R, B) for
+// the rows, the far-block map by (panel of 64 of the R rows, chunk of 32 columns), the rows' own loss terms.
+template <int TM_ER>
+__global__ __launch_bounds__(256) void tm_epilogue_rows_kernel(const float *__restrict__ z, const float *__restrict__ P,
+                                                               const float *__restrict__ D, int ksplit,
+                                                               const float *__restrict__ tm, int B, int n, int r0, int R, TmParams p,
+                                                               float *__restrict__ S, double *__restrict__ loss_slabs, int nt,
+                                                               const int *__restrict__ state, int *__restrict__ far_map)
+{
+    __shared__ float sT[TM_T][TM_ER + 1];                // tm[j0 + r][ib + c]
+    __shared__ double s_gi[TM_ER], s_gj[TM_T];
+    __shared__ double s_red[4];
+    constexpr int TM_EP = TM_T / TM_ER;
+    const int trow = blockIdx.x / nt, tcol = blockIdx.x % nt;
+    const int il0 = trow * TM_T + blockIdx.y * TM_ER;   // first local row of the workgroup
+    const int ib = r0 + il0, j0 = tcol * TM_T, rhi = r0 + R;
+    const long long RB = (long long)R * B;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6, lane = tx;
+#pragma unroll
+    for (int k = 0; k < TM_T * TM_ER / 256; ++k) {
+        const int e = threadIdx.x + 256 * k, r = e / TM_ER, c = e % TM_ER;
+        sT[r][c] = (j0 + r < B && ib + c < rhi) ? tm[(long long)(j0 + r) * B + ib + c] : 0.f;
+    }
+    const bool sparse = tm_sparse(state, B);
+    if (!sparse && threadIdx.x < TM_ER + TM_T) {         // chunk sums added in double, in the square epilogue's order
+        const int g = threadIdx.x < TM_ER ? ib + (int)threadIdx.x : j0 + (int)threadIdx.x - TM_ER;
+        double d = 0.0;
+        if (g < B)
+            for (int ks = 0; ks < ksplit; ++ks) d += (double)D[(long long)ks * B + g];
+        if (threadIdx.x < TM_ER) s_gi[threadIdx.x] = d; else s_gj[threadIdx.x - TM_ER] = d;
+    }
+    __syncthreads();
+    const float inv_count = p.mode == 0 ? 1.f : 1.f / (float)((long long)B * B);
+    const int j = j0 + tx;
+    const double gjj = s_gj[tx];
+    double val = 0.0;
+    bool any_far = false;
+#pragma unroll
+    for (int q = 0; q < TM_ER / 4; ++q) {
+        const int il = ty + 4 * q, i = ib + il;
+        const bool have = i < rhi && j < B;
+        float sim = 0.f;
+        bool near = false;
+        if (have && sparse) {
+            near = i != j && (tm[(long long)i * B + j] != 0.f || sT[tx][il] != 0.f);
+        } else if (have) {
+            double gij = 0.0;
+            for (int ks = 0; ks < ksplit; ++ks) gij += (double)P[ks * RB + (long long)(i - r0) * B + j];
+            const double gii = s_gi[il];
+            const double d2 = gii + gjj - 2.0 * gij;
+            sim = i == j ? 0.f : (float)(d2 / (double)n);
+            near = i != j && !(d2 >= (double)TM_NEAR * (gii + gjj));
+        }
+        tm_near_sims(z, n, i, j0, near, lane, sim);
+        if (have) {
+            float d_ij, d_ji;
+            double v_ij, v_ji;
+            tm_value(p, sim, tm[(long long)i * B + j], inv_count, v_ij, d_ij);
+            tm_value(p, sim, sT[tx][il], inv_count, v_ji, d_ji);
+            val += v_ij;
+            const float sij = d_ij + d_ji;
+            const long long o = (long long)(i - r0) * B + j;
+            S[o] = near ? 0.f : sij;
+            S[RB + o] = near ? sij : 0.f;
+            any_far |= !near && sij != 0.f;
+        }
+    }
+    if (far_map) {                                         // (a wave's rows share the panel; its lanes span two chunks of columns)
+        const unsigned long long bal = __ballot(any_far);
+        if (lane == 0) {
+            if (bal & 0xffffffffull) tm_map_set(far_map, B, il0, j0);
+            if (bal >> 32) tm_map_set(far_map, B, il0, j0 + 32);
+        }
+    }
+    const double tot = block_sum(val, s_red);
+    if (threadIdx.x == 0) {
+        const long long slab = (long long)blockIdx.x * TM_EP + blockIdx.y;
+        loss_slabs[2 * slab] = tot; loss_slabs[2 * slab + 1] = 0.0;
+    }
 }
 
 int tm_ksplit(int B, int n)
@@ -737,7 +876,7 @@ static int tm_backward_launch(const float *z, const float *S, const float *g_los
     DM_REQUIRE((((uintptr_t)S | (uintptr_t)z) & 15) == 0, "dm_time_matching_backward: z and S must be 16-byte aligned");
     const int *st = (const int *)state;
     hipLaunchKernelGGL(tm_backward_kernel, dim3((n + TM_T - 1) / TM_T, (B + TM_T - 1) / TM_T), dim3(256), 0, (hipStream_t)stream,
-                       z, S, g_loss_dev, scale * 2.f / (float)n, dz, B, n, add, st);
+                       z, S, g_loss_dev, scale * 2.f / (float)n, dz, B, n, add, st, 0, B);
     const size_t near_lds = (size_t)B * (sizeof(float) + sizeof(unsigned short));
     if (near_lds > 48 * 1024) {
         const hipError_t e = hipFuncSetAttribute((const void *)tm_near_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -748,6 +887,100 @@ static int tm_backward_launch(const float *z, const float *S, const float *g_los
         }
     }
     hipLaunchKernelGGL(tm_near_backward_kernel, dim3((unsigned)B), dim3(256), near_lds, (hipStream_t)stream, z,
-                       S + (long long)B * B, g_loss_dev, scale * 2.f / (float)n, dz, B, n);
+                       S + (long long)B * B, g_loss_dev, scale * 2.f / (float)n, dz, B, n, 0);
     return dm_launch_status("dm_time_matching_backward");
+}
+
+// ---- the row-range pair (include/dynamorph_hip.h, dm_time_matching_forward_rows)
+static int tm_rows_er(int B, int R)                       // rows per workgroup of tm_epilogue_rows_kernel
+{
+    const int tiles = ((R + TM_T - 1) / TM_T) * ((B + TM_T - 1) / TM_T);
+    return 4 * tiles >= 256 ? 16 : 4;
+}
+
+extern "C" int64_t dm_time_matching_rows_workspace_floats(int B, int R, int n)
+{
+    // Gram partials of the rows + the Gram diagonal of the whole batch, per K split (the square call's split of B)
+    return (long long)tm_ksplit(B, n) * ((long long)R * B + B);
+}
+
+extern "C" int dm_time_matching_rows_num_slabs(int B, int R)
+{
+    if (R <= 0) return 0;
+    return (TM_T / tm_rows_er(B, R)) * ((R + TM_T - 1) / TM_T) * ((B + TM_T - 1) / TM_T);
+}
+
+extern "C" int dm_time_matching_rows_state_ints(int B, int R)
+{
+    return TM_STATE_HDR + ((R + TM_T - 1) / TM_T) * tm_map_chunks(B);
+}
+
+extern "C" int dm_time_matching_forward_rows(const float *z, const float *tm, int B, int r0, int R, int n, int mode, float w_a,
+                                             float w_t, float w_n, float margin, float *workspace, int64_t workspace_floats,
+                                             float *S, double *loss_slabs, int32_t *state, void *stream)
+{
+    DM_REQUIRE(B > 0 && R >= 0 && r0 >= 0 && r0 + R <= B, "dm_time_matching_forward_rows: rows [%d, %d) outside a batch of %d",
+               r0, r0 + R, B);
+    if (R == 0) return 0;                                  // an empty shard: no rows, no loss terms, nothing launched
+    DM_REQUIRE(z && tm && workspace && S && loss_slabs && state, "dm_time_matching_forward_rows: NULL pointer");
+    DM_REQUIRE(dm_time_matching_supported(B, n), "dm_time_matching_forward_rows: latent length %d is not a multiple of %d", n, TM_KC);
+    DM_REQUIRE(mode == 0 || mode == 1, "dm_time_matching_forward_rows: mode %d", mode);
+    DM_REQUIRE((long long)B * n < (1LL << 31) && (long long)B * B < (1LL << 31), "dm_time_matching_forward_rows: tensor too large");
+    DM_REQUIRE(workspace_floats >= dm_time_matching_rows_workspace_floats(B, R, n), "dm_time_matching_forward_rows: workspace too small");
+    DM_REQUIRE((((uintptr_t)tm | (uintptr_t)z | (uintptr_t)S) & 15) == 0, "dm_time_matching_forward_rows: z, tm and S must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const int ks = tm_ksplit(B, n), nt = (B + TM_T - 1) / TM_T, ntr = (R + TM_T - 1) / TM_T;
+    int klen = (n + ks - 1) / ks;
+    klen = (klen + TM_KC - 1) / TM_KC * TM_KC;
+    const int ints = dm_time_matching_rows_state_ints(B, R);
+    hipLaunchKernelGGL(tm_state_clear_kernel, dim3((ints + 255) / 256), dim3(256), 0, s, (int *)state, ints);
+    int *far_map = (int *)state + TM_STATE_HDR;
+    const int *st = nullptr;
+    if (mode == 0) {
+        // the sparse decision counts the WHOLE relation block, as the square call does: every rank decides alike
+        const long long BB = (long long)B * B;
+        const long long units = (BB & 3) == 0 ? BB >> 2 : BB;
+        const int grid = (int)((units + 255) / 256 < 2048 ? (units + 255) / 256 : 2048);
+        hipLaunchKernelGGL(tm_count_kernel, dim3(grid), dim3(256), 0, s, tm, BB, (int *)state);
+        st = (const int *)state;
+    }
+    float *P = workspace, *D = workspace + (long long)ks * R * B;
+    hipLaunchKernelGGL(tm_gram_rows_kernel, dim3(ntr * nt + nt, 1, ks), dim3(256), 0, s, z, P, D, B, n, klen, r0, R, ntr, nt, st);
+    const TmParams p{mode, w_a, w_t, w_n, margin};
+    if (tm_rows_er(B, R) == 16)
+        hipLaunchKernelGGL(tm_epilogue_rows_kernel<16>, dim3(ntr * nt, TM_T / 16), dim3(256), 0, s, z, P, D, ks, tm, B, n, r0, R, p,
+                           S, loss_slabs, nt, st, far_map);
+    else
+        hipLaunchKernelGGL(tm_epilogue_rows_kernel<4>, dim3(ntr * nt, TM_T / 4), dim3(256), 0, s, z, P, D, ks, tm, B, n, r0, R, p,
+                           S, loss_slabs, nt, st, far_map);
+    return dm_launch_status("dm_time_matching_forward_rows");
+}
+
+extern "C" int dm_time_matching_backward_rows(const float *z, const float *S, const float *g_loss_dev, float scale,
+                                              const float *add, float *dz, int B, int r0, int R, int n, const int32_t *state,
+                                              void *stream)
+{
+    DM_REQUIRE(B > 0 && R >= 0 && r0 >= 0 && r0 + R <= B, "dm_time_matching_backward_rows: rows [%d, %d) outside a batch of %d",
+               r0, r0 + R, B);
+    if (R == 0) return 0;
+    DM_REQUIRE(z && S && dz && state, "dm_time_matching_backward_rows: NULL pointer");
+    DM_REQUIRE(dm_time_matching_supported(B, n), "dm_time_matching_backward_rows: latent length %d is not a multiple of %d", n, TM_KC);
+    DM_REQUIRE((long long)B * n < (1LL << 31), "dm_time_matching_backward_rows: tensor too large");
+    DM_REQUIRE(B <= 16384, "dm_time_matching_backward_rows: batch %d too large (a row of S is staged in LDS)", B);
+    DM_REQUIRE((((uintptr_t)S | (uintptr_t)z) & 15) == 0, "dm_time_matching_backward_rows: z and S must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(tm_backward_kernel, dim3((n + TM_T - 1) / TM_T, (R + TM_T - 1) / TM_T), dim3(256), 0, s,
+                       z, S, g_loss_dev, scale * 2.f / (float)n, dz, B, n, add, (const int *)state, r0, R);
+    const size_t near_lds = (size_t)B * (sizeof(float) + sizeof(unsigned short));
+    if (near_lds > 48 * 1024) {
+        const hipError_t e = hipFuncSetAttribute((const void *)tm_near_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)near_lds);
+        if (e != hipSuccess) {
+            dm_set_error("dm_time_matching_backward_rows: cannot reserve %zu bytes of LDS: %s", near_lds, hipGetErrorString(e));
+            return (int)e;
+        }
+    }
+    hipLaunchKernelGGL(tm_near_backward_kernel, dim3((unsigned)R), dim3(256), near_lds, s, z, S + (long long)R * B, g_loss_dev,
+                       scale * 2.f / (float)n, dz, B, n, r0);
+    return dm_launch_status("dm_time_matching_backward_rows");
 }

@@ -6,6 +6,11 @@ The reference has no multi-device code at all; what the path nee
     the default model, latency-bound), then the identical fused Adam on every rank.  Every loss is a mean
     over the local batch (vq_vae.py:74-75, 322), so the mean of per-rank gradients is the gradient of the
     global-batch mean loss given rank-local BatchNorm statistics (standard DDP semantics).
+    The pairwise time-matching term is the exception: it is a loss over all PAIRS of the batch (vq_vae.py:324-332,
+    vae.py:327-336), and by default a rank forms it on its own shard only, so every pair whose samples sit on different
+    ranks ((W - 1) / W of them) is dropped and a multi-GPU run trains a different objective from one process at the same
+    global batch.  global_time_matching=True (train / FusedTrainer) restores the global term: the latents are gathered
+    (all_gather_rows, one collective per step) and each rank forms its own rows against the whole batch.
 
 Everything here is host logic on torch tensors of any device, so it is covered by gloo tests on the CPU.
 """
@@ -82,6 +87,37 @@ def shard_weight(n, rank, world):
     shards, 0 for an empty one; the weights of all ranks sum to `world`)."""
     lo, hi = shard_range(n, rank, world)
     return (hi - lo) * world / n
+
+
+def all_gather_rows(local, n_global, group=None, out=None):
+    """The (n_global, ...) concatenation, in rank order, of every rank's contiguous shard (dist.shard_range(n_global, rank,
+    world) rows; sizes differ by at most one, an empty shard is allowed) -- on every rank, on the shards' device.  ONE
+    collective on equal-size buffers padded to the largest shard; the padding is dropped.  out: an (n_global, ...) tensor to
+    write the result into (a captured step's static input).  Collective: every rank calls it, with or without rows."""
+    w = world_size(group)
+    rank = get_rank(group)
+    lo, hi = shard_range(n_global, rank, w)
+    if local.shape[0] != hi - lo:
+        raise ValueError(f"all_gather_rows: rank {rank} holds {local.shape[0]} rows, its shard of {n_global} is {hi - lo}")
+    tail = tuple(local.shape[1:])
+    if w == 1:
+        if out is None:
+            return local
+        return out.copy_(local.reshape((n_global,) + tail))
+    cap = -(-n_global // w)                                 # the largest shard
+    send = local.new_zeros((cap,) + tail)
+    send[:hi - lo].copy_(local)
+    buf = local.new_empty((w * cap,) + tail)
+    dist.all_gather(list(buf.chunk(w)), send, group=group)
+    if out is None and n_global == w * cap:                 # equal shards: no padding to drop
+        return buf
+    if out is None:
+        out = local.new_empty((n_global,) + tail)
+    for r in range(w):
+        a, b = shard_range(n_global, r, w)
+        if b > a:
+            out[a:b].copy_(buf[r * cap:r * cap + (b - a)])
+    return out
 
 
 def gather_rank_values(value, device=None, group=None):

@@ -222,24 +222,30 @@ class Feed:
         list(self.gatherers.map(part, range(0, n, step)))
 
     # ------------------------------------------------------------------------------------------ targets
-    def _targets(self, n, want_tm, fused):
+    def _targets(self, n, want_tm, fused, ntm=None):
         xs = (n, self.C, self.H, self.H)
         ms = ((n,) + tuple((self.mplane if self.mode == "resident" else self.mplane_host).shape[1:])) if self.has_mask else None
-        ts = (n, n) if want_tm else None
+        ntm = n if ntm is None else ntm
+        ts = (ntm, ntm) if want_tm else None
         if fused and self.trainer is not None:
             return self.trainer.static_inputs(xs, ms, ts)
-        key = (n, want_tm)
+        key = (n, want_tm, ntm)
         if key not in self._own:
             self._own[key] = (torch.empty(xs, device=self.dev), torch.empty(ms, device=self.dev) if ms else None,
                               torch.empty(ts, device=self.dev) if ts else None)
         return self._own[key]
 
-    def phase(self, batches, transform=None, fused=True):
-        """Generator over the non-empty batches of one phase (lists of sample ids): (n, x, kwargs)."""
+    def phase(self, batches, transform=None, fused=True, tm_batches=None):
+        """Generator over the non-empty batches of one phase (lists of sample ids): (n, x, kwargs).  tm_batches: one id list
+        per entry of `batches` whose relation block is handed out instead of the batch's own (data parallel with the global
+        time-matching term: a rank's shard of a global batch, the block of the whole global batch)."""
+        if tm_batches is not None:
+            tm_batches = [np.asarray(g) for b, g in zip(batches, tm_batches) if len(b)]
         batches = [np.asarray(b) for b in batches if len(b)]
         if not batches:
             return
         total = sum(len(b) for b in batches)
+        tm_total = sum(len(g) for g in tm_batches) if tm_batches is not None else 0
         with torch.cuda.device(self.dev):
             # the ids and the augmentation codes of the WHOLE phase in ONE small asynchronous upload from pinned staging.
             # The codes are drawn batch by batch in the order the reference draws them (nothing else draws from numpy's
@@ -248,9 +254,11 @@ class Feed:
             if transform is not None:
                 # (one draw for the phase: per sample and in batch order, exactly the interleaved stream of the batch loop)
                 parts += list(ops.augment_codes(total))
+            if tm_batches is not None:
+                parts.append(np.concatenate(tm_batches).astype(np.int32, copy=False))
             # two pinned staging blocks, used in turn (the copy out of one may still be queued when the next phase fills
             # the other); a third phase waits for the first block's copy
-            need = len(parts) * total
+            need = sum(len(p) for p in parts)
             k = self._meta_turn = 1 - getattr(self, "_meta_turn", 1)
             if not hasattr(self, "_meta_pin"):
                 self._meta_pin, self._meta_ev = [None, None], [torch.cuda.Event(), torch.cuda.Event()]
@@ -263,15 +271,17 @@ class Feed:
             meta_dev = stage.to(self.dev, non_blocking=True)
             self._meta_ev[k].record(torch.cuda.current_stream(self.dev))
             ids_dev = meta_dev[:total]
-            flips, rots = (meta_dev[total:2 * total], meta_dev[2 * total:]) if transform is not None else (None, None)
+            flips, rots = (meta_dev[total:2 * total], meta_dev[2 * total:3 * total]) if transform is not None else (None, None)
+            tm_ids_dev = meta_dev[need - tm_total:need]
             compute = torch.cuda.current_stream(self.dev)
             pending = None
             if self.mode == "stream":
                 pending = self.helper.submit(self._stage, 0, batches[0])
-            off = 0
+            off = tm_off = 0
             for i, ids in enumerate(batches):
                 n = len(ids)
-                x, m, tm = self._targets(n, self.csr is not None, fused)
+                ntm = len(tm_batches[i]) if tm_batches is not None else n
+                x, m, tm = self._targets(n, self.csr is not None, fused, ntm)
                 sl = slice(off, off + n)
                 fl, ro = (flips[sl], rots[sl]) if flips is not None else (None, None)
                 if self.mode == "resident":
@@ -290,8 +300,10 @@ class Feed:
                     self.ev_used[k].record(compute)
                 if tm is not None:
                     self.stamp = self.stamp % ((1 << 31) - 2) + 1
-                    ops.csr_block(*self.csr, ids_dev[sl], self.pos, self.stamp, tm)
+                    ops.csr_block(*self.csr, ids_dev[sl] if tm_batches is None else tm_ids_dev[tm_off:tm_off + ntm], self.pos,
+                                  self.stamp, tm)
                 off += n
+                tm_off += ntm
                 yield n, x, {"time_matching_mat": tm, "batch_mask": m}
         assert off == total
 

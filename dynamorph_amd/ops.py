@@ -876,6 +876,49 @@ def time_matching_backward(z, S, g_loss=None, scale=1.0, add=None):
     return dz
 
 
+@_op
+def time_matching_forward_rows(z, tm, r0, R, mode, w_a=0.0, w_t=0.0, w_n=0.0, margin=0.0, want_slabs=False):
+    """The pairwise term for the rows [r0, r0 + R) of a batch against all of it (include/dynamorph_hip.h,
+    dm_time_matching_forward_rows): z (B, n) the latents of the WHOLE batch, tm (B, B) its whole relation block.  Returns
+    (the rows' share of the loss: 1-element float64 tensor -- the shares of a partition of the rows add up to
+    time_matching_forward's loss --, S (2, R, B) for time_matching_backward_rows).  want_slabs: the partial losses
+    (nslabs, 1, 2) float64 instead of their sum.  R = 0 is allowed (an empty shard: a zero share, nothing launched)."""
+    lib = L.load()
+    B, n = z.shape
+    if tm.shape != (B, B):
+        raise ValueError(f"time_matching_forward_rows: relation block {tuple(tm.shape)} for a batch of {B}")
+    wsf = lib.dm_time_matching_rows_workspace_floats(B, R, n)
+    ws = _new((max(wsf, 1),), z)
+    S = _new((2, R, B), z)
+    slabs = _new((lib.dm_time_matching_rows_num_slabs(B, R), 1, 2), z, torch.float64)
+    state = torch.empty(lib.dm_time_matching_rows_state_ints(B, R), dtype=torch.int32, device=z.device)
+    if R > 0:
+        L.check(lib.dm_time_matching_forward_rows(_ptr(z), _ptr(tm), B, r0, R, n, mode, w_a, w_t, w_n, margin, _ptr(ws), wsf,
+                                                  _ptr(S), _ptr(slabs, torch.float64), _ptr(state, torch.int32), _stream()),
+                "dm_time_matching_forward_rows")
+    S._dm_tm_state, S._dm_tm_rows = state, (r0, R)
+    if want_slabs:
+        return slabs, S
+    return slabs[:, 0, 0].sum().reshape(1), S
+
+
+@_op
+def time_matching_backward_rows(z, S, g_loss=None, scale=1.0, add=None):
+    """dz (R, n) = [add +] scale * g_loss[0] * d loss / d z for the rows S was formed for (time_matching_forward_rows on the
+    same z): rows r0 .. r0 + R - 1 of time_matching_backward's dz.  add: (R, n) or as many elements, summed in the store."""
+    lib = L.load()
+    B, n = z.shape
+    r0, R = S._dm_tm_rows
+    dz = _new((R, n), z)
+    if add is not None and add.numel() != R * n:
+        raise ValueError("dm_time_matching_backward_rows: `add` must have the rows' size")
+    if R > 0:
+        L.check(lib.dm_time_matching_backward_rows(_ptr(z), _ptr(S), _ptr(g_loss), scale, _ptr(add), _ptr(dz), B, r0, R, n,
+                                                   _ptr(S._dm_tm_state, torch.int32), _stream()),
+                "dm_time_matching_backward_rows")
+    return dz
+
+
 # ------------------------------------------------------------- composition / optimizer
 @_op
 def e1_compose(w0, b0, w1):

@@ -48,7 +48,8 @@ class _Marks:
 class FusedTrainer:
     """Adam(lr, betas=(.9,.999), eps=1e-8) exactly as run_training.py:485 builds it, fused."""
 
-    def __init__(self, model, lr=1e-3, betas=(.9, .999), eps=1e-8, process_group=None, use_graph=True):
+    def __init__(self, model, lr=1e-3, betas=(.9, .999), eps=1e-8, process_group=None, use_graph=True,
+                 global_time_matching=False):
         from .vq_vae import VQ_VAE, VQ_VAE_z32
         if not isinstance(model, (VQ_VAE, VQ_VAE_z32)):
             raise TypeError("FusedTrainer is built for VQ_VAE / VQ_VAE_z16 / VQ_VAE_z32; train other modules with a torch optimizer")
@@ -76,6 +77,12 @@ class FusedTrainer:
         self.w_recon = torch.tensor([float(getattr(model, "weight_recon", 1.0))], device=dev)
         self.w_commit = torch.tensor([float(getattr(model, "weight_commitment", 1.0))], device=dev)
         self.use_graph = use_graph
+        # global_time_matching: the pairwise term over the whole global batch (each rank: its rows against every sample,
+        # after one all-gather of the latents per step) instead of over the rank's own shard; nothing changes in one process
+        self.global_tm = bool(global_time_matching) and self.world > 1
+        if self.global_tm and self._extra:
+            raise ValueError("FusedTrainer: global_time_matching is not available together with extra_loss")
+        self._tm_gscale = torch.ones(1, device=dev)       # world / grad_weight: the rows' gradient through the exchange
         self._graphs = {}            # input shapes -> {x, mask, tm: static inputs; train / eval: (graph, static output)}
         self._static_x = None        # input tensor of the graph replayed last
         D.broadcast_(self.flat, list(model.buffers()), group=self.group)    # same replica everywhere
@@ -144,18 +151,29 @@ class FusedTrainer:
         """Backward half: decoder tail, decoder residual stack, the time-matching and (g_extra: d(sum of alpha * extra
         losses) / d z_after, from the caller's torch code) extra-loss gradients joining at z_after, the quantiser's
         straight-through backward, encoder -- ONE slab reduction for every weight / bias / codebook gradient."""
-        m = self.model
-        enc, dec = m.enc, m.dec
-        pending = []
-        g_r = E.z32_tail_backward(dec[1], dec[2], dec[4], st.tcx, self.w_recon, None, self.G, pending=pending,
-                                  zero_fed_biases=False)
-        g_zq, _ = E.residual_backward(st.dr, st.dsaved, g_r, self.G, None, pending=pending, zero_fed_biases=False)
+        g_zq, pending = self._z32_decoder_backward(st)
         if st.tm_S is not None:
             g_zq = ops.time_matching_backward(st.zf, st.tm_S, None, st.wm, add=g_zq).reshape(st.zq.shape)     # (summed in the kernel's store)
         elif st.tm_fallback is not None:
             g_zq = g_zq + st.tm_fallback
         if g_extra is not None:
             g_zq = g_zq + g_extra
+        return self._z32_encoder_backward(st, g_zq, pending)
+
+    def _z32_decoder_backward(self, st):
+        """Decoder tail and decoder residual stack of the backward half: (d loss / d z_after, the pending slab reductions)."""
+        m = self.model
+        dec = m.dec
+        pending = []
+        g_r = E.z32_tail_backward(dec[1], dec[2], dec[4], st.tcx, self.w_recon, None, self.G, pending=pending,
+                                  zero_fed_biases=False)
+        g_zq, _ = E.residual_backward(st.dr, st.dsaved, g_r, self.G, None, pending=pending, zero_fed_biases=False)
+        return g_zq, pending
+
+    def _z32_encoder_backward(self, st, g_zq, pending):
+        """From the gradient at z_after: the quantiser's straight-through backward, the encoder, ONE slab reduction."""
+        m = self.model
+        enc = m.enc
         gcb = self.G(m.vq.w.weight)
         dz, cb_slabs = ops.vq_backward_slabs(st.z, m.vq.w.weight.detach(), st.idx, g_zq, self.w_commit, st.cc)
         pending.append((cb_slabs, gcb))
@@ -283,6 +301,124 @@ class FusedTrainer:
         E.encoder_backward(L, ecx, dz, self.G, zero_fed_biases=False, pending_extra=extra)
         return scalars
 
+    # ------------------------------------------------------------------------------------------ global_time_matching
+    def latent_numel(self, sample_shape):
+        """Elements of one sample's latent the time-matching term acts on, for samples of shape (C, H, W): z_before (VQ_VAE,
+        VQ_VAE_z16: three stride-2 convolutions) or z_after (VQ_VAE_z32: two)."""
+        f = 4 if self._z32 else 8
+        return int(self.model.num_hiddens) * (int(sample_shape[-2]) // f) * (int(sample_shape[-1]) // f)
+
+    def _global_first(self, x, mask):
+        """First half of a global_time_matching step: everything that needs no other rank's latents -- the forward, the
+        decoder's backward and (VQ_VAE / VQ_VAE_z16) the quantiser's backward.  st.lat: the (B, n) latents the term acts on;
+        st.scalars: (recon, commitment, total without the term, perplexity)."""
+        import types
+        if self._z32:
+            st = self._z32_forward_part(x, mask, None)
+            st.g_zq, st.pending = self._z32_decoder_backward(st)
+            st.lat = st.zq.reshape(st.zq.shape[0], -1)
+            return st
+        model = self.model
+        L = E.Layers(model)
+        cc = float(model.commitment_cost)
+        z, ecx = E.encoder_forward(L, x, defer_last_join=L.codebook.weight.shape[0] if JOIN_IN_VQ else 0)
+        if z is None:
+            z, zq, idx, vqs = E.vq_forward_joined(L.codebook.weight, ecx.pending_join, cc)
+        else:
+            zq, idx, vqs = E.vq_forward(L.codebook.weight, z, cc, defer_scalars=True)
+        _, dcx = E.decoder_forward(L, zq, x, mask, defer_tail=True)
+        B, NIN, H, W = x.shape
+        dec_pending = []
+        g_zq = E.decoder_backward(L, dcx, self.w_recon, None, self.G, pending=dec_pending)
+        scalars = ops.vq_loss_finalize(vqs.slabs, vqs.ws, vqs.K, vqs.D, vqs.positions, vqs.cc, dcx.loss_slabs, B * NIN * H * W,
+                                       float(model.weight_recon), float(model.weight_commitment))
+        gcb = self.G(L.codebook.weight)
+        dz, cb_slabs = ops.vq_backward_slabs(z, L.codebook.weight.detach(), idx, g_zq, self.w_commit, cc)
+        return types.SimpleNamespace(L=L, ecx=ecx, z=z, dz=dz, extra=[(cb_slabs, gcb)] + dec_pending, scalars=scalars,
+                                     lat=z.reshape(B, -1))
+
+    def _global_second(self, st, zg, tm):
+        """Second half: this rank's rows of the global term (its latents are rows r0 .. r0 + B - 1 of the gathered zg), their
+        gradient summed into the quantiser's (z32: the decoder's) in the kernel's store, the encoder's backward, the slab
+        reductions.  Returns the rows' share of the term (float64, 1 element)."""
+        B, Bg = st.lat.shape[0], zg.shape[0]
+        r0, _ = D.shard_range(Bg, D.get_rank(self.group), self.world)
+        part, S = ops.time_matching_forward_rows(zg, tm, r0, B, *_tm_args(self.model, self._z32))
+        wm = float(self.model.weight_matching)
+        # the bucket is multiplied by grad_weight = B * world / Bg before the exchange and by 1 / world in Adam's load: the
+        # rows' gradient carries world / grad_weight (self._tm_gscale), so what arrives is the global term's gradient
+        if self._z32:
+            g = ops.time_matching_backward_rows(zg, S, self._tm_gscale, wm, add=st.g_zq).reshape(st.zq.shape)
+            self._z32_encoder_backward(st, g, st.pending)
+        else:
+            dz = ops.time_matching_backward_rows(zg, S, self._tm_gscale, wm, add=st.dz).reshape(st.z.shape)
+            E.encoder_backward(st.L, st.ecx, dz, self.G, zero_fed_biases=False, pending_extra=st.extra)
+        return part
+
+    def _global_total(self, part):
+        """Sum over ranks of the rows' shares: the global-batch value of the term on every rank (ONE 8-byte all-reduce)."""
+        tot = part.clone()
+        torch.distributed.all_reduce(tot, op=torch.distributed.ReduceOp.SUM, group=self.group)
+        return tot
+
+    def _global_step(self, x, mask, tm, grad_weight):
+        """One forward + backward with the global time-matching term: first half | all-gather of the latents | second half
+        (with use_graph: two captured HIP graphs, the collective between their replays) | the 8-byte all-reduce of the term.
+        Returns the five scalars with the global term (and total_loss built from it)."""
+        Bg = tm.shape[0]
+        lo, hi = D.shard_range(Bg, D.get_rank(self.group), self.world)
+        if hi - lo != x.shape[0]:
+            raise ValueError(f"FusedTrainer: global_time_matching needs the ({Bg}, {Bg}) relation block of the global batch "
+                             f"whose shard this rank's {x.shape[0]} samples are")
+        self._tm_gscale.fill_(self.world / float(grad_weight))
+        if not self.use_graph:
+            st = self._global_first(x, mask)
+            zg = D.all_gather_rows(st.lat, Bg, self.group)
+            part = self._global_second(st, zg, tm.to(torch.float32).contiguous())
+        else:
+            key = ("global", tuple(x.shape), None if mask is None else tuple(mask.shape), tuple(tm.shape))
+            ent = self._graphs.get(key)
+            if ent is None:
+                sx = x.clone()
+                smask = mask.clone() if mask is not None else None
+                stm = tm.clone().float()
+                bufs = list(self.model.buffers())
+                saved = [b.clone() for b in bufs]
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):                              # warm-up (allocator, lazy init): really executes
+                    st = self._global_first(sx, smask)
+                    self._global_second(st, torch.zeros((Bg, st.lat.shape[1]), device=sx.device), stm)
+                torch.cuda.current_stream().wait_stream(side)
+                for b, sv in zip(bufs, saved):
+                    b.copy_(sv)                                            # ... so the running statistics are put back
+                torch.cuda.synchronize(self.flat.device)                   # (no collective in flight during a capture)
+                gF = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gF):
+                    st = self._global_first(sx, smask)
+                szg = torch.zeros((Bg, st.lat.shape[1]), device=sx.device)
+                gB = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gB, pool=gF.pool()):
+                    part = self._global_second(st, szg, stm)
+                ent = self._graphs[key] = (gF, gB, st, szg, part, sx, smask, stm)
+            gF, gB, st, szg, part, sx, smask, stm = ent
+            if x.data_ptr() != sx.data_ptr():
+                sx.copy_(x)
+            if mask is not None:
+                smask.copy_(mask)
+            stm.copy_(tm)
+            gF.replay()
+            D.all_gather_rows(st.lat, Bg, self.group, out=szg)
+            gB.replay()
+        return _with_matching(st.scalars, self._global_total(part).float(), float(self.model.weight_matching))
+
+    def _join_without_data(self, global_rows):
+        """A rank with an empty shard in a global_time_matching step: it still takes part in the gather of the latents and
+        the all-reduce of the term (global_rows = (Bg, latent elements per sample)), so the collectives stay in step."""
+        Bg, n = global_rows
+        D.all_gather_rows(torch.empty((0, n), device=self.flat.device), Bg, self.group)
+        self._global_total(torch.zeros(1, dtype=torch.float64, device=self.flat.device))
+
     def _allreduce(self, weight=1.0):
         """SUM over ranks of the flat gradient bucket: ONE collective and nothing behind it -- the "x 1 / world" of the mean
         is applied by the optimizer's load (_adam, dm_adam_counted_scaled), so after the exchange the bucket holds the sum.
@@ -301,10 +437,13 @@ class FusedTrainer:
                          self.step_dev[a:a + 1], self.step_dev[b:b + 1], grad_scale=1.0 / self.world)
         self._step_slot = b
 
-    def step_without_data(self):
+    def step_without_data(self, global_rows=None):
         """This rank's shard of a ragged global batch is empty: it contributes a zero gradient to the exchange and takes
-        the same Adam step as the others."""
+        the same Adam step as the others.  global_rows = (Bg, latent elements per sample) when the other ranks take a
+        global_time_matching step (with a relation block): this rank joins its collectives too."""
         with torch.cuda.device(self.flat.device):
+            if self.global_tm and global_rows is not None:
+                self._join_without_data(global_rows)
             self.grad.zero_()
             self._allreduce()
             self._adam()
@@ -325,6 +464,8 @@ class FusedTrainer:
             if mark: mark()
             if self._extra:
                 out = self._step_with_extra_losses(x, mask, time_matching_mat, labels)
+            elif self.global_tm and time_matching_mat is not None:
+                out = self._global_step(x, mask, time_matching_mat, grad_weight)
             elif not self.use_graph:
                 out = self.forward_backward(x, mask, time_matching_mat)
             else:
@@ -351,6 +492,13 @@ class FusedTrainer:
             out[part + "_host_us"] = round(sum(m.t[i + 1] - m.t[i] for m in timers) * 1e6 / n, 2)
         out["steps"] = len(timers)
         return out
+
+    def evaluate_without_data(self, global_rows=None):
+        """The validation counterpart of step_without_data: a rank with an empty shard joins the collectives of a
+        global_time_matching validation pass (nothing to do otherwise)."""
+        if self.global_tm and global_rows is not None:
+            with torch.cuda.device(self.flat.device):
+                self._join_without_data(global_rows)
 
     def forward_only(self, x, mask=None, time_matching_mat=None):
         """The validation pass (run_training.py:522-531: forward with the module left in train mode, so BatchNorm uses
@@ -380,6 +528,11 @@ class FusedTrainer:
         if tm is None:
             return ops.vq_loss_finalize(*fin)
         zf = lat.reshape(B, -1)
+        if self.global_tm:                  # this rank's rows of the global term, on the gathered latents
+            zg = D.all_gather_rows(zf, tm.shape[0], self.group)
+            part, _ = ops.time_matching_forward_rows(zg, tm.to(torch.float32).contiguous(), D.shard_range(
+                tm.shape[0], D.get_rank(self.group), self.world)[0], B, *_tm_args(m, self._z32))
+            return _with_matching(ops.vq_loss_finalize(*fin), self._global_total(part).float(), float(m.weight_matching))
         tmf = tm.to(torch.float32).contiguous()
         if ops.time_matching_supported(zf.shape[0], zf.shape[1]):
             tm_slabs, _ = ops.time_matching_forward(zf, tmf, *_tm_args(m, self._z32), want_slabs=True)
@@ -392,7 +545,8 @@ class FusedTrainer:
         if not x.is_cuda or x.device != self.flat.device:
             raise RuntimeError(f"FusedTrainer.evaluate: batch on {x.device}, model on {self.flat.device}")
         with torch.cuda.device(self.flat.device):
-            if not self.use_graph:
+            # (global_time_matching: the validation pass runs eagerly -- its collective sits inside the forward)
+            if not self.use_graph or (self.global_tm and time_matching_mat is not None):
                 return self.forward_only(x.contiguous(), mask, time_matching_mat)
             return self._graph_step(x.contiguous(), mask, time_matching_mat, kind="eval")
 
@@ -598,10 +752,11 @@ def run_one_batch(model, batch, train_loss, model_kwargs=None, optimizer=None, t
     return model, train_loss
 
 
-def _step_without_data(model, optimizer):
-    """A rank whose shard of a ragged global batch is empty still joins the gradient exchange (with zeros) and the step."""
+def _step_without_data(model, optimizer, global_rows=None):
+    """A rank whose shard of a ragged global batch is empty still joins the gradient exchange (with zeros) and the step
+    (global_rows: see FusedTrainer.step_without_data)."""
     if isinstance(optimizer, FusedTrainer):
-        optimizer.step_without_data()
+        optimizer.step_without_data(global_rows)
         return
     params = [p for p in model.parameters() if p.requires_grad]
     for p in params:
@@ -665,11 +820,15 @@ class _EpochLosses:
         return {k: v / max(tot[-1], 1.0) for k, v in zip(keys, tot[:-1])}
 
 
-def _make_optimizer(model, lr, fused):
+def _make_optimizer(model, lr, fused, global_time_matching=False):
     from .vq_vae import VQ_VAE
     from .vq_vae import VQ_VAE_z32
     # (a model with caller-supplied extra losses, vae.py:463-469, runs arbitrary torch code per step: the autograd path)
     fusable = isinstance(model, (VQ_VAE, VQ_VAE_z32)) and getattr(model, "extra_loss", None) is None
+    if global_time_matching and not (fused and fused != "graph" and fusable):
+        raise ValueError("global_time_matching=True needs the fused step (FusedTrainer: fused=True and a VQ_VAE / VQ_VAE_z16 / "
+                         "VQ_VAE_z32 without extra_loss); the autograd route forms the time-matching term on each rank's "
+                         "shard only")
     if D.world_size() > 1 and not (fused and fused != "graph" and fusable):
         # FusedTrainer broadcasts its flat buffer itself; any other module: same replica everywhere before the first step
         for t in list(model.parameters()) + list(model.buffers()):
@@ -677,7 +836,7 @@ def _make_optimizer(model, lr, fused):
     if fused == "graph" and D.world_size() == 1:
         return GraphedTrainer(model, lr=lr)               # any module: the autograd step as a replayed HIP graph
     if fused and fusable:
-        return FusedTrainer(model, lr=lr)
+        return FusedTrainer(model, lr=lr, global_time_matching=global_time_matching)
     return torch.optim.Adam(model.parameters(), lr=lr, betas=(.9, .999))
 
 
@@ -755,7 +914,8 @@ def _device_step(model, optimizer, x, kw, training, grad_weight):
 
 def train(model, dataset, output_dir, relation_mat=None, mask=None, n_epochs=10, lr=0.001, batch_size=16,
           device='cuda:0', shuffle_data=False, transform=None, val_split_ratio=0.15, patience=20,
-          get_relation_tensor=None, get_mask=None, writer=None, fused=True, feed="auto", stats=None, probe=None):
+          get_relation_tensor=None, get_mask=None, writer=None, fused=True, feed="auto", stats=None, probe=None,
+          global_time_matching=False):
     """The training loop of run_training.py:455-551 -- Adam, a contiguous validation block at a random start, epoch and
     batch loops, TensorBoard-style scalars, EarlyStopping checkpoint of the state_dict to <output_dir>/model.pt -- made
     data parallel (one process per GPU, torch.distributed initialised by the launcher):
@@ -766,8 +926,12 @@ def train(model, dataset, output_dir, relation_mat=None, mask=None, n_epochs=10,
         batches;
       * each global batch of `batch_size` samples is cut into contiguous per-rank shards (dist.shard_range); a rank
         weights its gradient by n_local * world / n_global before the single all-reduce, so the averaged gradient is the
-        global-batch mean loss's (BatchNorm statistics and the pairwise time-matching term stay rank-local: standard
-        data-parallel semantics, the reference has no multi-device behaviour to match);
+        global-batch mean loss's (BatchNorm statistics and, by default, the pairwise time-matching term stay rank-local;
+        the reference has no multi-device behaviour to match);
+      * global_time_matching=True: the time-matching term is the global batch's -- every rank builds the relation block of
+        the batch's GLOBAL ids, gathers the latents (one collective per step) and forms its rows against the whole batch,
+        so the exchanged gradient is that of the one-process term and the epoch records print the one-process value
+        (fused step only: any other route raises ValueError; BatchNorm statistics stay rank-local);
       * epoch losses are exchanged once per epoch, the early-stopping decision is therefore the same everywhere;
       * rank 0 alone writes model.pt (atomically), the others wait at a barrier.
 
@@ -797,8 +961,10 @@ def train(model, dataset, output_dir, relation_mat=None, mask=None, n_epochs=10,
     if dev.type == "cuda":
         torch.cuda.set_device(dev)
     rank, world = D.get_rank(), D.world_size()
-    optimizer = _make_optimizer(model, lr, fused)
+    optimizer = _make_optimizer(model, lr, fused, global_time_matching)
     model.zero_grad()
+    # the global time-matching term: relation blocks of the global batch, and what an empty shard needs to join its collectives
+    global_tm = isinstance(optimizer, FusedTrainer) and optimizer.global_tm and relation_mat is not None
 
     if feed not in ("auto", "resident", "stream", "sync"):
         raise ValueError(f"train: unknown feed {feed!r}")
@@ -823,6 +989,11 @@ def train(model, dataset, output_dir, relation_mat=None, mask=None, n_epochs=10,
     if torch.is_tensor(dataset) or isinstance(dataset, np.ndarray):
         bare = torch.as_tensor(dataset)
     n_samples = len(dataset)
+    sample_shape = None
+    if global_tm:
+        from .feed import dataset_tensor
+        src = bare if bare is not None else dataset_tensor(dataset)
+        sample_shape = tuple(src.shape[1:]) if src is not None else tuple(dataset[[0]][0].shape[1:])
     # (an int array instead of the reference's list: the same draws shuffle it into the same order -- numpy's shuffle is
     # the same Fisher-Yates walk for both -- and slicing a phase into batches costs nothing)
     sample_ids = np.arange(n_samples, dtype=np.int64)
@@ -859,18 +1030,26 @@ def train(model, dataset, output_dir, relation_mat=None, mask=None, n_epochs=10,
             training = phase == "train"
             losses = _EpochLosses(dev if dev.type == "cuda" else None, world)
             # this rank's shard of every global batch and the weight of its gradient in the data-parallel mean
-            plan = []
+            plan, batch_ids = [], []
             for start in range(0, len(ids), batch_size):
                 ids_batch = ids[start:start + batch_size]
                 lo, hi = D.shard_range(len(ids_batch), rank, world)
                 plan.append((ids_batch[lo:hi], D.shard_weight(len(ids_batch), rank, world)))
+                batch_ids.append(ids_batch)
+
+            def no_data(k):
+                rows = (len(batch_ids[k]), optimizer.latent_numel(sample_shape)) if global_tm else None
+                if training:
+                    _step_without_data(model, optimizer, rows)
+                elif rows is not None:
+                    optimizer.evaluate_without_data(rows)
             if feeder is not None:
                 log = _LossLog(dev, len(plan), model=model)
-                batches = feeder.phase([p[0] for p in plan], transform, fused=isinstance(optimizer, FusedTrainer))
-                for ids_local, weight in plan:
+                batches = feeder.phase([p[0] for p in plan], transform, fused=isinstance(optimizer, FusedTrainer),
+                                       tm_batches=batch_ids if global_tm else None)
+                for k, (ids_local, weight) in enumerate(plan):
                     if not len(ids_local):
-                        if training:
-                            _step_without_data(model, optimizer)
+                        no_data(k)
                         continue
                     n, x, kw = next(batches)
                     if probe is not None:
@@ -882,25 +1061,33 @@ def train(model, dataset, output_dir, relation_mat=None, mask=None, n_epochs=10,
                 logs[phase] = (log, losses)                         # read back after BOTH phases are enqueued
             else:
                 per_step = []
-                for ids_local, weight in plan:
+                for k, (ids_local, weight) in enumerate(plan):
                     if not len(ids_local):
-                        if training:
-                            _step_without_data(model, optimizer)
+                        no_data(k)
                         continue
+                    ids_tm = batch_ids[k].tolist() if global_tm else ids_local.tolist()
                     ids_local = ids_local.tolist()                  # (the reference indexes with lists)
                     if bare is not None:
                         batch = bare[ids_local].to(dev)             # a bare tensor / ndarray: dataset[ids][0] would be ONE sample
                     else:
                         batch = dataset[ids_local][0].to(dev)
-                    kw = {'time_matching_mat': get_relation_tensor(relation_mat, ids_local, device=dev) if get_relation_tensor else None,
+                    kw = {'time_matching_mat': get_relation_tensor(relation_mat, ids_tm, device=dev) if get_relation_tensor else None,
                           'batch_mask': get_mask(mask, ids_local, device=dev) if get_mask else None}
                     last = {}
                     if transform is not None:
                         batch = _augment(batch)                     # (run_one_batch's first statement, run_training.py:396)
                     if probe is not None:
                         probe(phase, epoch, ids_local, batch, kw)
-                    run_one_batch(model, batch, last, optimizer=optimizer, model_kwargs=kw, transform=None,
-                                  training=training, grad_weight=weight)
+                    if global_tm and not training:
+                        # (the validation pass through the trainer: the global term's collectives sit in its forward, and
+                        # the ranks without data join them -- the module's own forward would leave them waiting)
+                        keys, vals = _device_step(model, optimizer, batch, kw, False, weight)
+                        row = dict(zip(keys, vals.tolist()))
+                        row.setdefault("time_matching_loss", 0.)
+                        last = {k: [v] for k, v in _in_model_order(model, row).items()}
+                    else:
+                        run_one_batch(model, batch, last, optimizer=optimizer, model_kwargs=kw, transform=None,
+                                      training=training, grad_weight=weight)
                     losses.add(last, len(ids_local))
                     if stats is not None:
                         per_step.append({k: v[-1] for k, v in last.items()})

@@ -540,6 +540,27 @@ int dm_time_matching_forward_state(const float *z, const float *tm, int B, int n
                                    int32_t *state, void *stream);
 int dm_time_matching_backward_state(const float *z, const float *S, const float *g_loss_dev, float scale, const float *add,
                                     float *dz, int B, int n, const int32_t *state, void *stream);
+/* The stateful pair for ONE RANGE OF ROWS of the batch (data parallel: a rank's rows of the global batch against every
+ * sample of it).  z (B, n): the latents of the whole batch; rows [r0, r0 + R) are the caller's; tm (B, B): the whole relation
+ * block (read as tm[i][j] and tm[j][i]: it need not be symmetric).  Every pair (i, j), i among the rows, is formed from the
+ * operands the square pair uses -- the same K split of the Gram product, near pairs from differences, S_ij = d_ij + d_ji,
+ * mode 0's sparse form decided on the count of the WHOLE block, the map of S's nonzero blocks -- so S and dz are rows
+ * r0 .. r0 + R - 1 of the square calls' on the same z / tm, to the bit.
+ *   forward: workspace dm_time_matching_rows_workspace_floats(B, R, n) floats; S (2, R, B) out; loss_slabs
+ *            dm_time_matching_rows_num_slabs(B, R) pairs of doubles holding sum_{i in rows, j} v_ij (mode 1 normalised by the
+ *            GLOBAL count B * B, mode 0 a plain sum: the slabs of all ranges of a partition add up to the square call's loss);
+ *            state dm_time_matching_rows_state_ints(B, R) int32.
+ *   backward: dz (R, n) = [add +] scale * g_loss_dev[0] * d loss / d z_i for the rows -- g_ij AND g_ji of the whole batch,
+ *            i.e. the rows of the square call's dz; `add` (R, n) or NULL, as in dm_time_matching_backward_add.
+ * R = 0 is allowed: nothing is launched, no slab written. */
+int64_t dm_time_matching_rows_workspace_floats(int B, int R, int n);
+int dm_time_matching_rows_num_slabs(int B, int R);
+int dm_time_matching_rows_state_ints(int B, int R);
+int dm_time_matching_forward_rows(const float *z, const float *tm, int B, int r0, int R, int n, int mode, float w_a, float w_t,
+                                  float w_n, float margin, float *workspace, int64_t workspace_floats, float *S,
+                                  double *loss_slabs, int32_t *state, void *stream);
+int dm_time_matching_backward_rows(const float *z, const float *S, const float *g_loss_dev, float scale, const float *add,
+                                   float *dz, int B, int r0, int R, int n, const int32_t *state, void *stream);
 
 /* ===== enc.0 o enc.1 composition (vq_vae.py:277-278) ========================== */
 
