@@ -103,6 +103,10 @@ SIGNATURES = {
     "dm_wgrad": (C.c_int, [OP, OP, vp, vp] + [C.c_int] * 6 + [vp]),
     "dm_bn_finalize": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64, vp, vp, vp, vp, vp, f32, f32, vp, vp, C.c_int, vp]),
     "dm_bn_backward_finalize": (C.c_int, [vp, C.c_int, C.c_int, i64, vp, vp, vp, vp, vp, vp]),
+    "dm_bn_sync_pack": (C.c_int, [vp, C.c_int, C.c_int, i64, vp, vp, vp]),
+    "dm_bn_finalize_payload": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp]),
+    "dm_bn_backward_pack": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "dm_bn_backward_payload": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp]),
     "dm_apply": (C.c_int, [OP, vp, vp] + [C.c_int] * 4 + [vp]),
     "dm_channel_stats_num_blocks": (C.c_int, [C.c_int] * 4),
     "dm_channel_stats": (C.c_int, [vp, vp, vp] + [C.c_int] * 4 + [vp]),

@@ -256,6 +256,108 @@ __global__ __launch_bounds__(256) void bn_backward_finalize_kernel(
     }
 }
 
+// ------------------------------------------------------------------ synchronized BatchNorm (data parallel)
+// A layer's statistics leave the rank as ONE payload of doubles that the ranks add up (all-reduce, SUM) between two
+// launches; the global count and the gradient weight live in device memory, so a captured graph keyed on the LOCAL shape
+// replays unchanged for any global batch.
+//   forward payload  [w*sum x (C), w*sum x^2 (C), w*n]     w: 1, or 0 for a rank that only joins the exchange
+//   backward payload [g*sum dy (C), g*sum dy*a (C)]        g: the rank's gradient weight (FusedTrainer: grad_weight)
+
+// One block per channel: the slabs in slab_partial's fixed order (the sums are bit-equal to bn_finalize_kernel's).
+__global__ __launch_bounds__(256) void bn_sync_pack_kernel(const double *__restrict__ stats, int nslabs, int C, double count,
+                                                          const double *__restrict__ weight, double *__restrict__ payload)
+{
+    __shared__ double s_red[4];
+    const int c = blockIdx.x;
+    double s1, s2;
+    slab_partial(stats, nslabs, C, c, s1, s2);
+    const double t1 = block_sum(s1, s_red);
+    const double t2 = block_sum(s2, s_red);
+    if (threadIdx.x == 0) {
+        const double w = weight[0];                 // (w = 0: exact zeros, whatever the placeholder's sums are)
+        payload[c] = w != 0.0 ? w * t1 : 0.0;
+        payload[C + c] = w != 0.0 ? w * t2 : 0.0;
+        if (c == 0) payload[2 * C] = w * count;
+    }
+}
+
+// One thread per channel: bn_finalize_kernel's arithmetic on the reduced payload, the count read from payload[2C].
+__global__ __launch_bounds__(256) void bn_finalize_payload_kernel(
+    const double *__restrict__ payload, int C, const float *__restrict__ gamma, const float *__restrict__ beta,
+    float *__restrict__ running_mean, float *__restrict__ running_var, long long *__restrict__ nbt,
+    float momentum, float eps, float *__restrict__ coef, float *__restrict__ saved)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const float g = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
+    const double n = payload[2 * C];
+    const double unbias = n > 1.0 ? n / (n - 1.0) : 1.0;        // nn.SyncBatchNorm: the GLOBAL count's Bessel factor
+    const double mean = n > 0.0 ? payload[c] / n : 0.0;
+    double var = n > 0.0 ? payload[C + c] / n - mean * mean : 0.0;
+    if (var < 0.0) var = 0.0;
+    const float mean_f = (float)mean;
+    const float invstd = (float)(1.0 / sqrt(var + (double)eps));
+    const float scale = g * invstd;
+    coef[c * 4 + 0] = scale;
+    coef[c * 4 + 1] = 0.f;
+    coef[c * 4 + 2] = bt - mean_f * scale;
+    coef[c * 4 + 3] = 0.f;
+    saved[c * 2 + 0] = mean_f;
+    saved[c * 2 + 1] = invstd;
+    const double mom = (double)momentum;
+    if (running_mean) running_mean[c] = (float)(mom * mean + (1.0 - mom) * (double)running_mean[c]);
+    if (running_var) running_var[c] = (float)(mom * (var * unbias) + (1.0 - mom) * (double)running_var[c]);
+    if (nbt && c == 0) nbt[0] += 1;
+}
+
+// One block per channel: dgamma / dbeta from the LOCAL sums (the gradient bucket's exchange averages them), the weighted
+// sums into the payload.
+__global__ __launch_bounds__(256) void bn_backward_pack_kernel(
+    const double *__restrict__ stats, int nslabs, int C, const float *__restrict__ saved, const double *__restrict__ weight,
+    float *__restrict__ dgamma, float *__restrict__ dbeta, double *__restrict__ payload)
+{
+    __shared__ double s_red[4];
+    const int c = blockIdx.x;
+    float mean_f = 0.f, invstd_f = 0.f;
+    if (threadIdx.x == 0) { mean_f = saved[c * 2 + 0]; invstd_f = saved[c * 2 + 1]; }
+    double s1, s2;
+    slab_partial(stats, nslabs, C, c, s1, s2);
+    const double sum_dy = block_sum(s1, s_red);
+    const double sum_dya = block_sum(s2, s_red);
+    if (threadIdx.x == 0) {
+        const double sum_dyxh = (double)invstd_f * (sum_dya - (double)mean_f * sum_dy);
+        if (dgamma) dgamma[c] = (float)sum_dyxh;
+        if (dbeta) dbeta[c] = (float)sum_dy;
+        const double w = weight[0];
+        payload[c] = w != 0.0 ? w * sum_dy : 0.0;
+        payload[C + c] = w != 0.0 ? w * sum_dya : 0.0;
+    }
+}
+
+// One thread per channel: bn_backward_finalize_kernel's coefficients from the reduced payload.  Rank r's dy is in the
+// scale of its local mean loss and its bucket is later multiplied by w_r, so the batch terms divide by w_r * N
+// (N = the global count, forward payload[2C]); w_r = 0 (a rank without data: its bucket is dropped) gives plain scale * dy.
+__global__ __launch_bounds__(256) void bn_backward_payload_kernel(
+    const double *__restrict__ payload, const double *__restrict__ fwd_payload, int C, const float *__restrict__ gamma,
+    const float *__restrict__ saved, const double *__restrict__ weight, float *__restrict__ coef_bwd)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const double wn = weight[0] * fwd_payload[2 * C];
+    const double inv_n = wn > 0.0 ? 1.0 / wn : 0.0;
+    const double mean = (double)saved[c * 2 + 0], invstd = (double)saved[c * 2 + 1];
+    const double g = gamma ? (double)gamma[c] : 1.0;
+    const double sum_dy = payload[c], sum_dya = payload[C + c];
+    const double sum_dyxh = invstd * (sum_dya - mean * sum_dy);
+    const double scale = g * invstd;
+    const double c1 = sum_dy * inv_n, c2 = sum_dyxh * inv_n;
+    const double Bc = -scale * invstd * c2;
+    coef_bwd[c * 4 + 0] = (float)scale;
+    coef_bwd[c * 4 + 1] = (float)Bc;
+    coef_bwd[c * 4 + 2] = (float)(-scale * c1 - Bc * mean);
+    coef_bwd[c * 4 + 3] = 0.f;
+}
+
 __global__ __launch_bounds__(256) void apply_kernel(Operand in, const float *__restrict__ resid,
                                                     float *__restrict__ out, int C, int HW4, long long total4)
 {
@@ -445,4 +547,45 @@ extern "C" int dm_sum_slabs(const double *stats, int nslabs, int N, float scale,
     DM_REQUIRE(stats && dst && nslabs > 0 && N > 0, "dm_sum_slabs: bad argument");
     hipLaunchKernelGGL(sum_slabs_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, stats, nslabs, N, scale, dst);
     return dm_launch_status("dm_sum_slabs");
+}
+
+extern "C" int dm_bn_sync_pack(const double *stats, int nslabs, int C, int64_t count, const double *weight, double *payload,
+                               void *stream)
+{
+    DM_REQUIRE(stats && weight && payload, "dm_bn_sync_pack: NULL pointer");
+    DM_REQUIRE(nslabs > 0 && C > 0 && count > 0, "dm_bn_sync_pack: bad sizes");
+    hipLaunchKernelGGL(bn_sync_pack_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, stats, nslabs, C, (double)count,
+                       weight, payload);
+    return dm_launch_status("dm_bn_sync_pack");
+}
+
+extern "C" int dm_bn_finalize_payload(const double *payload, int C, const float *gamma, const float *beta,
+                                      float *running_mean, float *running_var, int64_t *num_batches_tracked, float momentum,
+                                      float eps, float *coef, float *saved, void *stream)
+{
+    DM_REQUIRE(payload && coef && saved, "dm_bn_finalize_payload: NULL pointer");
+    DM_REQUIRE(C > 0, "dm_bn_finalize_payload: bad sizes");
+    hipLaunchKernelGGL(bn_finalize_payload_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, payload, C, gamma,
+                       beta, running_mean, running_var, (long long *)num_batches_tracked, momentum, eps, coef, saved);
+    return dm_launch_status("dm_bn_finalize_payload");
+}
+
+extern "C" int dm_bn_backward_pack(const double *stats, int nslabs, int C, const float *saved, const double *weight,
+                                   float *dgamma, float *dbeta, double *payload, void *stream)
+{
+    DM_REQUIRE(stats && saved && weight && payload, "dm_bn_backward_pack: NULL pointer");
+    DM_REQUIRE(nslabs > 0 && C > 0, "dm_bn_backward_pack: bad sizes");
+    hipLaunchKernelGGL(bn_backward_pack_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, stats, nslabs, C, saved, weight,
+                       dgamma, dbeta, payload);
+    return dm_launch_status("dm_bn_backward_pack");
+}
+
+extern "C" int dm_bn_backward_payload(const double *payload, const double *fwd_payload, int C, const float *gamma,
+                                      const float *saved, const double *weight, float *coef_bwd, void *stream)
+{
+    DM_REQUIRE(payload && fwd_payload && saved && weight && coef_bwd, "dm_bn_backward_payload: NULL pointer");
+    DM_REQUIRE(C > 0, "dm_bn_backward_payload: bad sizes");
+    hipLaunchKernelGGL(bn_backward_payload_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, payload,
+                       fwd_payload, C, gamma, saved, weight, coef_bwd);
+    return dm_launch_status("dm_bn_backward_payload");
 }

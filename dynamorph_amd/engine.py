@@ -77,10 +77,57 @@ class Layers:
 
 
 # ------------------------------------------------------------------------- BatchNorm glue
+# The synchronized-BatchNorm context of the step being enqueued (a BnSync), or None: every training-mode BatchNorm with batch
+# statistics then normalises with the statistics of the global batch.  Set by FusedTrainer (bn_sync); None is the default.
+_bn_sync = None
+
+
+class bn_sync:
+    """with bn_sync(ctx): the BatchNorm glue below routes through ctx (None: unchanged)."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+
+    def __enter__(self):
+        global _bn_sync
+        self.prev, _bn_sync = _bn_sync, self.ctx
+        return self.ctx
+
+    def __exit__(self, *exc):
+        global _bn_sync
+        _bn_sync = self.prev
+
+
+class BnSync:
+    """Statistics of the global batch for data-parallel training (nn.SyncBatchNorm's arithmetic).
+    weights: float64 device tensor [forward weight, gradient weight] -- 1 and grad_weight for a rank with data, 0 and 0 for a
+    rank that only joins the exchanges.  exchange(payload): the caller's SUM over ranks of a float64 payload, in place (inline
+    all-reduce; during a graph capture: the end of a segment).  One exchange per layer and direction, in launch order."""
+
+    def __init__(self, weights, exchange):
+        self.weights, self.exchange = weights, exchange
+        self.fwd = {}                     # BatchNorm module -> its all-reduced forward payload (the global count)
+
+    def forward(self, stats, bn, count):
+        momentum = 0.1 if bn.momentum is None else bn.momentum
+        payload = ops.bn_sync_pack(stats, count, self.weights[0:1])
+        self.exchange(payload)
+        self.fwd[bn] = payload
+        return ops.bn_finalize_payload(payload, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var,
+                                       bn.num_batches_tracked, momentum, bn.eps)
+
+    def backward(self, stats, bn, saved, G):
+        payload = ops.bn_backward_pack(stats, saved, self.weights[1:2], G(bn.weight), G(bn.bias))
+        self.exchange(payload)
+        return ops.bn_backward_payload(payload, self.fwd[bn], bn.weight.detach(), saved, self.weights[1:2])
+
+
 def _bn_coef(stats, bn, count, per_sample, nbatch, defer=None):
     """Batch statistics -> (coef, saved).  eval() mode (never used by the reference path) takes the
     running statistics instead; its coefficients are three tiny device ops, no HIP kernel needed.
     defer: list collecting the running-statistics updates of the per-sample path (ops.bn_running_replay)."""
+    if _bn_sync is not None and bn.training and not per_sample:
+        return _bn_sync.forward(stats, bn, count)
     if not bn.training:
         invstd = torch.rsqrt(bn.running_var + bn.eps)
         scale = bn.weight.detach() * invstd
@@ -103,6 +150,8 @@ def _w(p):
 def _bn_backward(stats, count, bn, saved, G):
     """native_batch_norm_backward's reductions for `bn` from the (sum dy, sum dy * a) slabs -> the AFFINE2 coefficients of
     da; eval() mode (fixed statistics: count 0) keeps only da = gamma * invstd * dy."""
+    if _bn_sync is not None and bn.training:
+        return _bn_sync.backward(stats, bn, saved, G)
     return ops.bn_backward_finalize(stats, count if bn.training else 0, _w(bn.weight), saved, G(bn.weight), G(bn.bias))
 
 

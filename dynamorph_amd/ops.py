@@ -637,6 +637,56 @@ def bn_backward_finalize(stats, count, gamma, saved, dgamma, dbeta):
     return coef_bwd
 
 
+# synchronized BatchNorm (data parallel): a layer's statistics as one float64 payload the ranks all-reduce between two launches;
+# weight is a 1-element float64 device tensor (read at run time: a captured graph replays for any global batch)
+@_op
+def bn_sync_pack(stats, count, weight):
+    """(nslabs, C, 2) slabs -> payload (2C+1,) = weight * [sum x, sum x^2, count]."""
+    lib = L.load()
+    nslabs, Cn = stats.shape[0], stats.shape[1]
+    payload = _new((2 * Cn + 1,), stats, torch.float64)
+    L.check(lib.dm_bn_sync_pack(_ptr(stats, torch.float64), nslabs, Cn, count, _ptr(weight, torch.float64),
+                                _ptr(payload, torch.float64), _stream()), "dm_bn_sync_pack")
+    return payload
+
+
+@_op
+def bn_finalize_payload(payload, gamma, beta, running_mean, running_var, nbt, momentum, eps):
+    """bn_finalize on the all-reduced payload (global count at payload[2C]) -> (coef, saved)."""
+    lib = L.load()
+    Cn = (payload.numel() - 1) // 2
+    coef = _new((Cn, 4), gamma)
+    saved = _new((Cn, 2), gamma)
+    L.check(lib.dm_bn_finalize_payload(_ptr(payload, torch.float64), Cn, _ptr(gamma), _ptr(beta), _ptr(running_mean),
+                                       _ptr(running_var), _ptr(nbt, torch.int64), momentum, eps, _ptr(coef), _ptr(saved),
+                                       _stream()), "dm_bn_finalize_payload")
+    return coef, saved
+
+
+@_op
+def bn_backward_pack(stats, saved, weight, dgamma, dbeta):
+    """dgamma / dbeta from the local (sum dy, sum dy*a) slabs; returns the payload (2C,) = weight * [sum dy, sum dy*a]."""
+    lib = L.load()
+    nslabs, Cn = stats.shape[0], stats.shape[1]
+    payload = _new((2 * Cn,), stats, torch.float64)
+    L.check(lib.dm_bn_backward_pack(_ptr(stats, torch.float64), nslabs, Cn, _ptr(saved), _ptr(weight, torch.float64),
+                                    _ptr(dgamma), _ptr(dbeta), _ptr(payload, torch.float64), _stream()), "dm_bn_backward_pack")
+    return payload
+
+
+@_op
+def bn_backward_payload(payload, fwd_payload, gamma, saved, weight):
+    """The AFFINE2 coefficients of da from the all-reduced backward payload; fwd_payload: the layer's all-reduced forward
+    payload (its global count), weight: this rank's gradient weight."""
+    lib = L.load()
+    Cn = payload.numel() // 2
+    coef_bwd = _new((Cn, 4), gamma)
+    L.check(lib.dm_bn_backward_payload(_ptr(payload, torch.float64), _ptr(fwd_payload, torch.float64), Cn, _ptr(gamma),
+                                       _ptr(saved), _ptr(weight, torch.float64), _ptr(coef_bwd), _stream()),
+            "dm_bn_backward_payload")
+    return coef_bwd
+
+
 @_op
 def apply(inp, B, Cn, H, W, resid=None, out=None):
     lib = L.load()

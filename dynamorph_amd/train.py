@@ -16,6 +16,7 @@ Two ways to train, same kernels underneath:
 
 `run_one_batch` / `train` mirror run_training.py:377-417 / :455-551 (same arguments and loop).
 """
+import contextlib
 import os
 
 import numpy as np
@@ -49,7 +50,7 @@ class FusedTrainer:
     """Adam(lr, betas=(.9,.999), eps=1e-8) exactly as run_training.py:485 builds it, fused."""
 
     def __init__(self, model, lr=1e-3, betas=(.9, .999), eps=1e-8, process_group=None, use_graph=True,
-                 global_time_matching=False):
+                 global_time_matching=False, sync_batchnorm=False):
         from .vq_vae import VQ_VAE, VQ_VAE_z32
         if not isinstance(model, (VQ_VAE, VQ_VAE_z32)):
             raise TypeError("FusedTrainer is built for VQ_VAE / VQ_VAE_z16 / VQ_VAE_z32; train other modules with a torch optimizer")
@@ -83,6 +84,12 @@ class FusedTrainer:
         if self.global_tm and self._extra:
             raise ValueError("FusedTrainer: global_time_matching is not available together with extra_loss")
         self._tm_gscale = torch.ones(1, device=dev)       # world / grad_weight: the rows' gradient through the exchange
+        # sync_batchnorm: every training-mode BatchNorm normalises with the statistics of the global batch (one all-reduced
+        # payload per layer and direction) instead of the rank's shard; nothing changes in one process
+        self.sync_bn = bool(sync_batchnorm) and self.world > 1
+        if self.sync_bn and self._extra:
+            raise ValueError("FusedTrainer: sync_batchnorm is not available together with extra_loss")
+        self._bn_w = torch.ones(2, dtype=torch.float64, device=dev)     # [forward weight, gradient weight] of those exchanges
         self._graphs = {}            # input shapes -> {x, mask, tm: static inputs; train / eval: (graph, static output)}
         self._static_x = None        # input tensor of the graph replayed last
         D.broadcast_(self.flat, list(model.buffers()), group=self.group)    # same replica everywhere
@@ -419,6 +426,110 @@ class FusedTrainer:
         D.all_gather_rows(torch.empty((0, n), device=self.flat.device), Bg, self.group)
         self._global_total(torch.zeros(1, dtype=torch.float64, device=self.flat.device))
 
+    # ------------------------------------------------------------------------------------------ sync_batchnorm
+    def _bn_ctx(self, exchange):
+        return E.bn_sync(E.BnSync(self._bn_w, exchange))
+
+    def _exchange_now(self, payload):
+        D.allreduce_payload_(payload, self.group)
+
+    def _sync_body(self, x, mask, tm, glob, gather):
+        """The step's launches with the BatchNorm exchanges routed through the active context; glob: the global
+        time-matching step, gather(st) -> the (Bg, n) latents of the whole batch.  Returns (scalars, the rows' share of the
+        term or None)."""
+        if not glob:
+            return self.forward_backward(x, mask, tm), None
+        st = self._global_first(x, mask)
+        part = self._global_second(st, gather(st), tm)
+        return st.scalars, part
+
+    def _sync_step(self, x, mask, tm, grad_weight, replay=True):
+        """One forward + backward with sync_batchnorm (world > 1).  Eagerly (use_graph=False) every exchange runs inline.
+        With graphs the step is captured once per input shape as segments cut at the exchanges (_Segments): a replay is
+        seg0 | all-reduce | seg1 | ... | segK, the collectives between the replays.  With global_time_matching and a relation
+        block the gather of the latents is one more cut.  Returns the step's scalars (global term included)."""
+        glob = self.global_tm and tm is not None
+        if glob:
+            Bg = tm.shape[0]
+            lo, hi = D.shard_range(Bg, D.get_rank(self.group), self.world)
+            if hi - lo != x.shape[0]:
+                raise ValueError(f"FusedTrainer: global_time_matching needs the ({Bg}, {Bg}) relation block of the global "
+                                 f"batch whose shard this rank's {x.shape[0]} samples are")
+            self._tm_gscale.fill_(self.world / float(grad_weight))
+        self._bn_w[0].fill_(1.0)
+        self._bn_w[1].fill_(float(grad_weight))
+        if not self.use_graph:
+            with self._bn_ctx(self._exchange_now):
+                scal, part = self._sync_body(x, mask, tm.to(torch.float32).contiguous() if glob else tm, glob,
+                                             lambda st: D.all_gather_rows(st.lat, Bg, self.group))
+        else:
+            sx, smask, stm = self.static_inputs(x.shape, None if mask is None else mask.shape, None if tm is None else tm.shape)
+            if x.data_ptr() != sx.data_ptr():
+                sx.copy_(x)
+            if mask is not None and mask.data_ptr() != smask.data_ptr():
+                smask.copy_(mask)
+            if tm is not None and tm.data_ptr() != stm.data_ptr():
+                stm.copy_(tm)
+            ent = self._graphs[(tuple(x.shape), None if mask is None else tuple(mask.shape), None if tm is None else tuple(tm.shape))]
+            if ent.get("sync") is None:
+                # warm-up (allocator, lazy init) with the collectives left out: ranks may capture at different steps (a
+                # ragged shard's shape), so nothing here may wait for another rank.  Its BatchNorm side effects are put back.
+                bufs = list(self.model.buffers())
+                saved = [b.clone() for b in bufs]
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side), self._bn_ctx(lambda payload: None):
+                    self._sync_body(sx, smask, stm, glob, lambda st: torch.zeros((Bg, st.lat.shape[1]), device=sx.device))
+                torch.cuda.current_stream().wait_stream(side)
+                for b, sv in zip(bufs, saved):
+                    b.copy_(sv)
+                segs = _Segments()
+
+                def gather(st):
+                    zg = torch.empty((Bg, st.lat.shape[1]), device=sx.device)
+                    segs.cut(lambda: D.all_gather_rows(st.lat, Bg, self.group, out=zg))
+                    return zg
+                exchange = lambda payload: segs.cut(lambda: D.allreduce_payload_(payload, self.group))     # noqa: E731
+                with segs.capture(), self._bn_ctx(exchange):
+                    out = self._sync_body(sx, smask, stm, glob, gather)
+                ent["sync"] = (segs, out)
+            self._static_x = sx
+            segs, (scal, part) = ent["sync"]
+            if not replay:
+                return None
+            segs.replay()
+        if glob:
+            return _with_matching(scal, self._global_total(part).float(), float(self.model.weight_matching))
+        return scal
+
+    def _bn_without_data(self, sample_shape, global_rows, training):
+        """A rank whose shard is empty in a sync_batchnorm step (training) or validation pass: it runs the pass on one zero
+        placeholder sample with forward and gradient weight 0 -- its payloads are zeros, its BatchNorm buffers still take
+        the global statistics -- so it joins every exchange in the others' order.  global_rows: see step_without_data (it
+        presents 0 rows to the gather).  The caller drops the placeholder's gradient."""
+        if sample_shape is None:
+            raise ValueError("FusedTrainer: with sync_batchnorm a rank without data needs sample_shape to join the exchanges")
+        x = torch.zeros((1,) + tuple(sample_shape), device=self.flat.device)
+        dev = self.flat.device
+        self._bn_w.zero_()
+        with self._bn_ctx(self._exchange_now):
+            if not training:
+                self.forward_only(x)
+            elif global_rows is None:
+                self.forward_backward(x)
+            else:
+                st = self._global_first(x, None)
+                D.all_gather_rows(torch.empty((0, global_rows[1]), device=dev), global_rows[0], self.group)
+                if self._z32:
+                    self._z32_encoder_backward(st, st.g_zq, st.pending)
+                else:
+                    E.encoder_backward(st.L, st.ecx, st.dz, self.G, zero_fed_biases=False, pending_extra=st.extra)
+        if global_rows is not None:
+            if training:
+                self._global_total(torch.zeros(1, dtype=torch.float64, device=dev))
+            else:
+                self._join_without_data(global_rows)
+
     def _allreduce(self, weight=1.0):
         """SUM over ranks of the flat gradient bucket: ONE collective and nothing behind it -- the "x 1 / world" of the mean
         is applied by the optimizer's load (_adam, dm_adam_counted_scaled), so after the exchange the bucket holds the sum.
@@ -437,12 +548,15 @@ class FusedTrainer:
                          self.step_dev[a:a + 1], self.step_dev[b:b + 1], grad_scale=1.0 / self.world)
         self._step_slot = b
 
-    def step_without_data(self, global_rows=None):
+    def step_without_data(self, global_rows=None, sample_shape=None):
         """This rank's shard of a ragged global batch is empty: it contributes a zero gradient to the exchange and takes
         the same Adam step as the others.  global_rows = (Bg, latent elements per sample) when the other ranks take a
-        global_time_matching step (with a relation block): this rank joins its collectives too."""
+        global_time_matching step (with a relation block): this rank joins its collectives too.  sample_shape = (C, H, W)
+        of the others' samples: with sync_batchnorm this rank joins every BatchNorm exchange (_bn_without_data)."""
         with torch.cuda.device(self.flat.device):
-            if self.global_tm and global_rows is not None:
+            if self.sync_bn:
+                self._bn_without_data(sample_shape, global_rows, training=True)
+            elif self.global_tm and global_rows is not None:
                 self._join_without_data(global_rows)
             self.grad.zero_()
             self._allreduce()
@@ -464,6 +578,8 @@ class FusedTrainer:
             if mark: mark()
             if self._extra:
                 out = self._step_with_extra_losses(x, mask, time_matching_mat, labels)
+            elif self.sync_bn:
+                out = self._sync_step(x, mask, time_matching_mat, grad_weight)
             elif self.global_tm and time_matching_mat is not None:
                 out = self._global_step(x, mask, time_matching_mat, grad_weight)
             elif not self.use_graph:
@@ -493,10 +609,13 @@ class FusedTrainer:
         out["steps"] = len(timers)
         return out
 
-    def evaluate_without_data(self, global_rows=None):
+    def evaluate_without_data(self, global_rows=None, sample_shape=None):
         """The validation counterpart of step_without_data: a rank with an empty shard joins the collectives of a
-        global_time_matching validation pass (nothing to do otherwise)."""
-        if self.global_tm and global_rows is not None:
+        global_time_matching / sync_batchnorm validation pass (nothing to do otherwise)."""
+        if self.sync_bn:
+            with torch.cuda.device(self.flat.device):
+                self._bn_without_data(sample_shape, global_rows, training=False)
+        elif self.global_tm and global_rows is not None:
             with torch.cuda.device(self.flat.device):
                 self._join_without_data(global_rows)
 
@@ -545,6 +664,10 @@ class FusedTrainer:
         if not x.is_cuda or x.device != self.flat.device:
             raise RuntimeError(f"FusedTrainer.evaluate: batch on {x.device}, model on {self.flat.device}")
         with torch.cuda.device(self.flat.device):
+            if self.sync_bn:            # (eagerly: every BatchNorm's exchange sits inside the forward)
+                self._bn_w[0].fill_(1.0)
+                with self._bn_ctx(self._exchange_now):
+                    return self.forward_only(x.contiguous(), mask, time_matching_mat)
             # (global_time_matching: the validation pass runs eagerly -- its collective sits inside the forward)
             if not self.use_graph or (self.global_tm and time_matching_mat is not None):
                 return self.forward_only(x.contiguous(), mask, time_matching_mat)
@@ -557,7 +680,10 @@ class FusedTrainer:
         if not self.use_graph:
             return None
         with torch.cuda.device(self.flat.device):
-            self._graph_step(x.contiguous(), mask, time_matching_mat, replay=False)
+            if self.sync_bn:
+                self._sync_step(x.contiguous(), mask, time_matching_mat, 1.0, replay=False)
+            else:
+                self._graph_step(x.contiguous(), mask, time_matching_mat, replay=False)
         return self._static_x
 
     def static_inputs(self, x_shape, mask_shape=None, tm_shape=None):
@@ -612,6 +738,45 @@ class FusedTrainer:
     def input_buffer(self):
         """Input tensor of the graph replayed last (None before the first step): fill it in place to skip the copy."""
         return self._static_x
+
+
+class _Segments:
+    """A step captured as HIP graphs cut where a collective must run: replay() is seg0 | after0 | seg1 | ... | segK, every
+    collective between two replays on the launch stream (none is captured).  All segments allocate from the first one's
+    memory pool, so a tensor one segment writes and a later one reads keeps its address."""
+
+    def __init__(self):
+        self.graphs, self.after = [], []
+
+    @contextlib.contextmanager
+    def capture(self):
+        torch.cuda.synchronize()                 # (no collective of this process in flight while a stream captures)
+        with torch.cuda.stream(torch.cuda.Stream()):
+            self._begin()
+            try:
+                yield self
+            finally:
+                self.graphs[-1].capture_end()            # (also on an error: the stream must not stay in capture mode)
+
+    def _begin(self):
+        g = torch.cuda.CUDAGraph()
+        if self.graphs:
+            g.capture_begin(pool=self.graphs[0].pool())
+        else:
+            g.capture_begin()
+        self.graphs.append(g)
+
+    def cut(self, action):
+        """End the current segment; action() runs after its replay, before the next segment's."""
+        self.graphs[-1].capture_end()
+        self.after.append(action)
+        self._begin()
+
+    def replay(self):
+        for i, g in enumerate(self.graphs):
+            g.replay()
+            if i < len(self.after):
+                self.after[i]()
 
 
 def _tm_args(model, z32=False):
@@ -752,11 +917,11 @@ def run_one_batch(model, batch, train_loss, model_kwargs=None, optimizer=None, t
     return model, train_loss
 
 
-def _step_without_data(model, optimizer, global_rows=None):
+def _step_without_data(model, optimizer, global_rows=None, sample_shape=None):
     """A rank whose shard of a ragged global batch is empty still joins the gradient exchange (with zeros) and the step
-    (global_rows: see FusedTrainer.step_without_data)."""
+    (global_rows, sample_shape: see FusedTrainer.step_without_data)."""
     if isinstance(optimizer, FusedTrainer):
-        optimizer.step_without_data(global_rows)
+        optimizer.step_without_data(global_rows, sample_shape)
         return
     params = [p for p in model.parameters() if p.requires_grad]
     for p in params:
@@ -820,7 +985,7 @@ class _EpochLosses:
         return {k: v / max(tot[-1], 1.0) for k, v in zip(keys, tot[:-1])}
 
 
-def _make_optimizer(model, lr, fused, global_time_matching=False):
+def _make_optimizer(model, lr, fused, global_time_matching=False, sync_batchnorm=False):
     from .vq_vae import VQ_VAE
     from .vq_vae import VQ_VAE_z32
     # (a model with caller-supplied extra losses, vae.py:463-469, runs arbitrary torch code per step: the autograd path)
@@ -829,6 +994,9 @@ def _make_optimizer(model, lr, fused, global_time_matching=False):
         raise ValueError("global_time_matching=True needs the fused step (FusedTrainer: fused=True and a VQ_VAE / VQ_VAE_z16 / "
                          "VQ_VAE_z32 without extra_loss); the autograd route forms the time-matching term on each rank's "
                          "shard only")
+    if sync_batchnorm and not (fused and fused != "graph" and fusable):
+        raise ValueError("sync_batchnorm=True needs the fused step (FusedTrainer: fused=True and a VQ_VAE / VQ_VAE_z16 / "
+                         "VQ_VAE_z32 without extra_loss); the autograd route normalises with each rank's shard only")
     if D.world_size() > 1 and not (fused and fused != "graph" and fusable):
         # FusedTrainer broadcasts its flat buffer itself; any other module: same replica everywhere before the first step
         for t in list(model.parameters()) + list(model.buffers()):
@@ -836,7 +1004,7 @@ def _make_optimizer(model, lr, fused, global_time_matching=False):
     if fused == "graph" and D.world_size() == 1:
         return GraphedTrainer(model, lr=lr)               # any module: the autograd step as a replayed HIP graph
     if fused and fusable:
-        return FusedTrainer(model, lr=lr, global_time_matching=global_time_matching)
+        return FusedTrainer(model, lr=lr, global_time_matching=global_time_matching, sync_batchnorm=sync_batchnorm)
     return torch.optim.Adam(model.parameters(), lr=lr, betas=(.9, .999))
 
 
@@ -915,7 +1083,7 @@ def _device_step(model, optimizer, x, kw, training, grad_weight):
 def train(model, dataset, output_dir, relation_mat=None, mask=None, n_epochs=10, lr=0.001, batch_size=16,
           device='cuda:0', shuffle_data=False, transform=None, val_split_ratio=0.15, patience=20,
           get_relation_tensor=None, get_mask=None, writer=None, fused=True, feed="auto", stats=None, probe=None,
-          global_time_matching=False):
+          global_time_matching=False, sync_batchnorm=False):
     """The training loop of run_training.py:455-551 -- Adam, a contiguous validation block at a random start, epoch and
     batch loops, TensorBoard-style scalars, EarlyStopping checkpoint of the state_dict to <output_dir>/model.pt -- made
     data parallel (one process per GPU, torch.distributed initialised by the launcher):
@@ -926,12 +1094,17 @@ def train(model, dataset, output_dir, relation_mat=None, mask=None, n_epochs=10,
         batches;
       * each global batch of `batch_size` samples is cut into contiguous per-rank shards (dist.shard_range); a rank
         weights its gradient by n_local * world / n_global before the single all-reduce, so the averaged gradient is the
-        global-batch mean loss's (BatchNorm statistics and, by default, the pairwise time-matching term stay rank-local;
+        global-batch mean loss's (by default BatchNorm statistics and the pairwise time-matching term stay rank-local;
         the reference has no multi-device behaviour to match);
       * global_time_matching=True: the time-matching term is the global batch's -- every rank builds the relation block of
         the batch's GLOBAL ids, gathers the latents (one collective per step) and forms its rows against the whole batch,
         so the exchanged gradient is that of the one-process term and the epoch records print the one-process value
-        (fused step only: any other route raises ValueError; BatchNorm statistics stay rank-local);
+        (fused step only: any other route raises ValueError);
+      * sync_batchnorm=True: every training-mode BatchNorm normalises with the statistics of the global batch and every
+        rank's running statistics are the global batch's (nn.SyncBatchNorm's arithmetic, one small all-reduce per layer and
+        direction); a rank with an empty shard joins those exchanges on a zero-weight placeholder sample.
+        Validation runs through the trainer, eagerly.  Together with global_time_matching=True a W-rank step computes
+        what one process computes on the whole batch (fused step only: any other route raises ValueError);
       * epoch losses are exchanged once per epoch, the early-stopping decision is therefore the same everywhere;
       * rank 0 alone writes model.pt (atomically), the others wait at a barrier.
 
@@ -961,10 +1134,11 @@ def train(model, dataset, output_dir, relation_mat=None, mask=None, n_epochs=10,
     if dev.type == "cuda":
         torch.cuda.set_device(dev)
     rank, world = D.get_rank(), D.world_size()
-    optimizer = _make_optimizer(model, lr, fused, global_time_matching)
+    optimizer = _make_optimizer(model, lr, fused, global_time_matching, sync_batchnorm)
     model.zero_grad()
     # the global time-matching term: relation blocks of the global batch, and what an empty shard needs to join its collectives
     global_tm = isinstance(optimizer, FusedTrainer) and optimizer.global_tm and relation_mat is not None
+    sync_bn = isinstance(optimizer, FusedTrainer) and optimizer.sync_bn
 
     if feed not in ("auto", "resident", "stream", "sync"):
         raise ValueError(f"train: unknown feed {feed!r}")
@@ -990,7 +1164,7 @@ def train(model, dataset, output_dir, relation_mat=None, mask=None, n_epochs=10,
         bare = torch.as_tensor(dataset)
     n_samples = len(dataset)
     sample_shape = None
-    if global_tm:
+    if global_tm or sync_bn:
         from .feed import dataset_tensor
         src = bare if bare is not None else dataset_tensor(dataset)
         sample_shape = tuple(src.shape[1:]) if src is not None else tuple(dataset[[0]][0].shape[1:])
@@ -1040,9 +1214,9 @@ def train(model, dataset, output_dir, relation_mat=None, mask=None, n_epochs=10,
             def no_data(k):
                 rows = (len(batch_ids[k]), optimizer.latent_numel(sample_shape)) if global_tm else None
                 if training:
-                    _step_without_data(model, optimizer, rows)
-                elif rows is not None:
-                    optimizer.evaluate_without_data(rows)
+                    _step_without_data(model, optimizer, rows, sample_shape)
+                elif rows is not None or sync_bn:
+                    optimizer.evaluate_without_data(rows, sample_shape)
             if feeder is not None:
                 log = _LossLog(dev, len(plan), model=model)
                 batches = feeder.phase([p[0] for p in plan], transform, fused=isinstance(optimizer, FusedTrainer),
@@ -1078,9 +1252,9 @@ def train(model, dataset, output_dir, relation_mat=None, mask=None, n_epochs=10,
                         batch = _augment(batch)                     # (run_one_batch's first statement, run_training.py:396)
                     if probe is not None:
                         probe(phase, epoch, ids_local, batch, kw)
-                    if global_tm and not training:
-                        # (the validation pass through the trainer: the global term's collectives sit in its forward, and
-                        # the ranks without data join them -- the module's own forward would leave them waiting)
+                    if (global_tm or sync_bn) and not training:
+                        # (the validation pass through the trainer: the global term's and the BatchNorm exchanges sit in its
+                        # forward, and the ranks without data join them -- the module's own forward would leave them waiting)
                         keys, vals = _device_step(model, optimizer, batch, kw, False, weight)
                         row = dict(zip(keys, vals.tolist()))
                         row.setdefault("time_matching_loss", 0.)

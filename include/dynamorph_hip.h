@@ -390,6 +390,25 @@ int dm_bn_backward_finalize(const double *stats, int nslabs, int C, int64_t coun
                             const float *gamma, const float *saved, float *dgamma, float *dbeta,
                             float *coef_bwd, void *stream);
 
+/* ----- synchronized BatchNorm (data parallel): a layer's statistics as ONE float64 payload the ranks all-reduce (SUM)
+ * between two launches.  The count and the weights are device values, so a graph captured for the local shape replays for
+ * any global batch.  weight: a device double.
+ * dm_bn_sync_pack: payload (2C+1) = weight * [sum x (C), sum x^2 (C), count], the slabs reduced in dm_bn_finalize's order.
+ * dm_bn_finalize_payload: dm_bn_finalize (batch mode) on the reduced payload, the count read from payload[2C]; the running
+ *   variance takes the global count's unbiased factor N / (N - 1) (nn.SyncBatchNorm).
+ * dm_bn_backward_pack: dgamma / dbeta from the local (sum dy, sum dy*a) slabs, payload (2C) = weight * [sum dy, sum dy*a].
+ * dm_bn_backward_payload: dm_bn_backward_finalize's AFFINE2 coefficients from the reduced payload, the batch terms divided by
+ *   weight * N (N = fwd_payload[2C]: the rank's dy is in the scale of its local mean loss; weight 0 -> scale * dy). */
+int dm_bn_sync_pack(const double *stats, int nslabs, int C, int64_t count, const double *weight, double *payload,
+                    void *stream);
+int dm_bn_finalize_payload(const double *payload, int C, const float *gamma, const float *beta, float *running_mean,
+                           float *running_var, int64_t *num_batches_tracked, float momentum, float eps, float *coef,
+                           float *saved, void *stream);
+int dm_bn_backward_pack(const double *stats, int nslabs, int C, const float *saved, const double *weight, float *dgamma,
+                        float *dbeta, double *payload, void *stream);
+int dm_bn_backward_payload(const double *payload, const double *fwd_payload, int C, const float *gamma, const float *saved,
+                           const double *weight, float *coef_bwd, void *stream);
+
 /* out = load(in) [+ resid];  used for h = BN(a) and h' = h + BN(r) (vq_vae.py:224). */
 int dm_apply(const dm_operand *in, const float *resid, float *out, int B, int C, int H, int W, void *stream);
 
