@@ -14,10 +14,16 @@ Two ways to train, same kernels underneath:
     no autograd bookkeeping, no host synchronisation, and the forward+backward launch sequence is
     captured into a HIP graph and replayed (hipGraph instead of a tracing compiler).
 
+    Every route (plain, global time-matching term, extra losses, synchronized BatchNorm) is ONE step body,
+    FusedTrainer._train_body: _forward | _backward_to_latent | _pairwise | _backward_from_latent.  Host work in
+    the middle of the step (a collective, the caller's torch code) is a cut: inline in an eager step, left out
+    in the warm-up, the end of a graph segment in the capture (_Segments).
+
 `run_one_batch` / `train` mirror run_training.py:377-417 / :455-551 (same arguments and loop).
 """
 import contextlib
 import os
+import types
 
 import numpy as np
 import torch
@@ -54,8 +60,8 @@ class FusedTrainer:
         from .vq_vae import VQ_VAE, VQ_VAE_z32
         if not isinstance(model, (VQ_VAE, VQ_VAE_z32)):
             raise TypeError("FusedTrainer is built for VQ_VAE / VQ_VAE_z16 / VQ_VAE_z32; train other modules with a torch optimizer")
-        # (a VQ_VAE_z32 with extra_loss, vae.py:463-469: the caller's torch code runs on z_after between the forward and the
-        # backward half of the step, _step_with_extra_losses; it needs the labels: step(..., labels=...))
+        # (a VQ_VAE_z32 with extra_loss, vae.py:463-469: the caller's torch code runs on z_after in the middle of the step,
+        # _train_body; it needs the labels: step(..., labels=...))
         self._extra = getattr(model, "extra_loss", None) is not None
         if self._extra and not hasattr(model, "alpha"):
             raise AttributeError("FusedTrainer: extra_loss needs model.alpha (vae.py:467; pass alpha= to VQ_VAE_z32)")
@@ -90,8 +96,9 @@ class FusedTrainer:
         if self.sync_bn and self._extra:
             raise ValueError("FusedTrainer: sync_batchnorm is not available together with extra_loss")
         self._bn_w = torch.ones(2, dtype=torch.float64, device=dev)     # [forward weight, gradient weight] of those exchanges
-        self._graphs = {}            # input shapes -> {x, mask, tm: static inputs; train / eval: (graph, static output)}
-        self._static_x = None        # input tensor of the graph replayed last
+        self._graphs = {}            # input shapes -> {inputs: static (x, mask, tm); train / eval: (_Segments, static output)}
+        self._static_x = None        # input tensor of the program replayed last
+        self._labels = None          # the extra losses' labels of the step being taken
         D.broadcast_(self.flat, list(model.buffers()), group=self.group)    # same replica everywhere
 
     # ------------------------------------------------------------------------------------------
@@ -101,6 +108,112 @@ class FusedTrainer:
     def expose_grads(self):
         """Make p.grad point at the flat gradient views (for inspection / torch tooling)."""
         self.fp.expose_grads()
+
+    def latent_numel(self, sample_shape):
+        """Elements of one sample's latent the time-matching term acts on, for samples of shape (C, H, W): z_before (VQ_VAE,
+        VQ_VAE_z16: three stride-2 convolutions) or z_after (VQ_VAE_z32: two)."""
+        f = 4 if self._z32 else 8
+        return int(self.model.num_hiddens) * (int(sample_shape[-2]) // f) * (int(sample_shape[-1]) // f)
+
+    # ------------------------------------------------------------------------------------------ the parts of a step
+    def _forward(self, x, mask, for_backward=True):
+        """The forward of either family: the same kernels as the autograd path (dynamorph_amd.vq_vae) called in order, no
+        autograd bookkeeping.  VQ_VAE / VQ_VAE_z16: encoder (its last residual join in the quantiser's load path,
+        dm_vq_forward_join), VectorQuantizer, decoder -- with for_backward its tail (dec.4, dec.6, loss) runs inside the
+        decoder's backward, fused with it.  VQ_VAE_z32 (vae.py:430-470): two-conv stem + residual stack, VectorQuantizer,
+        residual stack + BatchNorm tail.  Returns the state the other parts read: the finalize arguments (vqs, cx.loss_slabs,
+        n, w) and lat, the (B, n) latents the pairwise term acts on (z_before, vq_vae.py:324-332; z_after for VQ_VAE_z32,
+        vae.py:441-455, whose gradient reaches z through the straight-through value)."""
+        m = self.model
+        B, NIN, H, W = x.shape
+        st = types.SimpleNamespace(cc=float(m.commitment_cost), n=B * NIN * H * W)
+        if self._z32:
+            enc, dec = m.enc, m.dec
+            st.er, st.dr, st.cb, st.w = enc[5]._handles(), dec[0]._handles(), m.vq.w.weight, (1.0, 1.0)
+            h, st.scx = E.z32_stem_forward(enc[0], enc[1], enc[3], enc[4], x)
+            st.z, st.esaved = E.residual_forward(st.er, h)
+            zq, st.idx, st.vqs = E.vq_forward(st.cb, st.z, st.cc, defer_scalars=True)
+            r, st.dsaved = E.residual_forward(st.dr, zq)
+            _, st.cx = E.z32_tail_forward(dec[1], dec[2], dec[4], r, x, mask, m.channel_var)
+            lat = zq
+        else:
+            st.L = L = E.Layers(m)
+            st.cb, st.w = L.codebook.weight, (float(m.weight_recon), float(m.weight_commitment))
+            z, st.ecx = E.encoder_forward(L, x, defer_last_join=st.cb.shape[0] if JOIN_IN_VQ else 0)
+            if z is None:       # the last residual join runs in the quantiser's load path (dm_vq_forward_join), which writes z
+                z, zq, st.idx, st.vqs = E.vq_forward_joined(st.cb, st.ecx.pending_join, st.cc)
+            else:
+                zq, st.idx, st.vqs = E.vq_forward(st.cb, z, st.cc, defer_scalars=True)
+            _, st.cx = E.decoder_forward(L, zq, x, mask, defer_tail=for_backward)
+            st.z = lat = z
+        st.lat = lat.reshape(B, -1)
+        return st
+
+    def _backward_to_latent(self, st):
+        """The gradient at st.lat (shaped like the latent): the decoder's backward and, for VQ_VAE / VQ_VAE_z16, the
+        quantiser's straight-through backward.  The slabs of every weight / bias / codebook gradient collect in st.pending."""
+        m, st.pending = self.model, []
+        if self._z32:
+            dec = m.dec
+            g_r = E.z32_tail_backward(dec[1], dec[2], dec[4], st.cx, self.w_recon, None, self.G, pending=st.pending,
+                                      zero_fed_biases=False)
+            g_zq, _ = E.residual_backward(st.dr, st.dsaved, g_r, self.G, None, pending=st.pending, zero_fed_biases=False)
+            return g_zq
+        g_zq = E.decoder_backward(st.L, st.cx, self.w_recon, None, self.G, pending=st.pending)
+        # codebook gradient as slabs, added in the encoder's single slab reduction: nothing to zero, no global atomics
+        # (K <= 64: an ordered one-hot product on the matrix cores, bit-reproducible; larger K: LDS adds in arrival order)
+        dz, cb_slabs = ops.vq_backward_slabs(st.z, st.cb.detach(), st.idx, g_zq, self.w_commit, st.cc)
+        st.pending.insert(0, (cb_slabs, self.G(st.cb)))
+        return dz
+
+    def _backward_from_latent(self, st, g):
+        """From the gradient at the latent: the rest of the backward (VQ_VAE_z32: the quantiser's straight-through backward,
+        then the encoder) and ONE slab reduction for every weight / bias / codebook gradient of the step.  The flat gradient
+        buffer starts at zero and nothing ever writes the BatchNorm-fed conv biases' slots (zero_fed_biases=False)."""
+        if not self._z32:
+            E.encoder_backward(st.L, st.ecx, g, self.G, zero_fed_biases=False, pending_extra=st.pending)
+            return
+        enc = self.model.enc
+        dz, cb_slabs = ops.vq_backward_slabs(st.z, st.cb.detach(), st.idx, g, self.w_commit, st.cc)
+        st.pending.append((cb_slabs, self.G(st.cb)))
+        g_h, stats = E.residual_backward(st.er, st.esaved, dz, self.G, st.scx.a2, pending=st.pending, zero_fed_biases=False)
+        E.z32_stem_backward(enc[0], enc[1], enc[3], enc[4], st.scx, g_h, self.G, stats=stats, pending=st.pending,
+                            zero_fed_biases=False)
+        ops.reduce_slabs_multi(st.pending)
+
+    def _pairwise(self, st, tm, g=None, zg=None):
+        """The pass's scalars (recon, commitment, total, perplexity[, time matching]) with the pairwise term on st.lat (tm: the
+        relation block, None: no term); when training (g: the gradient at the latent) also g plus the term's gradient,
+        summed in the kernel's store.  Returns (scalars, g, part):
+          * local, latent lengths the MFMA kernels tile: the term's slabs finalized with the other scalars in one launch;
+          * local, other lengths: distances from dm_pair_msd, the B x B weighting in torch (_time_matching);
+          * global (zg: the gathered (Bg, n) latents of the whole batch): this rank's rows -- rows r0 .. r0 + B - 1 of zg --
+            against every sample; the scalars leave the term out and part is the rows' share (float64, 1 element), which
+            _with_global sums over the ranks."""
+        m = self.model
+        fin = (st.vqs.slabs, st.vqs.ws, st.vqs.K, st.vqs.D, st.vqs.positions, st.vqs.cc, st.cx.loss_slabs, st.n) + st.w
+        if tm is None:
+            return ops.vq_loss_finalize(*fin), g, None
+        B, n = st.lat.shape
+        wm, args = float(m.weight_matching), _tm_args(m, self._z32)
+        tm = tm.to(torch.float32).contiguous()
+        if zg is not None:
+            r0, _ = D.shard_range(zg.shape[0], D.get_rank(self.group), self.world)
+            part, S = ops.time_matching_forward_rows(zg, tm, r0, B, *args)
+            if g is not None:
+                # the bucket is multiplied by grad_weight = B * world / Bg before the exchange and by 1 / world in Adam's
+                # load: the rows' gradient carries world / grad_weight (self._tm_gscale), so what arrives is the global term's
+                g = ops.time_matching_backward_rows(zg, S, self._tm_gscale, wm, add=g).reshape(g.shape)
+            return ops.vq_loss_finalize(*fin), g, part
+        if ops.time_matching_supported(B, n):
+            tm_slabs, S = ops.time_matching_forward(st.lat, tm, *args, want_slabs=True)
+            if g is not None:
+                g = ops.time_matching_backward(st.lat, S, None, wm, add=g).reshape(g.shape)
+            return ops.vq_loss_finalize_tm(*fin, tm_slabs, wm), g, None
+        tml, g_sim = self._time_matching(ops.pair_msd(st.lat), tm, args[0] == 1)
+        if g is not None:
+            g = g + ops.pair_msd_backward(st.lat, (g_sim * wm).contiguous()).reshape(g.shape)
+        return _with_matching(ops.vq_loss_finalize(*fin), tml, wm), g, None
 
     def _time_matching(self, sim, tm, z16_form=None):
         """(loss, d loss / d sim) of the pairwise term on the (B, B) matrix of mean-squared latent distances:
@@ -120,304 +233,77 @@ class FusedTrainer:
         val = torch.where(hinge, torch.clamp(val + model.margin, min=0), val)
         return val.mean(), wts * live / float(sim.numel())
 
-    def _z32_forward_part(self, x, mask, tm):
-        """VQ_VAE_z32 (vae.py:430-470), forward half of the step: two-conv stem + residual stack | VectorQuantizer | residual
-        stack + BatchNorm tail, the weighted-hinge time-matching term on z_after.  Same kernels as the autograd path
-        (dynamorph_amd.vq_vae), called in order: no autograd bookkeeping -- and a launch sequence a HIP graph can replay.
-        Returns the state the backward half reads (st.scalars: recon, commitment, total, perplexity[, time matching];
-        st.zq: z_after, what a caller-supplied extra loss acts on, vae.py:463-469)."""
-        import types
-        m = self.model
-        enc, dec = m.enc, m.dec
-        st = types.SimpleNamespace(er=enc[5]._handles(), dr=dec[0]._handles(), cc=float(m.commitment_cost))
-        B, NIN, H, W = x.shape
-        h, st.scx = E.z32_stem_forward(enc[0], enc[1], enc[3], enc[4], x)
-        st.z, st.esaved = E.residual_forward(st.er, h)
-        st.zq, st.idx, vqs = E.vq_forward(m.vq.w.weight, st.z, st.cc, defer_scalars=True)
-        r, st.dsaved = E.residual_forward(st.dr, st.zq)
-        _, st.tcx = E.z32_tail_forward(dec[1], dec[2], dec[4], r, x, mask, m.channel_var)
-        # the pairwise term acts on z_after (vae.py:441-455); its gradient reaches z through the straight-through value
-        st.tm_S = st.tm_fallback = st.zf = None
-        st.wm = float(m.weight_matching)
-        fin = (vqs.slabs, vqs.ws, vqs.K, vqs.D, vqs.positions, vqs.cc, st.tcx.loss_slabs, B * NIN * H * W, 1.0, 1.0)
-        if tm is not None:
-            st.zf = st.zq.reshape(B, -1)
-            tmf = tm.to(torch.float32).contiguous()
-            if ops.time_matching_supported(st.zf.shape[0], st.zf.shape[1]):
-                tm_slabs, st.tm_S = ops.time_matching_forward(st.zf, tmf, *_tm_args(m, True), want_slabs=True)
-                st.scalars = ops.vq_loss_finalize_tm(*fin, tm_slabs, st.wm)        # the five scalars in one launch
-            else:
-                tml, g_sim = self._time_matching(ops.pair_msd(st.zf), tmf, True)      # (VQ_VAE_z32: always the weighted-hinge form)
-                st.tm_fallback = ops.pair_msd_backward(st.zf, (g_sim * st.wm).contiguous()).reshape(st.zq.shape)
-                st.scalars = _with_matching(ops.vq_loss_finalize(*fin), tml, st.wm)
-        else:
-            st.scalars = ops.vq_loss_finalize(*fin)
-        return st
-
-    def _z32_backward_part(self, st, g_extra=None):
-        """Backward half: decoder tail, decoder residual stack, the time-matching and (g_extra: d(sum of alpha * extra
-        losses) / d z_after, from the caller's torch code) extra-loss gradients joining at z_after, the quantiser's
-        straight-through backward, encoder -- ONE slab reduction for every weight / bias / codebook gradient."""
-        g_zq, pending = self._z32_decoder_backward(st)
-        if st.tm_S is not None:
-            g_zq = ops.time_matching_backward(st.zf, st.tm_S, None, st.wm, add=g_zq).reshape(st.zq.shape)     # (summed in the kernel's store)
-        elif st.tm_fallback is not None:
-            g_zq = g_zq + st.tm_fallback
-        if g_extra is not None:
-            g_zq = g_zq + g_extra
-        return self._z32_encoder_backward(st, g_zq, pending)
-
-    def _z32_decoder_backward(self, st):
-        """Decoder tail and decoder residual stack of the backward half: (d loss / d z_after, the pending slab reductions)."""
-        m = self.model
-        dec = m.dec
-        pending = []
-        g_r = E.z32_tail_backward(dec[1], dec[2], dec[4], st.tcx, self.w_recon, None, self.G, pending=pending,
-                                  zero_fed_biases=False)
-        g_zq, _ = E.residual_backward(st.dr, st.dsaved, g_r, self.G, None, pending=pending, zero_fed_biases=False)
-        return g_zq, pending
-
-    def _z32_encoder_backward(self, st, g_zq, pending):
-        """From the gradient at z_after: the quantiser's straight-through backward, the encoder, ONE slab reduction."""
-        m = self.model
-        enc = m.enc
-        gcb = self.G(m.vq.w.weight)
-        dz, cb_slabs = ops.vq_backward_slabs(st.z, m.vq.w.weight.detach(), st.idx, g_zq, self.w_commit, st.cc)
-        pending.append((cb_slabs, gcb))
-        g_h, stats = E.residual_backward(st.er, st.esaved, dz, self.G, st.scx.a2, pending=pending, zero_fed_biases=False)
-        E.z32_stem_backward(enc[0], enc[1], enc[3], enc[4], st.scx, g_h, self.G, stats=stats, pending=pending,
-                            zero_fed_biases=False)
-        ops.reduce_slabs_multi(pending)                     # every weight / bias / codebook gradient of the step
-        return st.scalars
-
-    def _forward_backward_z32(self, x, mask, tm):
-        return self._z32_backward_part(self._z32_forward_part(x, mask, tm))
-
-    def _extra_losses(self, zq, labels):
-        """The caller's extra losses (vae.py:463-469) on z_after, as torch code between the two halves of the step:
-        returns (sum of alpha * loss as a device scalar, its gradient w.r.t. z_after, {name: loss})."""
+    def _extra_losses(self, zq, out=None):
+        """The caller's extra losses (vae.py:463-469) on z_after, as torch code in the middle of the step, with the step's
+        labels (self._labels): returns d(sum of alpha * loss) / d z_after (written into out when given); the sum as a device
+        scalar in self._extra_total, {name: loss} in self.last_extra_losses."""
         m = self.model
         leaf = zq.detach().requires_grad_(True)
         flat = leaf.reshape((leaf.shape[0], -1))
         total, named = None, {}
         with torch.enable_grad():
             for name, fn in m.extra_loss.items():
-                loss, _frac_pos = fn(labels, flat)
+                loss, _frac_pos = fn(self._labels, flat)
                 named[name] = loss.detach()
                 total = loss * m.alpha if total is None else total + loss * m.alpha
             total.backward()
-        g = leaf.grad if leaf.grad is not None else torch.zeros_like(leaf)
-        return total.detach(), g.contiguous(), named
+        self._extra_total, self.last_extra_losses = total.detach(), named
+        g = (leaf.grad if leaf.grad is not None else torch.zeros_like(leaf)).contiguous()
+        return g if out is None else out.copy_(g)
 
-    def _step_with_extra_losses(self, x, mask, tm, labels):
-        """One forward + backward of a VQ_VAE_z32 with extra_loss: the two halves as captured HIP graphs (one pair per input
-        shape), the caller's torch code on z_after in between.  Returns the step's scalars with total_loss including the
-        extra terms; self.last_extra_losses = {name: device scalar}."""
-        if not self.use_graph:
-            st = self._z32_forward_part(x, mask, tm)
-            total, g, named = self._extra_losses(st.zq, labels)
-            scal = self._z32_backward_part(st, g)
-        else:
-            key = ("extra", tuple(x.shape), None if mask is None else tuple(mask.shape), None if tm is None else tuple(tm.shape))
-            ent = self._graphs.get(key)
-            if ent is None:
-                sx = x.clone()
-                smask = mask.clone() if mask is not None else None
-                stm = tm.clone().float() if tm is not None else None
-                bufs = list(self.model.buffers())
-                saved = [b.clone() for b in bufs]
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):                              # warm-up (allocator, lazy init): really executes
-                    st = self._z32_forward_part(sx, smask, stm)
-                    self._z32_backward_part(st, torch.zeros_like(st.zq))
-                torch.cuda.current_stream().wait_stream(side)
-                for b, sv in zip(bufs, saved):
-                    b.copy_(sv)                                            # ... so the running statistics are put back
-                if self.world > 1:
-                    torch.cuda.synchronize(self.flat.device)
-                gF = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gF):
-                    st = self._z32_forward_part(sx, smask, stm)
-                gx = torch.zeros_like(st.zq)
-                gB = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gB, pool=gF.pool()):
-                    scal = self._z32_backward_part(st, gx)
-                ent = self._graphs[key] = (gF, gB, st, gx, scal, sx, smask, stm)
-            gF, gB, st, gx, scal, sx, smask, stm = ent
-            if x.data_ptr() != sx.data_ptr():
-                sx.copy_(x)
-            if mask is not None:
-                smask.copy_(mask)
-            if tm is not None:
-                stm.copy_(tm)
-            gF.replay()
-            total, g, named = self._extra_losses(st.zq, labels)
-            gx.copy_(g)
-            gB.replay()
-        self.last_extra_losses = named
-        out = scal.clone()
-        out[2] += total                                                    # total_loss += alpha * extra (vae.py:467)
-        return out
+    def _bn_context(self, cut):
+        """With sync_batchnorm: every BatchNorm exchange of the launches enqueued inside is an all-reduce behind cut."""
+        return E.bn_sync(E.BnSync(self._bn_w, lambda payload: cut(lambda _: D.allreduce_payload_(payload, self.group)))
+                         if self.sync_bn else None)
+
+    def _train_body(self, x, mask, tm, cut):
+        """One forward + backward on this trainer's route.  Host work in the middle of the step sits behind cut(action,
+        shape) -- the gather of the latents for the global term, the caller's extra losses, each BatchNorm exchange with
+        sync_batchnorm -- so the same body is the eager step (_inline), the warm-up (_skip) and the capture (_Segments.cut).
+        Returns (scalars, the rows' share of the global term or None)."""
+        with self._bn_context(cut):
+            st = self._forward(x, mask)
+            g = self._backward_to_latent(st)
+            zg = None
+            if self.global_tm and tm is not None:
+                Bg = tm.shape[0]
+                zg = cut(lambda out: D.all_gather_rows(st.lat, Bg, self.group, out=out), (Bg, st.lat.shape[1]))
+            scalars, g, part = self._pairwise(st, tm, g, zg)
+            if self._extra:
+                shape = g.shape
+                g = g + cut(lambda out: self._extra_losses(st.lat.view(shape), out), shape)
+            self._backward_from_latent(st, g)
+        return scalars, part
 
     def forward_backward(self, x, mask=None, time_matching_mat=None):
-        """One forward + backward; returns the device tensor (recon, commitment, total, perplexity[, time matching])."""
-        if self._z32:
-            return self._forward_backward_z32(x, mask, time_matching_mat)
-        model = self.model
-        L = E.Layers(model)
-        cc = float(model.commitment_cost)
-        z, ecx = E.encoder_forward(L, x, defer_last_join=L.codebook.weight.shape[0] if JOIN_IN_VQ else 0)
-        if z is None:       # the last residual join runs in the quantiser's load path (dm_vq_forward_join), which writes z
-            z, zq, idx, vqs = E.vq_forward_joined(L.codebook.weight, ecx.pending_join, cc)
-        else:
-            zq, idx, vqs = E.vq_forward(L.codebook.weight, z, cc, defer_scalars=True)
-        # the tail of the decoder (dec.4, dec.6, loss) runs inside decoder_backward, fused with its own backward
-        dec, dcx = E.decoder_forward(L, zq, x, mask, defer_tail=True)
-        B, NIN, H, W = x.shape
-        dec_pending = []                 # the decoder's slabs ride in the encoder's single reduction at the end of the pass
-        g_zq = E.decoder_backward(L, dcx, self.w_recon, None, self.G, pending=dec_pending)
-        # (recon, commitment, total, perplexity[, time matching]): the VectorQuantizer's scalars, the reconstruction loss and
-        # the pairwise term on z_before (vq_vae.py:324-332) in one launch
-        fin = (vqs.slabs, vqs.ws, vqs.K, vqs.D, vqs.positions, vqs.cc, dcx.loss_slabs, B * NIN * H * W,
-               float(model.weight_recon), float(model.weight_commitment))
-        tm_S = tm_fallback = None
-        if time_matching_mat is not None:
-            zf = z.reshape(B, -1)
-            wm = float(model.weight_matching)
-            tm = time_matching_mat.to(torch.float32).contiguous()
-            if ops.time_matching_supported(zf.shape[0], zf.shape[1]):
-                tm_slabs, tm_S = ops.time_matching_forward(zf, tm, *_tm_args(model), want_slabs=True)
-                scalars = ops.vq_loss_finalize_tm(*fin, tm_slabs, wm)
-            else:       # latent lengths the MFMA kernels do not tile: distances from dm_pair_msd, the B x B weighting in torch
-                tml, g_sim = self._time_matching(ops.pair_msd(zf), tm)
-                tm_fallback = ops.pair_msd_backward(zf, (g_sim * wm).contiguous()).reshape(z.shape)
-                scalars = _with_matching(ops.vq_loss_finalize(*fin), tml, wm)
-        else:
-            scalars = ops.vq_loss_finalize(*fin)
-        gcb = self.G(L.codebook.weight)
-        # codebook gradient as slabs, added in the encoder's single slab reduction: nothing to zero, no global atomics
-        # (K <= 64: an ordered one-hot product on the matrix cores, bit-reproducible; larger K: LDS adds in arrival order)
-        dz, cb_slabs = ops.vq_backward_slabs(z, L.codebook.weight.detach(), idx, g_zq, self.w_commit, cc)
-        extra = [(cb_slabs, gcb)] + dec_pending
-        if tm_S is not None:
-            dz = ops.time_matching_backward(zf, tm_S, None, wm, add=dz).reshape(z.shape)      # (summed in the kernel's store)
-        elif tm_fallback is not None:
-            dz = dz + tm_fallback
-        # the flat gradient buffer starts at zero and nothing ever writes the BatchNorm-fed conv biases' slots
-        E.encoder_backward(L, ecx, dz, self.G, zero_fed_biases=False, pending_extra=extra)
+        """One forward + backward of the rank's own shard (no collective, no extra losses); returns the device tensor
+        (recon, commitment, total, perplexity[, time matching])."""
+        st = self._forward(x, mask)
+        scalars, g, _ = self._pairwise(st, time_matching_mat, self._backward_to_latent(st))
+        self._backward_from_latent(st, g)
         return scalars
 
-    # ------------------------------------------------------------------------------------------ global_time_matching
-    def latent_numel(self, sample_shape):
-        """Elements of one sample's latent the time-matching term acts on, for samples of shape (C, H, W): z_before (VQ_VAE,
-        VQ_VAE_z16: three stride-2 convolutions) or z_after (VQ_VAE_z32: two)."""
-        f = 4 if self._z32 else 8
-        return int(self.model.num_hiddens) * (int(sample_shape[-2]) // f) * (int(sample_shape[-1]) // f)
+    def forward_only(self, x, mask=None, time_matching_mat=None):
+        """The validation pass (run_training.py:522-531: forward with the module left in train mode, so BatchNorm uses
+        batch statistics and advances its running statistics; no backward, no step).  Same kernels as forward_backward;
+        returns the same device tensor (recon, commitment, total, perplexity[, time matching])."""
+        tm = time_matching_mat
+        st = self._forward(x, mask, for_backward=False)
+        zg = D.all_gather_rows(st.lat, tm.shape[0], self.group) if self.global_tm and tm is not None else None
+        scalars, _, part = self._pairwise(st, tm, zg=zg)
+        return self._with_global(scalars, part)
 
-    def _global_first(self, x, mask):
-        """First half of a global_time_matching step: everything that needs no other rank's latents -- the forward, the
-        decoder's backward and (VQ_VAE / VQ_VAE_z16) the quantiser's backward.  st.lat: the (B, n) latents the term acts on;
-        st.scalars: (recon, commitment, total without the term, perplexity)."""
-        import types
-        if self._z32:
-            st = self._z32_forward_part(x, mask, None)
-            st.g_zq, st.pending = self._z32_decoder_backward(st)
-            st.lat = st.zq.reshape(st.zq.shape[0], -1)
-            return st
-        model = self.model
-        L = E.Layers(model)
-        cc = float(model.commitment_cost)
-        z, ecx = E.encoder_forward(L, x, defer_last_join=L.codebook.weight.shape[0] if JOIN_IN_VQ else 0)
-        if z is None:
-            z, zq, idx, vqs = E.vq_forward_joined(L.codebook.weight, ecx.pending_join, cc)
-        else:
-            zq, idx, vqs = E.vq_forward(L.codebook.weight, z, cc, defer_scalars=True)
-        _, dcx = E.decoder_forward(L, zq, x, mask, defer_tail=True)
-        B, NIN, H, W = x.shape
-        dec_pending = []
-        g_zq = E.decoder_backward(L, dcx, self.w_recon, None, self.G, pending=dec_pending)
-        scalars = ops.vq_loss_finalize(vqs.slabs, vqs.ws, vqs.K, vqs.D, vqs.positions, vqs.cc, dcx.loss_slabs, B * NIN * H * W,
-                                       float(model.weight_recon), float(model.weight_commitment))
-        gcb = self.G(L.codebook.weight)
-        dz, cb_slabs = ops.vq_backward_slabs(z, L.codebook.weight.detach(), idx, g_zq, self.w_commit, cc)
-        return types.SimpleNamespace(L=L, ecx=ecx, z=z, dz=dz, extra=[(cb_slabs, gcb)] + dec_pending, scalars=scalars,
-                                     lat=z.reshape(B, -1))
-
-    def _global_second(self, st, zg, tm):
-        """Second half: this rank's rows of the global term (its latents are rows r0 .. r0 + B - 1 of the gathered zg), their
-        gradient summed into the quantiser's (z32: the decoder's) in the kernel's store, the encoder's backward, the slab
-        reductions.  Returns the rows' share of the term (float64, 1 element)."""
-        B, Bg = st.lat.shape[0], zg.shape[0]
-        r0, _ = D.shard_range(Bg, D.get_rank(self.group), self.world)
-        part, S = ops.time_matching_forward_rows(zg, tm, r0, B, *_tm_args(self.model, self._z32))
-        wm = float(self.model.weight_matching)
-        # the bucket is multiplied by grad_weight = B * world / Bg before the exchange and by 1 / world in Adam's load: the
-        # rows' gradient carries world / grad_weight (self._tm_gscale), so what arrives is the global term's gradient
-        if self._z32:
-            g = ops.time_matching_backward_rows(zg, S, self._tm_gscale, wm, add=st.g_zq).reshape(st.zq.shape)
-            self._z32_encoder_backward(st, g, st.pending)
-        else:
-            dz = ops.time_matching_backward_rows(zg, S, self._tm_gscale, wm, add=st.dz).reshape(st.z.shape)
-            E.encoder_backward(st.L, st.ecx, dz, self.G, zero_fed_biases=False, pending_extra=st.extra)
-        return part
-
+    # ------------------------------------------------------------------------------------------ collectives
     def _global_total(self, part):
         """Sum over ranks of the rows' shares: the global-batch value of the term on every rank (ONE 8-byte all-reduce)."""
         tot = part.clone()
         torch.distributed.all_reduce(tot, op=torch.distributed.ReduceOp.SUM, group=self.group)
         return tot
 
-    def _global_step(self, x, mask, tm, grad_weight):
-        """One forward + backward with the global time-matching term: first half | all-gather of the latents | second half
-        (with use_graph: two captured HIP graphs, the collective between their replays) | the 8-byte all-reduce of the term.
-        Returns the five scalars with the global term (and total_loss built from it)."""
-        Bg = tm.shape[0]
-        lo, hi = D.shard_range(Bg, D.get_rank(self.group), self.world)
-        if hi - lo != x.shape[0]:
-            raise ValueError(f"FusedTrainer: global_time_matching needs the ({Bg}, {Bg}) relation block of the global batch "
-                             f"whose shard this rank's {x.shape[0]} samples are")
-        self._tm_gscale.fill_(self.world / float(grad_weight))
-        if not self.use_graph:
-            st = self._global_first(x, mask)
-            zg = D.all_gather_rows(st.lat, Bg, self.group)
-            part = self._global_second(st, zg, tm.to(torch.float32).contiguous())
-        else:
-            key = ("global", tuple(x.shape), None if mask is None else tuple(mask.shape), tuple(tm.shape))
-            ent = self._graphs.get(key)
-            if ent is None:
-                sx = x.clone()
-                smask = mask.clone() if mask is not None else None
-                stm = tm.clone().float()
-                bufs = list(self.model.buffers())
-                saved = [b.clone() for b in bufs]
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):                              # warm-up (allocator, lazy init): really executes
-                    st = self._global_first(sx, smask)
-                    self._global_second(st, torch.zeros((Bg, st.lat.shape[1]), device=sx.device), stm)
-                torch.cuda.current_stream().wait_stream(side)
-                for b, sv in zip(bufs, saved):
-                    b.copy_(sv)                                            # ... so the running statistics are put back
-                torch.cuda.synchronize(self.flat.device)                   # (no collective in flight during a capture)
-                gF = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gF):
-                    st = self._global_first(sx, smask)
-                szg = torch.zeros((Bg, st.lat.shape[1]), device=sx.device)
-                gB = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gB, pool=gF.pool()):
-                    part = self._global_second(st, szg, stm)
-                ent = self._graphs[key] = (gF, gB, st, szg, part, sx, smask, stm)
-            gF, gB, st, szg, part, sx, smask, stm = ent
-            if x.data_ptr() != sx.data_ptr():
-                sx.copy_(x)
-            if mask is not None:
-                smask.copy_(mask)
-            stm.copy_(tm)
-            gF.replay()
-            D.all_gather_rows(st.lat, Bg, self.group, out=szg)
-            gB.replay()
-        return _with_matching(st.scalars, self._global_total(part).float(), float(self.model.weight_matching))
+    def _with_global(self, scalars, part):
+        if part is None:
+            return scalars
+        return _with_matching(scalars, self._global_total(part).float(), float(self.model.weight_matching))
 
     def _join_without_data(self, global_rows):
         """A rank with an empty shard in a global_time_matching step: it still takes part in the gather of the latents and
@@ -425,82 +311,6 @@ class FusedTrainer:
         Bg, n = global_rows
         D.all_gather_rows(torch.empty((0, n), device=self.flat.device), Bg, self.group)
         self._global_total(torch.zeros(1, dtype=torch.float64, device=self.flat.device))
-
-    # ------------------------------------------------------------------------------------------ sync_batchnorm
-    def _bn_ctx(self, exchange):
-        return E.bn_sync(E.BnSync(self._bn_w, exchange))
-
-    def _exchange_now(self, payload):
-        D.allreduce_payload_(payload, self.group)
-
-    def _sync_body(self, x, mask, tm, glob, gather):
-        """The step's launches with the BatchNorm exchanges routed through the active context; glob: the global
-        time-matching step, gather(st) -> the (Bg, n) latents of the whole batch.  Returns (scalars, the rows' share of the
-        term or None)."""
-        if not glob:
-            return self.forward_backward(x, mask, tm), None
-        st = self._global_first(x, mask)
-        part = self._global_second(st, gather(st), tm)
-        return st.scalars, part
-
-    def _sync_step(self, x, mask, tm, grad_weight, replay=True):
-        """One forward + backward with sync_batchnorm (world > 1).  Eagerly (use_graph=False) every exchange runs inline.
-        With graphs the step is captured once per input shape as segments cut at the exchanges (_Segments): a replay is
-        seg0 | all-reduce | seg1 | ... | segK, the collectives between the replays.  With global_time_matching and a relation
-        block the gather of the latents is one more cut.  Returns the step's scalars (global term included)."""
-        glob = self.global_tm and tm is not None
-        if glob:
-            Bg = tm.shape[0]
-            lo, hi = D.shard_range(Bg, D.get_rank(self.group), self.world)
-            if hi - lo != x.shape[0]:
-                raise ValueError(f"FusedTrainer: global_time_matching needs the ({Bg}, {Bg}) relation block of the global "
-                                 f"batch whose shard this rank's {x.shape[0]} samples are")
-            self._tm_gscale.fill_(self.world / float(grad_weight))
-        self._bn_w[0].fill_(1.0)
-        self._bn_w[1].fill_(float(grad_weight))
-        if not self.use_graph:
-            with self._bn_ctx(self._exchange_now):
-                scal, part = self._sync_body(x, mask, tm.to(torch.float32).contiguous() if glob else tm, glob,
-                                             lambda st: D.all_gather_rows(st.lat, Bg, self.group))
-        else:
-            sx, smask, stm = self.static_inputs(x.shape, None if mask is None else mask.shape, None if tm is None else tm.shape)
-            if x.data_ptr() != sx.data_ptr():
-                sx.copy_(x)
-            if mask is not None and mask.data_ptr() != smask.data_ptr():
-                smask.copy_(mask)
-            if tm is not None and tm.data_ptr() != stm.data_ptr():
-                stm.copy_(tm)
-            ent = self._graphs[(tuple(x.shape), None if mask is None else tuple(mask.shape), None if tm is None else tuple(tm.shape))]
-            if ent.get("sync") is None:
-                # warm-up (allocator, lazy init) with the collectives left out: ranks may capture at different steps (a
-                # ragged shard's shape), so nothing here may wait for another rank.  Its BatchNorm side effects are put back.
-                bufs = list(self.model.buffers())
-                saved = [b.clone() for b in bufs]
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side), self._bn_ctx(lambda payload: None):
-                    self._sync_body(sx, smask, stm, glob, lambda st: torch.zeros((Bg, st.lat.shape[1]), device=sx.device))
-                torch.cuda.current_stream().wait_stream(side)
-                for b, sv in zip(bufs, saved):
-                    b.copy_(sv)
-                segs = _Segments()
-
-                def gather(st):
-                    zg = torch.empty((Bg, st.lat.shape[1]), device=sx.device)
-                    segs.cut(lambda: D.all_gather_rows(st.lat, Bg, self.group, out=zg))
-                    return zg
-                exchange = lambda payload: segs.cut(lambda: D.allreduce_payload_(payload, self.group))     # noqa: E731
-                with segs.capture(), self._bn_ctx(exchange):
-                    out = self._sync_body(sx, smask, stm, glob, gather)
-                ent["sync"] = (segs, out)
-            self._static_x = sx
-            segs, (scal, part) = ent["sync"]
-            if not replay:
-                return None
-            segs.replay()
-        if glob:
-            return _with_matching(scal, self._global_total(part).float(), float(self.model.weight_matching))
-        return scal
 
     def _bn_without_data(self, sample_shape, global_rows, training):
         """A rank whose shard is empty in a sync_batchnorm step (training) or validation pass: it runs the pass on one zero
@@ -510,23 +320,20 @@ class FusedTrainer:
         if sample_shape is None:
             raise ValueError("FusedTrainer: with sync_batchnorm a rank without data needs sample_shape to join the exchanges")
         x = torch.zeros((1,) + tuple(sample_shape), device=self.flat.device)
-        dev = self.flat.device
         self._bn_w.zero_()
-        with self._bn_ctx(self._exchange_now):
+        with self._bn_context(_inline):
             if not training:
                 self.forward_only(x)
-            elif global_rows is None:
-                self.forward_backward(x)
             else:
-                st = self._global_first(x, None)
-                D.all_gather_rows(torch.empty((0, global_rows[1]), device=dev), global_rows[0], self.group)
-                if self._z32:
-                    self._z32_encoder_backward(st, st.g_zq, st.pending)
-                else:
-                    E.encoder_backward(st.L, st.ecx, st.dz, self.G, zero_fed_biases=False, pending_extra=st.extra)
+                st = self._forward(x, None)
+                g = self._backward_to_latent(st)
+                if global_rows is not None:
+                    D.all_gather_rows(torch.empty((0, global_rows[1]), device=x.device), global_rows[0], self.group)
+                self._pairwise(st, None)
+                self._backward_from_latent(st, g)
         if global_rows is not None:
             if training:
-                self._global_total(torch.zeros(1, dtype=torch.float64, device=dev))
+                self._global_total(torch.zeros(1, dtype=torch.float64, device=x.device))
             else:
                 self._join_without_data(global_rows)
 
@@ -548,6 +355,40 @@ class FusedTrainer:
                          self.step_dev[a:a + 1], self.step_dev[b:b + 1], grad_scale=1.0 / self.world)
         self._step_slot = b
 
+    # ------------------------------------------------------------------------------------------ public steps
+    def _fwd_bwd(self, x, mask, tm, grad_weight=1.0, labels=None, replay=True):
+        """One forward + backward on this trainer's route: eagerly, or as the captured program of the input shape (with
+        replay=False: only captured).  Returns the step's scalars -- with the global term summed over the ranks, with
+        alpha * extra losses in total_loss (vae.py:467)."""
+        if self.global_tm and tm is not None:
+            Bg = tm.shape[0]
+            lo, hi = D.shard_range(Bg, D.get_rank(self.group), self.world)
+            if hi - lo != x.shape[0]:
+                raise ValueError(f"FusedTrainer: global_time_matching needs the ({Bg}, {Bg}) relation block of the global "
+                                 f"batch whose shard this rank's {x.shape[0]} samples are")
+            self._tm_gscale.fill_(self.world / float(grad_weight))
+        if self.sync_bn:
+            self._bn_w[0].fill_(1.0)
+            self._bn_w[1].fill_(float(grad_weight))
+        self._labels = labels
+        if not self.use_graph:
+            scalars, part = self._train_body(x, mask, tm, _inline)
+        else:
+            segs, (scalars, part) = self._program("train", x, mask, tm)
+            if not replay:
+                return None
+            segs.replay()
+        scalars = self._with_global(scalars, part)
+        if self._extra:
+            scalars = scalars.clone()
+            scalars[2] += self._extra_total
+        return scalars
+
+    def _step_with_extra_losses(self, x, mask, tm, labels):
+        """The forward + backward of a VQ_VAE_z32 with extra_loss, without the exchange and Adam: the scalars with
+        total_loss including the extra terms; self.last_extra_losses = {name: device scalar}."""
+        return self._fwd_bwd(x, mask, tm, labels=labels)
+
     def step_without_data(self, global_rows=None, sample_shape=None):
         """This rank's shard of a ragged global batch is empty: it contributes a zero gradient to the exchange and takes
         the same Adam step as the others.  global_rows = (Bg, latent elements per sample) when the other ranks take a
@@ -564,7 +405,7 @@ class FusedTrainer:
 
     def step(self, x, mask=None, time_matching_mat=None, grad_weight=1.0, timers=None, labels=None):
         """One optimisation step on a device batch; returns the device tensor of LOSS_KEYS values (+ the time-matching
-        loss as a fifth entry when a matrix is given).  grad_weight: see _allreduce.
+        loss as a fifth entry when a matrix is given).  grad_weight: see _allreduce.  labels: the extra losses' (extra_loss).
         timers: a list -> this step appends (events, host_times): four events on the launch stream and four
         time.perf_counter() readings around its three parts (forward+backward | gradient exchange | Adam); read them with
         FusedTrainer.timer_summary after a synchronize.  Measurement only: the default path records nothing."""
@@ -576,16 +417,7 @@ class FusedTrainer:
         with torch.cuda.device(self.flat.device):       # graph capture / replay and the streams are the model's device's
             mark = _Marks() if timers is not None else None
             if mark: mark()
-            if self._extra:
-                out = self._step_with_extra_losses(x, mask, time_matching_mat, labels)
-            elif self.sync_bn:
-                out = self._sync_step(x, mask, time_matching_mat, grad_weight)
-            elif self.global_tm and time_matching_mat is not None:
-                out = self._global_step(x, mask, time_matching_mat, grad_weight)
-            elif not self.use_graph:
-                out = self.forward_backward(x, mask, time_matching_mat)
-            else:
-                out = self._graph_step(x, mask, time_matching_mat)
+            out = self._fwd_bwd(x, mask, time_matching_mat, grad_weight, labels)
             if mark: mark()
             self._allreduce(grad_weight)
             if mark: mark()
@@ -619,131 +451,88 @@ class FusedTrainer:
             with torch.cuda.device(self.flat.device):
                 self._join_without_data(global_rows)
 
-    def forward_only(self, x, mask=None, time_matching_mat=None):
-        """The validation pass (run_training.py:522-531: forward with the module left in train mode, so BatchNorm uses
-        batch statistics and advances its running statistics; no backward, no step).  Same kernels as forward_backward;
-        returns the same device tensor (recon, commitment, total, perplexity[, time matching])."""
-        m, tm = self.model, time_matching_mat
-        B, NIN, H, W = x.shape
-        cc = float(m.commitment_cost)
-        if self._z32:
-            enc, dec = m.enc, m.dec
-            h, _ = E.z32_stem_forward(enc[0], enc[1], enc[3], enc[4], x)
-            z, _ = E.residual_forward(enc[5]._handles(), h)
-            zq, _, vqs = E.vq_forward(m.vq.w.weight, z, cc, defer_scalars=True)
-            r, _ = E.residual_forward(dec[0]._handles(), zq)
-            _, tcx = E.z32_tail_forward(dec[1], dec[2], dec[4], r, x, mask, m.channel_var)
-            slabs, wr, wc, lat = tcx.loss_slabs, 1.0, 1.0, zq
-        else:
-            L = E.Layers(m)
-            z, ecx = E.encoder_forward(L, x, defer_last_join=L.codebook.weight.shape[0] if JOIN_IN_VQ else 0)
-            if z is None:
-                z, zq, _, vqs = E.vq_forward_joined(L.codebook.weight, ecx.pending_join, cc)
-            else:
-                zq, _, vqs = E.vq_forward(L.codebook.weight, z, cc, defer_scalars=True)
-            _, dcx = E.decoder_forward(L, zq, x, mask)
-            slabs, wr, wc, lat = dcx.loss_slabs, float(m.weight_recon), float(m.weight_commitment), z
-        fin = (vqs.slabs, vqs.ws, vqs.K, vqs.D, vqs.positions, vqs.cc, slabs, B * NIN * H * W, wr, wc)
-        if tm is None:
-            return ops.vq_loss_finalize(*fin)
-        zf = lat.reshape(B, -1)
-        if self.global_tm:                  # this rank's rows of the global term, on the gathered latents
-            zg = D.all_gather_rows(zf, tm.shape[0], self.group)
-            part, _ = ops.time_matching_forward_rows(zg, tm.to(torch.float32).contiguous(), D.shard_range(
-                tm.shape[0], D.get_rank(self.group), self.world)[0], B, *_tm_args(m, self._z32))
-            return _with_matching(ops.vq_loss_finalize(*fin), self._global_total(part).float(), float(m.weight_matching))
-        tmf = tm.to(torch.float32).contiguous()
-        if ops.time_matching_supported(zf.shape[0], zf.shape[1]):
-            tm_slabs, _ = ops.time_matching_forward(zf, tmf, *_tm_args(m, self._z32), want_slabs=True)
-            return ops.vq_loss_finalize_tm(*fin, tm_slabs, float(m.weight_matching))
-        tml, _ = self._time_matching(ops.pair_msd(zf), tmf, self._z32 or getattr(m, "_z16_loss", False))
-        return _with_matching(ops.vq_loss_finalize(*fin), tml, float(m.weight_matching))
-
     def evaluate(self, x, mask=None, time_matching_mat=None):
-        """forward_only through a captured HIP graph (one per input shape); returns the device tensor of loss values."""
+        """forward_only through a captured HIP graph (one per input shape); returns the device tensor of loss values.  With
+        sync_batchnorm or the global term the pass runs eagerly: its collectives sit inside the forward."""
         if not x.is_cuda or x.device != self.flat.device:
             raise RuntimeError(f"FusedTrainer.evaluate: batch on {x.device}, model on {self.flat.device}")
+        x = x.contiguous()
         with torch.cuda.device(self.flat.device):
-            if self.sync_bn:            # (eagerly: every BatchNorm's exchange sits inside the forward)
-                self._bn_w[0].fill_(1.0)
-                with self._bn_ctx(self._exchange_now):
-                    return self.forward_only(x.contiguous(), mask, time_matching_mat)
-            # (global_time_matching: the validation pass runs eagerly -- its collective sits inside the forward)
-            if not self.use_graph or (self.global_tm and time_matching_mat is not None):
-                return self.forward_only(x.contiguous(), mask, time_matching_mat)
-            return self._graph_step(x.contiguous(), mask, time_matching_mat, kind="eval")
+            if not self.use_graph or self.sync_bn or (self.global_tm and time_matching_mat is not None):
+                if self.sync_bn:
+                    self._bn_w[0].fill_(1.0)
+                with self._bn_context(_inline):
+                    return self.forward_only(x, mask, time_matching_mat)
+            segs, out = self._program("eval", x, mask, time_matching_mat)
+            segs.replay()
+            return out
 
     def prepare(self, x, mask=None, time_matching_mat=None):
-        """Capture the HIP graph for this input shape WITHOUT taking a step (the capture's internal warm-up run has its
+        """Capture the program step() replays for this input shape WITHOUT taking a step (the capture's warm-up run has its
         BatchNorm side effects put back, parameters and Adam state are untouched): a caller that times steps can keep the
-        one-off capture out of its timed region.  Returns the graph's input buffer (fill it in place to skip the copy)."""
+        one-off capture out of its timed region.  Returns the program's input buffer (fill it in place to skip the copy)."""
         if not self.use_graph:
             return None
         with torch.cuda.device(self.flat.device):
-            if self.sync_bn:
-                self._sync_step(x.contiguous(), mask, time_matching_mat, 1.0, replay=False)
-            else:
-                self._graph_step(x.contiguous(), mask, time_matching_mat, replay=False)
+            self._fwd_bwd(x.contiguous(), mask, time_matching_mat, replay=False)
         return self._static_x
 
+    # ------------------------------------------------------------------------------------------ captured programs
     def static_inputs(self, x_shape, mask_shape=None, tm_shape=None):
-        """(x, mask, matrix) buffers the graphs of this input shape read: a loader that fills them in place and passes
-        them to step() / evaluate() skips every copy (dynamorph_amd.train._Feed writes its gathered batches here).
-        Allocated on first use, shared by the training and the validation graph of the shape; nothing is captured here."""
-        key = (tuple(x_shape), None if mask_shape is None else tuple(mask_shape), None if tm_shape is None else tuple(tm_shape))
+        """(x, mask, matrix) buffers every program of this input shape reads: a loader that fills them in place and passes
+        them to step() / evaluate() skips every copy (dynamorph_amd.feed writes its gathered batches here).  Allocated on
+        first use, shared by the training and the validation program of the shape; nothing is captured here."""
+        return self._entry(x_shape, mask_shape, tm_shape)["inputs"]
+
+    def _entry(self, x_shape, mask_shape, tm_shape):
+        key = tuple(None if s is None else tuple(s) for s in (x_shape, mask_shape, tm_shape))
         ent = self._graphs.get(key)
         if ent is None:
             dev = self.flat.device
-            ent = self._graphs[key] = {
-                "x": torch.zeros(key[0], device=dev), "mask": torch.zeros(key[1], device=dev) if key[1] else None,
-                "tm": torch.zeros(key[2], device=dev) if key[2] else None, "train": None, "eval": None}
-        return ent["x"], ent["mask"], ent["tm"]
+            ent = self._graphs[key] = {"inputs": tuple(None if s is None else torch.zeros(s, device=dev) for s in key),
+                                       "train": None, "eval": None}
+        return ent
 
-    def _graph_step(self, x, mask, tm=None, replay=True, kind="train"):
-        """Graphs are cached per input shape (a ragged last batch gets its own, captured once, not once per epoch)."""
-        sx, smask, stm = self.static_inputs(x.shape, None if mask is None else mask.shape, None if tm is None else tm.shape)
-        if x.data_ptr() != sx.data_ptr():           # a loader may write straight into the static buffers
-            sx.copy_(x)
-        if mask is not None and mask.data_ptr() != smask.data_ptr():
-            smask.copy_(mask)
-        if tm is not None and tm.data_ptr() != stm.data_ptr():
-            stm.copy_(tm)
-        ent = self._graphs[(tuple(x.shape), None if mask is None else tuple(mask.shape), None if tm is None else tuple(tm.shape))]
-        if ent[kind] is None:
-            fn = self.forward_backward if kind == "train" else self.forward_only
-            # warm-up on a side stream (allocator + lazy init), then capture.  The warm-up really executes,
-            # so the BatchNorm running statistics it advanced are put back: only replays count as steps.
-            bufs = list(self.model.buffers())
-            saved = [b.clone() for b in bufs]
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                fn(sx, smask, stm)
-            torch.cuda.current_stream().wait_stream(s)
-            for b, sv in zip(bufs, saved):
-                b.copy_(sv)
-            if self.world > 1:
-                # no collective of this process may be in flight while the stream is capturing (the broadcast of the
-                # constructor, the previous step's all-reduce: their completion is polled by the backend's watchdog thread)
-                torch.cuda.synchronize(self.flat.device)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                sout = fn(sx, smask, stm)
-            ent[kind] = (g, sout)
+    def _program(self, kind, x, mask, tm):
+        """The captured program ("train": _train_body, "eval": forward_only) of this input shape, captured on first use
+        (a ragged last batch gets its own, captured once, not once per epoch), its static inputs holding x, mask, tm:
+        (_Segments, static output)."""
+        ent = self._entry(x.shape, None if mask is None else mask.shape, None if tm is None else tm.shape)
+        _fill_static(ent["inputs"], (x, mask, tm))
+        sx, smask, stm = ent["inputs"]
         self._static_x = sx
-        if replay:
-            ent[kind][0].replay()
-        return ent[kind][1]
+        if ent[kind] is None:
+            body = ((lambda cut: self._train_body(sx, smask, stm, cut)) if kind == "train" else
+                    (lambda cut: self.forward_only(sx, smask, stm)))
+            # warm-up (allocator, lazy init) with every cut's host work left out: ranks may capture at different steps (a
+            # ragged shard's shape), so nothing here may wait for another rank
+            _warm_up(lambda: body(_skip), self.model.buffers())
+            segs = _Segments()
+            with segs.capture():
+                out = body(segs.cut)
+            ent[kind] = (segs, out)
+        return ent[kind]
 
     def input_buffer(self):
-        """Input tensor of the graph replayed last (None before the first step): fill it in place to skip the copy."""
+        """Input tensor of the program replayed last (None before the first step): fill it in place to skip the copy."""
         return self._static_x
 
 
+def _inline(action, shape=None):
+    """cut() of an eager step: the host work runs in place (action(None) allocates what it returns)."""
+    return action(None)
+
+
+def _skip(action, shape=None):
+    """cut() of a warm-up: the host work is left out; zeros stand in for what it would return."""
+    return None if shape is None else torch.zeros(shape, device="cuda")
+
+
 class _Segments:
-    """A step captured as HIP graphs cut where a collective must run: replay() is seg0 | after0 | seg1 | ... | segK, every
-    collective between two replays on the launch stream (none is captured).  All segments allocate from the first one's
-    memory pool, so a tensor one segment writes and a later one reads keeps its address."""
+    """A step captured as HIP graphs cut where host work must run (a collective, the caller's torch code): replay() is
+    seg0 | after0 | seg1 | ... | segK, the host work between two replays on the launch stream (none is captured).  All
+    segments allocate from the first one's memory pool, so a tensor one segment writes and a later one reads keeps its
+    address.  A step without cuts is ONE graph."""
 
     def __init__(self):
         self.graphs, self.after = [], []
@@ -766,17 +555,35 @@ class _Segments:
             g.capture_begin()
         self.graphs.append(g)
 
-    def cut(self, action):
-        """End the current segment; action() runs after its replay, before the next segment's."""
+    def cut(self, action, shape=None):
+        """End the current segment; action(out) runs after its replay, before the next segment's.  shape: out is a buffer
+        of that shape (returned here) which the action fills and later segments read."""
+        out = None if shape is None else torch.empty(shape, device="cuda")
         self.graphs[-1].capture_end()
-        self.after.append(action)
+        self.after.append(lambda: action(out))
         self._begin()
+        return out
 
     def replay(self):
         for i, g in enumerate(self.graphs):
             g.replay()
             if i < len(self.after):
                 self.after[i]()
+
+
+def _warm_up(run, tensors):
+    """run() once on a side stream before a capture (allocator, lazy initialisation).  It really executes, so the tensors
+    it advances (BatchNorm running statistics, ...) are put back afterwards: only replays count as steps."""
+    tensors = list(tensors)
+    saved = [t.detach().clone() for t in tensors]
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        run()
+    torch.cuda.current_stream().wait_stream(side)
+    with torch.no_grad():
+        for t, sv in zip(tensors, saved):
+            t.copy_(sv)
 
 
 def _tm_args(model, z32=False):
@@ -790,6 +597,13 @@ def _with_matching(scalars, tml, wm):
     """(recon, commitment, total, perplexity) + the pairwise term -> the five values of a step with a relation matrix."""
     tml = tml.reshape(1)
     return torch.cat([scalars[:2], scalars[2:3] + wm * tml, scalars[3:4], tml])
+
+
+def _fill_static(static, inputs):
+    """Copy the caller's (x, mask, matrix) into a captured program's static inputs (a loader may have written them there)."""
+    for dst, src in zip(static, inputs):
+        if src is not None and src.data_ptr() != dst.data_ptr():
+            dst.copy_(src)
 
 
 class GraphedTrainer:
@@ -822,22 +636,14 @@ class GraphedTrainer:
         sx = x.clone()
         smask = mask.clone() if mask is not None else None
         stm = tm.clone().float() if tm is not None else None
-        # warm-up on a side stream (allocator, lazy state of the optimizer); it really executes, so parameters, buffers
-        # and the optimizer state it touched are put back afterwards: only replays count as steps
-        tensors = list(self.model.parameters()) + list(self.model.buffers())
-        saved = [t.detach().clone() for t in tensors]
+        # the warm-up (also the lazy state of the optimizer) puts parameters and buffers back; the optimizer state it
+        # touched is put back here
         had_state = len(self.opt.state) > 0
         opt_saved = [{k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in self.opt.state[p].items()}
                      for g in self.opt.param_groups for p in g["params"]] if had_state else None
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                self._eager(sx, smask, stm)
-        torch.cuda.current_stream().wait_stream(side)
+        _warm_up(lambda: [self._eager(sx, smask, stm) for _ in range(2)],
+                 list(self.model.parameters()) + list(self.model.buffers()))
         with torch.no_grad():
-            for t, sv in zip(tensors, saved):
-                t.copy_(sv)
             i = 0
             for g in self.opt.param_groups:
                 for p in g["params"]:
@@ -860,12 +666,7 @@ class GraphedTrainer:
             if key not in self._graphs:
                 self._graphs[key] = self._capture(x.contiguous(), mask, tm)       # (a ragged last batch gets its own graph)
             else:
-                _, sx, smask, stm, _ = self._graphs[key]
-                sx.copy_(x)
-                if mask is not None:
-                    smask.copy_(mask)
-                if tm is not None:
-                    stm.copy_(tm)
+                _fill_static(self._graphs[key][1:4], (x, mask, tm))
             g, _, _, _, out = self._graphs[key]
             g.replay()
         return out

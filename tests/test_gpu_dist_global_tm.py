@@ -70,7 +70,9 @@ def _step_worker(rank, world, port, kind, out_dir):
             # mode off: what train() hands a rank by default -- the block of its own shard
             block = tm if flag else tm[rank * B:(rank + 1) * B, rank * B:(rank + 1) * B].contiguous()
             vals = tr.step(x, None, block)
-            res[(use_graph, flag)] = (vals.cpu(), tr.grad.cpu().clone())      # the bucket after the exchange (sum)
+            # captured programs: the global step is 2 segments (cut at the gather), the plain step ONE graph
+            segs = len(tr._graphs[(tuple(x.shape), None, tuple(block.shape))]["train"][0].graphs) if use_graph else 0
+            res[(use_graph, flag)] = (vals.cpu(), tr.grad.cpu().clone(), segs)      # the bucket after the exchange (sum)
     if rank == 0:
         torch.save(res, os.path.join(out_dir, "ranks.pt"))
     dist.barrier()
@@ -113,11 +115,16 @@ def test_two_ranks_duplicate_shards_equal_one_process(tmp_path, kind):
     ref_vals = ref.step(xx, None, tm.cuda()).cpu()
     ref_grad = ref.grad.cpu()
     for use_graph in (True, False):
-        vals, bucket = got[(use_graph, True)]
+        vals, bucket, _ = got[(use_graph, True)]
         why = _mismatch(vals, bucket / world, ref_vals, ref_grad, names)     # (Adam's load applies the 1 / world)
         assert why is None, (kind, use_graph, why)
-        vals, bucket = got[(use_graph, False)]
+        vals, bucket, _ = got[(use_graph, False)]
         assert _mismatch(vals, bucket / world, ref_vals, ref_grad, names) is not None, (kind, use_graph)
+    for flag, segs in ((True, 2), (False, 1)):
+        assert got[(True, flag)][2] == segs, (kind, flag, got[(True, flag)][2])
+        # the captured step and the eager step run one body: bit-equal scalars and exchanged bucket
+        assert torch.equal(got[(True, flag)][0], got[(False, flag)][0]), (kind, flag)
+        assert torch.equal(got[(True, flag)][1], got[(False, flag)][1]), (kind, flag)
 
 
 def _relation(n, seed):

@@ -116,8 +116,11 @@ def _step_worker(rank, world, port, kind, sizes, modes, out_dir):
         for mode in modes:
             tr = FusedTrainer(_model(kind), lr=1e-3, use_graph=use_graph, sync_batchnorm=mode != "off",
                               global_time_matching=mode == "both")
-            vals = tr.step(x, None, tm if mode == "both" else None, grad_weight=w)
-            res[(use_graph, mode)] = (vals.cpu(), tr.grad.cpu().clone(), _buffers(tr.model))
+            block = tm if mode == "both" else None
+            vals = tr.step(x, None, block, grad_weight=w)
+            key = (tuple(x.shape), None, None if block is None else tuple(block.shape))
+            segs = len(tr._graphs[key]["train"][0].graphs) if use_graph else 0
+            res[(use_graph, mode)] = (vals.cpu(), tr.grad.cpu().clone(), _buffers(tr.model), segs)
     torch.save(res, os.path.join(out_dir, f"ranks{rank}.pt"))
     dist.barrier()
     dist.destroy_process_group()
@@ -147,6 +150,17 @@ def _run_steps(tmp_path, kind, sizes, modes):
         why = _mismatch(vals, bucket / world, ref_vals, ref_grad, _names(_model(kind)), idx)
         return why or _buffer_mismatch(got[0][(use_graph, mode)][2], ref_bufs)
 
+    # captured segments: cut at each BatchNorm exchange (16 for VQ_VAE / VQ_VAE_z16, 22 for VQ_VAE_z32) and at the gather
+    exchanges = 22 if kind == "VQ_VAE_z32" else 16
+    for mode in modes:
+        segs = {"off": 1, "sync": exchanges + 1, "both": exchanges + 2}[mode]
+        for r in range(world):
+            assert got[r][(True, mode)][3] == segs, (kind, mode, r, got[r][(True, mode)][3])
+            # the captured step and the eager step run one body: bit-equal scalars, bucket and BatchNorm buffers
+            ge, gg = got[r][(False, mode)], got[r][(True, mode)]
+            assert torch.equal(gg[0], ge[0]) and torch.equal(gg[1], ge[1]), (kind, mode, r)
+            for k, b in ge[2].items():
+                assert torch.equal(gg[2][k], b), (kind, mode, r, k)
     for use_graph in (True, False):
         for mode in modes:
             if mode == "off":

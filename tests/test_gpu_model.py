@@ -772,18 +772,29 @@ def test_fused_trainer_time_matching(z16, use_graph):
     x = torch.randn(B, 2, 128, 128, generator=torch.Generator().manual_seed(5))
     tm = torch.randint(0, 3, (B, B), generator=torch.Generator().manual_seed(6)).float()
     opt = O.make_adam(ref, 1e-4)
+    twin = FusedTrainer(copy.deepcopy(m), lr=1e-4, use_graph=not use_graph)     # the other of eager / captured
     tr = FusedTrainer(m, lr=1e-4, use_graph=use_graph)
+    graphed = tr if use_graph else twin
+    graphed.prepare(x.to(DEV), None, tm.to(DEV))
+    key = ((B, 2, 128, 128), None, (B, B))
+    prog = graphed._graphs[key]["train"]
+    assert len(prog[0].graphs) == 1 and not prog[0].after          # ONE graph, one replay
     for step in range(2):
         ld_r = O.train_step(ref, opt, x, time_matching_mat=tm)
-        vals = tr.step(x.to(DEV), None, tm.to(DEV)).tolist()
+        out = tr.step(x.to(DEV), None, tm.to(DEV))
+        assert torch.equal(out, twin.step(x.to(DEV), None, tm.to(DEV))), step
+        vals = out.tolist()
         assert len(vals) == 5
         for i, k in ((0, "recon_loss"), (1, "commitment_loss"), (2, "total_loss"), (4, "time_matching_loss")):
             assert abs(vals[i] - float(ld_r[k])) <= 3e-5 * max(1.0, abs(float(ld_r[k]))), (step, k, vals[i], float(ld_r[k]))
-    sd_r = ref.state_dict()
+    assert graphed._graphs[key]["train"] is prog                    # prepare() captured what step() replays
+    sd_r, sd_t = ref.state_dict(), twin.model.state_dict()
     for k, v in m.state_dict().items():
+        assert torch.equal(v, sd_t[k]), k
         if k in BN_FED_BIASES or "tracked" in k:
             continue
         close(v, sd_r[k], 0, 2.5e-4 if "running" not in k else 2e-5, k)
+    assert torch.equal(tr.m, twin.m) and torch.equal(tr.v, twin.v)
 
 
 def test_captured_step_follows_the_relation_matrix_between_sparse_and_dense():
@@ -1051,9 +1062,23 @@ def test_fused_trainer_z32_with_extra_losses_against_reference_vectors(golden, u
     m = dynamorph_amd.VQ_VAE_z32(extra_loss=dict(EXTRA), alpha=float(g["alpha"])).to(DEV)
     m.load_state_dict({k[3:]: torch.from_numpy(np.asarray(v)) for k, v in g.items() if k.startswith("sd/")})
     tr = FusedTrainer(m, lr=1e-4, use_graph=use_graph)
+    m2 = dynamorph_amd.VQ_VAE_z32(extra_loss=dict(EXTRA), alpha=float(g["alpha"])).to(DEV)
+    m2.load_state_dict(m.state_dict())
+    twin = FusedTrainer(m2, lr=1e-4, use_graph=not use_graph)     # the other of eager / captured
+    graphed = tr if use_graph else twin
+    graphed.prepare(x, None, tm)
+    key = (tuple(x.shape), None, tuple(tm.shape))
+    prog = graphed._graphs[key]["train"]
+    assert len(prog[0].graphs) == 2                               # cut once, at the extra losses
     for rep in range(2):                                    # (the second call replays the captured pair)
         tr.grad.zero_()
-        vals = tr._step_with_extra_losses(x, None, tm, labels).tolist()
+        twin.grad.zero_()
+        out = tr._step_with_extra_losses(x, None, tm, labels)
+        assert torch.equal(out, twin._step_with_extra_losses(x, None, tm, labels)), rep
+        assert torch.equal(tr.grad, twin.grad), rep
+        for name in EXTRA:
+            assert torch.equal(tr.last_extra_losses[name], twin.last_extra_losses[name]), (rep, name)
+        vals = out.tolist()
         for i, k in ((0, "recon_loss"), (1, "commitment_loss"), (2, "total_loss"), (4, "time_matching_loss")):
             loss_gate(vals[i], float(g["loss/" + k]), f"fused extra-loss step {k}")
         for name in EXTRA:
@@ -1069,6 +1094,9 @@ def test_fused_trainer_z32_with_extra_losses_against_reference_vectors(golden, u
             assert err <= 4e-3 * scale + 1e-8, (rep, k, err, scale)
             n += 1
         assert n >= 30
+    assert graphed._graphs[key]["train"] is prog                  # prepare() captured what the steps replay
+    for k, b in m2.state_dict().items():
+        assert torch.equal(m.state_dict()[k], b), k
     losses = {}
     run_one_batch(m, x, losses, model_kwargs={"labels": labels, "time_matching_mat": tm}, optimizer=tr, training=True)
     assert list(losses.keys()) == [str(k) for k in g["loss_keys"]]          # vae.py:456-469: ..., total_loss, then one entry per extra loss

@@ -42,8 +42,7 @@ def _worker(rank, world, port, args):
                 tr.step(x)
             torch.cuda.synchronize()
             ms = (time.perf_counter() - t0) * 1e3 / args.steps
-            ent = tr._graphs[(tuple(x.shape), None, None)]
-            segs = len(ent["sync"][0].graphs) if ent.get("sync") else 1
+            segs = len(tr._graphs[(tuple(x.shape), None, None)]["train"][0].graphs)
             if rank == 0:
                 print(json.dumps({"model": kind, "sync_batchnorm": bool(flag), "world": world, "batch_per_rank": args.batch,
                                   "steps": args.steps, "segments": segs, "ms_per_step_gloo": round(ms, 3)}), flush=True)
