@@ -14,10 +14,14 @@ Adam, batch 2048 per GPU; weak scaling, one RCCL all-reduce of the flat 96 KB gr
 
 `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (dump_outputs), for comparing two builds.
 
-Rank 0 prints ONE JSON line.  It also carries
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: set-up, the warm-up and timed steps,
+--dump-outputs if given, the line.  `--full` also measures, after the timed steps (the headline does not change with it):
+  collective   -- the gradient exchange: backend, world, per-rank ms/step, parts of a step timed with events
   roofline     -- the dominant kernel of the step, timed live with events on the launch stream
   cpu_baseline -- the CPU oracle (oracle/vqvae_oracle.py, "port") timed on this host's cores on a bounded
                   sample of the same workload (rank 0, N=1 only)
+  targets, c2, train_loop, c5, z32ex -- c3 on one GPU: the north-star targets and the other workloads' records
+`--no-roofline`, `--no-cpu-baseline` and `--no-targets` leave single parts out of a --full run.
 """
 import argparse
 import json
@@ -45,9 +49,13 @@ def parse():
                     help="per-GPU batch (default 2048 for c3, 1024 for c2, 1024 for c5, 768 for z32ex)")
     ap.add_argument("--no-graph", action="store_true", help="launch kernels eagerly instead of replaying a HIP graph")
     ap.add_argument("--no-fused", action="store_true", help="z32ex: the autograd + torch.optim.Adam loop instead of FusedTrainer")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-targets", action="store_true", help="skip the north-star target measurements and the C2 sub-record")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the records the headline does not need (collective, roofline, "
+                         "cpu_baseline; c3 on one GPU: targets, c2, train_loop, c5, z32ex)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline record")
+    ap.add_argument("--no-targets", action="store_true",
+                    help="--full without the north-star target measurements and the c2 / train_loop / c5 / z32ex records")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
@@ -903,8 +911,9 @@ def main():
     if world > 1:
         torch.distributed.barrier()
     elapsed = time.perf_counter() - t0
-    # every rank's own wall time of the timed region (after the closing barrier they differ only by launch skew)
-    rank_ms = D.gather_rank_values(1e3 * elapsed / args.steps, device=dev)
+    if args.full:
+        # every rank's own wall time of the timed region (after the closing barrier they differ only by launch skew)
+        rank_ms = D.gather_rank_values(1e3 * elapsed / args.steps, device=dev)
     elapsed = D.max_over_ranks(elapsed, device=dev)
     dumped = None
     if args.dump_outputs and rank == 0:
@@ -912,10 +921,11 @@ def main():
         dumped = dump_outputs(args.dump_outputs, out, model, train=args.workload != "c2")
 
     losses = out.tolist() if args.workload in ("c3", "c5", "z32ex") else None
+    # --full only, from here to the line: nothing below changes the headline or the dumped arrays
     # evidence of the gradient exchange (after the timed region, every rank takes part): backend, world size and the
     # device / host time of the three parts of a step, from events on the launch stream around FusedTrainer._allreduce
     collective = None
-    if trainer is not None:
+    if args.full and trainer is not None:
         import torch.distributed as dist
         marks = []
         for _ in range(20 if world > 1 else 5):
@@ -937,7 +947,7 @@ def main():
                              if world > 1 else "none (one process)")}
         if world > 1:
             dist.barrier()
-    if args.no_roofline or rank != 0:
+    if not args.full or args.no_roofline or rank != 0:
         roof = None
     elif args.workload == "z32ex":
         roof = roofline_wide_conv(B)
@@ -946,7 +956,7 @@ def main():
     else:
         roof = roofline_dominant_kernel(model, x, args.workload)
     targets = c2 = loop = c5 = z32 = None
-    if rank == 0 and world == 1 and args.workload == "c3" and not args.no_targets:
+    if args.full and rank == 0 and world == 1 and args.workload == "c3" and not args.no_targets:
         targets = north_star_targets(model, x)
         c2 = c2_record(model)
         loop = train_loop_record(dev, 1e3 * elapsed / args.steps, B=B)
@@ -957,7 +967,7 @@ def main():
         c5 = c5_record(dev)
         z32 = z32ex_record(dev)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.workload)
 
     if rank == 0:

@@ -7,15 +7,15 @@ root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/refresh
 mkdir -p $out
 export TMPDIR=/tmp
-python3 $root/bench.py > $out/${tag}_c3_b2048_bench.json 2> $out/bench.err
-python3 $root/bench.py --workload c2 --no-roofline > $out/${tag}_c2_b1024_bench.json 2>> $out/bench.err
-python3 $root/bench.py --workload c5 > $out/${tag}_c5_k4096_256px_b1024_bench.json 2>> $out/bench.err
-python3 $root/bench.py --workload z32ex > $out/${tag}_z32ex_b768_bench.json 2>> $out/bench.err
+python3 $root/bench.py --full > $out/${tag}_c3_b2048_bench.json 2> $out/bench.err
+python3 $root/bench.py --workload c2 --full --no-roofline > $out/${tag}_c2_b1024_bench.json 2>> $out/bench.err
+python3 $root/bench.py --workload c5 --full > $out/${tag}_c5_k4096_256px_b1024_bench.json 2>> $out/bench.err
+python3 $root/bench.py --workload z32ex --full > $out/${tag}_z32ex_b768_bench.json 2>> $out/bench.err
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/c3 -- python3 $root/bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-targets > $out/${tag}_c3_b2048_bench_under_profiler.json 2> $out/c3.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/c3 -- python3 $root/bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-targets > $out/${tag}_c3_b2048_bench_under_profiler.json 2> $out/c3.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/c2 -- python3 $root/bench.py --workload c2 --steps 30 --warmup 5 --no-cpu-baseline --no-roofline --no-targets > $out/c2_under_profiler.json 2> $out/c2.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/c5 -- python3 $root/bench.py --workload c5 --steps 10 --warmup 3 --no-cpu-baseline --no-roofline > $out/c5_under_profiler.json 2> $out/c5.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/z32 -- python3 $root/bench.py --workload z32ex --steps 10 --warmup 3 --no-cpu-baseline --no-roofline > $out/z32_under_profiler.json 2> $out/z32.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/c5 -- python3 $root/bench.py --workload c5 --steps 10 --warmup 3 --full --no-cpu-baseline --no-roofline > $out/c5_under_profiler.json 2> $out/c5.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/z32 -- python3 $root/bench.py --workload z32ex --steps 10 --warmup 3 --full --no-cpu-baseline --no-roofline > $out/z32_under_profiler.json 2> $out/z32.err
 cd $root
 cp $(ls $out/c3/*/*kernel_stats.csv | head -1) $out/${tag}_c3_b2048_kernel_stats.csv
 cp $(ls $out/c2/*/*kernel_stats.csv | head -1) $out/${tag}_c2_b1024_kernel_stats.csv
@@ -53,5 +53,5 @@ rm -rf $out/tb
 tools/sqprof.sh ${tag}_c3 python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-targets --no-roofline > /dev/null 2>&1
 cp gpurun_out/${tag}_c3_sq.txt $out/${tag}_c3_b2048_sq_counters.txt 2>/dev/null
 cp gpurun_out/${tag}_c3_sq.json $out/${tag}_c3_b2048_sq_counters.json 2>/dev/null
-DM_DIST_BACKEND=gloo python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 10 --warmup 3 2> $out/dp2.err | grep '^{' > $out/${tag}_bench_dp2_gloo_rehearsal.json   # (gloo prints its connection lines on stdout)
+DM_DIST_BACKEND=gloo python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 10 --warmup 3 --full 2> $out/dp2.err | grep '^{' > $out/${tag}_bench_dp2_gloo_rehearsal.json   # (gloo prints its connection lines on stdout)
 tail -c 600 $out/${tag}_c3_b2048_bench.json; echo; tail -3 $out/${tag}_c3_b2048_kernel_table.txt; tail -c 400 $out/${tag}_bench_dp2_gloo_rehearsal.json
