@@ -2014,6 +2014,7 @@ extern "C" int dm_conv3x3(const dm_operand *in, const dm_weight_view *w, float *
     DM_REQUIRE(taps == 9 || taps == 1, "dm_conv3x3: taps must be 9 or 1");
     DM_REQUIRE(!pixel_shuffle || (taps == 9 && NOUT % 4 == 0), "dm_conv3x3: pixel_shuffle needs taps=9, NOUT%%4==0");
     DM_REQUIRE(!in->ones_channel, "dm_conv3x3: ones_channel not supported");
+    DM_REQUIRE(!(ep && ep->bias_border), "dm_conv3x3: bias_border not supported (dm_conv4x4s2 only)");
     const int TW = conv3_tw(W, CIN);
     const bool fast = conv3_has_kernel(CIN, NOUT, H, W, taps, pixel_shuffle != 0, ep ? ep->stats_per_tile : 0);
     ConvArgs a{to_dev(in), to_dev(w), out, to_dev(ep), B, CIN, CIN, NOUT, H, W, ep ? ep->stats_per_tile : 0,

@@ -77,7 +77,7 @@ typedef struct dm_weight_view {
  *   slabs that is (reduced by dm_bn_finalize / dm_bn_backward_finalize / dm_sum_slabs: deterministic). */
 typedef struct dm_epilogue {
     const float *bias;
-    const float *bias_border; /* dm_conv4x4s2 only, [3][3][NOUT] (row class, column class, channel) with classes
+    const float *bias_border; /* dm_conv4x4s2 only (dm_conv3x3 refuses it), [3][3][NOUT] (row class, column class, channel) with classes
                                  first / interior / last output row or column: replaces `bias` by a per-position bias
                                  (the enc.0 bias seen through enc.1's zero padding, dm_e1_compose); NULL: plain bias */
     int32_t relu;
@@ -249,7 +249,7 @@ int dm_conv_bwd_s2_fused(const dm_operand *dy, const dm_operand *in, const dm_we
  * aten::convolution_backward(weight).
  * T may be an AFFINE2 operand (two tensors: a BatchNorm backward folded into the load) only where
  * dm_wgrad_t_affine2_supported says so (the wide decoder's first transposed convolution: S plain, 64 x 32 channels, k = 4);
- * elsewhere the caller materialises it (dm_apply). */
+ * elsewhere the caller materialises it (dm_apply).  Per-sample coefficients there take the tiled kernel, which loads T.p1 too. */
 int dm_wgrad_num_blocks(int B, int CS, int CT, int Hs, int Ws, int k);
 int dm_wgrad_t_affine2_supported(int CS, int CT, int Hs, int Ws, int k);
 int dm_wgrad(const dm_operand *S, const dm_operand *T, float *slabs, float *dst,
