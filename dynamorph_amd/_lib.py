@@ -161,6 +161,11 @@ SIGNATURES = {
     "dm_csr_block": (C.c_int, [vp, vp, vp, i64, vp, C.c_int, vp, i64, vp, vp]),
     "dm_augment_codes": (i64, [vp, i64, i64, vp, vp]),
     "dm_reorder_with_trajectories": (i64, [vp, i64, i64, vp, vp, vp, vp]),
+    "dm_pca_colsum_workspace_bytes": (i64, [i64, C.c_int]),
+    "dm_pca_colsum": (C.c_int, [vp, i64, C.c_int, i64, vp, vp, i64, vp]),
+    "dm_pca_gram_workspace_bytes": (i64, [i64, C.c_int]),
+    "dm_pca_gram": (C.c_int, [vp, i64, C.c_int, i64, vp, vp, C.c_int, vp, i64, vp]),
+    "dm_pca_transform": (C.c_int, [vp, i64, C.c_int, i64, vp, vp, C.c_int, vp, vp]),
 }
 
 _lib = None

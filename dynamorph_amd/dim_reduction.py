@@ -1,0 +1,108 @@
+"""PCA stage of the pipeline: mirror of run_dim_reduction.py (fit_PCA lines 14-50, process_PCA 52-92, the PCA branch of
+dim_reduction 177-281) on dynamorph_amd.pca.PCA.
+
+File names are the ones process_VAE writes: <prefix>_latent_space<suffix>.pkl in, <prefix>_latent_space<suffix>_PCAed.pkl
+out (the reference's '{}_latent_space_{}.pkl'.format(prefix, '_after') names a '..._latent_space__after.pkl' its own pipeline
+never writes).
+"""
+import os
+import pickle
+
+import numpy as np
+
+from .pca import PCA
+
+
+def _sklearn_available():
+    try:
+        import sklearn.decomposition  # noqa: F401
+    except ImportError:
+        return False
+    return True
+
+
+def fit_PCA(train_data, weights_dir, labels=None, conditions=None, n_components=0.5, **kw):
+    """Fit PCA(n_components) to the pooled latents, write <weights_dir>/pca_model.pkl (protocol 4) and return the fitted
+    device PCA.  The pickle holds the fitted sklearn PCA when scikit-learn is importable (what the reference's
+    process_PCA unpickles), else this package's PCA with its state on the host.  PCA.png is drawn when matplotlib imports."""
+    os.makedirs(weights_dir, exist_ok=True)
+    model_path = os.path.join(weights_dir, 'pca_model.pkl')
+    pca = PCA(n_components, **kw)
+    pcas = pca.fit_transform(train_data)
+    with open(model_path, 'wb') as f:
+        pickle.dump(pca.to_sklearn() if _sklearn_available() else pca, f, protocol=4)
+    _scatter(pcas, labels, conditions, weights_dir)
+    return pca
+
+
+def _scatter(pcas, labels, conditions, weights_dir, zoom_cutoff=1):
+    """run_dim_reduction.py:39-49: PC 1 against PC 2, coloured by label."""
+    try:
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+    except Exception:
+        return
+    if pcas.shape[1] < 2:
+        return
+    p = pcas[:, :2].cpu().numpy()
+    fig, ax = plt.subplots()
+    scatter = ax.scatter(p[:, 0], p[:, 1], s=7, c=labels, cmap='Paired', alpha=0.1)
+    scatter.set_facecolor("none")
+    ax.set_xlim(np.percentile(p[:, 0], zoom_cutoff), np.percentile(p[:, 0], 100 - zoom_cutoff))
+    ax.set_ylim(np.percentile(p[:, 1], zoom_cutoff), np.percentile(p[:, 1], 100 - zoom_cutoff))
+    if labels is not None and conditions is not None:
+        ax.legend(handles=scatter.legend_elements()[0], loc="upper right", title="condition", labels=conditions)
+    ax.set_xlabel('PC 1')
+    ax.set_ylabel('PC 2')
+    fig.savefig(os.path.join(weights_dir, 'PCA.png'), dpi=300)
+    plt.close(fig)
+
+
+def load_model(weights_dir, device=None):
+    """<weights_dir>/pca_model.pkl -- a fitted sklearn PCA (this package's or the reference's) or this package's PCA -- as a
+    device PCA."""
+    model_path = os.path.join(weights_dir, 'pca_model.pkl')
+    try:
+        with open(model_path, 'rb') as f:
+            obj = pickle.load(f)
+    except Exception as ex:
+        raise ValueError("Error in loading pre-saved PCA weights") from ex
+    return obj if isinstance(obj, PCA) else PCA.from_sklearn(obj, device=device)
+
+
+def process_PCA(input_dir, output_dir, weights_dir, prefix, suffix='_after', pca=None):
+    """<input_dir>/<prefix>_latent_space<suffix>.pkl -> <output_dir>/<prefix>_latent_space<suffix>_PCAed.pkl (float32,
+    protocol 4), transformed on the GPU by the model in <weights_dir> (or `pca`)."""
+    os.makedirs(output_dir, exist_ok=True)
+    if pca is None:
+        pca = load_model(weights_dir)
+    with open(os.path.join(input_dir, '{}_latent_space{}.pkl'.format(prefix, suffix)), 'rb') as f:
+        dats = pickle.load(f)
+    dats_ = pca.transform(np.asarray(dats)).cpu().numpy()
+    with open(os.path.join(output_dir, '{}_latent_space{}_PCAed.pkl'.format(prefix, suffix)), 'wb') as f:
+        pickle.dump(dats_, f, protocol=4)
+    return dats_
+
+
+def dim_reduction_pca(input_dirs, output_dirs, weights_dir, prefixes, fit_model, conditions=None, **kw):
+    """The PCA branch of run_dim_reduction.py::dim_reduction.  fit_model: pool <prefix>_latent_space_after.pkl of every
+    directory and prefix, in that order, one label per file, and fit (returns the PCA); else transform every (directory,
+    prefix) with the saved model (returns the list of outputs)."""
+    if isinstance(prefixes, str):
+        prefixes = [prefixes]
+    if not prefixes:
+        raise ValueError("latent space vector file name must contain a prefix: '<prefix>_latent_space.pkl'")
+    if conditions is None:
+        conditions = [os.path.basename(d) for d in input_dirs]
+    if fit_model:
+        weights_output = os.path.dirname(weights_dir) if os.path.isfile(weights_dir) else weights_dir
+        vectors, labels = [], []
+        for label, (d, p) in enumerate((d, p) for d in input_dirs for p in prefixes):
+            with open(os.path.join(d, '{}_latent_space_after.pkl'.format(p)), 'rb') as f:
+                vec = pickle.load(f)
+            vectors.append(np.asarray(vec))
+            labels += [label] * vec.shape[0]
+        return fit_PCA(np.concatenate(vectors, axis=0), weights_output, labels=labels, conditions=conditions, **kw)
+    pca = load_model(weights_dir)
+    return [process_PCA(d, o, weights_dir, p, pca=pca) for d, o in zip(input_dirs, output_dirs) for p in prefixes]

@@ -1159,3 +1159,78 @@ def augment_codes(n):
         m *= 2
     np.random.randint(0, 2 ** 32, size=int(used), dtype=np.uint32)      # advance by exactly the words consumed
     return flip, rot
+
+
+# ----------------------------------------------------------------------------- latent PCA (run_dim_reduction.py)
+def _rows(X):
+    """A 2-D fp32 device matrix with unit column stride: (pointer, N, F, leading dimension)."""
+    if not X.is_cuda:
+        raise ValueError("dynamorph_amd: tensor is not on the GPU (the HIP path has no CPU fallback)")
+    if X.dtype != torch.float32 or X.dim() != 2:
+        raise ValueError(f"dynamorph_amd: expected a 2-D float32 matrix, got {X.dtype} of shape {tuple(X.shape)}")
+    if X.shape[1] > 1 and X.stride(1) != 1:
+        raise ValueError("dynamorph_amd: the matrix needs unit column stride")
+    _note_device(X.device.index)
+    return X.data_ptr(), X.shape[0], X.shape[1], max(X.stride(0), X.shape[1])
+
+
+def _pca_workspace(nbytes, like):
+    return torch.empty(max(int(nbytes), 8) // 8, device=like.device, dtype=torch.float64)
+
+
+@_op
+def pca_colsum(X, sums=None, workspace=None):
+    """sums (F,) float64 = X.sum(0) in a fixed order (dm_pca_colsum)."""
+    lib = L.load()
+    p, N, F, ld = _rows(X)
+    nbytes = lib.dm_pca_colsum_workspace_bytes(N, F)
+    if nbytes < 0:
+        raise ValueError(f"dm_pca_colsum: bad shape ({N}, {F})")
+    if sums is None:
+        sums = _new((F,), X, torch.float64)
+    if workspace is None or workspace.numel() * 8 < nbytes:
+        workspace = _pca_workspace(nbytes, X)
+    L.check(lib.dm_pca_colsum(p, N, F, ld, _ptr(sums, torch.float64), _ptr(workspace, torch.float64), workspace.numel() * 8,
+                              _stream()), "dm_pca_colsum")
+    return sums
+
+
+@_op
+def pca_gram(X, shift=None, G=None, accumulate=False, workspace=None):
+    """G (F, F) float64 (+)= (X - shift)^T (X - shift) (dm_pca_gram); shift (F,) fp32 or None."""
+    lib = L.load()
+    p, N, F, ld = _rows(X)
+    nbytes = lib.dm_pca_gram_workspace_bytes(N, F)
+    if nbytes < 0:
+        raise ValueError(f"dm_pca_gram: bad shape ({N}, {F})")
+    if shift is not None and shift.numel() != F:
+        raise ValueError(f"dm_pca_gram: shift has {shift.numel()} entries, F = {F}")
+    if G is None:
+        if accumulate:
+            raise ValueError("dm_pca_gram: accumulate needs G")
+        G = _new((F, F), X, torch.float64)
+    elif tuple(G.shape) != (F, F):
+        raise ValueError(f"dm_pca_gram: G has shape {tuple(G.shape)}, need ({F}, {F})")
+    if workspace is None or workspace.numel() * 8 < nbytes:
+        workspace = _pca_workspace(nbytes, X)
+    L.check(lib.dm_pca_gram(p, N, F, ld, _ptr(shift), _ptr(G, torch.float64), 1 if accumulate else 0,
+                            _ptr(workspace, torch.float64), workspace.numel() * 8, _stream()), "dm_pca_gram")
+    return G
+
+
+@_op
+def pca_transform(X, V, shift=None, out=None):
+    """Y (N, k) fp32 = (X - shift) V^T (dm_pca_transform); V (k, F) fp32."""
+    lib = L.load()
+    p, N, F, ld = _rows(X)
+    if V.dim() != 2 or V.shape[1] != F:
+        raise ValueError(f"dm_pca_transform: V has shape {tuple(V.shape)}, need (k, {F})")
+    if shift is not None and shift.numel() != F:
+        raise ValueError(f"dm_pca_transform: shift has {shift.numel()} entries, F = {F}")
+    k = V.shape[0]
+    if out is None:
+        out = _new((N, k), X)
+    elif tuple(out.shape) != (N, k):
+        raise ValueError(f"dm_pca_transform: out has shape {tuple(out.shape)}, need ({N}, {k})")
+    L.check(lib.dm_pca_transform(p, N, F, ld, _ptr(shift), _ptr(V), k, _ptr(out), _stream()), "dm_pca_transform")
+    return out

@@ -662,6 +662,31 @@ int64_t dm_augment_codes(const uint32_t *raw, int64_t n_raw, int64_t n, int32_t 
 int64_t dm_reorder_with_trajectories(const uint32_t *raw, int64_t n_raw, int64_t n, const int64_t *adj_ptr,
                                      const int64_t *adj_idx, int64_t *order, int64_t *err_id);
 
+/* ===== latent PCA (run_dim_reduction.py:14-50 fit_PCA, :52-92 process_PCA) ============================== */
+/* X: N x F fp32 row-major with leading dimension ld >= F (floats), 1 <= F <= DM_PCA_MAX_FEATURES (the latents of VQ_VAE /
+ * VQ_VAE_z16 up to embedding_dim 64).  Results do not depend on the device: every summation order is fixed by (N, F). */
+#define DM_PCA_MAX_FEATURES 16384
+#define DM_PCA_MAX_COMPONENTS 512
+#define DM_PCA_GRAM_SLAB_ROWS 1024   /* rows accumulated in fp32 before a Gram partial is added in float64 */
+/* HOST: bytes of device workspace dm_pca_colsum needs (-1 for a bad shape). */
+int64_t dm_pca_colsum_workspace_bytes(int64_t N, int F);
+/* sums[f] = sum_n X[n][f] in float64, rows summed in a fixed order: the `X.mean(axis=0)` of sklearn PCA._fit_full
+ * (sklearn/decomposition/_pca.py, called by run_dim_reduction.py:35) once divided by N. */
+int dm_pca_colsum(const float *X, int64_t N, int F, int64_t ld, double *sums, void *workspace, int64_t workspace_bytes,
+                  void *stream);
+/* HOST: bytes of device workspace dm_pca_gram needs (-1 for a bad shape). */
+int64_t dm_pca_gram_workspace_bytes(int64_t N, int F);
+/* G (F x F float64, full and symmetric) = (X - shift)^T (X - shift), or G += that when accumulate != 0: the covariance
+ * product X^T X - n mu mu^T of PCA._fit_full's covariance route (run_dim_reduction.py:35) with the data centred in the
+ * operand load.  shift: F floats (the caller's fp32 mean), NULL = no centring.  fp32 products within slabs of
+ * DM_PCA_GRAM_SLAB_ROWS rows, slabs and row ranges added in float64 in a fixed order: repeated calls are bit-identical. */
+int dm_pca_gram(const float *X, int64_t N, int F, int64_t ld, const float *shift, double *G, int accumulate,
+                void *workspace, int64_t workspace_bytes, void *stream);
+/* Y (N x k fp32, row-major) = (X - shift) V^T, V: k x F fp32 row-major, 1 <= k <= DM_PCA_MAX_COMPONENTS: `pca.transform(dats)`
+ * of run_dim_reduction.py:85 (X @ components_.T - mean_ @ components_.T).  shift NULL = no centring. */
+int dm_pca_transform(const float *X, int64_t N, int F, int64_t ld, const float *shift, const float *V, int k, float *Y,
+                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif
