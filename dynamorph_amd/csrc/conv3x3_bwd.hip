@@ -326,18 +326,13 @@ void conv3x3_bwd_kernel(Operand dy, const float *__restrict__ x, const float *__
     }
 }
 
-bool conv3x3_bwd_band_on()
-{
-    static const bool off = [] { const char *e = getenv("DM_CONV3X3_BWD_BAND"); return e && e[0] == '0'; }();
-    return !off;
-}
 bool conv3x3_bwd_shape(int CD, int CX, int H, int W)
 {
     if (!((CD == 16 || CD == 32) && CX == 16)) return false;
     if (H == C3_HW && W == C3_HW) return true;
     // 32 x 32: bands of 8 rows x 32 columns -- for the residual layers' 32 output-gradient channels (238 us per layer against the
     // two kernels' 267 at C5's shape); with 16 (enc.10) the two kernels are as fast (120 against 125 us) and stay
-    return conv3x3_bwd_band_on() && CD == 32 && W == C3B_W && H == C3B_H;
+    return CD == 32 && W == C3B_W && H == C3B_H;
 }
 constexpr size_t conv3x3_bwd_lds(int CD, bool band = false)
 {

@@ -374,12 +374,10 @@ void conv4x4s2_patch_forward_kernel(Operand in, WeightView wv, const float *__re
 }  // namespace
 
 // Called by dm_conv4x4s2 (conv_mfma.hip) for the shape this kernel is built for; returns false when it does not apply.
-// DM_PATCH_CONV=0 in the environment keeps the tiled kernel (A/B runs).
 bool dm_conv4x4s2_patch_forward(const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B, int Cphys, int CIN,
                                 int NOUT, int H, int W, int per_tile, int nslabs, hipStream_t stream, int *rc)
 {
-    static const bool off = [] { const char *e = getenv("DM_PATCH_CONV"); return e && e[0] == '0'; }();
-    if (off || CIN != 16 || Cphys != 16 || NOUT != 16 || H != 32 || W != 32) return false;
+    if (CIN != 16 || Cphys != 16 || NOUT != 16 || H != 32 || W != 32) return false;
     if (in.mode == DM_LOAD_AFFINE2 || in.ones || ep.mask.p0 || ep.resid || ep.stat_q || ep.bias_border) return false;
     if (per_tile && (!ep.stats || nslabs % B != 0)) return false;
     static DmPerDeviceOnce attr_done;

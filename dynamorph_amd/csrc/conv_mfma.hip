@@ -45,21 +45,8 @@ long long dm_wide_conv_scratch_floats(int form, int CIN, int NOUT, int taps);
 int dm_wide_conv(int form, const Operand &in, const WeightView &wv, float *scratch, float *out, const Epilogue &ep, int B,
                  int Cphys, int CIN, int NOUT, int H, int W, int taps, int nslabs, int per_tile, hipStream_t st);
 
-// arithmetic of the gradient kernels (defined with the C ABI at the end of this file; also used by wgrad_mfma.hip)
-bool dm_backward_split_bf16();
 bool dm_conv4x4s2_patch_forward(const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B, int Cphys, int CIN,
                                 int NOUT, int H, int W, int per_tile, int nslabs, hipStream_t stream, int *rc);
-#ifdef DM_MEASURE
-// Measurement builds only (make measure): DM_FORWARD_SPLIT=1 runs the FORWARD convolutions on the two-piece split-bf16
-// products too.  Results are then not fp32 (latents pick codes): this exists to bound what ANY bf16-piece arithmetic could
-// buy the convolution family and is compiled out of the shipped library.
-static bool dm_forward_split() { static const bool v = getenv("DM_FORWARD_SPLIT") != nullptr; return v; }
-#define DM_FWD_SPLIT(cond) ((cond) && dm_forward_split())
-constexpr bool MEASURE_BF = true;
-#else
-#define DM_FWD_SPLIT(cond) false
-constexpr bool MEASURE_BF = false;
-#endif
 
 namespace {
 
@@ -197,8 +184,7 @@ __device__ __forceinline__ void zero_unowned_slabs(const Epilogue &ep, int NCH, 
 // ============================================================================ kernel A
 // BB: per-position bias from ep.bias_border[3][3][NOUT] (first / interior / last output row x column) instead of
 // ep.bias -- the enc.0 bias seen through enc.1's zero padding, so the first conv needs no ones channel (K = 32, not 48).
-// BF (gradients only: kernels with side inputs or the BatchNorm-backward operand): split-bf16 operands, tile.h
-template <int CIN, int NT, int TH, int TW, int SIDE, int WPS, bool BB, bool BF = false>
+template <int CIN, int NT, int TH, int TW, int SIDE, int WPS, bool BB>
 __global__ __launch_bounds__(DM_BLOCK, WPS)
 void conv4x4s2_kernel(Operand in, WeightView wv, float *__restrict__ out, Epilogue ep, int Cphys, int NOUT, int H,
                       int W, int ntiles, int nslabs, int per_tile)
@@ -244,10 +230,6 @@ void conv4x4s2_kernel(Operand in, WeightView wv, float *__restrict__ out, Epilog
 #pragma unroll
         for (int s = 0; s < KS; ++s)
             wreg[t][s] = n < NOUT ? wv.w[wv.off + n * wv.sn + (s >> 2) * wv.sc + (s & 3) * wv.sky + kq * wv.skx] : 0.f;
-        if constexpr (BF) {
-#pragma unroll
-            for (int s = 0; s < KS; ++s) wreg[t][s] = split_pack1(wreg[t][s]);
-        }
     }
 
     double s1[NT], s2[NT];
@@ -262,7 +244,7 @@ void conv4x4s2_kernel(Operand in, WeightView wv, float *__restrict__ out, Epilog
     for (int t = 0; t < NT; ++t) chan_off[t] = 16 * t + m < NOUT ? ((16 * t + m) * Ho * Wo + 4 * kq) * 4 : DM_VOFF_NONE;
     while (tidx < ntiles) {
         __syncthreads();                                   // previous tile consumed; coefficient table visible
-        stage.template commit<BF>(tile, s_coef, Cphys, H, W, 2 * oy0 - 1, 2 * ox0 - 4, in.mode);
+        stage.commit(tile, s_coef, Cphys, H, W, 2 * oy0 - 1, 2 * ox0 - 4, in.mode);
         __syncthreads();
         const int cb = b, cy0 = oy0, cx0 = ox0;            // the tile now in LDS
         const int next = tidx + gridDim.x;
@@ -306,8 +288,7 @@ void conv4x4s2_kernel(Operand in, WeightView wv, float *__restrict__ out, Epilog
             for (int i = 0; i < MP; ++i)
 #pragma unroll
                 for (int t = 0; t < NT; ++t) acc[i][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if constexpr (BF) mfma_tiles_split<MP, NT, KS>(ap, wreg, acc, off);
-            else mfma_tiles<MP, NT, KS, 4>(ap, wreg, acc, off);
+            mfma_tiles<MP, NT, KS, 4>(ap, wreg, acc, off);
 #pragma unroll
             for (int i = 0; i < MP; ++i)
 #pragma unroll
@@ -493,7 +474,7 @@ void conv4x4s2_pair_kernel(Operand in, WeightView wv, float *__restrict__ out, E
 }
 
 // ============================================================================ kernel B
-template <int CIN, int NT, int NPASS, int TAPS, bool PIX, int TH, int TW, bool TWO, int SIDE, int WPS, bool BF = false>
+template <int CIN, int NT, int NPASS, int TAPS, bool PIX, int TH, int TW, bool TWO, int SIDE, int WPS>
 __global__ __launch_bounds__(DM_BLOCK, WPS)
 void conv3x3_kernel(Operand in, WeightView wv, float *__restrict__ out, Epilogue ep, int Cphys, int NOUT, int H,
                     int W, int ntiles, int nslabs, int per_tile)
@@ -567,7 +548,7 @@ void conv3x3_kernel(Operand in, WeightView wv, float *__restrict__ out, Epilogue
                         wvl = wv.w[wv.off + n * wv.sn + c * wv.sc + tyy * wv.sky + txx * wv.skx];
                     }
                 }
-                wreg[t][s] = BF ? split_pack1(wvl) : wvl;
+                wreg[t][s] = wvl;
             }
         }
 
@@ -585,7 +566,7 @@ void conv3x3_kernel(Operand in, WeightView wv, float *__restrict__ out, Epilogue
 
         while (tidx < ntiles) {
             __syncthreads();
-            stage.template commit<BF>(tile, s_coef, Cphys, H, W, y0 - PADR, x0 - 4 * PADR, in.mode);
+            stage.commit(tile, s_coef, Cphys, H, W, y0 - PADR, x0 - 4 * PADR, in.mode);
             __syncthreads();
             const int cb = b, cy0 = y0, cx0 = x0;
             const int next = tidx + gridDim.x;
@@ -633,8 +614,7 @@ void conv3x3_kernel(Operand in, WeightView wv, float *__restrict__ out, Epilogue
                 for (int i = 0; i < MP; ++i)
 #pragma unroll
                     for (int t = 0; t < NT; ++t) acc[i][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                if constexpr (BF) mfma_tiles_split<MP, NT, KS>(ap, wreg, acc, off);
-                else mfma_tiles<MP, NT, KS, (TAPS == 9 ? 3 : 4)>(ap, wreg, acc, off);
+                mfma_tiles<MP, NT, KS, (TAPS == 9 ? 3 : 4)>(ap, wreg, acc, off);
 #pragma unroll
                 for (int i = 0; i < MP; ++i)
 #pragma unroll
@@ -675,7 +655,7 @@ void conv3x3_kernel(Operand in, WeightView wv, float *__restrict__ out, Epilogue
 // not matrix-pipe time -- and these kernels are matrix-pipe bound (60-70 % busy).
 // Output: the two x phases of a row are interleaved in registers (COUT = 16: both live in the lane, two 16-byte
 // stores per row; COUT = 8: lanes m and m^8 swap halves, one store), so stores stay 16 contiguous bytes per lane.
-template <int CIN, int COUT, int TH, int TW, bool TWO, int SIDE, int WPS, bool BF = false>
+template <int CIN, int COUT, int TH, int TW, bool TWO, int SIDE, int WPS>
 __global__ __launch_bounds__(DM_BLOCK, WPS)
 void convT_phase_kernel(Operand in, WeightView wv, float *__restrict__ out, Epilogue ep, int Cphys, int H, int W,
                         int ntiles, int nslabs)
@@ -725,7 +705,7 @@ void convT_phase_kernel(Operand in, WeightView wv, float *__restrict__ out, Epil
                 const int ky = py + 3 - 2 * row, kx = px + 3 - 2 * col;
                 float wvl = 0.f;
                 if (ky >= 0 && ky <= 3 && kx >= 0 && kx <= 3) wvl = wv.w[wv.off + co * wv.sn + c * wv.sc + ky * wv.sky + kx * wv.skx];
-                wreg[py][pxt][0][s] = BF ? split_pack1(wvl) : wvl;
+                wreg[py][pxt][0][s] = wvl;
             }
     const float bias = ep.bias ? ep.bias[co] : 0.f;
     float mc0, mc2;
@@ -740,7 +720,7 @@ void convT_phase_kernel(Operand in, WeightView wv, float *__restrict__ out, Epil
 
     while (tidx < ntiles) {
         __syncthreads();
-        stage.template commit<BF>(tile, s_coef, Cphys, H, W, y0 - 1, x0 - 4, in.mode);
+        stage.commit(tile, s_coef, Cphys, H, W, y0 - 1, x0 - 4, in.mode);
         __syncthreads();
         const int cb = b, cy0 = y0, cx0 = x0;
         const int next = tidx + gridDim.x;
@@ -786,8 +766,7 @@ void convT_phase_kernel(Operand in, WeightView wv, float *__restrict__ out, Epil
                         const int cg4 = s / (2 * TAPX), j = s % (2 * TAPX), a = j / TAPX, bb = j % TAPX;
                         return 4 * cg4 * PS + (py + a) * RS + (COUT == 16 ? pxt + bb : bb);
                     };
-                    if constexpr (BF) mfma_tiles_split<MP, 1, KS>(ap, wreg[py][pxt], acc[pxt], off);
-                    else mfma_tiles<MP, 1, KS, TAPX * 2>(ap, wreg[py][pxt], acc[pxt], off);
+                    mfma_tiles<MP, 1, KS, TAPX * 2>(ap, wreg[py][pxt], acc[pxt], off);
                 }
 #pragma unroll
                 for (int i = 0; i < MP; ++i) {
@@ -834,18 +813,13 @@ void convT_phase_kernel(Operand in, WeightView wv, float *__restrict__ out, Epil
 //   da  = A*dy + B*a_out + C   (BatchNorm backward folded into the load; CD channels on the dy grid, with a 1-pixel halo)
 //   T   = relu(scale*a_in + shift)   (the layer's input as the forward saw it; CX channels, the 2x grid, (2TH+2) x (2TW+8))
 // As two kernels each of them staged da (two tensors) and re-read a_in: 1.34 GB moved for 0.54 GB of tensors on enc.4 at
-// B = 2048.  One workgroup of 512 threads per CU (two waves per SIMD): the staging registers of both tiles are spread
-// over 512 threads (64 VGPRs per thread), which is what lets the transposed convolution's weights (48), the weight
-// gradient's accumulators (32) and the next tile's loads live together below 256 registers.
-//   data gradient   wave w takes M tiles w and w + 8 of the tile's TH x TW/16 (16 positions each), both output phase rows
-//   weight gradient wave w takes position row w: M = dy channels (one 16-row tile), N = (ct, ky, kx) in NTT tiles,
+// B = 2048.
+//   data gradient   M tiles of the tile's TH x TW/16 (16 positions each), both output phase rows
+//   weight gradient a wave takes position rows: M = dy channels (one 16-row tile), N = (ct, ky, kx) in NTT tiles,
 //                   K = the row's positions; the A operand is read 16 bytes per lane (positions 4 kq .. 4 kq + 3 of a
 //                   16-position span = K-steps 0..3), one ds_read_b128 per four MFMA steps
-// The weight-gradient accumulators persist over the workgroup's tiles; the eight waves are combined in wave order and the
+// The weight-gradient accumulators persist over the workgroup's tiles; the waves are combined in wave order and the
 // workgroup writes one slab (dm_reduce_slabs_multi adds the slabs in slab order): bit-reproducible.
-// FB_BLOCK threads per workgroup: 512 (one workgroup per CU, two waves per SIMD; the staging registers of both tiles
-// spread over 512 threads) or 256 (two independent workgroups per CU, whose load / commit phases can hide under each
-// other's matrix phase instead of all eight waves of a CU committing at the same time).
 template <int CD, int CX, int TH, int TW>
 struct FusedBwdGeom {
     static_assert(CD == 16 && CX == 8 && (TH == 8 || TH == 4) && TW % 16 == 0, "built for enc.4: 8 -> 16 channels");
@@ -854,232 +828,21 @@ struct FusedBwdGeom {
     static constexpr int TROWS = 2 * TH + 2, RST = 2 * TW + 8, TCOLS4 = RST / 4, PST = TROWS * RST;
     static constexpr int N = CX * 16, NTT = N / 16;
     static constexpr int TILE_FLOATS = CD * PS + CX * PST, RED_FLOATS = NTT * 256;
-    static constexpr int LDS_FLOATS = (TILE_FLOATS > RED_FLOATS ? TILE_FLOATS : RED_FLOATS) + 2 * DM_COEF_MAX_C * 4;
-    static constexpr size_t LDS_BYTES = (size_t)LDS_FLOATS * 4 + 8 * 16 * 2 * sizeof(double);
-    // role-split form: two tile buffers + the coefficient tables + the statistics scratch
-    static constexpr size_t SPLIT_LDS_BYTES = (size_t)(2 * TILE_FLOATS + 2 * DM_COEF_MAX_C * 4) * 4 + 8 * 16 * 2 * sizeof(double);
+    // two tile buffers + the coefficient tables + the statistics scratch
+    static constexpr size_t LDS_BYTES = (size_t)(2 * TILE_FLOATS + 2 * DM_COEF_MAX_C * 4) * 4 + 8 * 16 * 2 * sizeof(double);
     static_assert(RED_FLOATS <= TILE_FLOATS, "the slab combine reuses a tile buffer");
 };
 
-// TPRE: the next tile's T elements are prefetched into registers during the matrix phase like the da elements; false
-// (the 256-thread build): they are loaded at the top of the tile, while the da tile is committed -- their registers are
-// then dead during the matrix phase (64 fewer live there: no spills), and the load latency is left to the CU's other
-// workgroup to fill.
-template <int CD, int CX, int TH, int TW, int FB_BLOCK, bool TPRE>
-__global__ __launch_bounds__(FB_BLOCK, 2)
-void bwd_s2_fused_kernel(Operand dy, Operand tin, WeightView wv, float *__restrict__ dx, Epilogue ep,
-                         float *__restrict__ wslabs, int H, int W, int ntiles)
-{
-    using G = FusedBwdGeom<CD, CX, TH, TW>;
-    constexpr int FB_WAVES = FB_BLOCK / 64;
-    constexpr int IH = G::IH, RS = G::RS, COLS4 = G::COLS4, PS = G::PS;
-    constexpr int TROWS = G::TROWS, RST = G::RST, TCOLS4 = G::TCOLS4, PST = G::PST, NTT = G::NTT, N = G::N;
-    constexpr int CGN = TW / 16, MP = 2;                   // 16-position groups per row; M tiles in flight per wave
-    constexpr int NPASS = TH * CGN / (FB_WAVES * MP);      // data-gradient passes per wave: 1 (512 threads) or 2 (256)
-    constexpr int WROWS = TH / FB_WAVES;                   // weight-gradient position rows per wave: 1 or 2
-    static_assert(TH * CGN == FB_WAVES * MP * NPASS && TH == FB_WAVES * WROWS, "tile split over the waves");
-    constexpr int TAPX = 3, KS = (CD / 4) * 2 * TAPX;      // kernel C with 8 output channels: n = (px, co), 2 x 3 taps
-    extern __shared__ __attribute__((aligned(16))) float fb_lds[];
-    float *tileD = fb_lds, *tileT = fb_lds + CD * PS;
-    float *s_coefD = fb_lds + (G::LDS_FLOATS - 2 * DM_COEF_MAX_C * 4), *s_coefT = s_coefD + DM_COEF_MAX_C * 4;
-    double (*s_stat)[2] = reinterpret_cast<double (*)[2]>(fb_lds + G::LDS_FLOATS);
-
-    const int lane = threadIdx.x & 63, m = lane & 15, kq = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int OH = 2 * H, OW = 2 * W;
-    const int tiles_x = W / TW, tiles_y = H / TH;
-    const int co = m & 7, pxl = m >> 3;                    // data gradient: the lane's a_in channel and x phase
-
-    TileStage<CD, IH, COLS4, RS, PS, true, FB_BLOCK> stD;
-    TileStage<CX, TROWS, TCOLS4, RST, PST, false, FB_BLOCK> stT;
-    stD.init(H, W);
-    stT.init(OH, OW);
-    int tidx = blockIdx.x, b = 0, y0 = 0, x0 = 0;
-    if (tidx < ntiles) {
-        int t = tidx;
-        x0 = (t % tiles_x) * TW; t /= tiles_x;
-        y0 = (t % tiles_y) * TH; b = t / tiles_y;
-        stD.issue(dy, b, CD, H, W, y0 - 1, x0 - 4);
-        if constexpr (TPRE) stT.issue(tin, b, CX, OH, OW, 2 * y0 - 1, 2 * x0 - 4);
-        stage_coef(s_coefD, dy, b, CD);
-        stage_coef(s_coefT, tin, b, CX);
-    }
-
-    // data-gradient weights (kernel C, COUT = 8): N tile per phase row py, n = (px, co); step s = (cg4, a, bb)
-    float wreg[2][1][KS];
-#pragma unroll
-    for (int py = 0; py < 2; ++py)
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            const int cg4 = s / (2 * TAPX), j = s % (2 * TAPX), a = j / TAPX, bb = j % TAPX;
-            const int c = 4 * cg4 + kq;
-            const int ky = py + 3 - 2 * (py + a), kx = pxl + 3 - 2 * bb;
-            float wvl = 0.f;
-            if (ky >= 0 && ky <= 3 && kx >= 0 && kx <= 3) wvl = wv.w[wv.off + co * wv.sn + c * wv.sc + ky * wv.sky + kx * wv.skx];
-            wreg[py][0][s] = wvl;
-        }
-    float mc0, mc2;
-    mask_coef(ep, 0, co, mc0, mc2);
-    double s1 = 0.0, s2 = 0.0;
-    const int abase = kq * PS + m + 3;
-    EpiCtx<SIDE_MASK> cx;
-    const long long sample_elems = (long long)CX * OH * OW;
-    const int chan_off = (co * OH * OW + 8 * kq + 4 * pxl) * 4;
-
-    // weight gradient: B column n = 16 t + m = (ct, ky, kx); this lane's positions of a 16-position span are 4 kq .. 4 kq + 3
-    int bl[NTT];
-#pragma unroll
-    for (int t = 0; t < NTT; ++t) {
-        const int n = 16 * t + m;
-        bl[t] = (n >> 4) * PST + ((n >> 2) & 3) * RST + (n & 3) + 3 + 8 * kq + 2 * wave * RST;
-    }
-    const int al = m * PS + (wave + 1) * RS + 4 + 4 * kq;       // A row m = dy channel, position rows wave, wave + FB_WAVES
-    f32x4 wacc[NTT];
-#pragma unroll
-    for (int t = 0; t < NTT; ++t) wacc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    while (tidx < ntiles) {
-        if constexpr (!TPRE) stT.issue(tin, b, CX, OH, OW, 2 * y0 - 1, 2 * x0 - 4);      // (in flight across the barrier and the da commit)
-        __syncthreads();                                   // previous tile consumed
-        stD.commit(tileD, s_coefD, CD, H, W, y0 - 1, x0 - 4, dy.mode);
-        stT.commit(tileT, s_coefT, CX, OH, OW, 2 * y0 - 1, 2 * x0 - 4, tin.mode);
-        __syncthreads();
-        const int cb = b, cy0 = y0, cx0 = x0;
-        const int next = tidx + gridDim.x;
-        {
-            int t = next < ntiles ? next : tidx;
-            x0 = (t % tiles_x) * TW; t /= tiles_x;
-            y0 = (t % tiles_y) * TH; b = t / tiles_y;
-        }
-        const auto scD = stD.begin(dy, next < ntiles, b, CD, H, W, y0 - 1, x0 - 4);
-        const auto scT = stT.begin(tin, TPRE && next < ntiles, b, CX, OH, OW, 2 * y0 - 1, 2 * x0 - 4);
-        (void)scT;
-        cx.rebase(ep, dx, sample_elems, cb);
-        constexpr int NED = decltype(stD)::N, NET = decltype(stT)::N;
-
-        // ---- data gradient: M tiles wave + FB_WAVES * (MP * pass + i), phase rows py = 0, 1 ------------------------------
-#pragma unroll
-        for (int pass = 0; pass < NPASS; ++pass) {
-            const float *ap[MP];
-            int obase[MP];
-#pragma unroll
-            for (int i = 0; i < MP; ++i) {
-                const int ti = wave + FB_WAVES * (MP * pass + i);
-                const int r = ti / CGN, cg = ti % CGN;
-                ap[i] = tileD + r * RS + 16 * cg + abase;
-                obase[i] = chan_off + (2 * (cy0 + r) * OW + 2 * (cx0 + 16 * cg)) * 4;
-            }
-#pragma unroll
-            for (int py = 0; py < 2; ++py) {
-                // the next tile's da elements are requested under the products of this one
-                constexpr int NQ = 2 * NPASS;
-                const int qd = 2 * pass + py;
-#pragma unroll
-                for (int e = 0; e < NED; ++e)
-                    if (e >= qd * NED / NQ && e < (qd + 1) * NED / NQ) stD.issue_one(e, scD);
-                EpiIn<SIDE_MASK> e[MP];
-#pragma unroll
-                for (int i = 0; i < MP; ++i) epilogue_loads<SIDE_MASK>(e[i], cx, obase[i] + py * OW * 4);
-                f32x4 acc[MP][1];
-#pragma unroll
-                for (int i = 0; i < MP; ++i) acc[i][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                auto off = [py](int s) {
-                    const int cg4 = s / (2 * TAPX), j = s % (2 * TAPX), a = j / TAPX, bb = j % TAPX;
-                    return 4 * cg4 * PS + (py + a) * RS + bb;
-                };
-                mfma_tiles<MP, 1, KS, TAPX * 2>(ap, wreg[py], acc, off);
-#pragma unroll
-                for (int i = 0; i < MP; ++i) {
-                    const f32x4 v = acc[i][0];
-                    const f32x4 pv = lane_xor8(v);         // partner lane holds the other x phase of the same channel
-                    epilogue_tail<SIDE_MASK>(pxl ? (f32x4){pv.z, v.z, pv.w, v.w} : (f32x4){v.x, pv.x, v.y, pv.y}, ep, cx,
-                                             e[i], mc0, mc2, obase[i] + py * OW * 4, s1, s2);
-                }
-            }
-        }
-
-        // ---- weight gradient: position rows wave (+ FB_WAVES), TW / 16 spans of 16 positions, 4 K-steps per span ---------
-        {
-            constexpr int NSPAN = TW / 16, NQ = WROWS * NSPAN * 4;      // q = (row, span, K-step)
-            auto aoff = [](int q) { return (q / (NSPAN * 4)) * FB_WAVES * RS + 16 * ((q >> 2) % NSPAN); };
-            auto boff = [](int q) { return (q / (NSPAN * 4)) * FB_WAVES * 2 * RST + 32 * ((q >> 2) % NSPAN) + 2 * (q & 3); };
-            f32x4 av[2];
-            float bv[2][NTT];
-            av[0] = *reinterpret_cast<const f32x4 *>(tileD + al);
-#pragma unroll
-            for (int t = 0; t < NTT; ++t) bv[0][t] = tileT[bl[t]];
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                if (q + 1 < NQ) {
-                    if (((q + 1) & 3) == 0) av[((q + 1) >> 2) & 1] = *reinterpret_cast<const f32x4 *>(tileD + al + aoff(q + 1));
-#pragma unroll
-                    for (int t = 0; t < NTT; ++t) bv[(q + 1) & 1][t] = tileT[bl[t] + boff(q + 1)];
-                }
-                // the next tile's T elements trickle out between the steps
-                if constexpr (TPRE) {
-#pragma unroll
-                    for (int e = 0; e < NET; ++e)
-                        if (e >= q * NET / NQ && e < (q + 1) * NET / NQ) stT.issue_one(e, scT);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                const float a = av[(q >> 2) & 1][q & 3];
-#pragma unroll
-                for (int t = 0; t < NTT; ++t) wacc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv[q & 1][t], wacc[t], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        tidx = next;
-    }
-
-    // ---- statistics of the data gradient: (sum v, sum v * a_in) per a_in channel -> stats[blockIdx][CX][2] --------------
-    if (ep.stats) {
-        double a = s1, c = s2;
-        a += __shfl_xor(a, 16, 64); c += __shfl_xor(c, 16, 64);
-        a += __shfl_xor(a, 32, 64); c += __shfl_xor(c, 32, 64);
-        a += __shfl_xor(a, 8, 64); c += __shfl_xor(c, 8, 64);
-        if (lane < CX) { s_stat[wave * 16 + lane][0] = a; s_stat[wave * 16 + lane][1] = c; }
-        __syncthreads();
-        if (threadIdx.x < CX) {
-            double ta = 0.0, tc = 0.0;
-#pragma unroll
-            for (int w = 0; w < FB_WAVES; ++w) { ta += s_stat[w * 16 + threadIdx.x][0]; tc += s_stat[w * 16 + threadIdx.x][1]; }
-            ep.stats[((long long)blockIdx.x * CX + threadIdx.x) * 2 + 0] = ta;
-            ep.stats[((long long)blockIdx.x * CX + threadIdx.x) * 2 + 1] = tc;
-        }
-    }
-    // ---- weight-gradient slab: the waves in wave order.  wacc[t][j] is dy channel 4 (lane >> 4) + j, column 16 t + m
-    float *red = fb_lds;
-    for (int w = 0; w < FB_WAVES; ++w) {
-        __syncthreads();
-        if (wave == w) {
-#pragma unroll
-            for (int t = 0; t < NTT; ++t) {
-                f32x4 *p = reinterpret_cast<f32x4 *>(red + (t * 64 + lane) * 4);
-                if (w == 0) *p = wacc[t];
-                else *p = *p + wacc[t];
-            }
-        }
-    }
-    __syncthreads();
-    float *slab = wslabs + (long long)blockIdx.x * (CD * N);
-    for (int i = threadIdx.x; i < NTT * 256; i += FB_BLOCK) {
-        const int j = i & 3, l = (i >> 2) & 63, t = i >> 8;
-        slab[(4 * (l >> 4) + j) * N + 16 * t + (l & 15)] = red[i];
-    }
-}
-
-// ---- kernel D, role-split form.  One 512-thread workgroup per CU, TWO LDS buffers (2 x 67 KB), and two kinds of waves:
-//   waves 0..3  data gradient of tile i (kernel C's products and epilogue) -- they never touch global inputs;
-//   waves 4..7  request tile i+1 (every load up front), run the weight-gradient products of tile i while the loads are
-//               in flight, then transform + write tile i+1 into the other buffer.
-// Each SIMD hosts one wave of either kind, one barrier per tile.  With all eight waves in the same phase (the form above)
-// the matrix pipe idles while everybody commits and waits at the two barriers: 261 us for enc.4 at B = 2048 against a
-// 137 us matrix floor; here the commit, the load latency and the epilogue of one kind overlap the other kind's products.
-// The two kinds run separate loops (same trip count, one s_barrier per iteration each): their registers -- transposed-
-// convolution weights on one side, weight-gradient accumulators and 32 staged float4 on the other -- are then never live
-// together.
-// BF: split-bf16 operands (tile.h: split_pack4) -- both LDS tiles and the transposed-convolution weights hold (hi, lo) bf16
-// pairs, the products run on v_mfma_f32_16x16x32_bf16 at four K-steps per instruction pair: a quarter of the matrix time.
+// ---- kernel D: one 768-thread workgroup per CU, TWO LDS buffers and three kinds of waves (round 5), one barrier per tile:
+//   waves 0..3   data gradient of tile i (products + epilogue) -- they never touch global inputs
+//   waves 4..7   loads of tile i+1, BatchNorm-backward / ReLU transform, LDS writes into the other buffer -- vector work only
+//   waves 8..11  weight-gradient products of tile i
+// With every wave in the same phase (one buffer) the matrix pipe idled while everybody committed and waited at the two
+// barriers: 261 us for enc.4 at B = 2048 against a 137 us matrix floor.  With two roles (loads and weight gradient in the same
+// waves) a SIMD hosts two matrix-heavy waves and its port idles 37 % of the time (both waiting at once: LDS reads behind the
+// barrier, the loader's global loads, the epilogue's stores); the third wave's transform and commit fill those gaps.  Every role
+// stays below 168 registers: the staging registers (100) and the weight-gradient accumulators never meet in one wave.  (A second
+// group of data-gradient waves, 1024 threads, measured slower: 240.6 against 227.4 us.)
 // ZF (round 5; a tile spans the row, TW == W): the data gradient without structural zeros.  Folding both x phases of an
 // output pixel pair into the 16-wide N dimension makes them share a window of THREE dy columns of which each uses two: a third
 // of the 24 K-steps multiplies zeros.  The centre column (kx = 1 + px) is used by BOTH phases; the outer ones by one each
@@ -1089,19 +852,20 @@ void bwd_s2_fused_kernel(Operand dy, Operand tin, WeightView wv, float *__restri
 // the side accumulator shifted by one M row, a register rename inside a lane plus one cross-lane value per M tile
 // (ds_bpermute); columns -1 and W are the zero padding.  16 matrix instructions per M tile and phase row instead of 24, a
 // third of the A-operand LDS reads, 32 weight registers instead of 48.
-template <int CD, int CX, int TH, int TW, bool BF, bool ZF>
-__global__ __launch_bounds__(512, 2)
-void bwd_s2_split_kernel(Operand dy, Operand tin, WeightView wv, float *__restrict__ dx, Epilogue ep,
+template <int CD, int CX, int TH, int TW, bool ZF>
+__global__ __launch_bounds__(768, 1)
+void bwd_s2_roles3_kernel(Operand dy, Operand tin, WeightView wv, float *__restrict__ dx, Epilogue ep,
                          float *__restrict__ wslabs, int H, int W, int ntiles, int dbg)
 {
-    // dbg (DM_FUSED_BWD_DBG, measurements only; results are then wrong): 1 skips the weight-gradient products, 2 the data
-    // gradient, 4 the loads and commits of every tile but the first
+    // dbg: always 0 (it once switched parts off for measurements).  It stays a run-time argument because the compiler
+    // contracts a different set of multiply-adds in the 8 x 32 forms without its three tests, which changes enc.4's data
+    // gradient in the last bits.
     using G = FusedBwdGeom<CD, CX, TH, TW>;
     constexpr int RW = 4;                                   // waves per role
     constexpr int IH = G::IH, RS = G::RS, COLS4 = G::COLS4, PS = G::PS;
     constexpr int TROWS = G::TROWS, RST = G::RST, TCOLS4 = G::TCOLS4, PST = G::PST, NTT = G::NTT, N = G::N;
     constexpr int BUF = CD * PS + CX * PST;                 // floats of one (da, T) tile pair
-    constexpr int CGN = TW / 16, MP = 2, NPASS = TH * CGN / (RW * MP), WROWS = TH / RW;
+    constexpr int CGN = TW / 16, MP = ZF ? CGN : 2, NPASS = TH * CGN / (RW * MP), WROWS = TH / RW;     // ZF: a wave takes a whole row
     static_assert(TH * CGN == RW * MP * NPASS && TH == RW * WROWS, "tile split over the waves of a role");
     constexpr int TAPX = 3, KS = (CD / 4) * 2 * TAPX;
     extern __shared__ __attribute__((aligned(16))) float fb_lds[];
@@ -1110,7 +874,7 @@ void bwd_s2_split_kernel(Operand dy, Operand tin, WeightView wv, float *__restri
 
     const int lane = threadIdx.x & 63, m = lane & 15, kq = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const bool loader = wave >= RW;                         // (wave-uniform)
+    const int role = wave / RW;                             // (wave-uniform) 0: data gradient, 1: loads + commit, 2: weight gradient
     const int rw = wave & (RW - 1);
     const int OH = 2 * H, OW = 2 * W;
     const int tiles_x = W / TW, tiles_y = H / TH;
@@ -1122,8 +886,8 @@ void bwd_s2_split_kernel(Operand dy, Operand tin, WeightView wv, float *__restri
     stage_coef(s_coefT, tin, 0, CX);
     int tidx = blockIdx.x;
 
-    if (loader) {
-        // ================================================================ waves 4..7: loads, commits, weight gradient
+    if (role == 1) {
+        // ================================================================ waves 4..7: loads, transform, commits
         TileStage<CD, IH, COLS4, RS, PS, true, 256> stD;
         TileStage<CX, TROWS, TCOLS4, RST, PST, false, 256> stT;
         const int tl = (int)threadIdx.x - 256;
@@ -1133,8 +897,35 @@ void bwd_s2_split_kernel(Operand dy, Operand tin, WeightView wv, float *__restri
         if (tidx < ntiles) {
             coords(tidx, b, y0, x0);
             stD.issue(dy, b, CD, H, W, y0 - 1, x0 - 4);
-            stT.issue(tin, b, CX, OH, OW, 2 * y0 - 1, 2 * x0 - 4);
         }
+        __syncthreads();                                    // coefficient tables staged
+        if (tidx < ntiles) {
+            stD.commit(fb_lds, s_coefD, CD, H, W, y0 - 1, x0 - 4, dy.mode);
+            stT.issue(tin, b, CX, OH, OW, 2 * y0 - 1, 2 * x0 - 4);
+            stT.commit(fb_lds + CD * PS, s_coefT, CX, OH, OW, 2 * y0 - 1, 2 * x0 - 4, tin.mode);
+        }
+        __syncthreads();                                    // tile 0 in buffer 0
+        int p = 0;
+        while (tidx < ntiles) {
+            const int next = tidx + gridDim.x;
+            float *nxt = fb_lds + (1 - p) * BUF;
+            int nb = 0, ny0 = 0, nx0 = 0;
+            if (next < ntiles && !(dbg & 4)) {              // (uniform) the next tile into the other buffer (nobody reads it yet)
+                // the two tensors one after the other: these waves have the tile's whole duration for two round trips, and the
+                // staging registers of one tensor (56 / 44) fit where both (100) spilled
+                coords(next, nb, ny0, nx0);
+                stD.issue(dy, nb, CD, H, W, ny0 - 1, nx0 - 4);
+                stD.commit(nxt, s_coefD, CD, H, W, ny0 - 1, nx0 - 4, dy.mode);
+                stT.issue(tin, nb, CX, OH, OW, 2 * ny0 - 1, 2 * nx0 - 4);
+                stT.commit(nxt + CD * PS, s_coefT, CX, OH, OW, 2 * ny0 - 1, 2 * nx0 - 4, tin.mode);
+            }
+            __syncthreads();                                // tile i consumed by everybody, tile i+1 complete
+            p ^= 1;
+            tidx = next;
+        }
+        for (int w = 0; w < RW + 2; ++w) __syncthreads();      // (the other roles' slab combine and statistics)
+    } else if (role == 2) {
+        // ================================================================ waves 8..11: weight gradient
         int bl[NTT];
 #pragma unroll
         for (int t = 0; t < NTT; ++t) {
@@ -1146,62 +937,15 @@ void bwd_s2_split_kernel(Operand dy, Operand tin, WeightView wv, float *__restri
 #pragma unroll
         for (int t = 0; t < NTT; ++t) wacc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
         __syncthreads();                                    // coefficient tables staged
-        if (tidx < ntiles) {
-            stD.template commit<BF>(fb_lds, s_coefD, CD, H, W, y0 - 1, x0 - 4, dy.mode);
-            stT.template commit<BF>(fb_lds + CD * PS, s_coefT, CX, OH, OW, 2 * y0 - 1, 2 * x0 - 4, tin.mode);
-        }
         __syncthreads();                                    // tile 0 in buffer 0
         int p = 0;
         while (tidx < ntiles) {
-            const int next = tidx + gridDim.x;
             const float *cur = fb_lds + p * BUF;
-            float *nxt = fb_lds + (1 - p) * BUF;
-            int nb = 0, ny0 = 0, nx0 = 0;
-            if (next < ntiles && !(dbg & 4)) {              // (uniform) every load of the next tile, now
-                coords(next, nb, ny0, nx0);
-                stD.issue(dy, nb, CD, H, W, ny0 - 1, nx0 - 4);
-                stT.issue(tin, nb, CX, OH, OW, 2 * ny0 - 1, 2 * nx0 - 4);
-            }
             // ---- weight gradient of the current tile: position rows rw, rw + 4; spans of 16 positions; 4 K-steps per span
             if (!(dbg & 1)) {
                 constexpr int NSPAN = TW / 16, NQ = WROWS * NSPAN * 4;
                 auto aoff = [](int q) { return (q / (NSPAN * 4)) * RW * RS + 16 * ((q >> 2) % NSPAN); };
                 auto boff = [](int q) { return (q / (NSPAN * 4)) * RW * 2 * RST + 32 * ((q >> 2) % NSPAN) + 2 * (q & 3); };
-                if constexpr (BF) {
-                    // a span of 16 positions = four K-steps = ONE operand: A from one 16-byte read, B four 4-byte reads per
-                    // N tile; units of (span, half of the N tiles), the next unit's operands requested before this one's products
-                    constexpr int NU = WROWS * NSPAN * 2, HT = NTT / 2;
-                    f32x4 av[2];
-                    float bv[2][HT][4];
-                    av[0] = *reinterpret_cast<const f32x4 *>(cur + al);
-#pragma unroll
-                    for (int t = 0; t < HT; ++t)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) bv[0][t][j] = cur[bl[t] + boff(j)];
-#pragma unroll
-                    for (int u = 0; u < NU; ++u) {
-                        const int sp = u >> 1, half = u & 1;
-                        if (u + 1 < NU) {
-                            const int sp1 = (u + 1) >> 1, half1 = (u + 1) & 1;
-                            if (half1 == 0) av[sp1 & 1] = *reinterpret_cast<const f32x4 *>(cur + al + aoff(4 * sp1));
-#pragma unroll
-                            for (int t = 0; t < HT; ++t)
-#pragma unroll
-                                for (int j = 0; j < 4; ++j) bv[(u + 1) & 1][t][j] = cur[bl[half1 * HT + t] + boff(4 * sp1 + j)];
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                        const dm_u32x4_t a4 = __builtin_bit_cast(dm_u32x4_t, av[sp & 1]);
-                        const dm_u32x4_t ar = dm_rot16(a4);
-#pragma unroll
-                        for (int t = 0; t < HT; ++t) {
-                            const float(&b)[4] = bv[u & 1][t];
-                            const dm_u32x4_t b4 = {__builtin_bit_cast(unsigned, b[0]), __builtin_bit_cast(unsigned, b[1]),
-                                                   __builtin_bit_cast(unsigned, b[2]), __builtin_bit_cast(unsigned, b[3])};
-                            wacc[half * HT + t] = dm_mfma_split(a4, ar, b4, wacc[half * HT + t]);
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                } else {
                 f32x4 av[2];
                 float bv[2][NTT];
                 av[0] = *reinterpret_cast<const f32x4 *>(cur + al);
@@ -1220,17 +964,12 @@ void bwd_s2_split_kernel(Operand dy, Operand tin, WeightView wv, float *__restri
                     for (int t = 0; t < NTT; ++t) wacc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv[q & 1][t], wacc[t], 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                }
-            }
-            if (next < ntiles && !(dbg & 4)) {              // the next tile into the other buffer (nobody reads it yet)
-                stD.template commit<BF>(nxt, s_coefD, CD, H, W, ny0 - 1, nx0 - 4, dy.mode);
-                stT.template commit<BF>(nxt + CD * PS, s_coefT, CX, OH, OW, 2 * ny0 - 1, 2 * nx0 - 4, tin.mode);
             }
             __syncthreads();                                // tile i consumed by everybody, tile i+1 complete
             p ^= 1;
-            tidx = next;
+            tidx += gridDim.x;
         }
-        // ---- weight-gradient slab: the four loader waves in wave order (buffer 0 is free: the last barrier is behind us)
+        // ---- weight-gradient slab: the four weight-gradient waves in wave order (buffer 0 is free: the last barrier is behind us)
         float *red = fb_lds;
         for (int w = 0; w < RW; ++w) {
             __syncthreads();
@@ -1263,7 +1002,7 @@ void bwd_s2_split_kernel(Operand dy, Operand tin, WeightView wv, float *__restri
                     const int ky = py + 3 - 2 * (py + a);
                     float wvl = 0.f;
                     if (ky >= 0 && ky <= 3 && kx >= 0 && kx <= 3) wvl = wv.w[wv.off + co * wv.sn + c * wv.sc + ky * wv.sky + kx * wv.skx];
-                    wreg[py][t][s] = BF ? split_pack1(wvl) : wvl;
+                    wreg[py][t][s] = wvl;
                 }
         float mc0, mc2;
         mask_coef(ep, 0, co, mc0, mc2);
@@ -1314,323 +1053,7 @@ void bwd_s2_split_kernel(Operand dy, Operand tin, WeightView wv, float *__restri
                             return 4 * cg4 * PS + (py + a) * RS + bb;
                         }
                     };
-                    if constexpr (BF) mfma_tiles_split<MP, NTW, KSW>(ap, wreg[py], acc, off);
-                    else mfma_tiles<MP, NTW, KSW, ZF ? 4 : TAPX * 2>(ap, wreg[py], acc, off);
-                    f32x4 v[MP];
-                    if constexpr (ZF) {
-                        static_assert(MP == 2 && CGN == 2, "the two spans of a row in one wave");
-                        // row P of the side product goes to row P + 1 (px = 0) or P - 1 (px = 1) of the result; M row =
-                        // 16 i + 4 kq + register.  The one row per tile that crosses the lanes: the provider hands over its last
-                        // (px = 0) or first (px = 1) register, the receiver reads 16 lanes down / up (wrapping into the other span)
-                        float x[MP];
-#pragma unroll
-                        for (int i = 0; i < MP; ++i)
-                            x[i] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(
-                                       nb_addr, __builtin_bit_cast(int, pxl ? acc[i][1].x : acc[i][1].w)));
-#pragma unroll
-                        for (int i = 0; i < MP; ++i) {
-                            const f32x4 c = acc[i][0], sd = acc[i][1];
-                            // px = 0: first lane group of span 0 meets column -1 (zero), of span 1 the last group of span 0
-                            // px = 1: last lane group of span 1 meets column W (zero), of span 0 the first group of span 1
-                            const float e0 = grp_first ? (i == 0 ? 0.f : x[0]) : x[i];
-                            const float e1 = grp_last ? (i == MP - 1 ? 0.f : x[MP - 1]) : x[i];
-                            v[i] = pxl ? (f32x4){c.x + sd.y, c.y + sd.z, c.z + sd.w, c.w + e1}
-                                       : (f32x4){c.x + e0, c.y + sd.x, c.z + sd.y, c.w + sd.z};
-                        }
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < MP; ++i) v[i] = acc[i][0];
-                    }
-#pragma unroll
-                    for (int i = 0; i < MP; ++i) {
-                        const f32x4 pv = lane_xor8(v[i]);
-                        epilogue_tail<SIDE_MASK>(pxl ? (f32x4){pv.z, v[i].z, pv.w, v[i].w} : (f32x4){v[i].x, pv.x, v[i].y, pv.y}, ep, cx,
-                                                 e[i], mc0, mc2, obase[i] + py * OW * 4, s1, s2);
-                    }
-                }
-            }
-            }
-            __syncthreads();
-            p ^= 1;
-            tidx += gridDim.x;
-        }
-        // (the loaders combine their accumulators through LDS: RW + 1 barriers)
-        for (int w = 0; w < RW + 1; ++w) __syncthreads();
-        if (ep.stats) {
-            double a = s1, c = s2;
-            a += __shfl_xor(a, 16, 64); c += __shfl_xor(c, 16, 64);
-            a += __shfl_xor(a, 32, 64); c += __shfl_xor(c, 32, 64);
-            a += __shfl_xor(a, 8, 64); c += __shfl_xor(c, 8, 64);
-            if (lane < CX) { s_stat[rw * 16 + lane][0] = a; s_stat[rw * 16 + lane][1] = c; }
-        }
-        __syncthreads();
-        if (ep.stats && threadIdx.x < CX) {
-            double ta = 0.0, tc = 0.0;
-#pragma unroll
-            for (int w = 0; w < RW; ++w) { ta += s_stat[w * 16 + threadIdx.x][0]; tc += s_stat[w * 16 + threadIdx.x][1]; }
-            ep.stats[((long long)blockIdx.x * CX + threadIdx.x) * 2 + 0] = ta;
-            ep.stats[((long long)blockIdx.x * CX + threadIdx.x) * 2 + 1] = tc;
-        }
-    }
-    // (barriers after the tile loop: RW + 2 on either side)
-    // ---- all 512 threads: this workgroup's weight-gradient slab out of LDS.  red[(t * 64 + l) * 4 + j] is dy channel
-    //      4 (l >> 4) + j, column 16 t + (l & 15)
-    float *slab = wslabs + (long long)blockIdx.x * (CD * N);
-    for (int i = threadIdx.x; i < NTT * 256; i += 512) {
-        const int j = i & 3, l = (i >> 2) & 63, t = i >> 8;
-        slab[(4 * (l >> 4) + j) * N + 16 * t + (l & 15)] = fb_lds[i];
-    }
-}
-
-// ---- kernel D with three kinds of waves (round 5): 256 (2 + NDG) threads = 2 + NDG waves per SIMD, one barrier per tile as before.
-//   NDG groups of 4 waves   data gradient of tile i (products + epilogue); two groups: four rows of the tile each
-//   4 waves                 loads of tile i+1, BatchNorm-backward / ReLU transform, LDS writes into the other buffer -- vector work only
-//   4 waves                 weight-gradient products of tile i
-// In the two-role form a SIMD hosts two matrix-heavy waves and its port idles 37 % of the time (both waiting at once: LDS
-// reads behind the barrier, the loader's global loads, the epilogue's stores); the third wave's transform and commit fill
-// those gaps.  Every role stays below 168 registers: the staging registers (100) and the weight-gradient accumulators no
-// longer meet in one wave.
-template <int CD, int CX, int TH, int TW, bool BF, bool ZF, int NDG>
-__global__ __launch_bounds__(256 * (2 + NDG), 1)
-void bwd_s2_roles3_kernel(Operand dy, Operand tin, WeightView wv, float *__restrict__ dx, Epilogue ep,
-                         float *__restrict__ wslabs, int H, int W, int ntiles, int dbg)
-{
-    // dbg (DM_FUSED_BWD_DBG, measurements only; results are then wrong): 1 skips the weight-gradient products, 2 the data
-    // gradient, 4 the loads and commits of every tile but the first
-    using G = FusedBwdGeom<CD, CX, TH, TW>;
-    constexpr int RW = 4;                                   // waves per role
-    constexpr int IH = G::IH, RS = G::RS, COLS4 = G::COLS4, PS = G::PS;
-    constexpr int TROWS = G::TROWS, RST = G::RST, TCOLS4 = G::TCOLS4, PST = G::PST, NTT = G::NTT, N = G::N;
-    constexpr int BUF = CD * PS + CX * PST;                 // floats of one (da, T) tile pair
-    constexpr int CGN = TW / 16, MP = ZF ? CGN : 2, NPASS = TH * CGN / (RW * MP), WROWS = TH / RW;     // ZF: a wave takes a whole row
-    static_assert(TH * CGN == RW * MP * NPASS && TH == RW * WROWS, "tile split over the waves of a role");
-    constexpr int TAPX = 3, KS = (CD / 4) * 2 * TAPX;
-    extern __shared__ __attribute__((aligned(16))) float fb_lds[];
-    float *s_coefD = fb_lds + 2 * BUF, *s_coefT = s_coefD + DM_COEF_MAX_C * 4;
-    double (*s_stat)[2] = reinterpret_cast<double (*)[2]>(s_coefT + DM_COEF_MAX_C * 4);
-
-    const int lane = threadIdx.x & 63, m = lane & 15, kq = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    static_assert(NDG == 1 || NDG == 2, "one or two groups of data-gradient waves");
-    const int grp = wave / RW;                              // (wave-uniform) < NDG: data gradient, NDG: loads + commit, NDG + 1: weight gradient
-    const int role = grp < NDG ? 0 : grp - NDG + 1;
-    const int rw = wave & (RW - 1);
-    const int OH = 2 * H, OW = 2 * W;
-    const int tiles_x = W / TW, tiles_y = H / TH;
-    auto coords = [&](int t, int &tb, int &ty0, int &tx0) {
-        tx0 = (t % tiles_x) * TW; t /= tiles_x;
-        ty0 = (t % tiles_y) * TH; tb = t / tiles_y;
-    };
-    stage_coef(s_coefD, dy, 0, CD);
-    stage_coef(s_coefT, tin, 0, CX);
-    int tidx = blockIdx.x;
-
-    if (role == 1) {
-        // ================================================================ waves 4..7: loads, transform, commits
-        TileStage<CD, IH, COLS4, RS, PS, true, 256> stD;
-        TileStage<CX, TROWS, TCOLS4, RST, PST, false, 256> stT;
-        const int tl = (int)threadIdx.x - 256 * NDG;
-        stD.init(H, W, tl);
-        stT.init(OH, OW, tl);
-        int b, y0, x0;
-        if (tidx < ntiles) {
-            coords(tidx, b, y0, x0);
-            stD.issue(dy, b, CD, H, W, y0 - 1, x0 - 4);
-        }
-        __syncthreads();                                    // coefficient tables staged
-        if (tidx < ntiles) {
-            stD.template commit<BF>(fb_lds, s_coefD, CD, H, W, y0 - 1, x0 - 4, dy.mode);
-            stT.issue(tin, b, CX, OH, OW, 2 * y0 - 1, 2 * x0 - 4);
-            stT.template commit<BF>(fb_lds + CD * PS, s_coefT, CX, OH, OW, 2 * y0 - 1, 2 * x0 - 4, tin.mode);
-        }
-        __syncthreads();                                    // tile 0 in buffer 0
-        int p = 0;
-        while (tidx < ntiles) {
-            const int next = tidx + gridDim.x;
-            float *nxt = fb_lds + (1 - p) * BUF;
-            int nb = 0, ny0 = 0, nx0 = 0;
-            if (next < ntiles && !(dbg & 4)) {              // (uniform) the next tile into the other buffer (nobody reads it yet)
-                // the two tensors one after the other: these waves have the tile's whole duration for two round trips, and the
-                // staging registers of one tensor (56 / 44) fit where both (100) spilled
-                coords(next, nb, ny0, nx0);
-                stD.issue(dy, nb, CD, H, W, ny0 - 1, nx0 - 4);
-                stD.template commit<BF>(nxt, s_coefD, CD, H, W, ny0 - 1, nx0 - 4, dy.mode);
-                stT.issue(tin, nb, CX, OH, OW, 2 * ny0 - 1, 2 * nx0 - 4);
-                stT.template commit<BF>(nxt + CD * PS, s_coefT, CX, OH, OW, 2 * ny0 - 1, 2 * nx0 - 4, tin.mode);
-            }
-            __syncthreads();                                // tile i consumed by everybody, tile i+1 complete
-            p ^= 1;
-            tidx = next;
-        }
-        for (int w = 0; w < RW + 2; ++w) __syncthreads();      // (the other roles' slab combine and statistics)
-    } else if (role == 2) {
-        // ================================================================ waves 8..11: weight gradient
-        int bl[NTT];
-#pragma unroll
-        for (int t = 0; t < NTT; ++t) {
-            const int n = 16 * t + m;
-            bl[t] = CD * PS + (n >> 4) * PST + ((n >> 2) & 3) * RST + (n & 3) + 3 + 8 * kq + 2 * rw * RST;
-        }
-        const int al = m * PS + (rw + 1) * RS + 4 + 4 * kq;
-        f32x4 wacc[NTT];
-#pragma unroll
-        for (int t = 0; t < NTT; ++t) wacc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        __syncthreads();                                    // coefficient tables staged
-        __syncthreads();                                    // tile 0 in buffer 0
-        int p = 0;
-        while (tidx < ntiles) {
-            const float *cur = fb_lds + p * BUF;
-            // ---- weight gradient of the current tile: position rows rw, rw + 4; spans of 16 positions; 4 K-steps per span
-            if (!(dbg & 1)) {
-                constexpr int NSPAN = TW / 16, NQ = WROWS * NSPAN * 4;
-                auto aoff = [](int q) { return (q / (NSPAN * 4)) * RW * RS + 16 * ((q >> 2) % NSPAN); };
-                auto boff = [](int q) { return (q / (NSPAN * 4)) * RW * 2 * RST + 32 * ((q >> 2) % NSPAN) + 2 * (q & 3); };
-                if constexpr (BF) {
-                    // a span of 16 positions = four K-steps = ONE operand: A from one 16-byte read, B four 4-byte reads per
-                    // N tile; units of (span, half of the N tiles), the next unit's operands requested before this one's products
-                    constexpr int NU = WROWS * NSPAN * 2, HT = NTT / 2;
-                    f32x4 av[2];
-                    float bv[2][HT][4];
-                    av[0] = *reinterpret_cast<const f32x4 *>(cur + al);
-#pragma unroll
-                    for (int t = 0; t < HT; ++t)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) bv[0][t][j] = cur[bl[t] + boff(j)];
-#pragma unroll
-                    for (int u = 0; u < NU; ++u) {
-                        const int sp = u >> 1, half = u & 1;
-                        if (u + 1 < NU) {
-                            const int sp1 = (u + 1) >> 1, half1 = (u + 1) & 1;
-                            if (half1 == 0) av[sp1 & 1] = *reinterpret_cast<const f32x4 *>(cur + al + aoff(4 * sp1));
-#pragma unroll
-                            for (int t = 0; t < HT; ++t)
-#pragma unroll
-                                for (int j = 0; j < 4; ++j) bv[(u + 1) & 1][t][j] = cur[bl[half1 * HT + t] + boff(4 * sp1 + j)];
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                        const dm_u32x4_t a4 = __builtin_bit_cast(dm_u32x4_t, av[sp & 1]);
-                        const dm_u32x4_t ar = dm_rot16(a4);
-#pragma unroll
-                        for (int t = 0; t < HT; ++t) {
-                            const float(&b)[4] = bv[u & 1][t];
-                            const dm_u32x4_t b4 = {__builtin_bit_cast(unsigned, b[0]), __builtin_bit_cast(unsigned, b[1]),
-                                                   __builtin_bit_cast(unsigned, b[2]), __builtin_bit_cast(unsigned, b[3])};
-                            wacc[half * HT + t] = dm_mfma_split(a4, ar, b4, wacc[half * HT + t]);
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                } else {
-                f32x4 av[2];
-                float bv[2][NTT];
-                av[0] = *reinterpret_cast<const f32x4 *>(cur + al);
-#pragma unroll
-                for (int t = 0; t < NTT; ++t) bv[0][t] = cur[bl[t]];
-#pragma unroll
-                for (int q = 0; q < NQ; ++q) {
-                    if (q + 1 < NQ) {
-                        if (((q + 1) & 3) == 0) av[((q + 1) >> 2) & 1] = *reinterpret_cast<const f32x4 *>(cur + al + aoff(q + 1));
-#pragma unroll
-                        for (int t = 0; t < NTT; ++t) bv[(q + 1) & 1][t] = cur[bl[t] + boff(q + 1)];
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    const float a = av[(q >> 2) & 1][q & 3];
-#pragma unroll
-                    for (int t = 0; t < NTT; ++t) wacc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv[q & 1][t], wacc[t], 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                }
-            }
-            __syncthreads();                                // tile i consumed by everybody, tile i+1 complete
-            p ^= 1;
-            tidx += gridDim.x;
-        }
-        // ---- weight-gradient slab: the four weight-gradient waves in wave order (buffer 0 is free: the last barrier is behind us)
-        float *red = fb_lds;
-        for (int w = 0; w < RW; ++w) {
-            __syncthreads();
-            if (rw == w) {
-#pragma unroll
-                for (int t = 0; t < NTT; ++t) {
-                    f32x4 *pp = reinterpret_cast<f32x4 *>(red + (t * 64 + lane) * 4);
-                    if (w == 0) *pp = wacc[t];
-                    else *pp = *pp + wacc[t];
-                }
-            }
-        }
-        __syncthreads();
-        __syncthreads();                                    // (the statistics write-out of the other role)
-    } else {
-        // ================================================================ waves 0..3: data gradient
-        const int co = m & 7, pxl = m >> 3;
-        constexpr int NTW = ZF ? 2 : 1, KSW = ZF ? (CD / 4) * 2 : KS;       // ZF: N tiles (centre, side) of 8 K-steps (cg4, a)
-        float wreg[2][NTW][KSW];
-#pragma unroll
-        for (int py = 0; py < 2; ++py)
-#pragma unroll
-            for (int t = 0; t < NTW; ++t)
-#pragma unroll
-                for (int s = 0; s < KSW; ++s) {
-                    int cg4, a, kx;
-                    if constexpr (ZF) { cg4 = s >> 1; a = s & 1; kx = t == 0 ? 1 + pxl : (pxl ? 0 : 3); }
-                    else { cg4 = s / (2 * TAPX); const int j = s % (2 * TAPX); a = j / TAPX; kx = pxl + 3 - 2 * (j % TAPX); }
-                    const int c = 4 * cg4 + kq;
-                    const int ky = py + 3 - 2 * (py + a);
-                    float wvl = 0.f;
-                    if (ky >= 0 && ky <= 3 && kx >= 0 && kx <= 3) wvl = wv.w[wv.off + co * wv.sn + c * wv.sc + ky * wv.sky + kx * wv.skx];
-                    wreg[py][t][s] = BF ? split_pack1(wvl) : wvl;
-                }
-        float mc0, mc2;
-        mask_coef(ep, 0, co, mc0, mc2);
-        double s1 = 0.0, s2 = 0.0;
-        const int abase = kq * PS + m + 3;
-        EpiCtx<SIDE_MASK> cx;
-        const long long sample_elems = (long long)CX * OH * OW;
-        const int chan_off = (co * OH * OW + 8 * kq + 4 * pxl) * 4;
-        // ZF: the lane that holds the neighbouring M row of this lane's first (px = 0) or last (px = 1) row: 16 lanes down or up
-        const int nb_addr = ((pxl ? lane + 16 : lane - 16) & 63) * 4;
-        const bool grp_first = kq == 0, grp_last = kq == 3;
-        __syncthreads();                                    // (coefficient tables)
-        __syncthreads();                                    // tile 0 in buffer 0
-        int p = 0;
-        while (tidx < ntiles) {
-            int cb, cy0, cx0;
-            coords(tidx, cb, cy0, cx0);
-            const float *cur = fb_lds + p * BUF;
-            cx.rebase(ep, dx, sample_elems, cb);
-            if (!(dbg & 2)) {
-#pragma unroll
-            for (int pass0 = 0; pass0 < NPASS / NDG; ++pass0) {
-                const int pass = NDG == 1 ? pass0 : __builtin_amdgcn_readfirstlane(grp) + NDG * pass0;      // (two groups: one pass each)
-                const float *ap[MP];
-                int obase[MP];
-#pragma unroll
-                for (int i = 0; i < MP; ++i) {
-                    // ZF: a wave takes BOTH 16-position spans of a row (the side accumulators of neighbouring spans meet in
-                    // its registers); else M tile rw + RW * (MP * pass + i)
-                    const int ti = rw + RW * (MP * pass + i);
-                    const int r = ZF ? rw + RW * pass : ti / CGN, cg = ZF ? i : ti % CGN;
-                    ap[i] = cur + r * RS + 16 * cg + abase;
-                    obase[i] = chan_off + (2 * (cy0 + r) * OW + 2 * (cx0 + 16 * cg)) * 4;
-                }
-#pragma unroll
-                for (int py = 0; py < 2; ++py) {
-                    EpiIn<SIDE_MASK> e[MP];
-#pragma unroll
-                    for (int i = 0; i < MP; ++i) epilogue_loads<SIDE_MASK>(e[i], cx, obase[i] + py * OW * 4);
-                    f32x4 acc[MP][NTW];
-#pragma unroll
-                    for (int i = 0; i < MP; ++i)
-#pragma unroll
-                        for (int t = 0; t < NTW; ++t) acc[i][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                    auto off = [py](int s) {
-                        if constexpr (ZF) return 4 * (s >> 1) * PS + (py + (s & 1)) * RS + 1;
-                        else {
-                            const int cg4 = s / (2 * TAPX), j = s % (2 * TAPX), a = j / TAPX, bb = j % TAPX;
-                            return 4 * cg4 * PS + (py + a) * RS + bb;
-                        }
-                    };
-                    if constexpr (BF) mfma_tiles_split<MP, NTW, KSW>(ap, wreg[py], acc, off);
-                    else mfma_tiles<MP, NTW, KSW, ZF ? 4 : TAPX * 2>(ap, wreg[py], acc, off);
+                    mfma_tiles<MP, NTW, KSW, ZF ? 4 : TAPX * 2>(ap, wreg[py], acc, off);
                     f32x4 v[MP];
                     if constexpr (ZF) {
                         static_assert(MP == CGN, "every span of a row in one wave");
@@ -1676,13 +1099,13 @@ void bwd_s2_roles3_kernel(Operand dy, Operand tin, WeightView wv, float *__restr
             a += __shfl_xor(a, 16, 64); c += __shfl_xor(c, 16, 64);
             a += __shfl_xor(a, 32, 64); c += __shfl_xor(c, 32, 64);
             a += __shfl_xor(a, 8, 64); c += __shfl_xor(c, 8, 64);
-            if (lane < CX) { s_stat[(grp * RW + rw) * 16 + lane][0] = a; s_stat[(grp * RW + rw) * 16 + lane][1] = c; }
+            if (lane < CX) { s_stat[rw * 16 + lane][0] = a; s_stat[rw * 16 + lane][1] = c; }
         }
         __syncthreads();
         if (ep.stats && threadIdx.x < CX) {
             double ta = 0.0, tc = 0.0;
 #pragma unroll
-            for (int w = 0; w < RW * NDG; ++w) { ta += s_stat[w * 16 + threadIdx.x][0]; tc += s_stat[w * 16 + threadIdx.x][1]; }
+            for (int w = 0; w < RW; ++w) { ta += s_stat[w * 16 + threadIdx.x][0]; tc += s_stat[w * 16 + threadIdx.x][1]; }
             ep.stats[((long long)blockIdx.x * CX + threadIdx.x) * 2 + 0] = ta;
             ep.stats[((long long)blockIdx.x * CX + threadIdx.x) * 2 + 1] = tc;
         }
@@ -1691,7 +1114,7 @@ void bwd_s2_roles3_kernel(Operand dy, Operand tin, WeightView wv, float *__restr
     // ---- all 512 threads: this workgroup's weight-gradient slab out of LDS.  red[(t * 64 + l) * 4 + j] is dy channel
     //      4 (l >> 4) + j, column 16 t + (l & 15)
     float *slab = wslabs + (long long)blockIdx.x * (CD * N);
-    for (int i = threadIdx.x; i < NTT * 256; i += 256 * (2 + NDG)) {
+    for (int i = threadIdx.x; i < NTT * 256; i += 768) {
         const int j = i & 3, l = (i >> 2) & 63, t = i >> 8;
         slab[(4 * (l >> 4) + j) * N + 16 * t + (l & 15)] = fb_lds[i];
     }
@@ -1743,13 +1166,6 @@ int conv4_tw(int CIN, int Wo)
     return Wo < cap ? Wo : cap;
 }
 
-// the first convolution with output positions in pairs (kernel A2); DM_CONV4_PAIR=0 keeps kernel A for A/B runs
-bool conv4_pair_on()
-{
-    static const bool off = [] { const char *e = getenv("DM_CONV4_PAIR"); return e && e[0] == '0'; }();
-    return !off;
-}
-
 template <int CIN, int TW>
 void launch_conv4(const ConvArgs &a)
 {
@@ -1759,28 +1175,13 @@ void launch_conv4(const ConvArgs &a)
 #define DM_L4(SIDE_)                                                                                              \
     {                                                                                                             \
         constexpr int WPS = conv_wps(LDS, CIN * 4, F4, false, 2, 1, SIDE_);                                       \
-        if (DM_FWD_SPLIT(SIDE_ == SIDE_NONE)) {                                                                   \
-            if (CIN <= 5 && a.ep.bias_border)                                                                     \
-                hipLaunchKernelGGL((conv4x4s2_kernel<CIN, 1, TH, TW, SIDE_NONE, WPS, true, MEASURE_BF>),              \
-                                   dim3(conv_grid(ntiles, WPS, a.per_tile)), dim3(DM_BLOCK), 0, a.stream, a.in, a.wv, \
-                                   a.out, a.ep, a.Cphys, a.NOUT, a.H, a.W, ntiles, conv_slabs(ntiles, a.per_tile),    \
-                                   a.per_tile);                                                                       \
-            else                                                                                                  \
-                hipLaunchKernelGGL((conv4x4s2_kernel<CIN, 1, TH, TW, SIDE_NONE, WPS, false, MEASURE_BF>),             \
-                                   dim3(conv_grid(ntiles, WPS, a.per_tile)), dim3(DM_BLOCK), 0, a.stream, a.in, a.wv, \
-                                   a.out, a.ep, a.Cphys, a.NOUT, a.H, a.W, ntiles, conv_slabs(ntiles, a.per_tile),    \
-                                   a.per_tile);                                                                       \
-        } else if (SIDE_ == SIDE_NONE && CIN <= 4 && TW == 64 && a.NOUT == 8 && a.ep.bias_border && !a.ep.relu && conv4_pair_on()) \
+        /* the first convolution with output positions in pairs (kernel A2) */                                   \
+        if (SIDE_ == SIDE_NONE && CIN <= 4 && TW == 64 && a.NOUT == 8 && a.ep.bias_border && !a.ep.relu)             \
             hipLaunchKernelGGL((conv4x4s2_pair_kernel<CIN <= 4 ? CIN : 1, TH, WPS>),                                   \
                                dim3(conv_grid(ntiles, WPS, a.per_tile)), dim3(DM_BLOCK), 0, a.stream, a.in, a.wv,     \
                                a.out, a.ep, a.Cphys, a.H, a.W, ntiles, conv_slabs(ntiles, a.per_tile), a.per_tile);    \
         else if (SIDE_ == SIDE_NONE && CIN <= 5 && a.ep.bias_border)                                              \
             hipLaunchKernelGGL((conv4x4s2_kernel<CIN, 1, TH, TW, SIDE_NONE, WPS, true>),                              \
-                               dim3(conv_grid(ntiles, WPS, a.per_tile)), dim3(DM_BLOCK), 0, a.stream, a.in, a.wv,     \
-                               a.out, a.ep, a.Cphys, a.NOUT, a.H, a.W, ntiles, conv_slabs(ntiles, a.per_tile),        \
-                               a.per_tile);                                                                           \
-        else if (SIDE_ != SIDE_NONE && dm_backward_split_bf16())        /* a data gradient: split-bf16 operands */ \
-            hipLaunchKernelGGL((conv4x4s2_kernel<CIN, 1, TH, TW, SIDE_, WPS, false, DM_BUILD_SPLIT_BF16 && SIDE_ != SIDE_NONE>),             \
                                dim3(conv_grid(ntiles, WPS, a.per_tile)), dim3(DM_BLOCK), 0, a.stream, a.in, a.wv,     \
                                a.out, a.ep, a.Cphys, a.NOUT, a.H, a.W, ntiles, conv_slabs(ntiles, a.per_tile),        \
                                a.per_tile);                                                                           \
@@ -1821,13 +1222,6 @@ void launch_conv3(const ConvArgs &a)
 #define DM_L3(TWO_, SIDE_)                                                                                        \
     {                                                                                                             \
         constexpr int WPS = conv_wps(LDS, NT * (CIN / 4) * TAPS, F4, TWO_, NT == 1 ? 2 : 1, NT, SIDE_);          \
-        constexpr bool GRAD = (TWO_ || SIDE_ != SIDE_NONE) && ((CIN / 4) * TAPS) % 4 == 0;   /* a data gradient */      \
-        constexpr bool FWDK = ((CIN / 4) * TAPS) % 4 == 0;                                                        \
-        if ((GRAD && dm_backward_split_bf16()) || DM_FWD_SPLIT(!GRAD && FWDK))                                    \
-            hipLaunchKernelGGL((conv3x3_kernel<CIN, NT, NPASS, TAPS, PIX, TH, TW, TWO_, SIDE_, WPS, (DM_BUILD_SPLIT_BF16 && GRAD) || (MEASURE_BF && FWDK)>),           \
-                               dim3(conv_grid(ntiles, WPS, a.per_tile, NPASS)), dim3(DM_BLOCK), 0, a.stream, a.in, a.wv, \
-                               a.out, a.ep, a.Cphys, a.NOUT, a.H, a.W, ntiles, conv_slabs(ntiles, a.per_tile), a.per_tile); \
-        else                                                                                                      \
         hipLaunchKernelGGL((conv3x3_kernel<CIN, NT, NPASS, TAPS, PIX, TH, TW, TWO_, SIDE_, WPS>),                 \
                            dim3(conv_grid(ntiles, WPS, a.per_tile, NPASS)), dim3(DM_BLOCK), 0, a.stream, a.in, a.wv, \
                            a.out, a.ep, a.Cphys, a.NOUT, a.H, a.W, ntiles, conv_slabs(ntiles, a.per_tile), a.per_tile); \
@@ -1853,12 +1247,6 @@ void launch_convT_phase(const ConvArgs &a)
 #define DM_LP(TWO_, SIDE_)                                                                                        \
     {                                                                                                             \
         constexpr int WPS = clampi(conv_wps(LDS, KSW, F4, TWO_, 2, COUT == 16 ? 2 : 1, SIDE_), 1, 2);             \
-        constexpr bool GRAD = TWO_ || SIDE_ != SIDE_NONE;                  /* a data gradient */                     \
-        if ((GRAD && dm_backward_split_bf16()) || DM_FWD_SPLIT(!GRAD))                                            \
-            hipLaunchKernelGGL((convT_phase_kernel<CIN, COUT, TH, TW, TWO_, SIDE_, WPS, (DM_BUILD_SPLIT_BF16 && GRAD) || MEASURE_BF>),         \
-                               dim3(conv_grid(ntiles, WPS, a.per_tile)), dim3(DM_BLOCK), 0, a.stream, a.in, a.wv,     \
-                               a.out, a.ep, a.Cphys, a.H, a.W, ntiles, conv_slabs(ntiles, a.per_tile));               \
-        else                                                                                                      \
         hipLaunchKernelGGL((convT_phase_kernel<CIN, COUT, TH, TW, TWO_, SIDE_, WPS>),                             \
                            dim3(conv_grid(ntiles, WPS, a.per_tile)), dim3(DM_BLOCK), 0, a.stream, a.in, a.wv,     \
                            a.out, a.ep, a.Cphys, a.H, a.W, ntiles, conv_slabs(ntiles, a.per_tile));               \
@@ -2074,62 +1462,21 @@ static bool fused_bwd_shape(int CD, int CX, int H, int W)
 
 extern "C" int dm_conv_bwd_s2_fused_supported(int CD, int CX, int H, int W) { return fused_bwd_shape(CD, CX, H, W) ? 1 : 0; }
 
-// form of kernel D: 0 = role-split (default: one 512-thread workgroup per CU, two LDS buffers), 512 / 256 = the lockstep
-// forms with that many threads per workgroup (DM_FUSED_BWD_BLOCK=512|256 in the environment: A/B measurements)
-static int fused_bwd_block()
-{
-    static const int v = [] { const char *e = getenv("DM_FUSED_BWD_BLOCK"); const int n = e ? atoi(e) : 0; return (n == 512 || n == 256) ? n : 0; }();
-    return v;
-}
-
 // Arithmetic of the BACKWARD matrix products (data and weight gradients): the f32-input instruction, bit for bit the fp32
 // multiply-add chain -- every number the library produces is plain fp32 arithmetic.  The split-bf16 alternative of rounds
-// 4-5 is retired (dm_common.h, DM_BUILD_SPLIT_BF16): asking for it is an error unless a measurement build instantiated it.
-static int g_backward_split = -1;
-bool dm_backward_split_bf16()
-{
-#if DM_BUILD_SPLIT_BF16
-    if (g_backward_split < 0) {
-        const char *e = getenv("DM_BACKWARD_PRECISION");
-        g_backward_split = (e && e[0] == 's') ? 1 : 0;
-        // an environment variable that changes results says so, once
-        if (g_backward_split)
-            fprintf(stderr, "libdynamorph_hip: DM_BACKWARD_PRECISION=%s -- gradient products run on split-bf16 operands "
-                            "(~2^-17 relative per product, not the fp32 chain); forward pass and codes unchanged\n", e);
-    }
-    return g_backward_split != 0;
-#else
-    return false;
-#endif
-}
+// 4-5 is retired (dm_common.h): asking for it is an error.
 extern "C" int dm_backward_precision(int mode)
 {
-    const int cur = dm_backward_split_bf16() ? 1 : 0;
-#if DM_BUILD_SPLIT_BF16
-    if (mode == 0 || mode == 1) g_backward_split = mode;
-#else
-    (void)g_backward_split;
     DM_REQUIRE(mode != 1, "dm_backward_precision: the split-bf16 gradient kernels are not built (retired: slower than the "
-                          "exact fp32 path on these layer widths; -DDM_BUILD_SPLIT_BF16=1 builds them for measurements)");
-#endif
-    return cur;
-}
-
-static int fused_bwd_dbg()
-{
-#ifdef DM_MEASURE      // ablation switches exist only in a measurement build (make measure): they make results wrong
-    static const int v = [] { const char *e = getenv("DM_FUSED_BWD_DBG"); return e ? atoi(e) : 0; }();
-#else
-    static const int v = 0;
-#endif
-    return v;
+                          "exact fp32 path on these layer widths)");
+    return 0;
 }
 
 extern "C" int dm_conv_bwd_s2_fused_num_blocks(int B, int CD, int CX, int H, int W)
 {
     if (B <= 0 || !fused_bwd_shape(CD, CX, H, W)) return -1;
     const long long ntiles = (long long)B * (H / 8) * (W / 32);
-    const long long cap = fused_bwd_block() == 256 ? 512 : 256;       // resident workgroups: one slab each
+    const long long cap = 256;                                        // resident workgroups: one slab each
     return (int)(ntiles < cap ? ntiles : cap);
 }
 
@@ -2150,73 +1497,33 @@ extern "C" int dm_conv_bwd_s2_fused(const dm_operand *dy, const dm_operand *tin,
                "dm_conv_bwd_s2_fused: the epilogue must mask by (and take its statistics against) the layer input");
     if (dm_check_operand(&ep->mask, "dm_conv_bwd_s2_fused(mask)")) return -1;
     using G = FusedBwdGeom<16, 8, 8, 32>;
+    using G64 = FusedBwdGeom<16, 8, 4, 64>;
     static DmPerDeviceOnce attr_set;
     if (attr_set.need()) {
-        hipError_t e = hipFuncSetAttribute((const void *)bwd_s2_fused_kernel<16, 8, 8, 32, 512, true>,
+        hipError_t e = hipFuncSetAttribute((const void *)bwd_s2_roles3_kernel<16, 8, 8, 32, false>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
         if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void *)bwd_s2_fused_kernel<16, 8, 8, 32, 256, false>,
+            e = hipFuncSetAttribute((const void *)bwd_s2_roles3_kernel<16, 8, 8, 32, true>,
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
-#define DM_SPLIT_ATTR(BF_, ZF_)                                                                                       \
-        if (e == hipSuccess)                                                                                         \
-            e = hipFuncSetAttribute((const void *)bwd_s2_split_kernel<16, 8, 8, 32, DM_BUILD_SPLIT_BF16 && BF_, ZF_>,                       \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::SPLIT_LDS_BYTES);
-        DM_SPLIT_ATTR(false, false) DM_SPLIT_ATTR(true, false) DM_SPLIT_ATTR(false, true) DM_SPLIT_ATTR(true, true)
-#undef DM_SPLIT_ATTR
-#define DM_ROLES3_ATTR(BF_, ZF_)                                                                                      \
-        if (e == hipSuccess)                                                                                         \
-            e = hipFuncSetAttribute((const void *)bwd_s2_roles3_kernel<16, 8, 8, 32, DM_BUILD_SPLIT_BF16 && BF_, ZF_, 1>,                   \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::SPLIT_LDS_BYTES);
-        DM_ROLES3_ATTR(false, false) DM_ROLES3_ATTR(true, false) DM_ROLES3_ATTR(false, true) DM_ROLES3_ATTR(true, true)
-#undef DM_ROLES3_ATTR
         if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void *)bwd_s2_roles3_kernel<16, 8, 4, 64, false, true, 1>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedBwdGeom<16, 8, 4, 64>::SPLIT_LDS_BYTES);
+            e = hipFuncSetAttribute((const void *)bwd_s2_roles3_kernel<16, 8, 4, 64, true>,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)G64::LDS_BYTES);
         if (e != hipSuccess) { dm_set_error("dm_conv_bwd_s2_fused: cannot reserve %zu bytes of LDS: %s", G::LDS_BYTES, hipGetErrorString(e)); return (int)e; }
         attr_set.mark();
     }
     const int ntiles = B * (H / 8) * (W / 32);
     const int grid = dm_conv_bwd_s2_fused_num_blocks(B, CD, CX, H, W);
-    // the data gradient without structural zeros where a tile spans the row (W == 32: enc.4 of 128-pixel patches);
-    // DM_FUSED_BWD_ZF=0 keeps the three-column mapping for A/B runs
-    static const bool zf_off = [] { const char *e = getenv("DM_FUSED_BWD_ZF"); return e && e[0] == '0'; }();
-    const bool zf = W == 32 && !zf_off;
-#define DM_SPLIT_LAUNCH(BF_, ZF_)                                                                                                  \
-        hipLaunchKernelGGL((bwd_s2_split_kernel<16, 8, 8, 32, DM_BUILD_SPLIT_BF16 && BF_, ZF_>), dim3(grid), dim3(512), G::SPLIT_LDS_BYTES, (hipStream_t)stream, \
-                           to_dev(dy), to_dev(tin), to_dev(w), dx, to_dev(ep), w_slabs, H, W, ntiles, fused_bwd_dbg())
-    // three roles (768 threads) or two (512): DM_FUSED_BWD_ROLES=2 keeps the two-role form for A/B runs
-    static const int roles = [] { const char *e = getenv("DM_FUSED_BWD_ROLES"); return e ? atoi(e) : 3; }();
-    const bool roles3 = roles >= 3;
-#define DM_ROLES3_LAUNCH(BF_, ZF_)                                                                                                 \
-        /* (a second group of data-gradient waves, NDG = 2 / 1024 threads, measured slower: 240.6 against 227.4 us) */                 \
-        { hipLaunchKernelGGL((bwd_s2_roles3_kernel<16, 8, 8, 32, DM_BUILD_SPLIT_BF16 && BF_, ZF_, 1>), dim3(grid), dim3(768), G::SPLIT_LDS_BYTES, (hipStream_t)stream, \
-                               to_dev(dy), to_dev(tin), to_dev(w), dx, to_dev(ep), w_slabs, H, W, ntiles, fused_bwd_dbg()); }
-    // 64-column grids (enc.4 of 256-pixel patches): tiles of 4 rows x 64 columns span the row, so the zero-free mapping applies
-    // (the same number of tiles, hence of slabs, as 8 x 32)
-    const bool zf64 = W == 64 && H % 4 == 0 && !zf_off && roles3 && fused_bwd_block() == 0 && !dm_backward_split_bf16();
-    if (zf64) {
-        using G64 = FusedBwdGeom<16, 8, 4, 64>;
-        hipLaunchKernelGGL((bwd_s2_roles3_kernel<16, 8, 4, 64, false, true, 1>), dim3(grid), dim3(768), G64::SPLIT_LDS_BYTES,
-                           (hipStream_t)stream, to_dev(dy), to_dev(tin), to_dev(w), dx, to_dev(ep), w_slabs, H, W, B * (H / 4),
-                           fused_bwd_dbg());
-    } else if (fused_bwd_block() == 0 && roles3) {
-        const bool bf = dm_backward_split_bf16();
-        if (bf && zf) DM_ROLES3_LAUNCH(true, true)
-        else if (bf) DM_ROLES3_LAUNCH(true, false)
-        else if (zf) DM_ROLES3_LAUNCH(false, true)
-        else DM_ROLES3_LAUNCH(false, false)
-    } else if (fused_bwd_block() == 0 && dm_backward_split_bf16()) {
-        if (zf) DM_SPLIT_LAUNCH(true, true); else DM_SPLIT_LAUNCH(true, false);
-    } else if (fused_bwd_block() == 0) {
-        if (zf) DM_SPLIT_LAUNCH(false, true); else DM_SPLIT_LAUNCH(false, false);
-    }
-#undef DM_ROLES3_LAUNCH
-#undef DM_SPLIT_LAUNCH
-    else if (fused_bwd_block() == 512)
-        hipLaunchKernelGGL((bwd_s2_fused_kernel<16, 8, 8, 32, 512, true>), dim3(grid), dim3(512), G::LDS_BYTES, (hipStream_t)stream,
-                           to_dev(dy), to_dev(tin), to_dev(w), dx, to_dev(ep), w_slabs, H, W, ntiles);
+    // the data gradient without structural zeros where a tile spans the row (W == 32: enc.4 of 128-pixel patches); 64-column
+    // grids (enc.4 of 256-pixel patches) take tiles of 4 rows x 64 columns, which span the row too (the same number of tiles,
+    // hence of slabs, as 8 x 32)
+    if (W == 64 && H % 4 == 0)
+        hipLaunchKernelGGL((bwd_s2_roles3_kernel<16, 8, 4, 64, true>), dim3(grid), dim3(768), G64::LDS_BYTES, (hipStream_t)stream,
+                           to_dev(dy), to_dev(tin), to_dev(w), dx, to_dev(ep), w_slabs, H, W, B * (H / 4), 0);
+    else if (W == 32)
+        hipLaunchKernelGGL((bwd_s2_roles3_kernel<16, 8, 8, 32, true>), dim3(grid), dim3(768), G::LDS_BYTES, (hipStream_t)stream,
+                           to_dev(dy), to_dev(tin), to_dev(w), dx, to_dev(ep), w_slabs, H, W, ntiles, 0);
     else
-        hipLaunchKernelGGL((bwd_s2_fused_kernel<16, 8, 8, 32, 256, false>), dim3(grid), dim3(256), G::LDS_BYTES, (hipStream_t)stream,
-                           to_dev(dy), to_dev(tin), to_dev(w), dx, to_dev(ep), w_slabs, H, W, ntiles);
+        hipLaunchKernelGGL((bwd_s2_roles3_kernel<16, 8, 8, 32, false>), dim3(grid), dim3(768), G::LDS_BYTES, (hipStream_t)stream,
+                           to_dev(dy), to_dev(tin), to_dev(w), dx, to_dev(ep), w_slabs, H, W, ntiles, 0);
     return dm_launch_status("dm_conv_bwd_s2_fused");
 }

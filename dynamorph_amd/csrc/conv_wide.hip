@@ -843,15 +843,8 @@ bool dm_stream_conv3x3_wide(const Operand &in, const WeightView &wv, float *out,
 
 // ---- entry points used by the dispatchers in conv_mfma.hip / wgrad_mfma.hip (not part of the public header) ----------
 // base grid (output pixels for the strided / plain forms, input pixels for the transposed form) must tile by 8 x 16
-static int wide_disabled()
-{
-    static const int v = getenv("DM_NO_WIDE") ? atoi(getenv("DM_NO_WIDE")) : 0;       // debugging aid: 1 conv, 2 wgrad, 3 both
-    return v;
-}
-
 bool dm_wide_conv_ok(int form, int H, int W)
 {
-    if ((wide_disabled() & 1) || (wide_disabled() & (4 << form))) return false;       // 4 / 8 / 16: one form only
     const int BH = form == W_S2 ? H / 2 : H, BW = form == W_S2 ? W / 2 : W;
     return BH > 0 && BW > 0 && BH % 8 == 0 && BW % 16 == 0 && (form != W_S2 || (H % 2 == 0 && W % 2 == 0));
 }
@@ -956,7 +949,7 @@ bool dm_stream_wgrad_s2_thin(const Operand &S, const Operand &T, float *slabs, i
 // T as an AFFINE2 operand (two tensors): only where the one-pass kernel prefetches both
 bool dm_wide_wgrad_t_affine2_ok(int CS, int CT, int Hs, int Ws, int k);
 
-bool dm_wide_wgrad_ok(int Hs, int Ws) { return !(wide_disabled() & 2) && Hs > 0 && Ws > 0 && Hs % 8 == 0 && Ws % 16 == 0; }
+bool dm_wide_wgrad_ok(int Hs, int Ws) { return Hs > 0 && Ws > 0 && Hs % 8 == 0 && Ws % 16 == 0; }
 
 static void wide_wgrad_grid(int CS, int CT, int k, int &gy, int &gz, int &cap)
 {

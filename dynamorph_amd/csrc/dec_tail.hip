@@ -285,19 +285,6 @@ constexpr int tail_bwd_occ()
     return (!WIDE && !EDGE && NIN <= 2) ? 3 : 2;
 }
 
-#ifdef DM_MEASURE
-#define DT_DBG_PARAM , int dbg
-#define DT_DBG_ARG , tail_dbg()
-static int tail_dbg()
-{
-    static const int v = [] { const char *e = getenv("DM_DEC_TAIL_DBG"); return e ? atoi(e) : 0; }();
-    return v;
-}
-#else
-#define DT_DBG_PARAM
-#define DT_DBG_ARG
-#endif
-
 // ================================================================================== backward
 // FUSED (training pass, dm_dec_tail_train): decoded is not read but formed in phase B from the recomputed d4 tile
 // (dec.6 is 1x1), the reconstruction-loss partials are taken there too, and `decoded` never exists in HBM.
@@ -317,15 +304,8 @@ void dec_tail_backward_kernel(const float *__restrict__ d2, const float *__restr
                               const float *__restrict__ mask, int MC, const float *__restrict__ cvar,
                               const float *__restrict__ gscale_dev, float *__restrict__ g2, double *__restrict__ part,
                               float *__restrict__ wslabs, int H2, int ntiles, double inv_count, int nslabs, int W2arg,
-                              int tiles_x DT_DBG_PARAM)
+                              int tiles_x)
 {
-#ifndef DM_MEASURE
-    constexpr int dbg = 0;
-#endif
-    // dbg (DM_DEC_TAIL_DBG, measurement build only; results are then wrong, the time is what is read): 1 no phase A products,
-    // 2 no phase B, 4 no phase 3 (data gradient), 8 no phase 4 (weight-gradient matrix instructions), 16 no loads / commits
-    // after the first tile, 32 no workgroup barriers inside the tile loop
-#define DT_SYNC() do { if (!(dbg & 32)) __syncthreads(); } while (0)
     constexpr int AROWS = TT_TH + 4, APS = AROWS * TT_W + 4;     // d2 rows y0-2 .. y0+TH+1
     constexpr int GROWS = 2 * TT_TH + 2, GPS = GROWS * TT_DRS;   // g4 rows 2*y0-1 .. 2*y0+2*TH ; col j <-> ox = j - 4
     constexpr int NP = NIN * TT_C + NIN + TT_C + TT_C;           // dW6 | db6 | db4 | db2
@@ -478,23 +458,20 @@ void dec_tail_backward_kernel(const float *__restrict__ d2, const float *__restr
     }
     double loss = 0.0;
 
-    bool first_tile = true;
     while (tidx < ntiles) {
-        DT_SYNC();                                         // previous tile done with sA and sG
-        if (!(dbg & 16) || first_tile)
-            stage.template commit<false, true>(sA, s_coef, TT_C, H2, W2, y0 - 2, x0, DM_LOAD_IDENT);   // 192 staging threads: waves 0..2
+        __syncthreads();                                   // previous tile done with sA and sG
+        stage.template commit<true>(sA, s_coef, TT_C, H2, W2, y0 - 2, x0, DM_LOAD_IDENT);   // 192 staging threads: waves 0..2
         if constexpr (EDGE) {
             if (threadIdx.x < 2 * TT_C * AROWS) sE[threadIdx.x] = edge_v;
         }
-        first_tile = false;
-        DT_SYNC();
+        __syncthreads();
         const int cb = b, cy0 = y0, cx0 = x0;
         const int colx = x0 + lane;                        // this lane's d2 column (WIDE: may be halo / outside the image)
         const bool colin = !WIDE || (unsigned)colx < (unsigned)W2;
         const bool ownl = !WIDE || (lane >= TT_HALO && lane < TT_W - TT_HALO && colx < W2);
         const int next = tidx + gridDim.x;
         if (next < ntiles) tile_of(next, b, y0, x0);
-        const auto scx = stage.begin(in, next < ntiles && !(dbg & 16), b, TT_C, H2, W2, y0 - 2, x0);   // requested during phase A
+        const auto scx = stage.begin(in, next < ntiles, b, TT_C, H2, W2, y0 - 2, x0);   // requested during phase A
         if constexpr (EDGE) edge_v = edge_load(next < ntiles, b, y0, x0);
 
         // ---- phase A: recompute d4[co = wave] on position rows y0-1 .. y0+TH -> sG rows 2*pr+py-1 -----------------
@@ -558,33 +535,31 @@ void dec_tail_backward_kernel(const float *__restrict__ d2, const float *__restr
                 C = N;
                 if (pr < TT_TH) load_row(sA, APS, pr + 3, lane, N);
                 __builtin_amdgcn_sched_barrier(0);
-                if (!(dbg & 1)) {
-                    f32x2 T, U;
+                f32x2 T, U;
 #pragma unroll
-                    for (int ci = 0; ci < TT_C; ++ci) {
-                        const f32x2 pp = P.v[ci >> 1], cc = C.v[ci >> 1];
-                        const f32x2 pv2 = (ci & 1) ? __builtin_shufflevector(pp, pp, 1, 1) : __builtin_shufflevector(pp, pp, 0, 0);
-                        const f32x2 cv2 = (ci & 1) ? __builtin_shufflevector(cc, cc, 1, 1) : __builtin_shufflevector(cc, cc, 0, 0);
-                        if (ci == 0) { T = pv2 * w01[ci][1] + biasT; U = pv2 * w23[ci][1] + biasU; }
-                        else { T += pv2 * w01[ci][1]; U += pv2 * w23[ci][1]; }
-                        T += cv2 * w01[ci][0]; U += cv2 * w23[ci][0];
-                    }
-                    f32x2 o;
-                    o.x = T.y + lane_from_left(U.y);
-                    o.y = U.x + lane_from_right(T.x);
-                    if constexpr (EDGE) o += *reinterpret_cast<const f32x2 *>(sPA + ((ekind * TT_C + wave) * GROWS + 2 * pr + par) * 2);
-                    *reinterpret_cast<f32x2 *>(sG + wave * GPS + (2 * pr + par) * TT_DRS + 2 * lane + 4) = relu2(o);
+                for (int ci = 0; ci < TT_C; ++ci) {
+                    const f32x2 pp = P.v[ci >> 1], cc = C.v[ci >> 1];
+                    const f32x2 pv2 = (ci & 1) ? __builtin_shufflevector(pp, pp, 1, 1) : __builtin_shufflevector(pp, pp, 0, 0);
+                    const f32x2 cv2 = (ci & 1) ? __builtin_shufflevector(cc, cc, 1, 1) : __builtin_shufflevector(cc, cc, 0, 0);
+                    if (ci == 0) { T = pv2 * w01[ci][1] + biasT; U = pv2 * w23[ci][1] + biasU; }
+                    else { T += pv2 * w01[ci][1]; U += pv2 * w23[ci][1]; }
+                    T += cv2 * w01[ci][0]; U += cv2 * w23[ci][0];
                 }
+                f32x2 o;
+                o.x = T.y + lane_from_left(U.y);
+                o.y = U.x + lane_from_right(T.x);
+                if constexpr (EDGE) o += *reinterpret_cast<const f32x2 *>(sPA + ((ekind * TT_C + wave) * GROWS + 2 * pr + par) * 2);
+                *reinterpret_cast<f32x2 *>(sG + wave * GPS + (2 * pr + par) * TT_DRS + 2 * lane + 4) = relu2(o);
                 P = C;
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
         }
-        DT_SYNC();
+        __syncthreads();
 
         // ---- phase B: g4 = (W6^T g_dec) * (d4 > 0) in place; dW6 / db6 / db4 partial sums ---------------------------
         if constexpr (!AHEAD) {
-            const RowCtx rcc = rows_begin(!(dbg & 16), cb, cy0, cx0);
+            const RowCtx rcc = rows_begin(true, cb, cy0, cx0);
 #pragma unroll
             for (int j = 0; j < BR; ++j)
 #pragma unroll
@@ -604,7 +579,6 @@ void dec_tail_backward_kernel(const float *__restrict__ d2, const float *__restr
 #pragma unroll
         for (int j = 0; j < BR; ++j) {
             const int gr = wave + 4 * j;
-            if (dbg & 2) break;
             if ((PF && j < BR - 1) || gr < GROWS) {
                 const int oy = 2 * cy0 - 1 + gr;
                 const bool live = oy >= 0 && oy < OH && colin;
@@ -675,7 +649,7 @@ void dec_tail_backward_kernel(const float *__restrict__ d2, const float *__restr
         if constexpr (EDGE) {
             // the pad columns' d4 -> g4 (a neighbouring tile owns these pixels: no sums), lane = (g4-tile row, side), by the wave
             // with the fewest rows of its own; a pad column outside the image holds d4 = 0 and stays 0
-            if (wave == 3 && lane < 2 * GROWS && !(dbg & 2)) {
+            if (wave == 3 && lane < 2 * GROWS) {
                 const int oy = 2 * cy0 - 1 + p_gr, pj = p_side ? PADR : PADL;
                 const bool live = oy >= 0 && oy < OH;
                 float d4p[TT_C], gdp[NIN];
@@ -705,15 +679,14 @@ void dec_tail_backward_kernel(const float *__restrict__ d2, const float *__restr
             }
         }
         if (FUSED) loss += (double)tl.x + (double)tl.y;
-        const RowCtx rcn = rows_begin(next < ntiles && !(dbg & 16), b, y0, x0);   // next tile's rows: requested during the wgrad phase
+        const RowCtx rcn = rows_begin(next < ntiles, b, y0, x0);   // next tile's rows: requested during the wgrad phase
         if constexpr (EDGE) {
             if (wave == 3) issue_pad(rcn);
         }
-        DT_SYNC();
+        __syncthreads();
 
         // ---- phase 3: data gradient of dec.4 for input channel ci = wave:  g2[ci][y][x] = sum_co,ky,kx
         //      g4[co][2y-1+ky][2x-1+kx] * W4[ci][co][ky][kx], masked by d2 > 0 ------------------------------------------
-        if (!(dbg & 4)) {
         // per g4 value pair mid = (col 2x, 2x+1), left = col 2x-1, right = col 2x+2:
         //   g2[x] += left*w[ky][0] + mid.x*w[ky][1] + mid.y*w[ky][2] + right*w[ky][3]
         // left / right are the neighbours' mid.y / mid.x: instead of fetching them per value, every lane also accumulates
@@ -789,55 +762,52 @@ void dec_tail_backward_kernel(const float *__restrict__ d2, const float *__restr
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        }
 
         // ---- phase 4 (MFMA): weight gradient of dec.4 (wgrad_steps).  Position rows Yr = 0..TH: this wave takes rows
         //      wave and wave+4 whole and a quarter of row TH.  Row 0 has no own d2 row for sy = 1, row TH none for sy = 0.
-        if (!(dbg & 8)) {
-            constexpr int NR = BR * NIN;                   // next tile's (row, channel) requests, a third before each part
-            auto issue_part = [&](int part) {
-                if constexpr (AHEAD) {
+        constexpr int NR = BR * NIN;                   // next tile's (row, channel) requests, a third before each part
+        auto issue_part = [&](int part) {
+            if constexpr (AHEAD) {
 #pragma unroll
-                    for (int e = 0; e < NR; ++e)
-                        if (e >= part * NR / 3 && e < (part + 1) * NR / 3) issue_row(rcn, e / NIN, e % NIN);
-                }
-            };
-            // rows without an own d2 row for this lane's sy read zeros instead: the A operand's address goes to the zeroed
-            // tail of sA (one select per row call, not a multiplication per step)
-            const bool z0 = wave == 0 && wsy == 1, z8 = wsy != 1;
-            if constexpr (!WIDE) {
-                issue_part(0);
-                wgrad_steps<17, true, true>(sA, sG, z0 ? ZOFF : wa_base + wave * TT_W, wb_base + 2 * wave * TT_DRS, w_first_bad,
-                                            w_last_ok, wacc);
-                issue_part(1);
-                wgrad_steps<17, true, true>(sA, sG, wa_base + (wave + 4) * TT_W, wb_base + 2 * (wave + 4) * TT_DRS,
-                                            w_first_bad, w_last_ok, wacc);
-                issue_part(2);
-                const int a8 = z8 ? ZOFF : wa_base + TT_TH * TT_W + 16 * wave, b8 = wb_base + 2 * TT_TH * TT_DRS + 32 * wave;
-                if (wave < 3)
-                    wgrad_steps<4, true, false>(sA, sG, a8, b8, w_first_bad && wave == 0, false, wacc);
-                else
-                    wgrad_steps<5, false, true>(sA, sG, a8, b8, false, w_last_ok, wacc);
-            } else {
-                // owned d2 columns 4 .. 59 of the tile: the term (X, sx) has its d2 column at X - sx, so steps 1 .. 15 with
-                // X = 4 (sx = 1: column 3) struck from the first and only (X = 60, sx = 1: column 59) kept of the last --
-                // the full-row form's edge handling, one step in.  Columns beyond the image hold zeros in sA.
-                issue_part(0);
-                wgrad_steps<15, true, true>(sA, sG, z0 ? ZOFF : wa_base + wave * TT_W + 4, wb_base + 2 * wave * TT_DRS + 8,
-                                            w_first_bad, w_last_ok, wacc);
-                issue_part(1);
-                wgrad_steps<15, true, true>(sA, sG, wa_base + (wave + 4) * TT_W + 4, wb_base + 2 * (wave + 4) * TT_DRS + 8,
-                                            w_first_bad, w_last_ok, wacc);
-                issue_part(2);
-                const int a8r = wa_base + TT_TH * TT_W + 16 * wave, b8 = wb_base + 2 * TT_TH * TT_DRS + 32 * wave;
-                const int a8 = z8 ? ZOFF : a8r;
-                if (wave == 0)
-                    wgrad_steps<3, true, false>(sA, sG, z8 ? ZOFF : a8r + 4, b8 + 8, w_first_bad, false, wacc);
-                else if (wave < 3)
-                    wgrad_steps<4, false, false>(sA, sG, a8, b8, false, false, wacc);
-                else
-                    wgrad_steps<4, false, true>(sA, sG, a8, b8, false, w_last_ok, wacc);
+                for (int e = 0; e < NR; ++e)
+                    if (e >= part * NR / 3 && e < (part + 1) * NR / 3) issue_row(rcn, e / NIN, e % NIN);
             }
+        };
+        // rows without an own d2 row for this lane's sy read zeros instead: the A operand's address goes to the zeroed
+        // tail of sA (one select per row call, not a multiplication per step)
+        const bool z0 = wave == 0 && wsy == 1, z8 = wsy != 1;
+        if constexpr (!WIDE) {
+            issue_part(0);
+            wgrad_steps<17, true, true>(sA, sG, z0 ? ZOFF : wa_base + wave * TT_W, wb_base + 2 * wave * TT_DRS, w_first_bad,
+                                        w_last_ok, wacc);
+            issue_part(1);
+            wgrad_steps<17, true, true>(sA, sG, wa_base + (wave + 4) * TT_W, wb_base + 2 * (wave + 4) * TT_DRS,
+                                        w_first_bad, w_last_ok, wacc);
+            issue_part(2);
+            const int a8 = z8 ? ZOFF : wa_base + TT_TH * TT_W + 16 * wave, b8 = wb_base + 2 * TT_TH * TT_DRS + 32 * wave;
+            if (wave < 3)
+                wgrad_steps<4, true, false>(sA, sG, a8, b8, w_first_bad && wave == 0, false, wacc);
+            else
+                wgrad_steps<5, false, true>(sA, sG, a8, b8, false, w_last_ok, wacc);
+        } else {
+            // owned d2 columns 4 .. 59 of the tile: the term (X, sx) has its d2 column at X - sx, so steps 1 .. 15 with
+            // X = 4 (sx = 1: column 3) struck from the first and only (X = 60, sx = 1: column 59) kept of the last --
+            // the full-row form's edge handling, one step in.  Columns beyond the image hold zeros in sA.
+            issue_part(0);
+            wgrad_steps<15, true, true>(sA, sG, z0 ? ZOFF : wa_base + wave * TT_W + 4, wb_base + 2 * wave * TT_DRS + 8,
+                                        w_first_bad, w_last_ok, wacc);
+            issue_part(1);
+            wgrad_steps<15, true, true>(sA, sG, wa_base + (wave + 4) * TT_W + 4, wb_base + 2 * (wave + 4) * TT_DRS + 8,
+                                        w_first_bad, w_last_ok, wacc);
+            issue_part(2);
+            const int a8r = wa_base + TT_TH * TT_W + 16 * wave, b8 = wb_base + 2 * TT_TH * TT_DRS + 32 * wave;
+            const int a8 = z8 ? ZOFF : a8r;
+            if (wave == 0)
+                wgrad_steps<3, true, false>(sA, sG, z8 ? ZOFF : a8r + 4, b8 + 8, w_first_bad, false, wacc);
+            else if (wave < 3)
+                wgrad_steps<4, false, false>(sA, sG, a8, b8, false, false, wacc);
+            else
+                wgrad_steps<4, false, true>(sA, sG, a8, b8, false, w_last_ok, wacc);
         }
         tidx = next;
     }
@@ -898,16 +868,11 @@ void dec_tail_backward_kernel(const float *__restrict__ d2, const float *__restr
     }
 }
 
-#undef DT_SYNC
 int tail_tiles_x(int W2) { return W2 == TT_W ? 1 : (W2 + TT_OWN - 1) / TT_OWN; }               // (64 wide: one tile spans the row)
 int tail_grid(int ntiles) { return ntiles < TT_MAX_GRID ? ntiles : TT_MAX_GRID; }               // forward: 3 per CU
 int tail_grid_bwd(int ntiles, int occ)                                                          // backward: occ per CU
 {
-    int cap = 256 * occ;
-#ifdef DM_MEASURE      // occupancy experiments: DM_DEC_TAIL_GRID=256 leaves one workgroup per CU
-    static const int env_cap = [] { const char *e = getenv("DM_DEC_TAIL_GRID"); return e ? atoi(e) : 0; }();
-    if (env_cap > 0) cap = env_cap;
-#endif
+    const int cap = 256 * occ;
     return ntiles < cap ? ntiles : cap;
 }
 
@@ -972,20 +937,19 @@ int tail_backward_launch(const char *who, bool fused, const float *d2, const flo
 #define DM_TB(N_, F_, W_, M_) { const int grid = tail_grid_bwd(ntiles, tail_bwd_occ<N_, F_, W_, M_>()); \
                                 hipLaunchKernelGGL((dec_tail_backward_kernel<N_, F_, W_, M_>), dim3(grid), dim3(DM_BLOCK), 0, st, d2, w4, b4, \
                                                    w6, b6, loss_slabs, decoded, x, mask, mask_channels, channel_var, gscale_dev, g2, \
-                                                   part_slabs, w_slabs, H2, ntiles, inv_count, nslabs, W2, tiles_x DT_DBG_ARG); }
+                                                   part_slabs, w_slabs, H2, ntiles, inv_count, nslabs, W2, tiles_x); }
     // EDGE: tiles of 64 owned columns (the slab buffers stay sized for the forward kernel's grid: nslabs)
 #define DM_TBE(N_, M_) { const int tx_ = W2 / TT_W, nt_ = B * (H2 / TT_TH) * tx_;                                               \
                          const int grid = tail_grid_bwd(nt_, tail_bwd_occ<N_, true, false, M_, true>());                         \
                          hipLaunchKernelGGL((dec_tail_backward_kernel<N_, true, false, M_, true>), dim3(grid), dim3(DM_BLOCK), 0, st, d2, w4, \
                                             b4, w6, b6, loss_slabs, decoded, x, mask, mask_channels, channel_var, gscale_dev, g2, \
-                                            part_slabs, w_slabs, H2, nt_, inv_count, nslabs, W2, tx_ DT_DBG_ARG); }
+                                            part_slabs, w_slabs, H2, nt_, inv_count, nslabs, W2, tx_); }
 #define DM_TBEN(M_) switch (NIN) { case 1: DM_TBE(1, M_) break; case 2: DM_TBE(2, M_) break; case 3: DM_TBE(3, M_) break; default: DM_TBE(4, M_) }
 #define DM_TBN(F_, W_, M_) switch (NIN) { case 1: DM_TB(1, F_, W_, M_) break; case 2: DM_TB(2, F_, W_, M_) break; case 3: DM_TB(3, F_, W_, M_) break; default: DM_TB(4, F_, W_, M_) }
 #define DM_TBM(F_, W_) if (mask) { DM_TBN(F_, W_, true) } else { DM_TBN(F_, W_, false) }
-    static const bool edge_off = [] { const char *e = getenv("DM_DEC_TAIL_EDGE"); return e && e[0] == '0'; }();
     if (W2 == TT_W) {
         if (fused) { DM_TBM(true, false) } else { DM_TBM(false, false) }
-    } else if (fused && W2 % TT_W == 0 && !edge_off) {
+    } else if (fused && W2 % TT_W == 0) {
         if (mask) { DM_TBEN(true) } else { DM_TBEN(false) }
     } else {
         if (fused) { DM_TBM(true, true) } else { DM_TBM(false, true) }

@@ -20,8 +20,7 @@ constexpr int VQ_BLOCK = 256;
 constexpr int VQ_MAX_LDS_HIST = 4096;
 
 // Workspace of dm_vq_forward (float offsets; every region starts on a 16-byte boundary):
-//   header  32 ints: [0] = positions that went through the exact re-check of the MFMA path (statistics); [4..] = per-phase
-//           cycle sums of the diagnostic build (-DVQ2_STAMPS, never the shipped one)
+//   header  32 ints: [0] = positions that went through the exact re-check of the MFMA path (statistics)
 //   cbT     [ceil(K/2)][D][2]   pair-interleaved codebook of the exact kernel (v1)
 //   cbA     [K64/64][4 kt][SQ][64 lanes][4]  A operand of v_mfma_f32_16x16x4_f32: -2 * e[64 cc + 16 kt + (lane & 15)]
 //           [4 (4 sq + j) + (lane >> 4)], zero beyond K / D  (K64 = K rounded up to 64, SQ = ceil(D / 16))
@@ -499,7 +498,7 @@ __global__ __launch_bounds__(1024) void vq_hist_reduce_kernel(const int *__restr
 //     bound that clears the runner-up clears, code by code, every group whose minimum is farther away (s_pm in the kernel).
 //     4096 codes: 16 groups of 256 (one LDS buffer pair each; until round 5 six groups of 768, the LDS going to a 4096-entry
 //     counter array that large codebooks now keep in their global replicas): the re-checks of the 0.5-0.8 % of positions
-//     that fail went from 19 % of the kernel to 7 % on N(0,1) data (tools/exp/vq_parts.sh).
+//     that fail went from 19 % of the kernel to 7 % on N(0,1) data.
 // So the index is the reference's for every position; only the work per position differs.
 //
 // Layout: a wave owns a chunk of 64 consecutive positions of one sample; lane (h = lane >> 4, c = lane & 15) loads
@@ -507,34 +506,6 @@ __global__ __launch_bounds__(1024) void vq_hist_reduce_kernel(const int *__restr
 // exactly the B operand of step s for the four position tiles t = 0..3 (column c of tile t = position 4 c + t): no
 // transpose, no LDS.  The 16 x 16 result tile has code 16 kt + 4 h + r in register r, so a position's 64 scores sit in
 // 16 registers of 4 lanes: 16 in-lane updates, then two cross-lane steps (lanes l ^ 16, l ^ 32).
-
-// Diagnostic build only (make STAMPS=1): s_memtime at the phase boundaries of the chunk loop, per-wave sums added into the
-// workspace header.  The shipped library has no stamp (cdna_hip_programming.md section 7, In-kernel stamps).
-#ifdef VQ2_STAMPS
-#define VQ2_STAMP(i)                                                                                      \
-    {                                                                                                     \
-        __builtin_amdgcn_sched_barrier(0);                                                                \
-        unsigned long long t_;                                                                            \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                        \
-        __builtin_amdgcn_sched_barrier(0);                                                                \
-        st_sum[i] += t_ - st_prev;                                                                        \
-        st_prev = t_;                                                                                     \
-    }
-#define VQ2_USE(v) asm volatile("; use" ::"v"(v))
-#else
-#define VQ2_STAMP(i)
-#define VQ2_USE(v)
-#endif
-
-#ifdef DM_MEASURE
-// measurement build only (make measure; DM_VQ_DBG): 1 the codebook piece is staged once (stale operands), 4 no exact re-checks;
-// compile time: -DVQ_DBG_NOEMBED no index bits in the scores, -DVQ_DBG_MINONLY the in-lane minimum only (no runner-up).
-// Results are then wrong; the time is what is read (tools/exp/vq_parts.sh).
-__device__ int vq_dbg_dev;
-#define VQ_DBG(bit) (vq_dbg_dev & (bit))
-#else
-#define VQ_DBG(bit) false
-#endif
 
 // 16 bytes per lane from global memory straight into LDS (global_load_lds_dwordx4: no register in between; the LDS image is
 // lane-linear: wave-uniform base + 16 * lane, which is what a contiguous copy wants).  Completion is counted on vmcnt.
@@ -686,7 +657,7 @@ __global__ __launch_bounds__(256, MINW) void vq_forward_mfma_kernel(
     // where a chunk is larger): the copy of the next buffer (global_load_lds, no registers) runs under the products of the
     // current one, ONE barrier per buffer, and the stream wraps around from one chunk of positions to the next.  Up to round 5
     // a single 32 KB piece was refilled through registers between two barriers, its load latency exposed 16 times per 256
-    // positions at 4096 codes: 12 % of the kernel (tools/exp/vq_parts.sh).  A codebook that fits both buffers is staged once.
+    // positions at 4096 codes: 12 % of the kernel.  A codebook that fits both buffers is staged once.
     constexpr int PCH = SINGLE ? 1 : (1024 / CHUNK_F4 > 0 ? 1024 / CHUNK_F4 : 1);     // code chunks per LDS buffer
     constexpr int PIECE = 2 * PCH;
     constexpr float U = 5.9604645e-8f;                             // 2^-24
@@ -750,10 +721,6 @@ __global__ __launch_bounds__(256, MINW) void vq_forward_mfma_kernel(
     };
     double sse = 0.0;
     int nflag = 0;
-#ifdef VQ2_STAMPS
-    unsigned long long st_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_prev;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_prev)::"memory");
-#endif
     const unsigned sample_bytes = (unsigned)D * (unsigned)HW * 4u;
     const unsigned zvoff = ((unsigned)h * (unsigned)HW + 4u * (unsigned)c) * 4u;     // this lane's bytes inside a chunk's rows
     // (a wave without a chunk -- the tail of the last quad -- loads the last chunk and computes nothing)
@@ -948,7 +915,6 @@ __global__ __launch_bounds__(256, MINW) void vq_forward_mfma_kernel(
         f32x4 zn[S];
         z_load(zn, hq, nchunk, nb, nw);
 
-        VQ2_STAMP(1)                                           // prefetch issue
         float m1[4], m2[4], pmv[SINGLE ? 1 : 4];
         int c1[4];
 #pragma unroll
@@ -1027,19 +993,9 @@ __global__ __launch_bounds__(256, MINW) void vq_forward_mfma_kernel(
                 for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-#ifdef VQ_DBG_NOEMBED
-                        v[kt * 4 + r] = (float)acc[kt][r];
-#else
                         v[kt * 4 + r] = __builtin_bit_cast(float, (__builtin_bit_cast(unsigned, (float)acc[kt][r]) & ~15u) | (unsigned)(kt * 4 + r));
-#endif
                 float t1, t2;
-#ifdef VQ_DBG_MINONLY
-                t1 = vq2_min3(vq2_min3(vq2_min3(v[0], v[1], v[2]), vq2_min3(v[3], v[4], v[5]), vq2_min3(v[6], v[7], v[8])),
-                              vq2_min3(vq2_min3(v[9], v[10], v[11]), vq2_min3(v[12], v[13], v[14]), v[15]), v[15]);
-                t2 = t1;
-#else
                 vq2_top2_16(v, t1, t2);
-#endif
                 if constexpr (SINGLE) { m1[t] = t1; m2[t] = t2; }
                 else {
                     m2[t] = vq2_min3(m2[t], t2, vq2_max(m1[t], t1));
@@ -1056,7 +1012,7 @@ __global__ __launch_bounds__(256, MINW) void vq_forward_mfma_kernel(
             for (int hp = 0; hp < nhp; ++hp) {
                 const int p0 = hp * PCH, pn = min(PCH, ncc - p0);
                 const int buf = resident ? hp : (int)(hp_it & 1u);
-                if (!resident && !VQ_DBG(1)) {
+                if (!resident) {
                     // the buffer the previous barrier freed takes the next PCH chunks (of the next chunk of positions at the end)
                     const int hn = hp + 1 < nhp ? hp + 1 : 0;
                     vq2_stage(hn, buf ^ 1);
@@ -1101,8 +1057,6 @@ __global__ __launch_bounds__(256, MINW) void vq_forward_mfma_kernel(
             }
         }
 
-        VQ2_USE(m1[3]); VQ2_USE(m2[3]);
-        VQ2_STAMP(3)                                           // MFMAs + in-lane top-2
         f32x4 o[S];
         long long kpair[2] = {0, 0};
         int kown = 0;
@@ -1163,10 +1117,8 @@ __global__ __launch_bounds__(256, MINW) void vq_forward_mfma_kernel(
                 const int kt = (bits >> 2) & 3, r = bits & 3, hw = hb1 | ((bits >> 4) & 1);
                 kown = (SINGLE ? 0 : cc1 * 64) + kt * 16 + hw * 4 + r;
             }
-            VQ2_USE(kown);
-            VQ2_STAMP(4)                                       // reduce-scatter, tolerance
             // ---- exact re-check of the positions that failed the test: the whole wave, one position at a time ----
-            unsigned long long fm = VQ_DBG(4) ? 0ull : __ballot(flagged);
+            unsigned long long fm = __ballot(flagged);
             while (fm) {
                 const int fl = __builtin_ctzll(fm);
                 fm &= fm - 1;
@@ -1264,8 +1216,6 @@ __global__ __launch_bounds__(256, MINW) void vq_forward_mfma_kernel(
                 kb[0] = __builtin_bit_cast(int, e0); kb[2] = __builtin_bit_cast(int, o0);
                 kb[1] = __builtin_bit_cast(int, e1); kb[3] = __builtin_bit_cast(int, o1);
             }
-            VQ2_USE(kb[3]);
-            VQ2_STAMP(5)                                       // exact re-checks, all-gather
             // ---- gather + straight-through value + squared error, in the layout the lane already holds ----
             float ssef = 0.f;
 #pragma unroll
@@ -1292,8 +1242,6 @@ __global__ __launch_bounds__(256, MINW) void vq_forward_mfma_kernel(
             }
             sse += (double)ssef;
             kpair[0] = (long long)(h ? kb[2] : kb[0]); kpair[1] = (long long)(h ? kb[3] : kb[1]);
-            VQ2_USE(o[S - 1]); VQ2_USE(ssef);
-            VQ2_STAMP(6)                                       // gather, straight-through value, squared error
         }
         // The prefetched z replaces this chunk's BEFORE the stores are issued: the wait for the prefetch then counts loads
         // only (vmcnt retires loads and stores in issue order; after the stores it would be a wait for them too).
@@ -1307,7 +1255,6 @@ __global__ __launch_bounds__(256, MINW) void vq_forward_mfma_kernel(
             for (int s = 0; s < S; ++s) asm volatile("" : "+v"(hq[s]));
         }
         __builtin_amdgcn_sched_barrier(0);
-        VQ2_STAMP(0)                                           // wait for the prefetched z
         z_join_store(zr, hq, nchunk < NC, nb, nw);             // (JOIN) the next chunk's latents: formed and written here
         if (act) {
             if (out) {
@@ -1325,7 +1272,6 @@ __global__ __launch_bounds__(256, MINW) void vq_forward_mfma_kernel(
             if (lds_hist) atomicAdd(&s_hist[kown], 1);
             else atomicAdd(&hist[kown], 1);
         }
-        VQ2_STAMP(7)                                           // stores issued
         chunk = nchunk; cb_ = nb; cw_ = nw;
     }
 
@@ -1350,10 +1296,6 @@ __global__ __launch_bounds__(256, MINW) void vq_forward_mfma_kernel(
         return;
     }
     if (lane == 0 && nflag) atomicAdd(hdr, nflag);
-#ifdef VQ2_STAMPS
-    if (lane == 0)
-        for (int i = 0; i < 8; ++i) atomicAdd(reinterpret_cast<unsigned long long *>(hdr + 4) + i, st_sum[i]);
-#endif
     if (lds_hist) {
         __syncthreads();
         for (int k = threadIdx.x; k < K; k += BLOCK) {
@@ -1859,8 +1801,6 @@ bool vq2_auto_bf16()
     static const bool on = [] { const char *e = getenv("DM_VQ_FILTER"); return !(e && e[0] == 'f'); }();
     return on;
 }
-// measurement knobs of the headline shape (embedding_dim 16, <= 64 codes): DM_VQ_OCC=4 takes the build bounded to 128
-// registers (4 waves per SIMD), DM_VQ_WGS=n launches n workgroups per CU instead of the occupancy's
 // 0: off, 3 / 4: products of the bf16 split in vq_cells_kernel (default 3)
 int vq2_cells()
 {
@@ -1871,11 +1811,6 @@ int vq2_cells()
     }();
     return v;
 }
-// start delay of the CUs' second workgroups in percent of one pass's matrix time (DM_VQ_CELLS_STAGGER; 0 = none)
-int vq2_cells_stagger_pct() { static const int v = [] { const char *e = getenv("DM_VQ_CELLS_STAGGER"); return e ? atoi(e) : 90; }(); return v; }
-bool vq2_force_prep() { static const bool v = [] { const char *e = getenv("DM_VQ_PREP"); return e && e[0] == '1'; }(); return v; }
-int vq2_occ() { static const int v = [] { const char *e = getenv("DM_VQ_OCC"); return e ? atoi(e) : 3; }(); return v; }
-int vq2_wgs(int dflt) { static const int v = [] { const char *e = getenv("DM_VQ_WGS"); return e ? atoi(e) : 0; }(); return v > 0 ? v : dflt; }
 bool vq2_applicable(const float *z, const int64_t *idx, const float *out, const void *ws, int D, int HW)
 {
     const uintptr_t al = (uintptr_t)z | (uintptr_t)idx | (uintptr_t)out | (uintptr_t)ws;
@@ -1931,20 +1866,12 @@ int vq_forward_launch(const float *z, const float *codebook, int64_t *idx, float
     if (pgrid > 1024) pgrid = 1024;
     // <= 64 codes (every configuration of the reference), embedding_dim 16 / 32 / 64: the MFMA kernel prepares its own
     // operands and writes its counters as per-workgroup rows -- no preparation launch, no counter reduction
-    // (DM_VQ_PREP=1 in the environment keeps the separate preparation: A/B measurements)
-    const bool inl = use2 && K <= 64 && D % 16 == 0 && !vq2_force_prep();
+    const bool inl = use2 && K <= 64 && D % 16 == 0;
     DM_REQUIRE(!jz || (inl && D == 16), "dm_vq_forward_join: built for the one-launch form (<= 64 codes, embedding_dim 16, H*W %% 64 == 0)");
     if (!inl) hipLaunchKernelGGL(vq_prep_kernel, dim3(pgrid), dim3(256), 0, s, codebook, ws, L, K, D, sse_slabs, nslabs);
     // (vq_prep_kernel cleared the counter replicas and all slabs: there are fewer workgroups than slabs)
     int *hrep = reinterpret_cast<int *>(ws + L.hrep);
     if (use2) {
-#ifdef DM_MEASURE
-        {
-            static const int dbg = [] { const char *e = getenv("DM_VQ_DBG"); return e ? atoi(e) : 0; }();
-            static bool sent = false;
-            if (!sent) { (void)hipMemcpyToSymbol(HIP_SYMBOL(vq_dbg_dev), &dbg, sizeof(int)); sent = true; }
-        }
-#endif
         const long long groups = ((P >> 6) + 3) / 4;
 #define DM_VQ2K(DD, SINGLE_, MINW, WGS, BF_, INL_, JOIN_)                                                            \
     {                                                                                                                \
@@ -1981,10 +1908,10 @@ int vq_forward_launch(const float *z, const float *codebook, int64_t *idx, float
                 long long g_ = (passes + 3) / 4;
                 if (g_ > 512) g_ = 512;                              // two workgroups per CU, persistent over the passes
                 // half a pass in units of 64 cycles (s_sleep): a pass streams K / 32 chunks of 12 (16) matrix instructions of 32
-                // cycles; only where both slots of the CUs are taken and every wave has more than one pass
+                // cycles, started 90 % of the way in; only where both slots of the CUs are taken and every wave has more than one pass
                 const int prod = vq2_cells();
                 const long long chunk_cycles = (long long)(prod == 4 ? 16 : 12) * 32;
-                int stagger = (g_ > 256 && passes >= 2 * g_ * 4) ? (int)(((K + 31) / 32) * chunk_cycles * vq2_cells_stagger_pct() / 100 / 64) : 0;
+                int stagger = (g_ > 256 && passes >= 2 * g_ * 4) ? (int)(((K + 31) / 32) * chunk_cycles * 90 / 100 / 64) : 0;
                 if (prod == 4)
                     hipLaunchKernelGGL((vq_cells_kernel<4>), dim3((unsigned)g_), dim3(256), 0, s, z, codebook,
                                        reinterpret_cast<const vqc_u32x4 *>(ws + L.cbP), ws + L.nrmP, ws + L.nrm, (long long *)idx,
@@ -1998,8 +1925,7 @@ int vq_forward_launch(const float *z, const float *codebook, int64_t *idx, float
             switch (D) {
             case 8: if (single) DM_VQ2(8, true, 3, 3) else DM_VQ2(8, false, 3, 3) break;
             case 16:
-                if (single && vq2_occ() == 4) DM_VQ2(16, true, 4, vq2_wgs(4))
-                else if (single) DM_VQ2(16, true, 3, vq2_wgs(3))
+                if (single) DM_VQ2(16, true, 3, 3)
                 else DM_VQ2(16, false, 3, 3)
                 break;
             case 32: if (single) DM_VQ2(32, true, 2, 2) else DM_VQ2(32, false, 2, 2) break;
@@ -2058,7 +1984,7 @@ extern "C" int dm_vq_forward(const float *z, const float *codebook, int64_t *idx
 extern "C" int dm_vq_forward_join_supported(int D, int K, int H, int W)
 {
     // (embedding_dim 16 = the reference's num_hiddens: at 32 / 64 the second prefetched tensor does not fit the registers)
-    return (K > 0 && K <= 64 && D == 16 && H > 0 && W > 0 && (H * W) % 64 == 0 && !vq2_force_prep()) ? 1 : 0;
+    return (K > 0 && K <= 64 && D == 16 && H > 0 && W > 0 && (H * W) % 64 == 0) ? 1 : 0;
 }
 
 extern "C" int dm_vq_forward_join(const float *rb, const float *h_in, const float *coef, float *z_out, const float *codebook,

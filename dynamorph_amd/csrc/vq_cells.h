@@ -30,12 +30,6 @@
 
 // (constants, the row <-> code permutation and the operand preparation: vq.hip, above vq_prep_kernel)
 
-// measurement builds only (tools/exp/vq_cells_parts.sh; results are wrong, the time is what is read): compile-time switches
-// -DVQC_OFF=bits: 4 no exact re-checks, 8 no exact evaluation of the best cell, 16 no group ends, 32 no cell minima,
-// 64 the operand ring is never refilled (stale codes), 128 the norms are read once per pass, 256 every other group end skipped
-#ifndef VQC_OFF
-#define VQC_OFF 0
-#endif
 #ifndef VQC_CELL_BATCH
 #define VQC_CELL_BATCH 4         // rows of the best cell requested together (8: measured below)
 #endif
@@ -44,23 +38,6 @@
 #endif
 #ifndef VQC_ZPREFETCH
 #define VQC_ZPREFETCH 0          // 1: the next pass's latents are requested before this pass's tail (measured: no gain, more spills)
-#endif
-#define VQC_DBG(bit) ((VQC_OFF & (bit)) != 0)
-
-// diagnostic build only (-DVQ2_STAMPS, tools/exp/vq_cells_stamps.py): s_memtime at the phase boundaries of a pass, per-wave sums
-// added into the workspace header -- the shipped library has no stamp
-#ifdef VQ2_STAMPS
-#define VQC_STAMP(i)                                                                                      \
-    {                                                                                                     \
-        __builtin_amdgcn_sched_barrier(0);                                                                \
-        unsigned long long t_;                                                                            \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                        \
-        __builtin_amdgcn_sched_barrier(0);                                                                \
-        st_sum[i] += t_ - st_prev;                                                                        \
-        st_prev = t_;                                                                                     \
-    }
-#else
-#define VQC_STAMP(i)
 #endif
 
 template <int NPROD>
@@ -125,10 +102,6 @@ __global__ __launch_bounds__(256, 2) void vq_cells_kernel(
     const unsigned npass = (unsigned)(P >> 7), pps = (unsigned)HW >> 7;      // passes of 128 positions; per sample
     double sse = 0.0;
     int nflag = 0;
-#ifdef VQ2_STAMPS
-    unsigned long long st_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_prev;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_prev)::"memory");
-#endif
     const vqc_u32x4 *__restrict__ aP = cbP + lane;
     vqc_u32x4 ah[VQC_GCH], al[VQC_GCH];                                       // the operand ring: chunks cc .. cc + 3
 #pragma unroll
@@ -166,7 +139,6 @@ __global__ __launch_bounds__(256, 2) void vq_cells_kernel(
                 Zl[t] = (vqc_u32x4){lp[0], lp[1], lp[2], lp[3]};
             }
         }
-        VQC_STAMP(0)                                           // latents loaded, operands split
         float cm[NT][8], m1[NT], m2[NT];
         int G1[NT];
 #pragma unroll
@@ -264,27 +236,24 @@ __global__ __launch_bounds__(256, 2) void vq_cells_kernel(
                     acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, __builtin_bit_cast(vqc_bf16x8, Zh[t]), nr, 0, 0, 0);
                     acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, __builtin_bit_cast(vqc_bf16x8, Zl[t]), acc[t], 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
-                    if (!VQC_DBG(32)) cells(pt, 0, 4, pfirst);
+                    cells(pt, 0, 4, pfirst);
                     __builtin_amdgcn_sched_barrier(0);
                     acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, __builtin_bit_cast(vqc_bf16x8, Zh[t]), acc[t], 0, 0, 0);
                     if constexpr (NPROD == 4)
                         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, __builtin_bit_cast(vqc_bf16x8, Zl[t]), acc[t], 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
-                    if (!VQC_DBG(32)) cells(pt, 4, 8, pfirst);
+                    cells(pt, 4, 8, pfirst);
                     __builtin_amdgcn_sched_barrier(0);
                     // the previous group is complete once the last tile of its last chunk has been folded in
-                    if (t == 0 && ccl == 0 && g > 0 && !VQC_DBG(16) && !(VQC_DBG(256) && (g & 1))) group_end(g - 1);
-                    if (t == 1 && !VQC_DBG(128)) read_norms(nrb[(ccl + 1) & 1], cc + 1 < NCH ? cc + 1 : 0);
+                    if (t == 0 && ccl == 0 && g > 0) group_end(g - 1);
+                    if (t == 1) read_norms(nrb[(ccl + 1) & 1], cc + 1 < NCH ? cc + 1 : 0);
                 }
                 // this ring slot's next chunk (the stream wraps into the next pass)
                 const int nxt = cc + VQC_GCH < NCH ? cc + VQC_GCH : cc + VQC_GCH - NCH;
-                if (!VQC_DBG(64)) {
-                    ah[ccl] = aP[(nxt * 2) * 64];
-                    al[ccl] = aP[(nxt * 2 + 1) * 64];
-                }
+                ah[ccl] = aP[(nxt * 2) * 64];
+                al[ccl] = aP[(nxt * 2 + 1) * 64];
             }
         }
-        VQC_STAMP(1)                                           // the code stream
         // the owned positions' complete latent vectors are requested here: they land under the drain and the last group end
         const long long own = (long long)pw * 128 + 4 * n + 2 * kh;                 // first owned position inside the sample
         f32x2 zf[D];
@@ -298,9 +267,8 @@ __global__ __launch_bounds__(256, 2) void vq_cells_kernel(
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         cells(NT - 1, 0, 8, VQC_GCH == 1);
-        if (!VQC_DBG(16)) group_end(NG - 1);
+        group_end(NG - 1);
 
-        VQC_STAMP(2)                                           // drain + last group end
         if (VQC_ZPREFETCH) load_z(pass + gridDim.x * 4u);
         // ---- the tail: everything of a position is in its owner's registers ----
         if (!VQC_ZF_EARLY) {
@@ -337,9 +305,8 @@ __global__ __launch_bounds__(256, 2) void vq_cells_kernel(
             for (int d = 0; d < D; ++d) zv[d] = zf[d][s];
             float bd = __builtin_inff();
             int bk = 0x7fffffff;
-            if (VQC_DBG(8)) bk = min(base, K - 1);
 #pragma unroll
-            for (int c0 = 0; c0 < (VQC_DBG(8) ? 0 : 8); c0 += VQC_CELL_BATCH) {
+            for (int c0 = 0; c0 < 8; c0 += VQC_CELL_BATCH) {
                 float er[VQC_CELL_BATCH][D];
 #pragma unroll
                 for (int u = 0; u < VQC_CELL_BATCH; ++u) {
@@ -360,12 +327,11 @@ __global__ __launch_bounds__(256, 2) void vq_cells_kernel(
             }
             kown[s] = bk == 0x7fffffff ? 0 : bk;
         }
-        VQC_STAMP(3)                                           // owned latents, merge, exact evaluation of the best cells
         // ---- exact re-check of the positions the filter could not settle: the whole wave, one position at a time, over the
         // groups whose minimum lies within the tolerance of the best score (a NaN on either side keeps the group)
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            unsigned long long fm = VQC_DBG(4) ? 0ull : __ballot(flagged[s]);
+            unsigned long long fm = __ballot(flagged[s]);
             while (fm) {
                 const int fl = __builtin_ctzll(fm);
                 fm &= fm - 1;
@@ -384,10 +350,6 @@ __global__ __launch_bounds__(256, 2) void vq_cells_kernel(
                     const float pg = __builtin_bit_cast(float, (s ? (pk >> 24) | ((unsigned)s_pmh[wave][gq][fl] << 8) : pk & 0xffffffu) << 8);
                     gmask = (unsigned)__ballot(lane < NG && !(pg > thr));
                 }
-#ifdef VQ2_STAMPS
-                st_sum[6] += __builtin_popcount(gmask);        // (counts, not cycles: groups visited / positions re-checked)
-                st_sum[7] += 1;
-#endif
                 while (gmask) {
                     const int g = __builtin_ctz(gmask);
                     gmask &= gmask - 1;
@@ -430,7 +392,6 @@ __global__ __launch_bounds__(256, 2) void vq_cells_kernel(
                 ++nflag;
             }
         }
-        VQC_STAMP(4)                                           // exact re-checks
         // ---- gather, straight-through value z + (q - z) (vq_vae.py:71), squared error, stores, counters ----
         float ssef = 0.f;
         f32x2 o[D];
@@ -460,14 +421,9 @@ __global__ __launch_bounds__(256, 2) void vq_cells_kernel(
         }
         atomicAdd(&hist[kown[0]], 1);
         atomicAdd(&hist[kown[1]], 1);
-        VQC_STAMP(5)                                           // gather, value, stores, counters
     }
 
     const double tot = block_sum(sse, s_red);
     if (threadIdx.x == 0) sse_slabs[blockIdx.x] = tot;
     if (lane == 0 && nflag) atomicAdd(hdr, nflag);
-#ifdef VQ2_STAMPS
-    if (lane == 0)
-        for (int i = 0; i < 8; ++i) atomicAdd(reinterpret_cast<unsigned long long *>(hdr + 4) + i, st_sum[i]);
-#endif
 }

@@ -52,11 +52,12 @@ __device__ __forceinline__ float stream_floor(const Operand &op)
 // rows of their own channel once per group and the T rows of NTW channels.  A workgroup takes a contiguous range of the
 // B * HW / 32 pixel groups (coefficients are shared by all samples: batch-statistics BatchNorm, the host checks), so the
 // stream runs across sample boundaries; its partial result is slab blockIdx.x.
-// S2: the S operand is AFFINE2 (two tensors).  D: groups of 32 pixels in flight per wave.
-template <int MT, int NT, bool S2, int D>
-__global__ __launch_bounds__(256, D <= 1 ? 4 : 3) void wgrad1x1_stream_kernel(Operand S, Operand T, float *__restrict__ slabs,
-                                                                            int B, int CS, int CT, int HW, int nslabs)
+// S2: the S operand is AFFINE2 (two tensors).
+template <int MT, int NT, bool S2>
+__global__ __launch_bounds__(256, 3) void wgrad1x1_stream_kernel(Operand S, Operand T, float *__restrict__ slabs,
+                                                                 int B, int CS, int CT, int HW, int nslabs)
 {
+    constexpr int D = 2;                                         // groups of 32 pixels in flight per wave
     constexpr int NG = 4 / MT, NTW = NT / NG;
     static_assert(MT * NG == 4 && NTW * NG == NT, "four waves share MT x NT tiles");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, p = lane & 15, kq = lane >> 4;
@@ -1383,11 +1384,6 @@ int stream_switch()
     static const int v = getenv("DM_WIDE_STREAM") ? atoi(getenv("DM_WIDE_STREAM")) : 0x3ff;   // bit 0: 1x1 weight gradient, 1: 1x1 convolution, 2: thin 4x4/s2 weight gradient, 3: thin 4x4/s2 convolution, 4: thin transposed convolution, 5: 4x4/s2 convolution 32 -> 64 with the weights resident in LDS, 6: its transposed mirror 64 -> 32, 7 / 8: 3x3 64 -> 64 with the weights in LDS (forward form / forms with a gate), 9: both gradients of the 1x1 64 -> 64 in one launch
     return v;
 }
-int stream_depth()
-{
-    static const int v = getenv("DM_WIDE_STREAM_DEPTH") ? atoi(getenv("DM_WIDE_STREAM_DEPTH")) : 2;
-    return v;
-}
 
 }  // namespace
 
@@ -1415,13 +1411,11 @@ bool dm_stream_wgrad1x1(const Operand &S, const Operand &T, float *slabs, int B,
     int grid = dm_stream_wgrad1x1_slabs(B, Hs, Ws);
     if (grid > nslabs) grid = nslabs;
     const int HW = Hs * Ws;
-    const bool two = S.mode == DM_LOAD_AFFINE2, deep = stream_depth() >= 2;
+    const bool two = S.mode == DM_LOAD_AFFINE2;
 #define DM_SW(MT_, NT_)                                                                                                  \
     if (CS == 16 * MT_ && CT == 16 * NT_) {                                                                              \
-        if (two && deep) hipLaunchKernelGGL((wgrad1x1_stream_kernel<MT_, NT_, true, 2>), dim3(grid), dim3(256), 0, st, S, T, slabs, B, CS, CT, HW, nslabs); \
-        else if (two) hipLaunchKernelGGL((wgrad1x1_stream_kernel<MT_, NT_, true, 1>), dim3(grid), dim3(256), 0, st, S, T, slabs, B, CS, CT, HW, nslabs); \
-        else if (deep) hipLaunchKernelGGL((wgrad1x1_stream_kernel<MT_, NT_, false, 2>), dim3(grid), dim3(256), 0, st, S, T, slabs, B, CS, CT, HW, nslabs); \
-        else hipLaunchKernelGGL((wgrad1x1_stream_kernel<MT_, NT_, false, 1>), dim3(grid), dim3(256), 0, st, S, T, slabs, B, CS, CT, HW, nslabs); \
+        if (two) hipLaunchKernelGGL((wgrad1x1_stream_kernel<MT_, NT_, true>), dim3(grid), dim3(256), 0, st, S, T, slabs, B, CS, CT, HW, nslabs); \
+        else hipLaunchKernelGGL((wgrad1x1_stream_kernel<MT_, NT_, false>), dim3(grid), dim3(256), 0, st, S, T, slabs, B, CS, CT, HW, nslabs); \
     }
     DM_SW(4, 4) DM_SW(4, 2) DM_SW(2, 4) DM_SW(2, 2)
 #undef DM_SW

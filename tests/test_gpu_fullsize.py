@@ -61,8 +61,8 @@ def test_c3_training_step_at_batch_2048_against_the_oracle():
     # terms has the size of sqrt(N) of them, so ONE position that takes another code moves every gradient by ~1/724 of its scale
     # -- far above any fp32 error.  Where codes_gate has admitted flips (reference near-ties only), the yardsticks are evaluated
     # with the HIP path's codes, so that gradients are compared under the same discrete choices.  (Round 5: the paired
-    # first-convolution kernel's a1 is closer to float64 than kernel A's -- rms 3.3e-8 against 4.1e-8, the reference's own 9.6e-8,
-    # tools/exp/e1_accuracy.py -- and turns 2 near-ties of this batch the other way; with the reference's codes in the yardstick
+    # first-convolution kernel's a1 is closer to float64 than kernel A's -- rms 3.3e-8 against 4.1e-8, the reference's own 9.6e-8
+    # -- and turns 2 near-ties of this batch the other way; with the reference's codes in the yardstick
     # nine gradients sat 2-150 x beyond the reference's error, tools/exp/c3_grad_ratios.py.)
     nflip = int((idx != idx_r).sum())
     # (codes_gate has already restricted flips to the reference's own near-ties and to 1e-5 of the positions; at this batch

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The full-size C3 gradient gate (tests/test_gpu_fullsize.py) as a table: per tensor, the HIP gradient's and the fp32
-reference's max error against the float64 truth and their ratio, for the kernels the environment selects (DM_CONV4_PAIR etc.).
+reference's max error against the float64 truth and their ratio, for the kernels the environment selects.
 Caches the oracle's two runs in /tmp so that several configurations can be compared in one call."""
 import copy, gc, os, sys
 import torch

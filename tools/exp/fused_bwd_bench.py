@@ -1,5 +1,5 @@
 """Backward of enc.4 at the headline batch: the two kernels (transposed-convolution data gradient + weight gradient)
-against kernel D (one staging).  DM_FUSED_BWD_BLOCK=512 / 256 picks kernel D's workgroup size (read once per process)."""
+against kernel D (one staging)."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from dynamorph_amd import ops
@@ -54,5 +54,5 @@ flop = 2.0 * B * H * W * CD * CX * 16 * 2            # useful multiply-adds of b
 byt = B * (2 * CD * H * W + 2 * CX * 4 * H * W) * 4   # dy, a_out, a_in read once, dx written
 for name, fn in (("two kernels", pair), ("kernel D  ", fused)):
     ms = t_ms(fn)
-    print(f"B={B} block={os.environ.get('DM_FUSED_BWD_BLOCK', '256')} {name}: {ms * 1e3:7.1f} us  {flop / ms / 1e9:6.1f} TFLOP/s useful  "
+    print(f"B={B} {name}: {ms * 1e3:7.1f} us  {flop / ms / 1e9:6.1f} TFLOP/s useful  "
           f"{byt / ms / 1e6:7.1f} GB/s of distinct tensors", flush=True)

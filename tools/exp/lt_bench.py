@@ -1,6 +1,5 @@
 #!/usr/bin/env python3
-"""Latent-tail kernel alone (csrc/latent_tail.hip) on 1024 patches, graph-timed; DM_LT_DBG ablations are set by the caller:
-    for d in 0 1 2 4 3 7; do DM_LT_DBG=$d python3 tools/exp/lt_bench.py; done"""
+"""Latent-tail kernel alone (csrc/latent_tail.hip) on 1024 patches, graph-timed."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import dynamorph_amd
@@ -30,4 +29,4 @@ e0.record()
 for _ in range(10):
     g.replay()
 e1.record(); e1.synchronize()
-print(f"DM_LT_DBG={os.environ.get('DM_LT_DBG', '0')}  B={B}: {e0.elapsed_time(e1) * 10:.1f} us per launch")
+print(f"B={B}: {e0.elapsed_time(e1) * 10:.1f} us per launch")
