@@ -30,7 +30,12 @@ __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const 
     const float bc2_sqrt = (float)sqrt(bc2);
     const float w1 = 1.f - b1, w2 = 1.f - b2;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float gi = g[i] * grad_scale;
+        float gi;
+        {
+            // rounded on its own: contracted into `gi - m` (an fma) it would not be the separate launch's product
+#pragma clang fp contract(off)
+            gi = g[i] * grad_scale;
+        }
         const float mi = m[i] + w1 * (gi - m[i]);
         const float vi = v[i] * b2 + w2 * (gi * gi);
         m[i] = mi;

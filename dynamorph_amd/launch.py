@@ -139,6 +139,9 @@ def self_launch(script, argv, n, timeout=None, env=None, stdout=None, stderr=Non
     child_env = dict(os.environ if env is None else env)
     child_env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # dmabuf IPC: what this pool's driver supports (RCCL needs it)
     child_env["DM_SELF_LAUNCHED"] = "1"
+    # the ranks share ONE stdout pipe and flush every line themselves; unbuffered, Python writes a line and its newline
+    # as two system calls, and another rank's line can land between them -- the JSON line then no longer stands alone
+    child_env.pop("PYTHONUNBUFFERED", None)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         child_env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",

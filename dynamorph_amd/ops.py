@@ -709,9 +709,12 @@ def channel_stats(p, q=None):
 
 @_op
 def sum_slabs(stats, dst, scale=1.0, n=None):
-    """dst[i] = scale * sum_slabs stats[slab][i][0] for the first n = dst.numel() entries of the slab rows."""
+    """dst[i] = scale * sum_slabs stats[slab][i][0] for all N = stats.shape[1] entries of the slab rows.  The kernel
+    writes N values: a shorter dst (or an n other than N) is refused here instead of being written past its end."""
     lib = L.load()
     N = stats.shape[1]
+    if dst.numel() < N or (n is not None and n != N):
+        raise ValueError(f"dm_sum_slabs: the slab rows have {N} entries, dst {dst.numel()}, n {n}")
     L.check(lib.dm_sum_slabs(_ptr(stats, torch.float64), stats.shape[0], N, scale, _ptr(dst), _stream()), "dm_sum_slabs")
     return dst
 

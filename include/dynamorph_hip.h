@@ -629,7 +629,8 @@ int dm_zscore_channels(const void *in, int in_is_f64, int diff_f64, int quot_f64
 
 /* ===== on-device augmentation (run_training.py:396-403) ======================= */
 /* out[b] = rot90(flip(in[b], flip_code[b]), k = rot_code[b]) on square (C,H,H) patches;
- * flip_code 0 none / 1 flip H / 2 flip W, rot_code 0..3 (counter-clockwise, dims [1,2]). */
+ * flip_code 0 none / 1 flip H / 2 flip W, rot_code 0..3 (counter-clockwise, dims [1,2]).  Only the two low bits of
+ * rot_code count (k = rot_code & 3: 5 turns once, -1 three times); a flip_code other than 1 or 2 does not flip. */
 int dm_augment(const float *in, float *out, const int32_t *flip_code, const int32_t *rot_code,
                int B, int C, int H, void *stream);
 

@@ -1000,6 +1000,16 @@ def test_bn_finalize_and_backward(ops):
     close(da, a_ref.grad, 1e-4, 2e-6, "bn backward dx")
     close(dgamma, bn.weight.grad, 1e-5, 1e-4, "dgamma")
     close(dbeta, bn.bias.grad, 1e-5, 1e-4, "dbeta")
+    # the same outputs against float64 BatchNorm and the derived bound (tests/helpers/glue_reference.py): the hand-picked
+    # tolerances above and the bound are seen to agree on this shape
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+    import glue_reference as G
+    ref = G.bn_apply_chain_ref(a, dy, bn.weight.detach(), bn.bias.detach(), 1e-5)
+    for name, got in (("y", y), ("da", da), ("dgamma", dgamma), ("dbeta", dbeta)):
+        err = (got.cpu().double().reshape(ref[name].shape) - ref[name]).abs()
+        print(f"bn {name}: worst error / derived bound {float((err / ref['b_' + name]).max()):.3f}")
+        assert bool((err <= ref["b_" + name]).all()), f"bn {name}: {float((err / ref['b_' + name]).max()):.2f} derived bounds"
 
 
 def test_bn_per_sample_statistics(ops):
