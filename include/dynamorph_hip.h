@@ -432,7 +432,8 @@ int dm_sum_slabs_scatter(const double *stats, int nslabs, int N, float scale, co
 /* decoded = Conv2d(C4 -> NIN, 1x1)(d4) + bias; loss partials
  * sum ((decoded*m - x*m)^2 / channel_var[c]) as one double per workgroup.
  * mask: (B,MC,H,W) with MC in {1, NIN}, or NULL (= ones).
- * x = NULL: decoder-only call (VQ_VAE.dec(z)), no loss partials are written.
+ * b6 = NULL: no bias.  x = NULL: decoder-only call (VQ_VAE.dec(z)): loss_slabs may be NULL; where it is given, zeros are
+ * written.
  * Built for C4 = num_hiddens//4 in {4, 8, 16} and NIN 1..4 (dm_head_supported tells); other widths run the same
  * arithmetic as dm_conv3x3(taps=1) + dm_recon_loss + dm_wgrad. */
 int dm_head_supported(int C4, int NIN);
@@ -459,12 +460,14 @@ int dm_head_backward(const float *decoded, const float *x, const float *mask, in
 int dm_dec_tail_supported(int C2, int NIN, int H2, int W2);
 int dm_dec_tail_num_blocks(int B, int H2, int W2);
 /* d2 (B,4,H2,W2) post-ReLU input of dec.4; w4 (4,4,4,4) ConvTranspose2d weight [ci][co][ky][kx]; w6 (NIN,4).
- * decoded (B,NIN,2H2,2W2); loss_slabs: dm_dec_tail_num_blocks doubles (x = NULL: decoder-only, no loss). */
+ * decoded (B,NIN,2H2,2W2); loss_slabs: dm_dec_tail_num_blocks doubles (x = NULL: decoder-only: loss_slabs may be NULL,
+ * where it is given zeros are written).  b6 = NULL: no bias.  mask (B,MC,2H2,2W2) with MC in {1, NIN}, or NULL (= ones). */
 int dm_dec_tail_forward(const float *d2, const float *w4, const float *b4, const float *w6, const float *b6,
                         const float *x, const float *mask, int mask_channels, const float *channel_var,
                         float *decoded, double *loss_slabs, int B, int C2, int NIN, int H2, int W2, void *stream);
 /* Backward of the same block for d(total)/d(recon_loss) = gscale_dev[0]:
- *   g2 (B,4,H2,64) = gradient w.r.t. the PRE-ReLU output of dec.2 (already masked by d2 > 0);
+ *   gscale_dev is required (not NULL);
+ *   g2 (B,4,H2,W2) = gradient w.r.t. the PRE-ReLU output of dec.2 (already masked by d2 > 0);
  *   part_slabs [nblocks][NIN*4 + NIN + 4 + 4][2] doubles = partial sums of dW6 | db6 | db4 | db2 (dm_sum_slabs);
  *   w_slabs [nblocks][256] floats = partial dW4 in the parameter's layout (dm_reduce_slabs). */
 int dm_dec_tail_backward(const float *d2, const float *w4, const float *b4, const float *w6,
