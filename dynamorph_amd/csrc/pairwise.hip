@@ -123,6 +123,13 @@ extern "C" int dm_pair_msd_backward(const float *z, const float *g_sim, float *d
 // by the whole wave, fp32 products added in double -- in the epilogue, and its gradient term S_ij (z_i - z_j) is taken
 // from differences too (tm_near_backward_kernel) instead of the second GEMM, where rowsum(S) z_i - sum_j S_ij z_j
 // cancels the same way.  Every other pair keeps a relative error <= c u / TM_NEAR ~ 3e-6 on sim.
+//
+// Two forms of the forward: the SQUARE one (a whole batch; half the tiles, each pair formed once for both orientations) and
+// the ROW-RANGE one (data parallel: one rank's rows r0 .. r0 + R - 1 of a global batch of B against all of it).  They are
+// thin kernels around the same pieces -- tm_gram_tile / tm_gram_store, tm_pair and its helpers -- and one host path
+// (tm_forward, tm_backward: the square backward is the range (0, B)), so every pair is formed from the same operands by the
+// same arithmetic: S and dz of a row range are rows of the square call's, to the bit.
+// Layout: state and count kernels; the Gram kernels; the per-pair arithmetic; the epilogues; the backward; the host side.
 namespace {
 
 constexpr int TM_T = 64;          // 64 x 64 output tile per workgroup: 4 waves, 32 x 32 each (2 x 2 MFMA tiles)
@@ -227,15 +234,28 @@ __device__ __forceinline__ void tm_gram_tile(const float *__restrict__ z, int n,
     }
 }
 
-// P[ks][i][j] = sum_{d in split ks} z[i][d] z[j][d] for the tiles ON AND ABOVE the diagonal: G is symmetric and the epilogue
-// reads one orientation of every entry (P[min][max]), so the nt (nt - 1) / 2 tiles below the diagonal are never formed --
-// at B = 2048 that is 496 of 1024 workgroups (blockIdx.x walks the upper triangle row by row)
+// store(i, j, value) for the 16 entries a thread holds of the tile at (i0, j0) after tm_gram_tile
+template <class Store>
+__device__ __forceinline__ void tm_gram_store(const f32x4 (&acc)[2][2], int i0, int j0, Store store)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wr = wave >> 1, wc = wave & 1;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                store(i0 + wr * 32 + a * 16 + (lane >> 4) * 4 + r, j0 + wc * 32 + b * 16 + (lane & 15), acc[a][b][r]);
+}
+
+// The square form.  P[ks][i][j] = sum_{d in split ks} z[i][d] z[j][d] for the tiles ON AND ABOVE the diagonal: G is symmetric
+// and the epilogue reads one orientation of every entry (P[min][max]), so the nt (nt - 1) / 2 tiles below the diagonal are
+// never formed -- at B = 2048 that is 496 of 1024 workgroups (blockIdx.x walks the upper triangle row by row)
 __global__ __launch_bounds__(256) void tm_gram_kernel(const float *__restrict__ z, float *__restrict__ P, int B, int n, int klen,
                                                       int nt, const int *__restrict__ state)
 {
     __shared__ float sA[TM_T * TM_LDA], sB[TM_T * TM_LDA];
     if (tm_sparse(state, B)) return;                       // (uniform) the epilogue will not read P
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wr = wave >> 1, wc = wave & 1;
     int tcol = blockIdx.x, trow = 0;
     for (int len = nt; tcol >= len; --len) { tcol -= len; ++trow; }    // (uniform: at most nt scalar steps)
     tcol += trow;
@@ -244,15 +264,34 @@ __global__ __launch_bounds__(256) void tm_gram_kernel(const float *__restrict__ 
     f32x4 acc[2][2];
     tm_gram_tile(z, n, i0, B, j0, B, k_lo, k_hi, sA, sB, acc);
     float *__restrict__ Pk = P + (long long)blockIdx.z * B * B;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int i = i0 + wr * 32 + a * 16 + (lane >> 4) * 4 + r, j = j0 + wc * 32 + b * 16 + (lane & 15);
-                if (i < B && j < B) Pk[(long long)i * B + j] = acc[a][b][r];
-            }
+    tm_gram_store(acc, i0, j0, [=](int i, int j, float v) {
+        if (i < B && j < B) Pk[(long long)i * B + j] = v;
+    });
+}
+
+// The row-range form (data parallel: one rank's rows r0 .. r0 + R - 1 of a global batch of B).  P[ks][i - r0][j] for the R
+// rows against all B columns (tiles of 64 rows from r0, of 64 columns from 0), and behind them one workgroup per 64 x 64
+// diagonal tile of the whole batch for the Gram diagonal D[ks][g] (the epilogue needs G_jj of every column; only the
+// diagonal of those tiles is stored).  The same K split as the square call's: every entry is the square form's, to the bit.
+__global__ __launch_bounds__(256) void tm_gram_rows_kernel(const float *__restrict__ z, float *__restrict__ P, float *__restrict__ D,
+                                                           int B, int n, int klen, int r0, int R, int ntr, int nt,
+                                                           const int *__restrict__ state)
+{
+    __shared__ float sA[TM_T * TM_LDA], sB[TM_T * TM_LDA];
+    if (tm_sparse(state, B)) return;                       // (uniform) the epilogue will not read P or D
+    const int k_lo = blockIdx.z * klen, k_hi = min(n, k_lo + klen);
+    const bool diag = (int)blockIdx.x >= ntr * nt;
+    const int i0 = diag ? (blockIdx.x - ntr * nt) * TM_T : r0 + (blockIdx.x / nt) * TM_T;
+    const int j0 = diag ? i0 : (blockIdx.x % nt) * TM_T;
+    f32x4 acc[2][2];
+    tm_gram_tile(z, n, i0, diag ? B : r0 + R, j0, B, k_lo, k_hi, sA, sB, acc);
+    tm_gram_store(acc, i0, j0, [=](int i, int j, float v) {
+        if (diag) {
+            if (i == j && i < B) D[(long long)blockIdx.z * B + i] = v;
+        } else if (i < r0 + R && j < B) {
+            P[((long long)blockIdx.z * R + (i - r0)) * B + j] = v;
+        }
+    });
 }
 
 struct TmParams { int mode; float w_a, w_t, w_n, margin; };
@@ -309,14 +348,103 @@ __device__ __forceinline__ void tm_near_sims(const float *__restrict__ z, int n,
     }
 }
 
-// The 64 x 64 tiles ON OR ABOVE the diagonal (the tiles tm_gram_kernel forms), TM_EP workgroups per tile (16 rows i each),
-// one thread per 4 of its pairs (i, j), i <= j: sim from the Gram slabs (near pairs: from differences, by the wave), BOTH
-// orientations of the loss term -- the pair's two entries of tm -- and S_ij = S_ji written to both places, the mirrored
-// entries through LDS.  (The first form, one thread per entry of the (B, B) matrix, read P and tm across the diagonal with a
-// stride of B floats between lanes: 0.22 of the 0.38 ms forward at B = 2048.)  S: (2, B, B), the far part (for the gradient
-// GEMM) and the near part (for tm_near_backward_kernel); loss partials per workgroup.
-// TM_ER rows i per workgroup = TM_T / TM_ER workgroups per tile: 16 rows, or 4 where 16 would leave most of the chip without a
-// workgroup (B <= 640: fewer than 66 tiles)
+// ---- the epilogue.  Two kernels, the square form's and the row-range form's, around ONE body per pair and shared pieces:
+// every pair (i, j) is formed from the same operands by the same instructions in both, so the rows' S and dz are rows of
+// the square call's, to the bit.  The kernels differ in how a tile is found (triangle walk or rectangle), where the Gram
+// diagonal is read (P[g][g] or D[g]), whether the mirrored entry is written through LDS, and whether the loss counts one
+// orientation of a pair or both.
+
+// sT[r][c] = tm[j0 + r][ib + c], rows i = ib + c below ihi: the pair's other orientation (tm need not be symmetric)
+template <int TM_ER>
+__device__ __forceinline__ void tm_stage_transposed(float (&sT)[TM_T][TM_ER + 1], const float *__restrict__ tm, int B, int j0,
+                                                    int ib, int ihi)
+{
+#pragma unroll
+    for (int k = 0; k < TM_T * TM_ER / 256; ++k) {
+        const int e = threadIdx.x + 256 * k, r = e / TM_ER, c = e % TM_ER;
+        sT[r][c] = (j0 + r < B && ib + c < ihi) ? tm[(long long)(j0 + r) * B + ib + c] : 0.f;
+    }
+}
+
+// Gram diagonal of the workgroup's rows ib .. (s_gi) and of the tile's columns j0 .. (s_gj): split ks of G_gg lies at
+// diag[ks * ks_stride + g * g_stride]; the chunk sums are added in double, in a fixed order
+template <int TM_ER>
+__device__ __forceinline__ void tm_gram_diagonal(const float *__restrict__ diag, long long ks_stride, long long g_stride,
+                                                 int ksplit, int B, int ib, int j0, double (&s_gi)[TM_ER], double (&s_gj)[TM_T])
+{
+    if (threadIdx.x < TM_ER + TM_T) {
+        const int g = threadIdx.x < TM_ER ? ib + (int)threadIdx.x : j0 + (int)threadIdx.x - TM_ER;
+        double d = 0.0;
+        if (g < B)
+            for (int ks = 0; ks < ksplit; ++ks) d += (double)diag[ks * ks_stride + g * g_stride];
+        if (threadIdx.x < TM_ER) s_gi[threadIdx.x] = d; else s_gj[threadIdx.x - TM_ER] = d;
+    }
+}
+
+struct TmPair { double v_ij, v_ji; float far, near; };    // both orientations' loss terms; S_ij as its far and its near part
+
+// The pair (i, j) of lane j - j0 (`have`: the thread has one; the whole wave calls, its lanes share i): t_ij, t_ji its two
+// relation entries, gii / gjj the Gram diagonal, gram_ij(ks) split ks of G_ij.  sim from the Gram partials added in double
+// (the sparse form: not at all), the near pairs from differences, the two loss terms, S_ij = dloss/dsim_ij + dloss/dsim_ji.
+template <class GramIJ>
+__device__ __forceinline__ TmPair tm_pair(const float *__restrict__ z, int n, const TmParams &p, float inv_count, bool sparse,
+                                          bool have, int i, int j, int j0, int lane, float t_ij, float t_ji, double gii,
+                                          double gjj, int ksplit, GramIJ gram_ij)
+{
+    float sim = 0.f;
+    bool near = false;
+    if (have && sparse) {                                  // every related pair from differences, nothing else matters
+        near = i != j && (t_ij != 0.f || t_ji != 0.f);
+    } else if (have) {
+        double gij = 0.0;
+        for (int ks = 0; ks < ksplit; ++ks) gij += (double)gram_ij(ks);
+        const double d2 = gii + gjj - 2.0 * gij;
+        sim = i == j ? 0.f : (float)(d2 / (double)n);
+        near = i != j && !(d2 >= (double)TM_NEAR * (gii + gjj));    // (also when the Gram value is not finite)
+    }
+    tm_near_sims(z, n, i, j0, near, lane, sim);
+    TmPair r = {0.0, 0.0, 0.f, 0.f};
+    if (have) {
+        float d_ij, d_ji;
+        tm_value(p, sim, t_ij, inv_count, r.v_ij, d_ij);
+        tm_value(p, sim, t_ji, inv_count, r.v_ji, d_ji);
+        const float sij = d_ij + d_ji;
+        r.far = near ? 0.f : sij;
+        r.near = near ? sij : 0.f;
+    }
+    return r;
+}
+
+// The chunks of the far part this wave put a nonzero into, rows of panel `row`: its lanes span two chunks of columns from j0.
+// mirror_row >= 0: the mirrored entries as well, rows mirror_row .., columns row ..
+__device__ __forceinline__ void tm_map_mark(int *far_map, int B, bool any_far, int lane, int row, int j0, int mirror_row)
+{
+    if (!far_map) return;
+    const unsigned long long bal = __ballot(any_far);
+    if (lane == 0) {
+        if (bal & 0xffffffffull) tm_map_set(far_map, B, row, j0);
+        if (bal >> 32) tm_map_set(far_map, B, row, j0 + 32);
+        if (bal && mirror_row >= 0) tm_map_set(far_map, B, mirror_row, row);
+    }
+}
+
+template <int TM_ER>
+__device__ __forceinline__ void tm_store_slab(double val, double *s_red, double *__restrict__ loss_slabs)
+{
+    const double tot = block_sum(val, s_red);
+    if (threadIdx.x == 0) {
+        const long long slab = (long long)blockIdx.x * (TM_T / TM_ER) + blockIdx.y;
+        loss_slabs[2 * slab] = tot; loss_slabs[2 * slab + 1] = 0.0;
+    }
+}
+
+// The square form: the 64 x 64 tiles ON OR ABOVE the diagonal (the tiles tm_gram_kernel forms), TM_T / TM_ER workgroups per
+// tile (TM_ER rows i each), one thread per TM_ER / 4 of its pairs (i, j), i <= j: BOTH orientations of the loss term -- the
+// pair's two entries of tm -- and S_ij = S_ji written to both places, the mirrored entries through LDS.  (The first form, one
+// thread per entry of the (B, B) matrix, read P and tm across the diagonal with a stride of B floats between lanes: 0.22 of
+// the 0.38 ms forward at B = 2048.)  S: (2, B, B), the far part (for the gradient GEMM) and the near part (for
+// tm_near_backward_kernel); loss partials per workgroup.
+// TM_ER = 16 rows, or 4 where 16 would leave most of the chip without a workgroup (tm_er: fewer than 64 tiles)
 template <int TM_ER>
 __global__ __launch_bounds__(256) void tm_epilogue_kernel(const float *__restrict__ z, const float *__restrict__ P, int ksplit,
                                                           const float *__restrict__ tm, int B, int n, TmParams p,
@@ -330,24 +458,13 @@ __global__ __launch_bounds__(256) void tm_epilogue_kernel(const float *__restric
     int tcol = blockIdx.x, trow = 0;
     for (int len = nt; tcol >= len; --len) { tcol -= len; ++trow; }
     tcol += trow;
-    constexpr int TM_EP = TM_T / TM_ER;
     const int ib = trow * TM_T + blockIdx.y * TM_ER, j0 = tcol * TM_T;
     const bool diag = trow == tcol;
     const long long BB = (long long)B * B;
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6, lane = tx;
-#pragma unroll
-    for (int k = 0; k < TM_T * TM_ER / 256; ++k) {
-        const int e = threadIdx.x + 256 * k, r = e / TM_ER, c = e % TM_ER;
-        sT[r][c] = (j0 + r < B && ib + c < B) ? tm[(long long)(j0 + r) * B + ib + c] : 0.f;
-    }
+    tm_stage_transposed<TM_ER>(sT, tm, B, j0, ib, B);
     const bool sparse = tm_sparse(state, B);
-    if (!sparse && threadIdx.x < TM_ER + TM_T) {         // chunk sums added in double, in a fixed order
-        const int g = threadIdx.x < TM_ER ? ib + (int)threadIdx.x : j0 + (int)threadIdx.x - TM_ER;
-        double d = 0.0;
-        if (g < B)
-            for (int ks = 0; ks < ksplit; ++ks) d += (double)P[ks * BB + (long long)g * B + g];
-        if (threadIdx.x < TM_ER) s_gi[threadIdx.x] = d; else s_gj[threadIdx.x - TM_ER] = d;
-    }
+    if (!sparse) tm_gram_diagonal<TM_ER>(P, BB, B + 1, ksplit, B, ib, j0, s_gi, s_gj);
     __syncthreads();
     const float inv_count = p.mode == 0 ? 1.f : 1.f / (float)BB;
     const int j = j0 + tx;
@@ -358,42 +475,19 @@ __global__ __launch_bounds__(256) void tm_epilogue_kernel(const float *__restric
     for (int q = 0; q < TM_ER / 4; ++q) {
         const int il = ty + 4 * q, i = ib + il;
         const bool have = i < B && j < B && (!diag || i <= j);
-        float sim = 0.f;
-        bool near = false;
-        if (have && sparse) {                              // every related pair from differences, nothing else matters
-            near = i != j && (tm[(long long)i * B + j] != 0.f || sT[tx][il] != 0.f);
-        } else if (have) {
-            double gij = 0.0;
-            for (int ks = 0; ks < ksplit; ++ks) gij += (double)P[ks * BB + (long long)i * B + j];
-            const double gii = s_gi[il];
-            const double d2 = gii + gjj - 2.0 * gij;
-            sim = i == j ? 0.f : (float)(d2 / (double)n);
-            near = i != j && !(d2 >= (double)TM_NEAR * (gii + gjj));    // (also when the Gram value is not finite)
-        }
-        tm_near_sims(z, n, i, j0, near, lane, sim);
-        float sij = 0.f;
+        const long long o = (long long)i * B + j;
+        const TmPair r = tm_pair(z, n, p, inv_count, sparse, have, i, j, j0, lane, have ? tm[o] : 0.f, sT[tx][il], s_gi[il], gjj,
+                                 ksplit, [=](int ks) { return P[ks * BB + o]; });
         if (have) {
-            float d_ij, d_ji;
-            double v_ij, v_ji;
-            tm_value(p, sim, tm[(long long)i * B + j], inv_count, v_ij, d_ij);
-            tm_value(p, sim, sT[tx][il], inv_count, v_ji, d_ji);
-            val += i == j ? v_ij : v_ij + v_ji;
-            sij = d_ij + d_ji;
-            S[(long long)i * B + j] = near ? 0.f : sij;
-            S[BB + (long long)i * B + j] = near ? sij : 0.f;
+            val += i == j ? r.v_ij : r.v_ij + r.v_ji;
+            S[o] = r.far;
+            S[BB + o] = r.near;
         }
-        sF[il][tx] = near ? 0.f : sij;
-        sN[il][tx] = near ? sij : 0.f;
-        any_far |= !near && sij != 0.f;
+        sF[il][tx] = r.far;
+        sN[il][tx] = r.near;
+        any_far |= r.far != 0.f;
     }
-    if (far_map) {                                         // the chunks of the far part this workgroup put a nonzero into
-        const unsigned long long bal = __ballot(any_far);  // (a wave's rows share the panel; its lanes span two chunks of columns)
-        if (lane == 0) {
-            if (bal & 0xffffffffull) tm_map_set(far_map, B, ib, j0);
-            if (bal >> 32) tm_map_set(far_map, B, ib, j0 + 32);
-            if (bal) tm_map_set(far_map, B, j0, ib);       // the mirrored entries: rows j0 .. j0 + 63, columns ib .. ib + TM_ER - 1
-        }
-    }
+    tm_map_mark(far_map, B, any_far, lane, ib, j0, j0);    // (the mirrored entries: rows j0 .. j0 + 63, columns ib .. ib + TM_ER - 1)
     __syncthreads();
     // the mirrored entries: S[j][i] = S[i][j] (the loss counts both orientations of a pair, so S is symmetric)
 #pragma unroll
@@ -405,11 +499,53 @@ __global__ __launch_bounds__(256) void tm_epilogue_kernel(const float *__restric
             S[BB + (long long)jj * B + ii] = sN[c][jl];
         }
     }
-    const double tot = block_sum(val, s_red);
-    if (threadIdx.x == 0) {
-        const long long slab = (long long)blockIdx.x * TM_EP + blockIdx.y;
-        loss_slabs[2 * slab] = tot; loss_slabs[2 * slab + 1] = 0.0;
+    tm_store_slab<TM_ER>(val, s_red, loss_slabs);
+}
+
+// The row-range form: one workgroup per (tile of 64 rows i among the R, tile of 64 columns j) and TM_ER rows of it: thread =
+// column j, TM_ER / 4 of the rows.  S (2, R, B) for the rows, the far-block map by (panel of 64 of the R rows, chunk of 32
+// columns), and the rows' OWN loss terms, sum_{i in rows, j} v_ij (mode 1 normalised by B * B): the shares of a partition
+// of the rows add up to the square call's loss.
+template <int TM_ER>
+__global__ __launch_bounds__(256) void tm_epilogue_rows_kernel(const float *__restrict__ z, const float *__restrict__ P,
+                                                               const float *__restrict__ D, int ksplit,
+                                                               const float *__restrict__ tm, int B, int n, int r0, int R, TmParams p,
+                                                               float *__restrict__ S, double *__restrict__ loss_slabs, int nt,
+                                                               const int *__restrict__ state, int *__restrict__ far_map)
+{
+    __shared__ float sT[TM_T][TM_ER + 1];                // tm[j0 + r][ib + c]
+    __shared__ double s_gi[TM_ER], s_gj[TM_T];
+    __shared__ double s_red[4];
+    const int trow = blockIdx.x / nt, tcol = blockIdx.x % nt;
+    const int il0 = trow * TM_T + blockIdx.y * TM_ER;   // first local row of the workgroup
+    const int ib = r0 + il0, j0 = tcol * TM_T, rhi = r0 + R;
+    const long long RB = (long long)R * B;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6, lane = tx;
+    tm_stage_transposed<TM_ER>(sT, tm, B, j0, ib, rhi);
+    const bool sparse = tm_sparse(state, B);
+    if (!sparse) tm_gram_diagonal<TM_ER>(D, B, 1, ksplit, B, ib, j0, s_gi, s_gj);
+    __syncthreads();
+    const float inv_count = p.mode == 0 ? 1.f : 1.f / (float)((long long)B * B);
+    const int j = j0 + tx;
+    const double gjj = s_gj[tx];
+    double val = 0.0;
+    bool any_far = false;
+#pragma unroll
+    for (int q = 0; q < TM_ER / 4; ++q) {
+        const int il = ty + 4 * q, i = ib + il;
+        const bool have = i < rhi && j < B;
+        const long long o = (long long)(i - r0) * B + j;
+        const TmPair r = tm_pair(z, n, p, inv_count, sparse, have, i, j, j0, lane, have ? tm[(long long)i * B + j] : 0.f,
+                                 sT[tx][il], s_gi[il], gjj, ksplit, [=](int ks) { return P[ks * RB + o]; });
+        if (have) {
+            val += r.v_ij;
+            S[o] = r.far;
+            S[RB + o] = r.near;
+        }
+        any_far |= r.far != 0.f;
     }
+    tm_map_mark(far_map, B, any_far, lane, il0, j0, -1);
+    tm_store_slab<TM_ER>(val, s_red, loss_slabs);
 }
 
 // dz[i][d] += scale * g * sum_{j near i} S_ij (z[i][d] - z[j][d]): the near pairs' share of the gradient from differences.
@@ -623,128 +759,16 @@ __global__ __launch_bounds__(256) void tm_backward_kernel(const float *__restric
             }
 }
 
-// ---- the row-range form (data parallel: one rank's rows r0 .. r0 + R - 1 of a global batch of B).  Every pair (i, j) with i
-// among the rows is formed from exactly the operands the square kernels use -- Gram partials with the same K split, the
-// Gram diagonal, differences for the near pairs, S_ij = d_ij + d_ji -- so S and dz are rows r0 .. r0 + R - 1 of the square
-// call's, to the bit.  The loss slabs hold the rows' own share, sum_{i in rows, j} v_ij (mode 1 normalised by B * B).
+// ---- the host side: ONE forward launch and ONE backward launch behind the seven entry points
+constexpr int tm_tiles(int rows) { return (rows + TM_T - 1) / TM_T; }
+int tm_square_tiles(int B) { return tm_tiles(B) * (tm_tiles(B) + 1) / 2; }      // the upper triangle of tiles
+int tm_rows_tiles(int B, int R) { return tm_tiles(R) * tm_tiles(B); }
+// rows per epilogue workgroup: 16, or 4 where 16 would leave most of the chip without a workgroup
+int tm_er(int tiles) { return 4 * tiles >= 256 ? 16 : 4; }
 
-// P[ks][i - r0][j] for the R rows against all B columns (tiles of 64 rows from r0, of 64 columns from 0), and behind them
-// one workgroup per 64 x 64 diagonal tile of the whole batch for the Gram diagonal D[ks][g] (the epilogue needs G_jj of
-// every column; only the diagonal of those tiles is stored)
-__global__ __launch_bounds__(256) void tm_gram_rows_kernel(const float *__restrict__ z, float *__restrict__ P, float *__restrict__ D,
-                                                           int B, int n, int klen, int r0, int R, int ntr, int nt,
-                                                           const int *__restrict__ state)
+int tm_ksplit(int B, int n)                               // of the square call, whichever form asks: the same partial sums
 {
-    __shared__ float sA[TM_T * TM_LDA], sB[TM_T * TM_LDA];
-    if (tm_sparse(state, B)) return;                       // (uniform) the epilogue will not read P or D
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wr = wave >> 1, wc = wave & 1;
-    const int k_lo = blockIdx.z * klen, k_hi = min(n, k_lo + klen);
-    const bool diag = (int)blockIdx.x >= ntr * nt;
-    const int i0 = diag ? (blockIdx.x - ntr * nt) * TM_T : r0 + (blockIdx.x / nt) * TM_T;
-    const int j0 = diag ? i0 : (blockIdx.x % nt) * TM_T;
-    f32x4 acc[2][2];
-    tm_gram_tile(z, n, i0, diag ? B : r0 + R, j0, B, k_lo, k_hi, sA, sB, acc);
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int i = i0 + wr * 32 + a * 16 + (lane >> 4) * 4 + r, j = j0 + wc * 32 + b * 16 + (lane & 15);
-                if (diag) {
-                    if (i == j && i < B) D[(long long)blockIdx.z * B + i] = acc[a][b][r];
-                } else if (i < r0 + R && j < B) {
-                    P[((long long)blockIdx.z * R + (i - r0)) * B + j] = acc[a][b][r];
-                }
-            }
-}
-
-// One workgroup per (tile of 64 rows i among the R, tile of 64 columns j) and TM_ER rows of it: thread = column j, 4 of the
-// rows.  Both entries of the pair's relation (tm[i][j], and tm[j][i] through LDS: tm need not be symmetric), S (2, R, B) for
-// the rows, the far-block map by (panel of 64 of the R rows, chunk of 32 columns), the rows' own loss terms.
-template <int TM_ER>
-__global__ __launch_bounds__(256) void tm_epilogue_rows_kernel(const float *__restrict__ z, const float *__restrict__ P,
-                                                               const float *__restrict__ D, int ksplit,
-                                                               const float *__restrict__ tm, int B, int n, int r0, int R, TmParams p,
-                                                               float *__restrict__ S, double *__restrict__ loss_slabs, int nt,
-                                                               const int *__restrict__ state, int *__restrict__ far_map)
-{
-    __shared__ float sT[TM_T][TM_ER + 1];                // tm[j0 + r][ib + c]
-    __shared__ double s_gi[TM_ER], s_gj[TM_T];
-    __shared__ double s_red[4];
-    constexpr int TM_EP = TM_T / TM_ER;
-    const int trow = blockIdx.x / nt, tcol = blockIdx.x % nt;
-    const int il0 = trow * TM_T + blockIdx.y * TM_ER;   // first local row of the workgroup
-    const int ib = r0 + il0, j0 = tcol * TM_T, rhi = r0 + R;
-    const long long RB = (long long)R * B;
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6, lane = tx;
-#pragma unroll
-    for (int k = 0; k < TM_T * TM_ER / 256; ++k) {
-        const int e = threadIdx.x + 256 * k, r = e / TM_ER, c = e % TM_ER;
-        sT[r][c] = (j0 + r < B && ib + c < rhi) ? tm[(long long)(j0 + r) * B + ib + c] : 0.f;
-    }
-    const bool sparse = tm_sparse(state, B);
-    if (!sparse && threadIdx.x < TM_ER + TM_T) {         // chunk sums added in double, in the square epilogue's order
-        const int g = threadIdx.x < TM_ER ? ib + (int)threadIdx.x : j0 + (int)threadIdx.x - TM_ER;
-        double d = 0.0;
-        if (g < B)
-            for (int ks = 0; ks < ksplit; ++ks) d += (double)D[(long long)ks * B + g];
-        if (threadIdx.x < TM_ER) s_gi[threadIdx.x] = d; else s_gj[threadIdx.x - TM_ER] = d;
-    }
-    __syncthreads();
-    const float inv_count = p.mode == 0 ? 1.f : 1.f / (float)((long long)B * B);
-    const int j = j0 + tx;
-    const double gjj = s_gj[tx];
-    double val = 0.0;
-    bool any_far = false;
-#pragma unroll
-    for (int q = 0; q < TM_ER / 4; ++q) {
-        const int il = ty + 4 * q, i = ib + il;
-        const bool have = i < rhi && j < B;
-        float sim = 0.f;
-        bool near = false;
-        if (have && sparse) {
-            near = i != j && (tm[(long long)i * B + j] != 0.f || sT[tx][il] != 0.f);
-        } else if (have) {
-            double gij = 0.0;
-            for (int ks = 0; ks < ksplit; ++ks) gij += (double)P[ks * RB + (long long)(i - r0) * B + j];
-            const double gii = s_gi[il];
-            const double d2 = gii + gjj - 2.0 * gij;
-            sim = i == j ? 0.f : (float)(d2 / (double)n);
-            near = i != j && !(d2 >= (double)TM_NEAR * (gii + gjj));
-        }
-        tm_near_sims(z, n, i, j0, near, lane, sim);
-        if (have) {
-            float d_ij, d_ji;
-            double v_ij, v_ji;
-            tm_value(p, sim, tm[(long long)i * B + j], inv_count, v_ij, d_ij);
-            tm_value(p, sim, sT[tx][il], inv_count, v_ji, d_ji);
-            val += v_ij;
-            const float sij = d_ij + d_ji;
-            const long long o = (long long)(i - r0) * B + j;
-            S[o] = near ? 0.f : sij;
-            S[RB + o] = near ? sij : 0.f;
-            any_far |= !near && sij != 0.f;
-        }
-    }
-    if (far_map) {                                         // (a wave's rows share the panel; its lanes span two chunks of columns)
-        const unsigned long long bal = __ballot(any_far);
-        if (lane == 0) {
-            if (bal & 0xffffffffull) tm_map_set(far_map, B, il0, j0);
-            if (bal >> 32) tm_map_set(far_map, B, il0, j0 + 32);
-        }
-    }
-    const double tot = block_sum(val, s_red);
-    if (threadIdx.x == 0) {
-        const long long slab = (long long)blockIdx.x * TM_EP + blockIdx.y;
-        loss_slabs[2 * slab] = tot; loss_slabs[2 * slab + 1] = 0.0;
-    }
-}
-
-int tm_ksplit(int B, int n)
-{
-    const int nt = (B + TM_T - 1) / TM_T, tiles = nt * (nt + 1) / 2;         // the upper triangle of tiles
-    int ks = 1024 / tiles;
+    int ks = 1024 / tm_square_tiles(B);
     const int maxks = n / 256 > 0 ? n / 256 : 1;
     if (ks > maxks) ks = maxks;
     if (ks > 64) ks = 64;
@@ -752,66 +776,33 @@ int tm_ksplit(int B, int n)
     return ks;
 }
 
-}  // namespace
+// What an entry point asks of the shared launch
+struct TmCall {
+    const char *name;               // the entry point, for messages
+    int r0, R;                      // rows r0 .. r0 + R - 1 of the batch (the square form: 0, B)
+    bool square;                    // the triangle walk over the whole batch; else the R x B rectangle
+    bool need_state, need_add;      // optional operands this entry point requires
+};
 
-extern "C" int dm_time_matching_supported(int B, int n) { return (B > 0 && n > 0 && n % TM_KC == 0) ? 1 : 0; }
-
-extern "C" int64_t dm_time_matching_workspace_floats(int B, int n)
+int tm_forward(const TmCall &c, const float *z, const float *tm, int B, int n, int mode, float w_a, float w_t, float w_n,
+               float margin, float *workspace, int64_t workspace_floats, float *S, double *loss_slabs, int32_t *state,
+               void *stream)
 {
-    // Gram slabs + (double) loss partials of the epilogue
-    const long long blocks = ((long long)B * B + 255) / 256;
-    return (long long)tm_ksplit(B, n) * B * B + 4 * blocks + 4;
-}
-
-static int tm_epilogue_rows(int B)                        // rows per workgroup of tm_epilogue_kernel
-{
-    const int nt = (B + TM_T - 1) / TM_T;
-    return 4 * (nt * (nt + 1) / 2) >= 256 ? 16 : 4;
-}
-
-extern "C" int dm_time_matching_state_ints(int B)         // the state block of the _state entries
-{
-    return TM_STATE_HDR + ((B + TM_T - 1) / TM_T) * tm_map_chunks(B);
-}
-
-extern "C" int dm_time_matching_num_slabs(int B)          // one per epilogue workgroup: TM_T / rows per tile on or above the diagonal
-{
-    const int nt = (B + TM_T - 1) / TM_T;
-    return (TM_T / tm_epilogue_rows(B)) * (nt * (nt + 1) / 2);
-}
-
-static int tm_forward_launch(const float *z, const float *tm, int B, int n, int mode, float w_a, float w_t, float w_n,
-                             float margin, float *workspace, int64_t workspace_floats, float *S, double *loss_slabs,
-                             int32_t *state, void *stream);
-
-extern "C" int dm_time_matching_forward(const float *z, const float *tm, int B, int n, int mode, float w_a, float w_t,
-                                        float w_n, float margin, float *workspace, int64_t workspace_floats, float *S,
-                                        double *loss_slabs, void *stream)
-{
-    return tm_forward_launch(z, tm, B, n, mode, w_a, w_t, w_n, margin, workspace, workspace_floats, S, loss_slabs, nullptr, stream);
-}
-
-extern "C" int dm_time_matching_forward_state(const float *z, const float *tm, int B, int n, int mode, float w_a, float w_t,
-                                              float w_n, float margin, float *workspace, int64_t workspace_floats, float *S,
-                                              double *loss_slabs, int32_t *state, void *stream)
-{
-    DM_REQUIRE(state, "dm_time_matching_forward_state: NULL pointer");
-    return tm_forward_launch(z, tm, B, n, mode, w_a, w_t, w_n, margin, workspace, workspace_floats, S, loss_slabs, state, stream);
-}
-
-static int tm_forward_launch(const float *z, const float *tm, int B, int n, int mode, float w_a, float w_t, float w_n,
-                             float margin, float *workspace, int64_t workspace_floats, float *S, double *loss_slabs,
-                             int32_t *state, void *stream)
-{
-    DM_REQUIRE(z && tm && workspace && S && loss_slabs, "dm_time_matching_forward: NULL pointer");
-    DM_REQUIRE(dm_time_matching_supported(B, n), "dm_time_matching_forward: latent length %d is not a multiple of %d", n, TM_KC);
-    DM_REQUIRE(mode == 0 || mode == 1, "dm_time_matching_forward: mode %d", mode);
-    DM_REQUIRE((long long)B * n < (1LL << 31) && (long long)B * B < (1LL << 31), "dm_time_matching_forward: tensor too large");
-    DM_REQUIRE(workspace_floats >= dm_time_matching_workspace_floats(B, n), "dm_time_matching_forward: workspace too small");
+    DM_REQUIRE(B > 0 && c.R >= 0 && c.r0 >= 0 && c.r0 + c.R <= B, "%s: rows [%d, %d) outside a batch of %d", c.name, c.r0,
+               c.r0 + c.R, B);
+    if (c.R == 0) return 0;                                // an empty shard: no rows, no loss terms, nothing launched
+    DM_REQUIRE(z && tm && workspace && S && loss_slabs && (state || !c.need_state), "%s: NULL pointer", c.name);
+    DM_REQUIRE(dm_time_matching_supported(B, n), "%s: latent length %d is not a multiple of %d", c.name, n, TM_KC);
+    DM_REQUIRE(mode == 0 || mode == 1, "%s: mode %d", c.name, mode);
+    DM_REQUIRE((long long)B * n < (1LL << 31) && (long long)B * B < (1LL << 31), "%s: tensor too large", c.name);
+    DM_REQUIRE(workspace_floats >= (c.square ? dm_time_matching_workspace_floats(B, n)
+                                             : dm_time_matching_rows_workspace_floats(B, c.R, n)),
+               "%s: workspace too small", c.name);
     // (tm_count_kernel and the epilogue read tm 16 bytes at a time where B * B is a multiple of four)
-    DM_REQUIRE((((uintptr_t)tm | (uintptr_t)z | (uintptr_t)S) & 15) == 0, "dm_time_matching_forward: z, tm and S must be 16-byte aligned");
+    DM_REQUIRE((((uintptr_t)tm | (uintptr_t)z | (uintptr_t)S) & 15) == 0, "%s: z, tm and S must be 16-byte aligned", c.name);
     hipStream_t s = (hipStream_t)stream;
-    const int ks = tm_ksplit(B, n), nt = (B + TM_T - 1) / TM_T;
+    const int ks = tm_ksplit(B, n), nt = tm_tiles(B), ntr = tm_tiles(c.R);
+    const int tiles = c.square ? tm_square_tiles(B) : tm_rows_tiles(B, c.R);
     int klen = (n + ks - 1) / ks;
     klen = (klen + TM_KC - 1) / TM_KC * TM_KC;
     // the sparse form: mode 0 only (in mode 1 the unrelated pairs carry the hinge term), and only where the caller keeps a state
@@ -820,10 +811,11 @@ static int tm_forward_launch(const float *z, const float *tm, int B, int n, int 
     int *far_map = nullptr;
     if (state) {
         // (cleared by a kernel of this stream, ordered like every other launch of the call)
-        const int ints = dm_time_matching_state_ints(B);
+        const int ints = dm_time_matching_rows_state_ints(B, c.R);
         hipLaunchKernelGGL(tm_state_clear_kernel, dim3((ints + 255) / 256), dim3(256), 0, s, (int *)state, ints);
         far_map = (int *)state + TM_STATE_HDR;
         if (mode == 0) {
+            // the count is of the WHOLE relation block, in the row-range form too: every rank decides alike
             const long long BB = (long long)B * B;
             const long long units = (BB & 3) == 0 ? BB >> 2 : BB;
             const int grid = (int)((units + 255) / 256 < 2048 ? (units + 255) / 256 : 2048);
@@ -831,71 +823,65 @@ static int tm_forward_launch(const float *z, const float *tm, int B, int n, int 
             st = (const int *)state;
         }
     }
-    hipLaunchKernelGGL(tm_gram_kernel, dim3(nt * (nt + 1) / 2, 1, ks), dim3(256), 0, s, z, workspace, B, n, klen, nt, st);
-    const TmParams p{mode, w_a, w_t, w_n, margin};
-    if (tm_epilogue_rows(B) == 16)
-        hipLaunchKernelGGL(tm_epilogue_kernel<16>, dim3(nt * (nt + 1) / 2, TM_T / 16), dim3(256), 0, s, z, workspace, ks, tm, B, n,
-                           p, S, loss_slabs, nt, st, far_map);
+    float *P = workspace, *D = workspace + (long long)ks * c.R * B;      // (D: the row-range form's)
+    if (c.square)
+        hipLaunchKernelGGL(tm_gram_kernel, dim3(tiles, 1, ks), dim3(256), 0, s, z, P, B, n, klen, nt, st);
     else
-        hipLaunchKernelGGL(tm_epilogue_kernel<4>, dim3(nt * (nt + 1) / 2, TM_T / 4), dim3(256), 0, s, z, workspace, ks, tm, B, n,
-                           p, S, loss_slabs, nt, st, far_map);
-    return dm_launch_status("dm_time_matching_forward");
+        hipLaunchKernelGGL(tm_gram_rows_kernel, dim3(tiles + nt, 1, ks), dim3(256), 0, s, z, P, D, B, n, klen, c.r0, c.R, ntr, nt, st);
+    const TmParams p{mode, w_a, w_t, w_n, margin};
+    auto epilogue = [&](auto er) {
+        constexpr int ER = decltype(er)::value;
+        const dim3 grid(tiles, TM_T / ER);
+        if (c.square)
+            hipLaunchKernelGGL(tm_epilogue_kernel<ER>, grid, dim3(256), 0, s, z, P, ks, tm, B, n, p, S, loss_slabs, nt, st, far_map);
+        else
+            hipLaunchKernelGGL(tm_epilogue_rows_kernel<ER>, grid, dim3(256), 0, s, z, P, D, ks, tm, B, n, c.r0, c.R, p, S,
+                               loss_slabs, nt, st, far_map);
+    };
+    if (tm_er(tiles) == 16) epilogue(std::integral_constant<int, 16>()); else epilogue(std::integral_constant<int, 4>());
+    return dm_launch_status(c.name);
 }
 
-static int tm_backward_launch(const float *z, const float *S, const float *g_loss_dev, float scale, const float *add,
-                              float *dz, int B, int n, const int32_t *state, void *stream);
-
-extern "C" int dm_time_matching_backward(const float *z, const float *S, const float *g_loss_dev, float scale, float *dz,
-                                         int B, int n, void *stream)
+// Rows of S, dz and add are the rows of the call; the square entry points are the range (0, B)
+int tm_backward(const TmCall &c, const float *z, const float *S, const float *g_loss_dev, float scale, const float *add,
+                float *dz, int B, int n, const int32_t *state, void *stream)
 {
-    return tm_backward_launch(z, S, g_loss_dev, scale, nullptr, dz, B, n, nullptr, stream);
-}
-
-extern "C" int dm_time_matching_backward_add(const float *z, const float *S, const float *g_loss_dev, float scale,
-                                             const float *add, float *dz, int B, int n, void *stream)
-{
-    DM_REQUIRE(add, "dm_time_matching_backward_add: NULL pointer");
-    return tm_backward_launch(z, S, g_loss_dev, scale, add, dz, B, n, nullptr, stream);
-}
-
-extern "C" int dm_time_matching_backward_state(const float *z, const float *S, const float *g_loss_dev, float scale,
-                                               const float *add, float *dz, int B, int n, const int32_t *state, void *stream)
-{
-    DM_REQUIRE(state, "dm_time_matching_backward_state: NULL pointer");
-    return tm_backward_launch(z, S, g_loss_dev, scale, add, dz, B, n, state, stream);
-}
-
-static int tm_backward_launch(const float *z, const float *S, const float *g_loss_dev, float scale, const float *add,
-                              float *dz, int B, int n, const int32_t *state, void *stream)
-{
-    DM_REQUIRE(z && S && dz, "dm_time_matching_backward: NULL pointer");
-    DM_REQUIRE(dm_time_matching_supported(B, n), "dm_time_matching_backward: latent length %d is not a multiple of %d", n, TM_KC);
-    DM_REQUIRE((long long)B * n < (1LL << 31), "dm_time_matching_backward: tensor too large");
-    DM_REQUIRE(B <= 16384, "dm_time_matching_backward: batch %d too large (a row of S is staged in LDS)", B);
+    DM_REQUIRE(B > 0 && c.R >= 0 && c.r0 >= 0 && c.r0 + c.R <= B, "%s: rows [%d, %d) outside a batch of %d", c.name, c.r0,
+               c.r0 + c.R, B);
+    if (c.R == 0) return 0;
+    DM_REQUIRE(z && S && dz && (state || !c.need_state) && (add || !c.need_add), "%s: NULL pointer", c.name);
+    DM_REQUIRE(dm_time_matching_supported(B, n), "%s: latent length %d is not a multiple of %d", c.name, n, TM_KC);
+    DM_REQUIRE((long long)B * n < (1LL << 31), "%s: tensor too large", c.name);
+    DM_REQUIRE(B <= 16384, "%s: batch %d too large (a row of S is staged in LDS)", c.name, B);
     // (rows of S are read as 16-byte vectors where B is a multiple of four; z tiles always are)
-    DM_REQUIRE((((uintptr_t)S | (uintptr_t)z) & 15) == 0, "dm_time_matching_backward: z and S must be 16-byte aligned");
-    const int *st = (const int *)state;
-    hipLaunchKernelGGL(tm_backward_kernel, dim3((n + TM_T - 1) / TM_T, (B + TM_T - 1) / TM_T), dim3(256), 0, (hipStream_t)stream,
-                       z, S, g_loss_dev, scale * 2.f / (float)n, dz, B, n, add, st, 0, B);
+    DM_REQUIRE((((uintptr_t)S | (uintptr_t)z) & 15) == 0, "%s: z and S must be 16-byte aligned", c.name);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(tm_backward_kernel, dim3(tm_tiles(n), tm_tiles(c.R)), dim3(256), 0, s, z, S, g_loss_dev,
+                       scale * 2.f / (float)n, dz, B, n, add, (const int *)state, c.r0, c.R);
     const size_t near_lds = (size_t)B * (sizeof(float) + sizeof(unsigned short));
     if (near_lds > 48 * 1024) {
         const hipError_t e = hipFuncSetAttribute((const void *)tm_near_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                  (int)near_lds);
         if (e != hipSuccess) {
-            dm_set_error("dm_time_matching_backward: cannot reserve %zu bytes of LDS: %s", near_lds, hipGetErrorString(e));
+            dm_set_error("%s: cannot reserve %zu bytes of LDS: %s", c.name, near_lds, hipGetErrorString(e));
             return (int)e;
         }
     }
-    hipLaunchKernelGGL(tm_near_backward_kernel, dim3((unsigned)B), dim3(256), near_lds, (hipStream_t)stream, z,
-                       S + (long long)B * B, g_loss_dev, scale * 2.f / (float)n, dz, B, n, 0);
-    return dm_launch_status("dm_time_matching_backward");
+    hipLaunchKernelGGL(tm_near_backward_kernel, dim3((unsigned)c.R), dim3(256), near_lds, s, z, S + (long long)c.R * B, g_loss_dev,
+                       scale * 2.f / (float)n, dz, B, n, c.r0);
+    return dm_launch_status(c.name);
 }
 
-// ---- the row-range pair (include/dynamorph_hip.h, dm_time_matching_forward_rows)
-static int tm_rows_er(int B, int R)                       // rows per workgroup of tm_epilogue_rows_kernel
+}  // namespace
+
+extern "C" int dm_time_matching_supported(int B, int n) { return (B > 0 && n > 0 && n % TM_KC == 0) ? 1 : 0; }
+
+extern "C" int64_t dm_time_matching_workspace_floats(int B, int n)
 {
-    const int tiles = ((R + TM_T - 1) / TM_T) * ((B + TM_T - 1) / TM_T);
-    return 4 * tiles >= 256 ? 16 : 4;
+    // Gram slabs.  The 4 * blocks + 4 floats behind them held the epilogue's loss partials before those got a buffer of
+    // their own (loss_slabs); nothing reads them now, the reported size is kept as callers know it.
+    const long long blocks = ((long long)B * B + 255) / 256;
+    return (long long)tm_ksplit(B, n) * B * B + 4 * blocks + 4;
 }
 
 extern "C" int64_t dm_time_matching_rows_workspace_floats(int B, int R, int n)
@@ -904,83 +890,66 @@ extern "C" int64_t dm_time_matching_rows_workspace_floats(int B, int R, int n)
     return (long long)tm_ksplit(B, n) * ((long long)R * B + B);
 }
 
+// the state block: the header and one map word per (panel of 64 rows, chunk of 32 columns)
+extern "C" int dm_time_matching_state_ints(int B) { return dm_time_matching_rows_state_ints(B, B); }
+extern "C" int dm_time_matching_rows_state_ints(int B, int R) { return TM_STATE_HDR + tm_tiles(R) * tm_map_chunks(B); }
+
+// one slab per epilogue workgroup
+extern "C" int dm_time_matching_num_slabs(int B) { return (TM_T / tm_er(tm_square_tiles(B))) * tm_square_tiles(B); }
 extern "C" int dm_time_matching_rows_num_slabs(int B, int R)
 {
-    if (R <= 0) return 0;
-    return (TM_T / tm_rows_er(B, R)) * ((R + TM_T - 1) / TM_T) * ((B + TM_T - 1) / TM_T);
+    return R <= 0 ? 0 : (TM_T / tm_er(tm_rows_tiles(B, R))) * tm_rows_tiles(B, R);
 }
 
-extern "C" int dm_time_matching_rows_state_ints(int B, int R)
+extern "C" int dm_time_matching_forward(const float *z, const float *tm, int B, int n, int mode, float w_a, float w_t,
+                                        float w_n, float margin, float *workspace, int64_t workspace_floats, float *S,
+                                        double *loss_slabs, void *stream)
 {
-    return TM_STATE_HDR + ((R + TM_T - 1) / TM_T) * tm_map_chunks(B);
+    return tm_forward({"dm_time_matching_forward", 0, B, true, false, false}, z, tm, B, n, mode, w_a, w_t, w_n, margin, workspace,
+                      workspace_floats, S, loss_slabs, nullptr, stream);
+}
+
+extern "C" int dm_time_matching_forward_state(const float *z, const float *tm, int B, int n, int mode, float w_a, float w_t,
+                                              float w_n, float margin, float *workspace, int64_t workspace_floats, float *S,
+                                              double *loss_slabs, int32_t *state, void *stream)
+{
+    return tm_forward({"dm_time_matching_forward_state", 0, B, true, true, false}, z, tm, B, n, mode, w_a, w_t, w_n, margin,
+                      workspace, workspace_floats, S, loss_slabs, state, stream);
 }
 
 extern "C" int dm_time_matching_forward_rows(const float *z, const float *tm, int B, int r0, int R, int n, int mode, float w_a,
                                              float w_t, float w_n, float margin, float *workspace, int64_t workspace_floats,
                                              float *S, double *loss_slabs, int32_t *state, void *stream)
 {
-    DM_REQUIRE(B > 0 && R >= 0 && r0 >= 0 && r0 + R <= B, "dm_time_matching_forward_rows: rows [%d, %d) outside a batch of %d",
-               r0, r0 + R, B);
-    if (R == 0) return 0;                                  // an empty shard: no rows, no loss terms, nothing launched
-    DM_REQUIRE(z && tm && workspace && S && loss_slabs && state, "dm_time_matching_forward_rows: NULL pointer");
-    DM_REQUIRE(dm_time_matching_supported(B, n), "dm_time_matching_forward_rows: latent length %d is not a multiple of %d", n, TM_KC);
-    DM_REQUIRE(mode == 0 || mode == 1, "dm_time_matching_forward_rows: mode %d", mode);
-    DM_REQUIRE((long long)B * n < (1LL << 31) && (long long)B * B < (1LL << 31), "dm_time_matching_forward_rows: tensor too large");
-    DM_REQUIRE(workspace_floats >= dm_time_matching_rows_workspace_floats(B, R, n), "dm_time_matching_forward_rows: workspace too small");
-    DM_REQUIRE((((uintptr_t)tm | (uintptr_t)z | (uintptr_t)S) & 15) == 0, "dm_time_matching_forward_rows: z, tm and S must be 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    const int ks = tm_ksplit(B, n), nt = (B + TM_T - 1) / TM_T, ntr = (R + TM_T - 1) / TM_T;
-    int klen = (n + ks - 1) / ks;
-    klen = (klen + TM_KC - 1) / TM_KC * TM_KC;
-    const int ints = dm_time_matching_rows_state_ints(B, R);
-    hipLaunchKernelGGL(tm_state_clear_kernel, dim3((ints + 255) / 256), dim3(256), 0, s, (int *)state, ints);
-    int *far_map = (int *)state + TM_STATE_HDR;
-    const int *st = nullptr;
-    if (mode == 0) {
-        // the sparse decision counts the WHOLE relation block, as the square call does: every rank decides alike
-        const long long BB = (long long)B * B;
-        const long long units = (BB & 3) == 0 ? BB >> 2 : BB;
-        const int grid = (int)((units + 255) / 256 < 2048 ? (units + 255) / 256 : 2048);
-        hipLaunchKernelGGL(tm_count_kernel, dim3(grid), dim3(256), 0, s, tm, BB, (int *)state);
-        st = (const int *)state;
-    }
-    float *P = workspace, *D = workspace + (long long)ks * R * B;
-    hipLaunchKernelGGL(tm_gram_rows_kernel, dim3(ntr * nt + nt, 1, ks), dim3(256), 0, s, z, P, D, B, n, klen, r0, R, ntr, nt, st);
-    const TmParams p{mode, w_a, w_t, w_n, margin};
-    if (tm_rows_er(B, R) == 16)
-        hipLaunchKernelGGL(tm_epilogue_rows_kernel<16>, dim3(ntr * nt, TM_T / 16), dim3(256), 0, s, z, P, D, ks, tm, B, n, r0, R, p,
-                           S, loss_slabs, nt, st, far_map);
-    else
-        hipLaunchKernelGGL(tm_epilogue_rows_kernel<4>, dim3(ntr * nt, TM_T / 4), dim3(256), 0, s, z, P, D, ks, tm, B, n, r0, R, p,
-                           S, loss_slabs, nt, st, far_map);
-    return dm_launch_status("dm_time_matching_forward_rows");
+    return tm_forward({"dm_time_matching_forward_rows", r0, R, false, true, false}, z, tm, B, n, mode, w_a, w_t, w_n, margin,
+                      workspace, workspace_floats, S, loss_slabs, state, stream);
+}
+
+extern "C" int dm_time_matching_backward(const float *z, const float *S, const float *g_loss_dev, float scale, float *dz,
+                                         int B, int n, void *stream)
+{
+    return tm_backward({"dm_time_matching_backward", 0, B, true, false, false}, z, S, g_loss_dev, scale, nullptr, dz, B, n, nullptr,
+                       stream);
+}
+
+extern "C" int dm_time_matching_backward_add(const float *z, const float *S, const float *g_loss_dev, float scale,
+                                             const float *add, float *dz, int B, int n, void *stream)
+{
+    return tm_backward({"dm_time_matching_backward_add", 0, B, true, false, true}, z, S, g_loss_dev, scale, add, dz, B, n, nullptr,
+                       stream);
+}
+
+extern "C" int dm_time_matching_backward_state(const float *z, const float *S, const float *g_loss_dev, float scale,
+                                               const float *add, float *dz, int B, int n, const int32_t *state, void *stream)
+{
+    return tm_backward({"dm_time_matching_backward_state", 0, B, true, true, false}, z, S, g_loss_dev, scale, add, dz, B, n, state,
+                       stream);
 }
 
 extern "C" int dm_time_matching_backward_rows(const float *z, const float *S, const float *g_loss_dev, float scale,
                                               const float *add, float *dz, int B, int r0, int R, int n, const int32_t *state,
                                               void *stream)
 {
-    DM_REQUIRE(B > 0 && R >= 0 && r0 >= 0 && r0 + R <= B, "dm_time_matching_backward_rows: rows [%d, %d) outside a batch of %d",
-               r0, r0 + R, B);
-    if (R == 0) return 0;
-    DM_REQUIRE(z && S && dz && state, "dm_time_matching_backward_rows: NULL pointer");
-    DM_REQUIRE(dm_time_matching_supported(B, n), "dm_time_matching_backward_rows: latent length %d is not a multiple of %d", n, TM_KC);
-    DM_REQUIRE((long long)B * n < (1LL << 31), "dm_time_matching_backward_rows: tensor too large");
-    DM_REQUIRE(B <= 16384, "dm_time_matching_backward_rows: batch %d too large (a row of S is staged in LDS)", B);
-    DM_REQUIRE((((uintptr_t)S | (uintptr_t)z) & 15) == 0, "dm_time_matching_backward_rows: z and S must be 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(tm_backward_kernel, dim3((n + TM_T - 1) / TM_T, (R + TM_T - 1) / TM_T), dim3(256), 0, s,
-                       z, S, g_loss_dev, scale * 2.f / (float)n, dz, B, n, add, (const int *)state, r0, R);
-    const size_t near_lds = (size_t)B * (sizeof(float) + sizeof(unsigned short));
-    if (near_lds > 48 * 1024) {
-        const hipError_t e = hipFuncSetAttribute((const void *)tm_near_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)near_lds);
-        if (e != hipSuccess) {
-            dm_set_error("dm_time_matching_backward_rows: cannot reserve %zu bytes of LDS: %s", near_lds, hipGetErrorString(e));
-            return (int)e;
-        }
-    }
-    hipLaunchKernelGGL(tm_near_backward_kernel, dim3((unsigned)R), dim3(256), near_lds, s, z, S + (long long)R * B, g_loss_dev,
-                       scale * 2.f / (float)n, dz, B, n, r0);
-    return dm_launch_status("dm_time_matching_backward_rows");
+    return tm_backward({"dm_time_matching_backward_rows", r0, R, false, true, false}, z, S, g_loss_dev, scale, add, dz, B, n, state,
+                       stream);
 }

@@ -875,58 +875,77 @@ def time_matching_supported(B, n):
     return bool(L.load().dm_time_matching_supported(B, n))
 
 
+def _tm_forward(z, tm, mode, weights, rows=None, stateless=False):
+    """Both forward wrappers: the size queries, the allocations, the launch, and the state block attached to S.  rows:
+    (r0, R) for the row-range form, None for the square one.  Returns (slabs, S)."""
+    lib = L.load()
+    B, n = z.shape
+    if rows is None:
+        r0, R = 0, B
+        wsf, nsl, ints = (lib.dm_time_matching_workspace_floats(B, n), lib.dm_time_matching_num_slabs(B),
+                          lib.dm_time_matching_state_ints(B))
+    else:
+        r0, R = rows
+        wsf, nsl, ints = (lib.dm_time_matching_rows_workspace_floats(B, R, n), lib.dm_time_matching_rows_num_slabs(B, R),
+                          lib.dm_time_matching_rows_state_ints(B, R))
+    ws = _new((max(wsf, 1),), z)
+    S = _new((2, R, B), z)
+    slabs = _new((nsl, 1, 2), z, torch.float64)
+    # the state block the backward call reads (the pair count of mode 0's sparse form and the map of S's nonzero blocks:
+    # include/dynamorph_hip.h) travels with S as an attribute; an S that lost it (a copy, a slice) takes the dense product,
+    # which gives the same gradient
+    state = None if stateless else torch.empty(ints, dtype=torch.int32, device=z.device)
+    if R > 0:
+        name = "dm_time_matching_forward" + ("_rows" if rows is not None else "" if stateless else "_state")
+        shape = (B, n) if rows is None else (B, r0, R, n)
+        L.check(getattr(lib, name)(_ptr(z), _ptr(tm), *shape, mode, *weights, _ptr(ws), wsf, _ptr(S), _ptr(slabs, torch.float64),
+                                   *(() if stateless else (_ptr(state, torch.int32),)), _stream()), name)
+    if not stateless:
+        S._dm_tm_state = state
+    if rows is not None:
+        S._dm_tm_rows = (r0, R)
+    return slabs, S
+
+
+def _tm_backward(z, S, g_loss, scale, add, rows=None):
+    """Both backward wrappers: dz for the rows S was formed for, by the entry point that takes what the call has."""
+    lib = L.load()
+    B, n = z.shape
+    r0, R = rows if rows is not None else (0, B)
+    dz = _new((R, n), z)
+    state = getattr(S, "_dm_tm_state", None)
+    if R > 0:
+        head = (_ptr(z), _ptr(S), _ptr(g_loss), scale)
+        if rows is not None:
+            name, args = "dm_time_matching_backward_rows", (_ptr(add), _ptr(dz), B, r0, R, n, _ptr(state, torch.int32))
+        elif state is not None:
+            name, args = "dm_time_matching_backward_state", (_ptr(add), _ptr(dz), B, n, _ptr(state, torch.int32))
+        elif add is not None:
+            name, args = "dm_time_matching_backward_add", (_ptr(add), _ptr(dz), B, n)
+        else:
+            name, args = "dm_time_matching_backward", (_ptr(dz), B, n)
+        L.check(getattr(lib, name)(*head, *args, _stream()), name)
+    return dz
+
+
 @_op
 def time_matching_forward(z, tm, mode, w_a=0.0, w_t=0.0, w_n=0.0, margin=0.0, want_slabs=False, allow_sparse=True):
     """The whole pairwise term on the MFMA (include/dynamorph_hip.h, dm_time_matching_forward).  z (B, n), tm (B, B) float32.
     Returns (loss: 1-element device tensor, S (2, B, B) = dloss/dsim + its transpose, far pairs / near pairs, for
     time_matching_backward).  want_slabs: the partial losses (nslabs, 1, 2) float64 instead of their sum (the training
     step's scalar launch adds them: vq_loss_finalize_tm)."""
-    lib = L.load()
-    B, n = z.shape
-    wsf = lib.dm_time_matching_workspace_floats(B, n)
-    ws = _new((wsf,), z)
-    S = _new((2, B, B), z)
-    nsl = lib.dm_time_matching_num_slabs(B)
-    slabs = _new((nsl, 1, 2), z, torch.float64)
-    # the state block the backward call reads (the pair count of mode 0's sparse form and the map of S's nonzero blocks:
-    # include/dynamorph_hip.h) travels with S as an attribute; an S that lost it (a copy, a slice) takes the dense product,
-    # which gives the same gradient
-    if not allow_sparse:                                   # (tests / measurements: the stateless, dense form whatever tm holds)
-        L.check(lib.dm_time_matching_forward(_ptr(z), _ptr(tm), B, n, mode, w_a, w_t, w_n, margin, _ptr(ws), wsf, _ptr(S),
-                                             _ptr(slabs, torch.float64), _stream()), "dm_time_matching_forward")
-        return (slabs, S) if want_slabs else (sum_slabs(slabs, _new((1,), z)), S)
-    state = torch.empty(lib.dm_time_matching_state_ints(B), dtype=torch.int32, device=z.device)
-    L.check(lib.dm_time_matching_forward_state(_ptr(z), _ptr(tm), B, n, mode, w_a, w_t, w_n, margin, _ptr(ws), wsf, _ptr(S),
-                                               _ptr(slabs, torch.float64), _ptr(state, torch.int32), _stream()),
-            "dm_time_matching_forward_state")
-    S._dm_tm_state = state
-    if want_slabs:
-        return slabs, S
-    loss = sum_slabs(slabs, _new((1,), z))
-    return loss, S
+    # (allow_sparse=False -- tests / measurements --: the stateless, dense form whatever tm holds)
+    slabs, S = _tm_forward(z, tm, mode, (w_a, w_t, w_n, margin), stateless=not allow_sparse)
+    return (slabs, S) if want_slabs else (sum_slabs(slabs, _new((1,), z)), S)
 
 
 @_op
 def time_matching_backward(z, S, g_loss=None, scale=1.0, add=None):
     """dz = [add +] scale * g_loss[0] * d loss / d z  (g_loss: 1-element device tensor or None = 1; add: a gradient of the
     same latents, (B, n) or any shape with as many elements, summed in the kernel's store instead of an elementwise pass)."""
-    lib = L.load()
-    B, n = z.shape
-    dz = torch.empty_like(z)
     if add is not None and add.numel() != z.numel():
         raise ValueError("dm_time_matching_backward_add: `add` must have the latents' size")
-    state = getattr(S, "_dm_tm_state", None)
-    if state is not None:
-        L.check(lib.dm_time_matching_backward_state(_ptr(z), _ptr(S), _ptr(g_loss), scale, _ptr(add), _ptr(dz), B, n,
-                                                    _ptr(state, torch.int32), _stream()), "dm_time_matching_backward_state")
-        return dz
-    if add is not None:
-        L.check(lib.dm_time_matching_backward_add(_ptr(z), _ptr(S), _ptr(g_loss), scale, _ptr(add), _ptr(dz), B, n, _stream()),
-                "dm_time_matching_backward_add")
-        return dz
-    L.check(lib.dm_time_matching_backward(_ptr(z), _ptr(S), _ptr(g_loss), scale, _ptr(dz), B, n, _stream()),
-            "dm_time_matching_backward")
-    return dz
+    return _tm_backward(z, S, g_loss, scale, add)
 
 
 @_op
@@ -936,40 +955,20 @@ def time_matching_forward_rows(z, tm, r0, R, mode, w_a=0.0, w_t=0.0, w_n=0.0, ma
     (the rows' share of the loss: 1-element float64 tensor -- the shares of a partition of the rows add up to
     time_matching_forward's loss --, S (2, R, B) for time_matching_backward_rows).  want_slabs: the partial losses
     (nslabs, 1, 2) float64 instead of their sum.  R = 0 is allowed (an empty shard: a zero share, nothing launched)."""
-    lib = L.load()
-    B, n = z.shape
+    B = z.shape[0]
     if tm.shape != (B, B):
         raise ValueError(f"time_matching_forward_rows: relation block {tuple(tm.shape)} for a batch of {B}")
-    wsf = lib.dm_time_matching_rows_workspace_floats(B, R, n)
-    ws = _new((max(wsf, 1),), z)
-    S = _new((2, R, B), z)
-    slabs = _new((lib.dm_time_matching_rows_num_slabs(B, R), 1, 2), z, torch.float64)
-    state = torch.empty(lib.dm_time_matching_rows_state_ints(B, R), dtype=torch.int32, device=z.device)
-    if R > 0:
-        L.check(lib.dm_time_matching_forward_rows(_ptr(z), _ptr(tm), B, r0, R, n, mode, w_a, w_t, w_n, margin, _ptr(ws), wsf,
-                                                  _ptr(S), _ptr(slabs, torch.float64), _ptr(state, torch.int32), _stream()),
-                "dm_time_matching_forward_rows")
-    S._dm_tm_state, S._dm_tm_rows = state, (r0, R)
-    if want_slabs:
-        return slabs, S
-    return slabs[:, 0, 0].sum().reshape(1), S
+    slabs, S = _tm_forward(z, tm, mode, (w_a, w_t, w_n, margin), rows=(r0, R))
+    return (slabs, S) if want_slabs else (slabs[:, 0, 0].sum().reshape(1), S)
 
 
 @_op
 def time_matching_backward_rows(z, S, g_loss=None, scale=1.0, add=None):
     """dz (R, n) = [add +] scale * g_loss[0] * d loss / d z for the rows S was formed for (time_matching_forward_rows on the
     same z): rows r0 .. r0 + R - 1 of time_matching_backward's dz.  add: (R, n) or as many elements, summed in the store."""
-    lib = L.load()
-    B, n = z.shape
-    r0, R = S._dm_tm_rows
-    dz = _new((R, n), z)
-    if add is not None and add.numel() != R * n:
+    if add is not None and add.numel() != S._dm_tm_rows[1] * z.shape[1]:
         raise ValueError("dm_time_matching_backward_rows: `add` must have the rows' size")
-    if R > 0:
-        L.check(lib.dm_time_matching_backward_rows(_ptr(z), _ptr(S), _ptr(g_loss), scale, _ptr(add), _ptr(dz), B, r0, R, n,
-                                                   _ptr(S._dm_tm_state, torch.int32), _stream()),
-                "dm_time_matching_backward_rows")
-    return dz
+    return _tm_backward(z, S, g_loss, scale, add, rows=S._dm_tm_rows)
 
 
 # ------------------------------------------------------------- composition / optimizer

@@ -81,8 +81,8 @@ def test_row_ranges_equal_square_rows(mode, Bg, n):
         dz_sq = ops.time_matching_backward(z, S_sq, None, 3.0, add=add)
         ref = _reference_loss(z, tm, mode)
         assert abs(float(loss_sq) - ref) <= 1e-5 * max(abs(ref), 1e-6 * Bg * Bg), (kind, float(loss_sq), ref)
-        for parts in (2, 3, 8):
-            for ranges in _splits(Bg, parts):
+        for parts in (1, 2, 3, 8):                  # 1: the single range (0, Bg), the row-range pair as the square one
+            for ranges in ([[(0, Bg)]] if parts == 1 else _splits(Bg, parts)):
                 total = 0.0
                 covered = 0
                 for r0, r1 in ranges:
@@ -97,6 +97,53 @@ def test_row_ranges_equal_square_rows(mode, Bg, n):
                     covered += R
                 assert covered == Bg
                 assert abs(total - float(loss_sq)) <= 1e-6 * max(abs(float(loss_sq)), 1e-30), (kind, parts, total, float(loss_sq))
+
+
+def _relations_filled(Bg, per_row, seed):
+    """An asymmetric relation block with `per_row` nonzero entries (1 or 2) in every row, the diagonal included or not as the
+    draw has it: above 32 per row mode 0 takes the Gram path, at or below it the sparse one."""
+    g = torch.Generator().manual_seed(seed)
+    t = torch.zeros(Bg, Bg)
+    for i in range(Bg):
+        cols = torch.randperm(Bg, generator=g)[:per_row]
+        t[i, cols] = torch.randint(1, 3, (len(cols),), generator=g).float()
+    return t.to(DEV).contiguous()
+
+
+@pytest.mark.parametrize("Bg", [6, 70, 130])
+@pytest.mark.parametrize("mode", [0, 1])
+def test_whole_range_equals_square_at_small_batches(mode, Bg):
+    """The row-range pair with r0 = 0, R = B against the square pair -- the identity the shared backward launch rests on --
+    and a ragged two-way cut, on one, two and three tiles of 64 with a ragged last tile; 6, 70 and 130 are no multiples of
+    four (the scalar S loads) and keep 4 rows per epilogue workgroup.  Two asymmetric relation blocks: 40 entries per row
+    (6 at Bg = 6: every entry) where a row can hold them -- above the sparse form's 32 per row --, and 3 per row, sparse."""
+    from dynamorph_amd import ops
+    n = 256
+    z = _latents(Bg, n, seed=Bg + mode)
+    add = torch.randn(Bg, n, generator=torch.Generator().manual_seed(5)).to(DEV)
+    args = (mode, W_A, W_T, W_N, MARGIN)
+    for per_row in (min(40, Bg), 3):
+        tm = _relations_filled(Bg, per_row, seed=Bg + per_row)
+        dense = int((tm != 0).sum()) > 32 * Bg
+        assert dense == (per_row > 32)
+        slabs_sq, S_sq = ops.time_matching_forward(z, tm, *args, want_slabs=True)
+        loss_sq = float(slabs_sq[:, 0, 0].sum())
+        dz_sq = ops.time_matching_backward(z, S_sq, None, 3.0, add=add)
+        dz_sq_plain = ops.time_matching_backward(z, S_sq, None, 3.0)
+        ref = _reference_loss(z, tm, mode)
+        assert abs(loss_sq - ref) <= 1e-5 * max(abs(ref), 1e-6 * Bg * Bg), (per_row, loss_sq, ref)
+        for ranges in ([(0, Bg)], [(0, Bg // 3), (Bg // 3, Bg)]):
+            total = 0.0
+            for r0, r1 in ranges:
+                slabs, S = ops.time_matching_forward_rows(z, tm, r0, r1 - r0, *args, want_slabs=True)
+                dz = ops.time_matching_backward_rows(z, S, None, 3.0, add=add[r0:r1].contiguous())
+                dz_plain = ops.time_matching_backward_rows(z, S, None, 3.0)
+                what = (per_row, r0, r1)
+                assert torch.equal(S, S_sq[:, r0:r1]), what
+                assert torch.equal(dz, dz_sq[r0:r1]), what
+                assert torch.equal(dz_plain, dz_sq_plain[r0:r1]), what
+                total += float(slabs[:, 0, 0].sum())
+            assert abs(total - loss_sq) <= 1e-6 * max(abs(loss_sq), 1e-30), (per_row, ranges, total, loss_sq)
 
 
 def test_row_ranges_on_a_side_stream():
