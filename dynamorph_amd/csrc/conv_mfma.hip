@@ -1124,6 +1124,7 @@ void bwd_s2_roles3_kernel(Operand dy, Operand tin, WeightView wv, float *__restr
 struct ConvArgs {
     Operand in; WeightView wv; float *out; Epilogue ep;
     int B, Cphys, CIN, NOUT, H, W, per_tile;
+    int ntiles, nslabs;          // of the route the entry point chose (ConvRoute)
     hipStream_t stream;
 };
 
@@ -1171,25 +1172,24 @@ void launch_conv4(const ConvArgs &a)
 {
     constexpr int TH = 8;
     constexpr int F4 = CIN * (2 * TH + 2) * ((2 * TW + 8) / 4), LDS = 16 * F4;
-    const int ntiles = a.B * ((a.H / 2) / TH) * ((a.W / 2) / TW);
 #define DM_L4(SIDE_)                                                                                              \
     {                                                                                                             \
         constexpr int WPS = conv_wps(LDS, CIN * 4, F4, false, 2, 1, SIDE_);                                       \
-        /* the first convolution with output positions in pairs (kernel A2) */                                   \
-        if (SIDE_ == SIDE_NONE && CIN <= 4 && TW == 64 && a.NOUT == 8 && a.ep.bias_border && !a.ep.relu)             \
-            hipLaunchKernelGGL((conv4x4s2_pair_kernel<CIN <= 4 ? CIN : 1, TH, WPS>),                                   \
-                               dim3(conv_grid(ntiles, WPS, a.per_tile)), dim3(DM_BLOCK), 0, a.stream, a.in, a.wv,     \
-                               a.out, a.ep, a.Cphys, a.H, a.W, ntiles, conv_slabs(ntiles, a.per_tile), a.per_tile);    \
+        /* the first convolution with output positions in pairs (kernel A2) */                                    \
+        if (SIDE_ == SIDE_NONE && CIN <= 4 && TW == 64 && a.NOUT == 8 && a.ep.bias_border && !a.ep.relu)          \
+            hipLaunchKernelGGL((conv4x4s2_pair_kernel<CIN <= 4 ? CIN : 1, TH, WPS>),                              \
+                               dim3(conv_grid(a.ntiles, WPS, a.per_tile)), dim3(DM_BLOCK), 0, a.stream, a.in, a.wv, \
+                               a.out, a.ep, a.Cphys, a.H, a.W, a.ntiles, a.nslabs, a.per_tile);                   \
         else if (SIDE_ == SIDE_NONE && CIN <= 5 && a.ep.bias_border)                                              \
-            hipLaunchKernelGGL((conv4x4s2_kernel<CIN, 1, TH, TW, SIDE_NONE, WPS, true>),                              \
-                               dim3(conv_grid(ntiles, WPS, a.per_tile)), dim3(DM_BLOCK), 0, a.stream, a.in, a.wv,     \
-                               a.out, a.ep, a.Cphys, a.NOUT, a.H, a.W, ntiles, conv_slabs(ntiles, a.per_tile),        \
-                               a.per_tile);                                                                           \
+            hipLaunchKernelGGL((conv4x4s2_kernel<CIN, 1, TH, TW, SIDE_NONE, WPS, true>),                          \
+                               dim3(conv_grid(a.ntiles, WPS, a.per_tile)), dim3(DM_BLOCK), 0, a.stream, a.in, a.wv, \
+                               a.out, a.ep, a.Cphys, a.NOUT, a.H, a.W, a.ntiles, a.nslabs,                        \
+                               a.per_tile);                                                                       \
         else                                                                                                      \
-            hipLaunchKernelGGL((conv4x4s2_kernel<CIN, 1, TH, TW, SIDE_, WPS, false>),                                 \
-                               dim3(conv_grid(ntiles, WPS, a.per_tile)), dim3(DM_BLOCK), 0, a.stream, a.in, a.wv,     \
-                               a.out, a.ep, a.Cphys, a.NOUT, a.H, a.W, ntiles, conv_slabs(ntiles, a.per_tile),        \
-                               a.per_tile);                                                                           \
+            hipLaunchKernelGGL((conv4x4s2_kernel<CIN, 1, TH, TW, SIDE_, WPS, false>),                             \
+                               dim3(conv_grid(a.ntiles, WPS, a.per_tile)), dim3(DM_BLOCK), 0, a.stream, a.in, a.wv, \
+                               a.out, a.ep, a.Cphys, a.NOUT, a.H, a.W, a.ntiles, a.nslabs,                        \
+                               a.per_tile);                                                                       \
     }
     switch (side_mode(a.ep)) {
     case SIDE_NONE: DM_L4(SIDE_NONE) break;
@@ -1216,15 +1216,14 @@ void launch_conv3(const ConvArgs &a)
     constexpr int TH = conv3_th(TW, CIN);
     constexpr int PADR = TAPS == 9 ? 1 : 0;
     constexpr int F4 = CIN * (TH + 2 * PADR) * ((TW + 8 * PADR) / 4), LDS = 16 * F4 + 2048;
-    const int ntiles = a.B * (a.H / TH) * (a.W / TW);
     const int side = side_mode(a.ep);
     const bool two = a.in.mode == DM_LOAD_AFFINE2;
 #define DM_L3(TWO_, SIDE_)                                                                                        \
     {                                                                                                             \
-        constexpr int WPS = conv_wps(LDS, NT * (CIN / 4) * TAPS, F4, TWO_, NT == 1 ? 2 : 1, NT, SIDE_);          \
+        constexpr int WPS = conv_wps(LDS, NT * (CIN / 4) * TAPS, F4, TWO_, NT == 1 ? 2 : 1, NT, SIDE_);           \
         hipLaunchKernelGGL((conv3x3_kernel<CIN, NT, NPASS, TAPS, PIX, TH, TW, TWO_, SIDE_, WPS>),                 \
-                           dim3(conv_grid(ntiles, WPS, a.per_tile, NPASS)), dim3(DM_BLOCK), 0, a.stream, a.in, a.wv, \
-                           a.out, a.ep, a.Cphys, a.NOUT, a.H, a.W, ntiles, conv_slabs(ntiles, a.per_tile), a.per_tile); \
+                           dim3(conv_grid(a.ntiles, WPS, a.per_tile, NPASS)), dim3(DM_BLOCK), 0, a.stream, a.in, a.wv, \
+                           a.out, a.ep, a.Cphys, a.NOUT, a.H, a.W, a.ntiles, a.nslabs, a.per_tile);               \
     }
     // built variants: forward (no side inputs), data gradients with a mask-only side input (with or without
     // the BatchNorm-backward AFFINE2 operand), and the fully general one (residual join)
@@ -1241,15 +1240,14 @@ void launch_convT_phase(const ConvArgs &a)
     constexpr int TH = conv3_th(TW, CIN);
     constexpr int F4 = CIN * (TH + 2) * ((TW + 8) / 4), LDS = 16 * F4 + 2048;
     constexpr int KSW = (CIN / 4) * (COUT == 16 ? 4 : 6) * (COUT == 16 ? 4 : 2);      // weight registers
-    const int ntiles = a.B * (a.H / TH) * (a.W / TW);
     const int side = side_mode(a.ep);
     const bool two = a.in.mode == DM_LOAD_AFFINE2;
 #define DM_LP(TWO_, SIDE_)                                                                                        \
     {                                                                                                             \
         constexpr int WPS = clampi(conv_wps(LDS, KSW, F4, TWO_, 2, COUT == 16 ? 2 : 1, SIDE_), 1, 2);             \
         hipLaunchKernelGGL((convT_phase_kernel<CIN, COUT, TH, TW, TWO_, SIDE_, WPS>),                             \
-                           dim3(conv_grid(ntiles, WPS, a.per_tile)), dim3(DM_BLOCK), 0, a.stream, a.in, a.wv,     \
-                           a.out, a.ep, a.Cphys, a.H, a.W, ntiles, conv_slabs(ntiles, a.per_tile));               \
+                           dim3(conv_grid(a.ntiles, WPS, a.per_tile)), dim3(DM_BLOCK), 0, a.stream, a.in, a.wv,   \
+                           a.out, a.ep, a.Cphys, a.H, a.W, a.ntiles, a.nslabs);                                   \
     }
     if (!two && side == SIDE_NONE) DM_LP(false, SIDE_NONE)
     else if (!two && side == SIDE_MASK) DM_LP(false, SIDE_MASK)
@@ -1279,40 +1277,90 @@ static int conv_common_checks(const char *who, const dm_operand *in, const dm_we
     return 0;
 }
 
-// tile width of the MFMA path for this shape, 0 when the shape is not tileable by it
-static int conv4_fast_tw(int CIN, int NOUT, int H, int W)
+// ---- routes -----------------------------------------------------------------------------------------------------------
+// Which kernel family a shape runs on and the numbers that go with the choice.  conv4_route / conv3_route fill it from the
+// shape alone; dm_conv*_num_blocks, dm_conv*_scratch_floats and the launch all read it, so the slab count a caller
+// allocates and the one the kernel is told cannot drift apart.
+enum { ROUTE_RESIDENT, ROUTE_WIDE, ROUTE_GENERIC };     // weights in registers (this file), conv_wide.hip, conv_generic.hip
+struct ConvRoute {
+    int kind;
+    int TW, TH, ntiles;         // tiling of the register-resident kernel (ROUTE_RESIDENT only, else 0)
+    int nslabs;                 // statistics slabs of `kind`: what the caller allocates, whichever kernel then runs
+    bool wide_ok;               // conv_wide.hip tiles the shape (the operands may send a ROUTE_RESIDENT shape there)
+    long long wide_floats;      // scratch its packed weights take (dm_weight_view.scratch); 0 when it cannot run
+};
+
+// form 0: 4x4/s2, 1: 3x3 or 1x1, 2: transposed.  resident: a register-resident kernel with TH x TW tiles takes the shape; without
+// one, the implicit-GEMM kernel when its base grid tiles by 8 x 16, else the generic kernel
+static ConvRoute conv_route(int form, int taps, bool resident, int TW, int TH, int B, int CIN, int NOUT, int H, int W, int per_tile)
 {
-    const int Wo = W / 2, Ho = H / 2;
-    const int TW = conv4_tw(CIN, Wo);
-    if (H % 16 || W % 32 || NOUT > 16 || (TW != 16 && TW != 32 && TW != 64) || Ho % 8 || Wo % TW) return 0;
-    return TW;
+    ConvRoute r{};
+    r.wide_ok = dm_wide_conv_ok(form, H, W);
+    r.wide_floats = r.wide_ok && CIN > 0 && NOUT > 0 ? dm_wide_conv_scratch_floats(form, CIN, NOUT, taps) : 0;
+    r.kind = resident ? ROUTE_RESIDENT : (r.wide_ok ? ROUTE_WIDE : ROUTE_GENERIC);
+    if (resident) {
+        r.TW = TW; r.TH = TH;
+        r.ntiles = B * ((form == 0 ? H / 2 : H) / TH) * ((form == 0 ? W / 2 : W) / TW);
+    }
+    r.nslabs = resident ? conv_slabs(r.ntiles, per_tile)
+                        : (r.wide_ok ? dm_wide_conv_slabs(form, B, H, W, per_tile) : dm_generic_conv_slabs(B, per_tile));
+    return r;
 }
 
-// the register-resident kernels instantiated below (DM_C4 table)
+// ---- dm_conv4x4s2 -----------------------------------------------------------------------------------------------------
+// The register-resident 4x4/s2 kernels, one row per launch_conv4<CIN, TW>.  The tile width is the output width up to a cap
+// by channel count (conv4_tw), which is why the 8- and 16-channel rows stop at 32 and 16.
+#define DM_CONV4_ROWS(X)                                                                   \
+    X(3, 64) X(3, 32) X(3, 16)                                                             \
+    X(4, 64) X(4, 32) X(4, 16)                                                             \
+    X(5, 64) X(5, 32) X(5, 16)                                                             \
+    X(2, 64) X(2, 32) X(2, 16)                                                             \
+    X(1, 64) X(1, 32) X(1, 16)                                                             \
+    X(8, 32) X(8, 16)                                                                      \
+    X(16, 16)
+
 static bool conv4_has_kernel(int CIN, int TW)
 {
-    if (CIN >= 1 && CIN <= 5) return TW == 64 || TW == 32 || TW == 16;
-    if (CIN == 8) return TW == 32 || TW == 16;
-    return CIN == 16 && TW == 16;
+#define DM_C4(C, T) if (CIN == C && TW == T) return true;
+    DM_CONV4_ROWS(DM_C4)
+#undef DM_C4
+    return false;
+}
+
+static void conv4_launch_resident(const ConvArgs &a, int TW)
+{
+#define DM_C4(C, T) if (a.CIN == C && TW == T) return launch_conv4<C, T>(a);
+    DM_CONV4_ROWS(DM_C4)
+#undef DM_C4
+}
+
+static ConvRoute conv4_route(int B, int CIN, int NOUT, int H, int W, int per_tile)
+{
+    const int Wo = W / 2, Ho = H / 2, TW = conv4_tw(CIN, Wo);
+    const bool tileable = !(H % 16 || W % 32 || NOUT > 16 || (TW != 16 && TW != 32 && TW != 64) || Ho % 8 || Wo % TW);
+    return conv_route(0, 16, tileable && conv4_has_kernel(CIN, TW), TW, 8, B, CIN, NOUT, H, W, per_tile);
+}
+
+// Operands the register-resident kernels do not take whatever the shape: an AFFINE2 input, and the border-bias table
+// (kernel A / A2 only: up to 5 channels, no side input, at least 8 output columns).  ops.conv4x4s2 mirrors this as `fallback`.
+static bool conv4_resident_takes(const dm_operand *in, const dm_epilogue *ep, int CIN, int W)
+{
+    const bool border_ok = !(ep && ep->bias_border) || (CIN <= 5 && !ep->mask.p0 && !ep->resid && !ep->stat_q && W / 2 >= 8);
+    return in->mode != DM_LOAD_AFFINE2 && border_ok;
 }
 
 extern "C" int dm_conv4x4s2_num_blocks(int B, int CIN, int NOUT, int H, int W, int per_tile)
 {
     if (B <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return -1;
-    const int TW = conv4_fast_tw(CIN, NOUT, H, W);
-    if (TW && conv4_has_kernel(CIN, TW)) return conv_slabs(B * ((H / 2) / 8) * ((W / 2) / TW), per_tile);
-    if (dm_wide_conv_ok(0, H, W)) return dm_wide_conv_slabs(0, B, H, W, per_tile);
-    return dm_generic_conv_slabs(B, per_tile);
+    return conv4_route(B, CIN, NOUT, H, W, per_tile).nslabs;
 }
 
 // scratch the weight view should carry (dm_weight_view.scratch): 0 when a register-resident kernel takes the shape.
-// fallback != 0: the caller knows that kernel cannot be used (AFFINE2 input, border-bias table with side inputs).
+// fallback != 0: the caller knows that kernel cannot be used (conv4_resident_takes).
 extern "C" int64_t dm_conv4x4s2_scratch_floats(int CIN, int NOUT, int H, int W, int fallback)
 {
-    if (CIN <= 0 || NOUT <= 0 || !dm_wide_conv_ok(0, H, W)) return 0;
-    const int TW = conv4_fast_tw(CIN, NOUT, H, W);
-    if (TW && conv4_has_kernel(CIN, TW) && !fallback) return 0;
-    return dm_wide_conv_scratch_floats(0, CIN, NOUT, 16);
+    const ConvRoute r = conv4_route(1, CIN, NOUT, H, W, 0);
+    return r.kind == ROUTE_RESIDENT && !fallback ? 0 : r.wide_floats;
 }
 
 extern "C" int dm_conv4x4s2(const dm_operand *in, const dm_weight_view *w, float *out, const dm_epilogue *ep,
@@ -1320,79 +1368,88 @@ extern "C" int dm_conv4x4s2(const dm_operand *in, const dm_weight_view *w, float
 {
     if (conv_common_checks("dm_conv4x4s2", in, w, out, ep, B, CIN, NOUT, H, W)) return -1;
     DM_REQUIRE(H % 2 == 0 && W % 2 == 0, "dm_conv4x4s2: H and W must be even (got %dx%d)", H, W);
+    const int per_tile = ep ? ep->stats_per_tile : 0;
+    const ConvRoute r = conv4_route(B, CIN, NOUT, H, W, per_tile);
     ConvArgs a{to_dev(in), to_dev(w), out, to_dev(ep), B, CIN - (in->ones_channel ? 1 : 0), CIN, NOUT, H, W,
-               ep ? ep->stats_per_tile : 0, (hipStream_t)stream};
+               per_tile, r.ntiles, r.nslabs, (hipStream_t)stream};
     {   // enc.7's shape: the whole-patch kernel (conv4x4s2_patch.hip)
         int rc = 0;
-        if (dm_conv4x4s2_patch_forward(a.in, a.wv, out, a.ep, B, a.Cphys, CIN, NOUT, H, W, a.per_tile,
-                                       dm_conv4x4s2_num_blocks(B, CIN, NOUT, H, W, a.per_tile), a.stream, &rc))
+        if (dm_conv4x4s2_patch_forward(a.in, a.wv, out, a.ep, B, a.Cphys, CIN, NOUT, H, W, per_tile, r.nslabs, a.stream, &rc))
             return rc;
     }
-    const int TW = conv4_fast_tw(CIN, NOUT, H, W);
-    const bool border_ok = !(ep && ep->bias_border) || (CIN <= 5 && !ep->mask.p0 && !ep->resid && !ep->stat_q && W / 2 >= 8);
-    if (TW && conv4_has_kernel(CIN, TW) && in->mode != DM_LOAD_AFFINE2 && border_ok) {
-#define DM_C4(C, T) if (CIN == C && TW == T) { launch_conv4<C, T>(a); return dm_launch_status("dm_conv4x4s2"); }
-        DM_C4(3, 64) DM_C4(3, 32) DM_C4(3, 16)
-        DM_C4(4, 64) DM_C4(4, 32) DM_C4(4, 16)
-        DM_C4(5, 64) DM_C4(5, 32) DM_C4(5, 16)
-        DM_C4(2, 64) DM_C4(2, 32) DM_C4(2, 16)
-        DM_C4(1, 64) DM_C4(1, 32) DM_C4(1, 16)
-        DM_C4(8, 32) DM_C4(8, 16)
-        DM_C4(16, 16)
-#undef DM_C4
-    }
-    // no register-resident instantiation for this channel count / shape / operand mode: the implicit-GEMM kernel
-    // (conv_wide.hip) when the output tiles by 8 x 16, else the generic kernel (conv_generic.hip)
-    const int nslabs = dm_conv4x4s2_num_blocks(B, CIN, NOUT, H, W, a.per_tile);
-    if (dm_wide_conv_ok(0, H, W) && w->scratch && w->scratch_floats >= dm_wide_conv_scratch_floats(0, CIN, NOUT, 16))
-        dm_wide_conv(0, a.in, a.wv, w->scratch, out, a.ep, B, a.Cphys, CIN, NOUT, H, W, 16, nslabs, a.per_tile, a.stream);
+    if (r.kind == ROUTE_RESIDENT && conv4_resident_takes(in, ep, CIN, W))
+        conv4_launch_resident(a, r.TW);
+    else if (r.wide_ok && w->scratch && w->scratch_floats >= r.wide_floats)
+        dm_wide_conv(0, a.in, a.wv, w->scratch, out, a.ep, B, a.Cphys, CIN, NOUT, H, W, 16, r.nslabs, per_tile, a.stream);
     else
-        dm_generic_conv(0, a.in, a.wv, out, a.ep, B, a.Cphys, CIN, NOUT, H, W, 16, nslabs, a.per_tile, a.stream);
+        dm_generic_conv(0, a.in, a.wv, out, a.ep, B, a.Cphys, CIN, NOUT, H, W, 16, r.nslabs, per_tile, a.stream);
     return dm_launch_status("dm_conv4x4s2");
 }
 
-static bool conv3_fast_tileable(int CIN, int H, int W)
+// ---- dm_conv3x3 -------------------------------------------------------------------------------------------------------
+// ConvTranspose2d with 16 input and 8 / 16 output channels (dec.0, data gradients of enc.4 / enc.7): the phase-decomposed
+// kernel C, one row per launch_convT_phase<16, COUT, TW>.  Per-tile statistics slabs (per-sample BatchNorm) stay with the
+// neighbourhood kernel B below, so these rows are tried first and only without per_tile.
+#define DM_CONVT_PHASE_ROWS(X) X(8, 16) X(8, 32) X(16, 16) X(16, 32)
+// Kernel B, one row per launch_conv3<CIN, NT, NPASS, TAPS, PIX, TW>; NTOT = NT * NPASS 16-channel output tiles.
+#define DM_CONV3_ROWS(X)                                                                   \
+    /* 3x3 plain: enc.10, residual 3x3 and their data gradients */                         \
+    X(16, 1, 1, 1, 9, false, 16) X(16, 1, 1, 1, 9, false, 32)                              \
+    X(16, 2, 2, 1, 9, false, 16) X(16, 2, 2, 1, 9, false, 32)                              \
+    X(32, 1, 1, 1, 9, false, 16) X(32, 1, 1, 1, 9, false, 32)                              \
+    /* 1x1: residual 1x1 and its data gradient */                                          \
+    X(32, 1, 1, 1, 1, false, 16) X(32, 1, 1, 1, 1, false, 32)                              \
+    X(16, 2, 2, 1, 1, false, 16) X(16, 2, 2, 1, 1, false, 32)                              \
+    /* pixel shuffle: ConvTranspose2d forward (dec.0/2/4) and data gradients of enc.4 / enc.7 */ \
+    X(16, 2, 2, 1, 9, true, 16) X(16, 2, 2, 1, 9, true, 32) X(16, 2, 2, 1, 9, true, 64)    \
+    X(16, 4, 2, 2, 9, true, 16) X(16, 4, 2, 2, 9, true, 32)                                \
+    X(8, 1, 1, 1, 9, true, 32) X(8, 1, 1, 1, 9, true, 64)                                  \
+    X(4, 1, 1, 1, 9, true, 64)
+#define DM_CP_IS(CO, T) (pix && CIN == 16 && NOUT == 4 * CO && TW == T && !per_tile)
+#define DM_C3_IS(C, NTOT, TP, PX, T) (CIN == C && (NOUT + 15) / 16 == NTOT && taps == TP && pix == PX && TW == T)
+
+static bool conv3_has_kernel(int CIN, int NOUT, int taps, bool pix, int per_tile, int TW)
 {
-    const int TW = conv3_tw(W, CIN), TH = conv3_th(TW, CIN);
-    return (TW == 16 || TW == 32 || TW == 64) && W % TW == 0 && H % TH == 0 && CIN % 4 == 0 && CIN <= 32;
+#define DM_CP(CO, T) if (DM_CP_IS(CO, T)) return true;
+#define DM_C3(C, NTOT, NT_, NP_, TP, PX, T) if (DM_C3_IS(C, NTOT, TP, PX, T)) return true;
+    DM_CONVT_PHASE_ROWS(DM_CP)
+    DM_CONV3_ROWS(DM_C3)
+#undef DM_CP
+#undef DM_C3
+    return false;
 }
 
-// the register-resident kernels instantiated below (DM_CP / DM_C3 tables)
-static bool conv3_has_kernel(int CIN, int NOUT, int H, int W, int taps, bool pix, int per_tile)
+static void conv3_launch_resident(const ConvArgs &a, int taps, bool pix, int TW)
 {
-    if (!conv3_fast_tileable(CIN, H, W)) return false;
-    const int TW = conv3_tw(W, CIN), NTT = (NOUT + 15) / 16;
-    const bool t13 = TW == 16 || TW == 32;
-    if (pix && CIN == 16 && (NOUT == 32 || NOUT == 64) && t13 && !per_tile) return true;
-    if (!pix && taps == 9) return t13 && ((CIN == 16 && (NTT == 1 || NTT == 2)) || (CIN == 32 && NTT == 1));
-    if (!pix && taps == 1) return t13 && ((CIN == 32 && NTT == 1) || (CIN == 16 && NTT == 2));
-    if (pix && taps == 9) {
-        if (CIN == 16 && NTT == 2) return true;
-        if (CIN == 16 && NTT == 4) return t13;
-        if (CIN == 8 && NTT == 1) return TW == 32 || TW == 64;
-        if (CIN == 4 && NTT == 1) return TW == 64;
-    }
-    return false;
+    const int CIN = a.CIN, NOUT = a.NOUT, per_tile = a.per_tile;
+#define DM_CP(CO, T) if (DM_CP_IS(CO, T)) return launch_convT_phase<16, CO, T>(a);
+#define DM_C3(C, NTOT, NT_, NP_, TP, PX, T) if (DM_C3_IS(C, NTOT, TP, PX, T)) return launch_conv3<C, NT_, NP_, TP, PX, T>(a);
+    DM_CONVT_PHASE_ROWS(DM_CP)
+    DM_CONV3_ROWS(DM_C3)
+#undef DM_CP
+#undef DM_C3
+}
+#undef DM_CP_IS
+#undef DM_C3_IS
+
+static ConvRoute conv3_route(int B, int CIN, int NOUT, int H, int W, int taps, bool pix, int per_tile)
+{
+    const int TW = conv3_tw(W, CIN), TH = conv3_th(TW, CIN);
+    const bool tileable = (TW == 16 || TW == 32 || TW == 64) && W % TW == 0 && H % TH == 0 && CIN % 4 == 0 && CIN <= 32;
+    return conv_route(pix ? 2 : 1, taps, tileable && conv3_has_kernel(CIN, NOUT, taps, pix, per_tile, TW), TW, TH, B, CIN, NOUT,
+                      H, W, per_tile);
 }
 
 extern "C" int dm_conv3x3_num_blocks(int B, int CIN, int NOUT, int H, int W, int taps, int pixel_shuffle, int per_tile)
 {
     if (B <= 0 || H <= 0 || W <= 0) return -1;
-    if (conv3_has_kernel(CIN, NOUT, H, W, taps, pixel_shuffle != 0, per_tile)) {
-        const int TW = conv3_tw(W, CIN), TH = conv3_th(TW, CIN);
-        return conv_slabs(B * (H / TH) * (W / TW), per_tile);
-    }
-    const int form = pixel_shuffle ? 2 : 1;
-    if (dm_wide_conv_ok(form, H, W)) return dm_wide_conv_slabs(form, B, H, W, per_tile);
-    return dm_generic_conv_slabs(B, per_tile);
+    return conv3_route(B, CIN, NOUT, H, W, taps, pixel_shuffle != 0, per_tile).nslabs;
 }
 
 extern "C" int64_t dm_conv3x3_scratch_floats(int CIN, int NOUT, int H, int W, int taps, int pixel_shuffle, int per_tile)
 {
-    const int form = pixel_shuffle ? 2 : 1;
-    if (CIN <= 0 || NOUT <= 0 || (taps != 9 && taps != 1) || !dm_wide_conv_ok(form, H, W)) return 0;
-    if (conv3_has_kernel(CIN, NOUT, H, W, taps, pixel_shuffle != 0, per_tile)) return 0;
-    return dm_wide_conv_scratch_floats(form, CIN, NOUT, taps);
+    const ConvRoute r = conv3_route(1, CIN, NOUT, H, W, taps, pixel_shuffle != 0, per_tile);
+    return r.kind == ROUTE_RESIDENT || (taps != 9 && taps != 1) ? 0 : r.wide_floats;
 }
 
 extern "C" int dm_conv3x3(const dm_operand *in, const dm_weight_view *w, float *out, const dm_epilogue *ep,
@@ -1403,53 +1460,17 @@ extern "C" int dm_conv3x3(const dm_operand *in, const dm_weight_view *w, float *
     DM_REQUIRE(!pixel_shuffle || (taps == 9 && NOUT % 4 == 0), "dm_conv3x3: pixel_shuffle needs taps=9, NOUT%%4==0");
     DM_REQUIRE(!in->ones_channel, "dm_conv3x3: ones_channel not supported");
     DM_REQUIRE(!(ep && ep->bias_border), "dm_conv3x3: bias_border not supported (dm_conv4x4s2 only)");
-    const int TW = conv3_tw(W, CIN);
-    const bool fast = conv3_has_kernel(CIN, NOUT, H, W, taps, pixel_shuffle != 0, ep ? ep->stats_per_tile : 0);
-    ConvArgs a{to_dev(in), to_dev(w), out, to_dev(ep), B, CIN, CIN, NOUT, H, W, ep ? ep->stats_per_tile : 0,
-               (hipStream_t)stream};
-    const int NTT = (NOUT + 15) / 16;
     const bool pix = pixel_shuffle != 0;
-    if (fast) {
-    // ConvTranspose2d with 16 input and 8 / 16 output channels (dec.0, data gradients of enc.4 / enc.7): phase-decomposed
-    // kernel C; per-tile statistics slabs (per-sample BatchNorm) stay with the neighbourhood kernel B
-#define DM_CP(CO, T)                                                                       \
-    if (pix && CIN == 16 && NOUT == 4 * CO && TW == T && !a.per_tile) {                    \
-        launch_convT_phase<16, CO, T>(a);                                                  \
-        return dm_launch_status("dm_conv3x3");                                             \
-    }
-    DM_CP(8, 16) DM_CP(8, 32) DM_CP(16, 16) DM_CP(16, 32)
-#undef DM_CP
-#define DM_C3(C, NTOT, NT_, NP_, TP, PX, T)                                                \
-    if (CIN == C && NTT == NTOT && taps == TP && pix == PX && TW == T) {                   \
-        launch_conv3<C, NT_, NP_, TP, PX, T>(a);                                           \
-        return dm_launch_status("dm_conv3x3");                                             \
-    }
-    // 3x3 plain: enc.10, residual 3x3 and their data gradients
-    DM_C3(16, 1, 1, 1, 9, false, 16) DM_C3(16, 1, 1, 1, 9, false, 32)
-    DM_C3(16, 2, 2, 1, 9, false, 16) DM_C3(16, 2, 2, 1, 9, false, 32)
-    DM_C3(32, 1, 1, 1, 9, false, 16) DM_C3(32, 1, 1, 1, 9, false, 32)
-    // 1x1: residual 1x1 and its data gradient
-    DM_C3(32, 1, 1, 1, 1, false, 16) DM_C3(32, 1, 1, 1, 1, false, 32)
-    DM_C3(16, 2, 2, 1, 1, false, 16) DM_C3(16, 2, 2, 1, 1, false, 32)
-    // pixel shuffle: ConvTranspose2d forward (dec.0/2/4) and data gradients of enc.4 / enc.7
-    DM_C3(16, 2, 2, 1, 9, true, 16) DM_C3(16, 2, 2, 1, 9, true, 32) DM_C3(16, 2, 2, 1, 9, true, 64)
-    DM_C3(16, 4, 2, 2, 9, true, 16) DM_C3(16, 4, 2, 2, 9, true, 32)
-    DM_C3(8, 1, 1, 1, 9, true, 32) DM_C3(8, 1, 1, 1, 9, true, 64)
-    DM_C3(4, 1, 1, 1, 9, true, 64)
-#undef DM_C3
-    }
-    // no register-resident instantiation for this channel count / shape: the implicit-GEMM kernel (conv_wide.hip)
-    // when the base grid tiles by 8 x 16, else the generic kernel (conv_generic.hip)
-    const int nslabs = dm_conv3x3_num_blocks(B, CIN, NOUT, H, W, taps, pixel_shuffle, a.per_tile);
-    if (fast) {
-        dm_set_error("dm_conv3x3: kernel table and conv3_has_kernel disagree (CIN %d NOUT %d %dx%d)", CIN, NOUT, H, W);
-        return -1;
-    }
-    if (dm_wide_conv_ok(pix ? 2 : 1, H, W) && w->scratch &&
-        w->scratch_floats >= dm_wide_conv_scratch_floats(pix ? 2 : 1, CIN, NOUT, taps))
-        dm_wide_conv(pix ? 2 : 1, a.in, a.wv, w->scratch, out, a.ep, B, CIN, CIN, NOUT, H, W, taps, nslabs, a.per_tile, a.stream);
+    const int form = pix ? 2 : 1, per_tile = ep ? ep->stats_per_tile : 0;
+    const ConvRoute r = conv3_route(B, CIN, NOUT, H, W, taps, pix, per_tile);
+    ConvArgs a{to_dev(in), to_dev(w), out, to_dev(ep), B, CIN, CIN, NOUT, H, W, per_tile, r.ntiles, r.nslabs,
+               (hipStream_t)stream};
+    if (r.kind == ROUTE_RESIDENT)
+        conv3_launch_resident(a, taps, pix, r.TW);
+    else if (r.wide_ok && w->scratch && w->scratch_floats >= r.wide_floats)
+        dm_wide_conv(form, a.in, a.wv, w->scratch, out, a.ep, B, CIN, CIN, NOUT, H, W, taps, r.nslabs, per_tile, a.stream);
     else
-        dm_generic_conv(pix ? 2 : 1, a.in, a.wv, out, a.ep, B, CIN, CIN, NOUT, H, W, taps, nslabs, a.per_tile, a.stream);
+        dm_generic_conv(form, a.in, a.wv, out, a.ep, B, CIN, CIN, NOUT, H, W, taps, r.nslabs, per_tile, a.stream);
     return dm_launch_status("dm_conv3x3");
 }
 

@@ -16,14 +16,12 @@
 // inside each 32-lane half: strides are chosen so that the two k lanes x 16 column lanes of a half hit 32 banks
 // (HISTORY.md section 3a has the measurements behind each of these choices).
 #include "dm_common.h"
+#include "wide_host.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
 
-#ifndef DM_WIDE_OCC3
-#define DM_WIDE_OCC3 0              // 1: every form compiled for three workgroups per CU (measurement builds)
-#endif
 enum { W_S2 = 0, W_S1 = 1, W_PIX = 2 };
 constexpr int WKC = 8;                 // input channels per K chunk
 constexpr int WIDE_MAX_BLOCKS = 768;   // persistent grid cap (x dimension)
@@ -249,7 +247,7 @@ struct RowPrefetch {
 //                  other slabs are zeroed (per-sample BatchNorm sums the slabs of a sample).
 // wpk: the packed weights (wide_pack_kernel, same <FORM, TAPS, NPW>).
 template <int FORM, int TAPS, int NPW>
-__global__ __launch_bounds__(256, ((FORM == W_S1 && TAPS == 9 && NPW == 4) || DM_WIDE_OCC3) ? 3 : 2) void conv_wide_kernel(Operand in, const float *__restrict__ wpk, float *__restrict__ out,
+__global__ __launch_bounds__(256, (FORM == W_S1 && TAPS == 9 && NPW == 4) ? 3 : 2) void conv_wide_kernel(Operand in, const float *__restrict__ wpk, float *__restrict__ out,
                                                         Epilogue ep, int B, int Cphys, int CIN, int NOUT, int H, int W,
                                                         int nslabs, int per_tile)
 {
@@ -849,11 +847,17 @@ bool dm_wide_conv_ok(int form, int H, int W)
     return BH > 0 && BW > 0 && BH % 8 == 0 && BW % 16 == 0 && (form != W_S2 || (H % 2 == 0 && W % 2 == 0));
 }
 
+// 8 x 16 tiles of the base grid
+static long long wide_conv_tiles(int form, int B, int H, int W)
+{
+    const int BH = form == W_S2 ? H / 2 : H, BW = form == W_S2 ? W / 2 : W;
+    return (long long)B * (BH / 8) * (BW / 16);
+}
+
 int dm_wide_conv_slabs(int form, int B, int H, int W, int per_tile)
 {
     if (per_tile) return B;
-    const int BH = form == W_S2 ? H / 2 : H, BW = form == W_S2 ? W / 2 : W;
-    const long long nt = (long long)B * (BH / 8) * (BW / 16);
+    const long long nt = wide_conv_tiles(form, B, H, W);
     return (int)(nt < WIDE_MAX_BLOCKS ? nt : WIDE_MAX_BLOCKS);
 }
 
@@ -907,11 +911,7 @@ int dm_wide_conv(int form, const Operand &in, const WeightView &wv, float *scrat
     if (form == W_S2 && dm_stream_conv_s2_wide(in, wv, out, ep, B, Cphys, CIN, NOUT, H, W, nslabs, per_tile, st)) return 0;
     if (form == W_S2 && dm_stream_conv_s2_thin(in, wv, out, ep, B, Cphys, CIN, NOUT, H, W, nslabs, per_tile, st)) return 0;
     if (form == W_S1 && taps == 1 && dm_stream_conv1x1(in, wv, out, ep, B, Cphys, CIN, NOUT, H, W, nslabs, per_tile, st)) return 0;
-    const int BH = form == W_S2 ? H / 2 : H, BW = form == W_S2 ? W / 2 : W;
-    const long long ntiles = (long long)B * (BH / 8) * (BW / 16);
-    long long gx = per_tile ? B : ntiles;
-    if (gx > WIDE_MAX_BLOCKS) gx = WIDE_MAX_BLOCKS;
-    if (ep.stats && !per_tile && gx > nslabs) gx = nslabs;
+    const int gx = persistent_grid(per_tile ? B : wide_conv_tiles(form, B, H, W), 1, WIDE_MAX_BLOCKS, ep.stats && !per_tile, nslabs);
     const int np = wide_npw(form, NOUT);
     const int nn = form == W_PIX ? NOUT / 4 : NOUT;
     const int passes = (nn + 16 * np - 1) / (16 * np), nchunks = (CIN + WKC - 1) / WKC;
@@ -967,6 +967,15 @@ static int wide_wgrad_one_pass()
     return v;
 }
 static bool wide_wgrad1_shape(int CS, int CT, int k) { return wide_wgrad_one_pass() && CS == 64 && ((k == 3 && CT == 64) || (k == 4 && CT == 32)); }
+// operands the one-pass kernel takes at such a shape: no ones channel, shared coefficients, T as AFFINE2 only for k = 4 beside a
+// one-tensor S (it prefetches two tensors on one side)
+static bool wide_wgrad1_takes(const Operand &S, const Operand &T, int CT, int CTphys, int k)
+{
+    return CT == CTphys && !T.ones && (T.mode != DM_LOAD_AFFINE2 || (k == 4 && S.mode != DM_LOAD_AFFINE2)) &&
+           !per_sample_coef(S) && !per_sample_coef(T);
+}
+// 8 x 16 tiles of the S grid: the persistent loop's units
+static long long wide_wgrad_units(int B, int Hs, int Ws) { return (long long)B * (Hs / 8) * (Ws / 16); }
 
 bool dm_wide_wgrad_t_affine2_ok(int CS, int CT, int Hs, int Ws, int k)
 {
@@ -977,13 +986,10 @@ int dm_wide_wgrad_slabs(int B, int CS, int CT, int Hs, int Ws, int k)
 {
     if (k == 1 && dm_stream_wgrad1x1_shape(B, CS, CT, Hs, Ws)) return dm_stream_wgrad1x1_slabs(B, Hs, Ws);
     if (k == 4 && dm_stream_wgrad_s2_thin_shape(B, CS, CT, Hs, Ws)) return dm_stream_wgrad_s2_thin_slabs(B, Hs, Ws);
-    if (wide_wgrad1_shape(CS, CT, k)) {
-        const long long units = (long long)B * (Hs / 8) * (Ws / 16);
-        return (int)(units < 256 ? units : 256);                // one workgroup of eight waves per CU
-    }
     int gy, gz, cap;
     wide_wgrad_grid(CS, CT, k, gy, gz, cap);
-    const long long units = (long long)B * (Hs / 8) * (Ws / 16);
+    if (wide_wgrad1_shape(CS, CT, k)) cap = 256;                // one workgroup of eight waves per CU
+    const long long units = wide_wgrad_units(B, Hs, Ws);
     return (int)(units < cap ? units : cap);
 }
 
@@ -992,11 +998,8 @@ int dm_wide_wgrad(const Operand &S, const Operand &T, float *slabs, int B, int C
 {
     if (k == 1 && dm_stream_wgrad1x1(S, T, slabs, B, CS, CT, Hs, Ws, nslabs, st)) return 0;
     if (k == 4 && CT == CTphys && dm_stream_wgrad_s2_thin(S, T, slabs, B, CS, CT, Hs, Ws, nslabs, st)) return 0;
-    if (wide_wgrad1_shape(CS, CT, k) && CT == CTphys && !T.ones && (T.mode != DM_LOAD_AFFINE2 || (k == 4 && S.mode != DM_LOAD_AFFINE2)) &&
-        !(S.mode >= DM_LOAD_AFFINE && S.coef_bstride) && !(T.mode >= DM_LOAD_AFFINE && T.coef_bstride)) {
-        const long long units = (long long)B * (Hs / 8) * (Ws / 16);
-        int g1 = (int)(units < 256 ? units : 256);
-        if (g1 > nslabs) g1 = nslabs;
+    if (wide_wgrad1_shape(CS, CT, k) && wide_wgrad1_takes(S, T, CT, CTphys, k)) {
+        const int g1 = persistent_grid(wide_wgrad_units(B, Hs, Ws), 1, 256, true, nslabs);
         const bool two = S.mode == DM_LOAD_AFFINE2;
         if (T.mode == DM_LOAD_AFFINE2) {       // the decoder's first transposed convolution: T = BatchNorm backward of its output gradient
             hipLaunchKernelGGL((wgrad_wide1_kernel<4, 32, false, true>), dim3(g1), dim3(512), 0, st, S, T, slabs, B, Hs, Ws, nslabs);

@@ -488,47 +488,78 @@ extern "C" int dm_reduce_slabs(const float *slabs, int nslabs, int E, float *dst
     return dm_launch_status("dm_reduce_slabs");
 }
 
-static bool wgrad_fast_tileable(int CS, int CT, int Hs, int Ws, int k)
+// ---- dm_wgrad ---------------------------------------------------------------------------------------------------------
+// The register-resident kernels, one row per launch_wgrad<CS, CT, K, TW>.  The tile width is the S width up to 64 (wgrad_tw),
+// so a family without a 64 row serves grids up to 32 columns only.
+#define DM_WGRAD_ROWS(X)                                                                                              \
+    /* enc.0 o enc.1 composite (x with ones channel), enc.4, enc.7 */                                                 \
+    X(8, 3, 4, 64) X(8, 3, 4, 32) X(8, 3, 4, 16) X(8, 5, 4, 64) X(8, 2, 4, 64) X(8, 4, 4, 64)                         \
+    X(8, 1, 4, 64)                                                                                                    \
+    X(16, 8, 4, 32) X(16, 8, 4, 64) X(16, 8, 4, 16)                                                                   \
+    X(16, 16, 4, 16) X(16, 16, 4, 32)                                                                                 \
+    /* enc.10 and residual convs */                                                                                   \
+    X(16, 16, 3, 16) X(16, 16, 3, 32)                                                                                 \
+    X(32, 16, 3, 16) X(32, 16, 3, 32)                                                                                 \
+    X(16, 32, 1, 16) X(16, 32, 1, 32)                                                                                 \
+    /* decoder ConvTranspose2d layers (S = layer input, T = output gradient); their 64-wide (8, 4) row is above */    \
+    X(8, 4, 4, 32)                                                                                                    \
+    X(4, 4, 4, 64)
+
+static bool wgrad_has_kernel(int CS, int CT, int k, int TW)
 {
-    const int TW = wgrad_tw(Ws);
-    if (TW != 16 && TW != 32 && TW != 64) return false;
-    const int TH = wgrad_th(CS, CT, k, TW);
-    return Hs % TH == 0 && Ws % TW == 0;
+#define DM_WG(CS_, CT_, K_, TW_) if (CS == CS_ && CT == CT_ && k == K_ && TW == TW_) return true;
+    DM_WGRAD_ROWS(DM_WG)
+#undef DM_WG
+    return false;
 }
 
-// the register-resident kernels instantiated below (DM_WG table)
-static bool wgrad_has_kernel(int CS, int CT, int Hs, int Ws, int k)
+static void wgrad_launch_resident(const Operand &s, const Operand &t, float *slabs, int B, int CS, int CT, int CTphys, int Hs,
+                                  int Ws, int k, int TW, int grid, hipStream_t st)
 {
-    if (!wgrad_fast_tileable(CS, CT, Hs, Ws, k)) return false;
-    const int TW = wgrad_tw(Ws);
-    const bool t13 = TW == 16 || TW == 32;
-    if (k == 4 && CS == 8) {
-        if (CT == 3) return true;
-        if (CT == 5 || CT == 2 || CT == 1) return TW == 64;
-        if (CT == 4) return TW == 64 || TW == 32;
+#define DM_WG(CS_, CT_, K_, TW_)                                                         \
+    if (CS == CS_ && CT == CT_ && k == K_ && TW == TW_) return launch_wgrad<CS_, CT_, K_, TW_>(s, t, slabs, B, CTphys, Hs, Ws, grid, st);
+    DM_WGRAD_ROWS(DM_WG)
+#undef DM_WG
+}
+
+// Which kernel family a shape runs on and its slab count (= its persistent grid): filled from the shape alone and read by
+// dm_wgrad_num_blocks, dm_wgrad_t_affine2_supported and the launch.
+enum { ROUTE_RESIDENT, ROUTE_WIDE, ROUTE_GENERIC };     // S x T tile in registers (this file), conv_wide.hip, conv_generic.hip
+struct WgradRoute {
+    int kind;
+    int TW, TH;                 // tiling of the register-resident kernel (ROUTE_RESIDENT only)
+    int nslabs;
+};
+
+static WgradRoute wgrad_route(int B, int CS, int CT, int Hs, int Ws, int k)
+{
+    WgradRoute r{};
+    r.TW = wgrad_tw(Ws);
+    const bool tw_ok = r.TW == 16 || r.TW == 32 || r.TW == 64;
+    r.TH = tw_ok ? wgrad_th(CS, CT, k, r.TW) : 0;
+    if (tw_ok && Hs % r.TH == 0 && Ws % r.TW == 0 && wgrad_has_kernel(CS, CT, k, r.TW)) {
+        r.kind = ROUTE_RESIDENT;
+        const long long ntiles = (long long)B * (Hs / r.TH) * (Ws / r.TW);
+        r.nslabs = (int)(ntiles < WG_MAX_BLOCKS ? ntiles : WG_MAX_BLOCKS);
+    } else if (dm_wide_wgrad_ok(Hs, Ws)) {
+        r.kind = ROUTE_WIDE;
+        r.nslabs = dm_wide_wgrad_slabs(B, CS, CT, Hs, Ws, k);
+    } else {
+        r.kind = ROUTE_GENERIC;
+        r.nslabs = B < WG_MAX_BLOCKS ? B : WG_MAX_BLOCKS;
     }
-    if (k == 4 && CS == 16) return CT == 8 || (CT == 16 && t13);
-    if (k == 4 && CS == 4) return CT == 4 && TW == 64;
-    if (k == 3) return (CS == 16 || CS == 32) && CT == 16 && t13;
-    if (k == 1) return CS == 16 && CT == 32 && t13;
-    return false;
+    return r;
 }
 
 extern "C" int dm_wgrad_t_affine2_supported(int CS, int CT, int Hs, int Ws, int k)
 {
-    return (!wgrad_has_kernel(CS, CT, Hs, Ws, k) && dm_wide_wgrad_t_affine2_ok(CS, CT, Hs, Ws, k)) ? 1 : 0;
+    return (wgrad_route(1, CS, CT, Hs, Ws, k).kind != ROUTE_RESIDENT && dm_wide_wgrad_t_affine2_ok(CS, CT, Hs, Ws, k)) ? 1 : 0;
 }
 
 extern "C" int dm_wgrad_num_blocks(int B, int CS, int CT, int Hs, int Ws, int k)
 {
     if (B <= 0 || (k != 4 && k != 3 && k != 1)) return -1;
-    if (!wgrad_has_kernel(CS, CT, Hs, Ws, k)) {
-        if (dm_wide_wgrad_ok(Hs, Ws)) return dm_wide_wgrad_slabs(B, CS, CT, Hs, Ws, k);
-        return B < WG_MAX_BLOCKS ? B : WG_MAX_BLOCKS;
-    }
-    const int TW = wgrad_tw(Ws), TH = wgrad_th(CS, CT, k, TW);
-    const long long ntiles = (long long)B * (Hs / TH) * (Ws / TW);
-    return (int)(ntiles < WG_MAX_BLOCKS ? ntiles : WG_MAX_BLOCKS);
+    return wgrad_route(B, CS, CT, Hs, Ws, k).nslabs;
 }
 
 extern "C" int dm_wgrad(const dm_operand *S, const dm_operand *T, float *slabs, float *dst,
@@ -539,43 +570,20 @@ extern "C" int dm_wgrad(const dm_operand *S, const dm_operand *T, float *slabs, 
     DM_REQUIRE((long long)B * (CS > 4 * CT ? CS : 4 * CT) * Hs * Ws < (1LL << 31), "dm_wgrad: tensor too large for 32-bit offsets");
     DM_REQUIRE(k == 4 || k == 3 || k == 1, "dm_wgrad: kernel size %d not built", k);
     DM_REQUIRE(!S->ones_channel, "dm_wgrad: S cannot carry a ones channel");
-    const int TW = wgrad_tw(Ws);
-    const bool fast = wgrad_has_kernel(CS, CT, Hs, Ws, k);
-    const int grid = dm_wgrad_num_blocks(B, CS, CT, Hs, Ws, k);
-    DM_REQUIRE(T->mode != DM_LOAD_AFFINE2 || (dm_wgrad_t_affine2_supported(CS, CT, Hs, Ws, k) && S->mode != DM_LOAD_AFFINE2 && !T->ones_channel),
+    DM_REQUIRE(B > 0, "dm_wgrad: bad shape");
+    const WgradRoute r = wgrad_route(B, CS, CT, Hs, Ws, k);
+    const int grid = r.nslabs;          // = slabs: every workgroup writes one
+    DM_REQUIRE(T->mode != DM_LOAD_AFFINE2 || (r.kind != ROUTE_RESIDENT && dm_wide_wgrad_t_affine2_ok(CS, CT, Hs, Ws, k) &&
+                                              S->mode != DM_LOAD_AFFINE2 && !T->ones_channel),
                "dm_wgrad: T operand cannot be AFFINE2 for this shape (dm_wgrad_t_affine2_supported)");
     const int CTphys = CT - (T->ones_channel ? 1 : 0);
     DM_REQUIRE(CTphys > 0, "dm_wgrad: no physical T channel");
     hipStream_t st = (hipStream_t)stream;
     const Operand s = to_dev(S), t = to_dev(T);
     const int E = CS * CT * k * k;
-    bool done = false;
-#define DM_WG(CS_, CT_, K_, TW_)                                                         \
-    if (fast && !done && CS == CS_ && CT == CT_ && k == K_ && TW == TW_) {               \
-        launch_wgrad<CS_, CT_, K_, TW_>(s, t, slabs, B, CTphys, Hs, Ws, grid, st);       \
-        done = true;                                                                     \
-    }
-    // enc.0 o enc.1 composite (x with ones channel), enc.4, enc.7
-    DM_WG(8, 3, 4, 64) DM_WG(8, 3, 4, 32) DM_WG(8, 3, 4, 16) DM_WG(8, 5, 4, 64) DM_WG(8, 2, 4, 64) DM_WG(8, 4, 4, 64)
-    DM_WG(8, 1, 4, 64)
-    DM_WG(16, 8, 4, 32) DM_WG(16, 8, 4, 64) DM_WG(16, 8, 4, 16)
-    DM_WG(16, 16, 4, 16) DM_WG(16, 16, 4, 32)
-    // enc.10 and residual convs
-    DM_WG(16, 16, 3, 16) DM_WG(16, 16, 3, 32)
-    DM_WG(32, 16, 3, 16) DM_WG(32, 16, 3, 32)
-    DM_WG(16, 32, 1, 16) DM_WG(16, 32, 1, 32)
-    // decoder ConvTranspose2d layers (S = layer input, T = output gradient)
-    DM_WG(8, 4, 4, 32) DM_WG(8, 4, 4, 64)
-    DM_WG(4, 4, 4, 64)
-#undef DM_WG
-    if (!done && fast) {
-        dm_set_error("dm_wgrad: kernel table and wgrad_has_kernel disagree (CS %d CT %d k %d %dx%d)", CS, CT, k, Hs, Ws);
-        return -1;
-    }
-    if (!done) {     // no register-resident instantiation: implicit-GEMM kernel (conv_wide.hip), else the generic one
-        if (dm_wide_wgrad_ok(Hs, Ws)) dm_wide_wgrad(s, t, slabs, B, CS, CT, CTphys, Hs, Ws, k, grid, st);
-        else dm_generic_wgrad(s, t, slabs, B, CS, CT, CTphys, Hs, Ws, k, grid, st);
-    }
+    if (r.kind == ROUTE_RESIDENT) wgrad_launch_resident(s, t, slabs, B, CS, CT, CTphys, Hs, Ws, k, r.TW, grid, st);
+    else if (r.kind == ROUTE_WIDE) dm_wide_wgrad(s, t, slabs, B, CS, CT, CTphys, Hs, Ws, k, grid, st);
+    else dm_generic_wgrad(s, t, slabs, B, CS, CT, CTphys, Hs, Ws, k, grid, st);
     int rc = dm_launch_status("dm_wgrad");
     if (rc || !dst) return rc;          // dst == NULL: the caller reduces the slabs later (dm_reduce_slabs_multi)
     hipLaunchKernelGGL(slab_reduce_kernel, dim3((E + 15) / 16), dim3(256), 0, st, slabs, grid, E, dst);

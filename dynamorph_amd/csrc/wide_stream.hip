@@ -13,6 +13,7 @@
 // write is shared.  The image-side 4x4 / stride 2 layers (1-4 channels) follow the same idea with the taps as a matrix
 // dimension; the last transposed convolution (eight outputs per input pixel) is vector-unit work and sits here too.
 #include "dm_common.h"
+#include "wide_host.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -839,6 +840,12 @@ __global__ __launch_bounds__(512, 1) void conv_s2_wide_stream_kernel(Operand in,
     }
 }
 
+// A lane's pixel quad A of one row as the 6 columns T[] a 3-wide window needs: the left neighbour's last and the right
+// neighbour's first pixel come by DPP and are 0 at the row's ends (ls / rs: the lane holds the row's first / last quad).
+#define DM_ROW6(T, A)                                                                                            \
+    { const float l = dpp_mov<0x111>(A.w), r = dpp_mov<0x101>(A.x);                                               \
+      T[0] = ls ? 0.f : l; T[1] = A.x; T[2] = A.y; T[3] = A.z; T[4] = A.w; T[5] = rs ? 0.f : r; }
+
 // --------------------------------------- ConvTranspose2d(64 -> 32, 4, 2, 1) on a 32 x 32 grid (-> 64 x 64), weights in LDS
 // The wide decoder's first transposed convolution and the data gradient of the encoder's second convolution: the mirror image
 // of conv_s2_wide_stream_kernel.  out[co][2 y + py][2 x + px] = sum over (ci, a, b) of in'[ci][y - 1 + py + a][x - 1 + px + b] *
@@ -949,11 +956,7 @@ __global__ __launch_bounds__(512, 1) void convT_wide_stream_kernel(Operand in, W
                     // rows as 6 columns: 4 pc - 1 (left neighbour; 0 at the row's start), 4 pc .. + 3, 4 pc + 4 (right neighbour)
                     float t[3][6];
                     const bool ls = pc == 0, rs = pc == 7;
-#define DM_ROW6(T, A)                                                                                            \
-                    { const float l = dpp_mov<0x111>(A.w), r = dpp_mov<0x101>(A.x);                               \
-                      T[0] = ls ? 0.f : l; T[1] = A.x; T[2] = A.y; T[3] = A.z; T[4] = A.w; T[5] = rs ? 0.f : r; }
                     DM_ROW6(t[0], a0) DM_ROW6(t[1], a1) DM_ROW6(t[2], a2)
-#undef DM_ROW6
                     const float *wp = sa + ks * (16 * MT * 64);
 #pragma unroll
                     for (int py = 0; py < 2; ++py)
@@ -1155,11 +1158,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wide_stream_kernel(Operand in,
                     }
                     float t[3][6];
                     const bool ls = pc == 0, rs = pc == 7;
-#define DM_ROW6(T, A)                                                                                            \
-                    { const float l = dpp_mov<0x111>(A.w), r = dpp_mov<0x101>(A.x);                               \
-                      T[0] = ls ? 0.f : l; T[1] = A.x; T[2] = A.y; T[3] = A.z; T[4] = A.w; T[5] = rs ? 0.f : r; }
                     DM_ROW6(t[0], a0) DM_ROW6(t[1], a1) DM_ROW6(t[2], a2)
-#undef DM_ROW6
                     const float *wp = sa + ks * (9 * MT * 64);
 #pragma unroll
                     for (int ky = 0; ky < 3; ++ky)
@@ -1198,6 +1197,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wide_stream_kernel(Operand in,
             for (int i = tid; i < CO * 2; i += 512) ep.stats[((long long)sl * CO + (i >> 1)) * 2 + (i & 1)] = 0.0;
     }
 }
+#undef DM_ROW6
 
 // ------------------------------------------- backward of the wide residual blocks' 1x1 convolution (64 -> 64), both gradients
 // dm_conv1x1_bwd_fused at 64 channels.  As two launches (data gradient + weight gradient, above) the pair read dy, its
@@ -1407,7 +1407,7 @@ bool dm_stream_wgrad1x1(const Operand &S, const Operand &T, float *slabs, int B,
                         hipStream_t st)
 {
     if (!dm_stream_wgrad1x1_shape(B, CS, CT, Hs, Ws) || T.ones || S.ones || T.mode == DM_LOAD_AFFINE2) return false;
-    if ((S.mode >= DM_LOAD_AFFINE && S.coef_bstride) || (T.mode >= DM_LOAD_AFFINE && T.coef_bstride)) return false;
+    if (per_sample_coef(S) || per_sample_coef(T)) return false;
     int grid = dm_stream_wgrad1x1_slabs(B, Hs, Ws);
     if (grid > nslabs) grid = nslabs;
     const int HW = Hs * Ws;
@@ -1427,15 +1427,10 @@ bool dm_stream_wgrad1x1(const Operand &S, const Operand &T, float *slabs, int B,
 bool dm_stream_conv1x1(const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B, int Cphys, int CIN,
                        int NOUT, int H, int W, int nslabs, int per_tile, hipStream_t st)
 {
-    if (!(stream_switch() & 2) || per_tile || Cphys != CIN || in.ones || ep.bias_border) return false;
+    if (!(stream_switch() & 2) || !stream_operand_ok(in, ep, Cphys, CIN, per_tile) || !stream_mask_ok(ep)) return false;
     const long long HW = (long long)H * W;
     if (!((CIN == 64 || CIN == 32) && (NOUT == 64 || NOUT == 32)) || HW % 64 || (long long)B * 64 * HW * 4 >= (1LL << 32)) return false;
-    if (in.mode >= DM_LOAD_AFFINE && in.coef_bstride) return false;
-    if (ep.mask.p0 && (ep.mask.mode == DM_LOAD_RELU || ep.mask.mode > DM_LOAD_AFFINE || ep.mask.coef_bstride || ep.mask.ones)) return false;
-    long long units = (long long)B * HW / 64;
-    int grid = (int)(units / 4 < 512 ? (units + 3) / 4 : 512);
-    if (ep.stats && grid > nslabs) grid = nslabs;
-    if (grid < 1) grid = 1;
+    const int grid = persistent_grid((long long)B * HW / 64, 4, 512, ep.stats, nslabs);
     const bool two = in.mode == DM_LOAD_AFFINE2;
 #define DM_SC(K4_, MT_)                                                                                                      \
     if (CIN == 16 * K4_ && NOUT == 16 * MT_) {                                                                                \
@@ -1465,7 +1460,7 @@ bool dm_stream_wgrad_s2_thin(const Operand &S, const Operand &T, float *slabs, i
                              hipStream_t st)
 {
     if (!dm_stream_wgrad_s2_thin_shape(B, CS, CT, Hs, Ws) || T.ones || S.ones || T.mode == DM_LOAD_AFFINE2) return false;
-    if ((S.mode >= DM_LOAD_AFFINE && S.coef_bstride) || (T.mode >= DM_LOAD_AFFINE && T.coef_bstride)) return false;
+    if (per_sample_coef(S) || per_sample_coef(T)) return false;
     int grid = dm_stream_wgrad_s2_thin_slabs(B, Hs, Ws);
     if (grid > nslabs) grid = nslabs;
     const bool two = S.mode == DM_LOAD_AFFINE2;
@@ -1483,15 +1478,10 @@ bool dm_stream_wgrad_s2_thin(const Operand &S, const Operand &T, float *slabs, i
 bool dm_stream_conv_s2_thin(const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B, int Cphys, int CIN,
                             int NOUT, int H, int W, int nslabs, int per_tile, hipStream_t st)
 {
-    if (!(stream_switch() & 8) || per_tile || Cphys != CIN || in.ones || ep.bias_border || in.mode == DM_LOAD_AFFINE2) return false;
+    if (!(stream_switch() & 8) || !stream_operand_ok(in, ep, Cphys, CIN, per_tile) || !stream_mask_ok(ep) || in.mode == DM_LOAD_AFFINE2) return false;
     if (CIN < 1 || CIN > 4 || !(NOUT == 16 || NOUT == 32 || (NOUT == 64 && CIN <= 2)) || W != 128 || H % 2) return false;
     if ((long long)B * NOUT * (H / 2) * (W / 2) * 4 >= (1LL << 32) || (long long)B * CIN * H * W * 4 >= (1LL << 31)) return false;
-    if (in.mode >= DM_LOAD_AFFINE && in.coef_bstride) return false;
-    if (ep.mask.p0 && (ep.mask.mode == DM_LOAD_RELU || ep.mask.mode > DM_LOAD_AFFINE || ep.mask.coef_bstride || ep.mask.ones)) return false;
-    const long long units = (long long)B * (H / 2);
-    int grid = (int)(units / 4 < 768 ? (units + 3) / 4 : 768);
-    if (ep.stats && grid > nslabs) grid = nslabs;
-    if (grid < 1) grid = 1;
+    const int grid = persistent_grid((long long)B * (H / 2), 4, 768, ep.stats, nslabs);
 #define DM_CT(C_, MT_)                                                                                                       \
     if (CIN == C_ && NOUT == 16 * MT_)                                                                                        \
         hipLaunchKernelGGL((conv_s2_thin_stream_kernel<C_, MT_>), dim3(grid), dim3(256), 0, st, in, wv, out, ep, B, H, nslabs);
@@ -1504,13 +1494,11 @@ bool dm_stream_conv_s2_thin(const Operand &in, const WeightView &wv, float *out,
 bool dm_stream_convT_thin(const Operand &in, const WeightView &wv, float *scratch, float *out, const Epilogue &ep, int B, int Cphys,
                           int CIN, int NOUT, int H, int W, int per_tile, hipStream_t st)
 {
-    if (!(stream_switch() & 16) || per_tile || Cphys != CIN || in.ones || in.mode == DM_LOAD_AFFINE2) return false;
+    if (!(stream_switch() & 16) || !stream_operand_ok(in, ep, Cphys, CIN, per_tile) || in.mode == DM_LOAD_AFFINE2) return false;
     if (!(NOUT == 4 || NOUT == 8) || W != 64 || H % 4 || CIN < 1 || CIN > 64 || !scratch) return false;
-    if (ep.mask.p0 || ep.resid || ep.stats || ep.bias_border) return false;
-    if ((in.mode >= DM_LOAD_AFFINE && in.coef_bstride) || (long long)B * CIN * H * W * 4 >= (1LL << 31)) return false;
+    if (ep.mask.p0 || ep.resid || ep.stats || (long long)B * CIN * H * W * 4 >= (1LL << 31)) return false;
     hipLaunchKernelGGL(convT_thin_pack_kernel, dim3((CIN * 32 + 255) / 256), dim3(256), 0, st, wv, scratch, CIN, NOUT / 4);
-    const long long units = (long long)B * (H / 4);
-    const int grid = (int)(units / 4 < 1024 ? (units + 3) / 4 : 1024);
+    const int grid = persistent_grid((long long)B * (H / 4), 4, 1024, false, 0);
     if (NOUT == 8) hipLaunchKernelGGL((convT_thin_stream_kernel<2>), dim3(grid), dim3(256), 0, st, in, (const float *)scratch, out, ep, B, CIN, H);
     else hipLaunchKernelGGL((convT_thin_stream_kernel<1>), dim3(grid), dim3(256), 0, st, in, (const float *)scratch, out, ep, B, CIN, H);
     return true;
@@ -1521,20 +1509,13 @@ bool dm_stream_convT_thin(const Operand &in, const WeightView &wv, float *scratc
 bool dm_stream_conv_s2_wide(const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B, int Cphys, int CIN,
                             int NOUT, int H, int W, int nslabs, int per_tile, hipStream_t st)
 {
-    if (!(stream_switch() & 32) || per_tile || Cphys != CIN || in.ones || ep.bias_border) return false;
+    if (!(stream_switch() & 32) || !stream_operand_ok(in, ep, Cphys, CIN, per_tile) || !stream_mask_ok(ep)) return false;
     if (CIN != 32 || NOUT != 64 || H != 64 || W != 64 || (long long)B * 64 * 32 * 32 * 4 >= (1LL << 31)) return false;
-    if (in.mode >= DM_LOAD_AFFINE && in.coef_bstride) return false;
-    if (ep.mask.p0 && (ep.mask.mode == DM_LOAD_RELU || ep.mask.mode > DM_LOAD_AFFINE || ep.mask.coef_bstride || ep.mask.ones)) return false;
     const int lds = 128 * 1024;
-    // (per launch, as dm_vq_backward does: the attribute belongs to the current device's copy of the kernel)
-    if (hipFuncSetAttribute((const void *)conv_s2_wide_stream_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-            hipFuncSetAttribute((const void *)conv_s2_wide_stream_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-            hipFuncSetAttribute((const void *)conv_s2_wide_stream_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+    if (!reserve_dynamic_lds({(const void *)conv_s2_wide_stream_kernel<true>, (const void *)conv_s2_wide_stream_kernel<false>,
+                              (const void *)conv_s2_wide_stream_kernel<true, true>}, lds))
         return false;
-    const long long units = (long long)B * 16;
-    int grid = (int)(units / 8 < 256 ? (units + 7) / 8 : 256);
-    if (ep.stats && grid > nslabs) grid = nslabs;
-    if (grid < 1) grid = 1;
+    const int grid = persistent_grid((long long)B * 16, 8, 256, ep.stats, nslabs);
     if (in.mode == DM_LOAD_AFFINE2)
         hipLaunchKernelGGL((conv_s2_wide_stream_kernel<true, true>), dim3(grid), dim3(512), lds, st, in, wv, out, ep, B, nslabs);
     else if (in.mode >= DM_LOAD_AFFINE || in.mode == DM_LOAD_RELU)
@@ -1549,19 +1530,12 @@ bool dm_stream_conv_s2_wide(const Operand &in, const WeightView &wv, float *out,
 bool dm_stream_convT_wide(const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B, int Cphys, int CIN,
                           int NOUT, int H, int W, int nslabs, int per_tile, hipStream_t st)
 {
-    if (!(stream_switch() & 64) || per_tile || Cphys != CIN || in.ones || ep.bias_border) return false;
+    if (!(stream_switch() & 64) || !stream_operand_ok(in, ep, Cphys, CIN, per_tile) || !stream_mask_ok(ep)) return false;
     if (CIN != 64 || NOUT != 128 || H != 32 || W != 32 || (long long)B * 64 * 32 * 32 * 4 >= (1LL << 31)) return false;
-    if (in.mode >= DM_LOAD_AFFINE && in.coef_bstride) return false;
-    if (ep.mask.p0 && (ep.mask.mode == DM_LOAD_RELU || ep.mask.mode > DM_LOAD_AFFINE || ep.mask.coef_bstride || ep.mask.ones)) return false;
     const int lds = 128 * 1024;
-    // (per launch, as dm_vq_backward does: the attribute belongs to the current device's copy of the kernel)
-    if (hipFuncSetAttribute((const void *)convT_wide_stream_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-            hipFuncSetAttribute((const void *)convT_wide_stream_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+    if (!reserve_dynamic_lds({(const void *)convT_wide_stream_kernel<true>, (const void *)convT_wide_stream_kernel<false>}, lds))
         return false;
-    const long long units = (long long)B * 16;
-    int grid = (int)(units / 8 < 256 ? (units + 7) / 8 : 256);
-    if (ep.stats && grid > nslabs) grid = nslabs;
-    if (grid < 1) grid = 1;
+    const int grid = persistent_grid((long long)B * 16, 8, 256, ep.stats, nslabs);
     if (in.mode == DM_LOAD_AFFINE2)
         hipLaunchKernelGGL((convT_wide_stream_kernel<true>), dim3(grid), dim3(512), lds, st, in, wv, out, ep, B, nslabs);
     else
@@ -1574,19 +1548,12 @@ bool dm_stream_conv3x3_wide(const Operand &in, const WeightView &wv, float *out,
                             int NOUT, int H, int W, int nslabs, int per_tile, hipStream_t st)
 {
     const int bit = ep.mask.p0 ? 256 : 128;
-    if (!(stream_switch() & bit) || per_tile || Cphys != CIN || in.ones || ep.bias_border) return false;
+    if (!(stream_switch() & bit) || !stream_operand_ok(in, ep, Cphys, CIN, per_tile) || !stream_mask_ok(ep)) return false;
     if (CIN != 64 || NOUT != 64 || H != 32 || W != 32 || (long long)B * 64 * 32 * 32 * 4 >= (1LL << 31)) return false;
-    if (in.mode >= DM_LOAD_AFFINE && in.coef_bstride) return false;
-    if (ep.mask.p0 && (ep.mask.mode == DM_LOAD_RELU || ep.mask.mode > DM_LOAD_AFFINE || ep.mask.coef_bstride || ep.mask.ones)) return false;
     const int lds = 9 * 64 * 64 * 4;
-    // (per launch, as dm_vq_backward does: the attribute belongs to the current device's copy of the kernel)
-    if (hipFuncSetAttribute((const void *)conv3x3_wide_stream_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-            hipFuncSetAttribute((const void *)conv3x3_wide_stream_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+    if (!reserve_dynamic_lds({(const void *)conv3x3_wide_stream_kernel<true>, (const void *)conv3x3_wide_stream_kernel<false>}, lds))
         return false;
-    const long long units = (long long)B * 16;
-    int grid = (int)(units / 8 < 256 ? (units + 7) / 8 : 256);
-    if (ep.stats && grid > nslabs) grid = nslabs;
-    if (grid < 1) grid = 1;
+    const int grid = persistent_grid((long long)B * 16, 8, 256, ep.stats, nslabs);
     if (in.mode == DM_LOAD_AFFINE2)
         hipLaunchKernelGGL((conv3x3_wide_stream_kernel<true>), dim3(grid), dim3(512), lds, st, in, wv, out, ep, B, nslabs);
     else

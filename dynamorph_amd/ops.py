@@ -289,6 +289,7 @@ def conv4x4s2(inp, wv, B, CIN, NOUT, H, W, ep=None, out=None, want_stats=False, 
         stats = _new((nb, NOUT, 2), like, torch.float64)
     e = epilogue(stats=stats, **epkw)
     o = inp.struct()
+    # the operand / epilogue forms dm_conv4x4s2 keeps off its register-resident kernels (conv_mfma.hip, conv4_resident_takes)
     fallback = inp.mode == L.DM_LOAD_AFFINE2 or (epkw.get("bias_border") is not None and
                                                   any(epkw.get(k) is not None for k in ("mask", "resid", "stat_q")))
     wv.with_scratch(lib.dm_conv4x4s2_scratch_floats(CIN, NOUT, H, W, 1 if fallback else 0))
@@ -352,6 +353,15 @@ def backward_precision(mode=None):
     return names[prev]
 
 
+def _queue_or_reduce(slabs, dst, pending):
+    """Weight-gradient slabs of a fused backward: queued as (slabs, dst) for reduce_slabs_multi, or (pending None) reduced
+    into dst at once."""
+    if pending is not None:
+        pending.append((slabs, dst))
+    else:
+        reduce_slabs(slabs, dst)
+
+
 def conv_bwd_s2_fused_supported(CD, CX, H, W):
     return bool(L.load().dm_conv_bwd_s2_fused_supported(CD, CX, H, W))
 
@@ -374,10 +384,7 @@ def conv_bwd_s2_fused(dy, tin, wv, dst, B, CD, CX, H, W, mask, stat_q=None, pend
     d, t = dy.struct(), tin.struct()
     L.check(lib.dm_conv_bwd_s2_fused(C.byref(d), C.byref(t), wv.ref(), _ptr(dx), C.byref(e), _ptr(slabs), B, CD, CX, H, W,
                                      _stream()), "dm_conv_bwd_s2_fused")
-    if pending is not None:
-        pending.append((slabs, dst))
-    else:
-        reduce_slabs(slabs, dst)
+    _queue_or_reduce(slabs, dst, pending)
     return dx, stats
 
 
@@ -401,10 +408,7 @@ def conv1x1_bwd_fused(dy, x, xcoef, w, dst, B, CD, CX, H, W, pending=None):
     d = dy.struct()
     L.check(lib.dm_conv1x1_bwd_fused(C.byref(d), _ptr(x), _ptr(xcoef), _ptr(w), _ptr(dx), _ptr(stats, torch.float64),
                                      _ptr(slabs), B, CD, CX, H, W, _stream()), "dm_conv1x1_bwd_fused")
-    if pending is not None:
-        pending.append((slabs, dst))
-    else:
-        reduce_slabs(slabs, dst)
+    _queue_or_reduce(slabs, dst, pending)
     return dx, stats
 
 
@@ -430,10 +434,7 @@ def conv3x3_bwd_fused(dy, x, xcoef, w, dst, B, CD, resid=None, q=None, want_stat
     L.check(lib.dm_conv3x3_bwd_fused(C.byref(d), _ptr(x), _ptr(xcoef), _ptr(w), _ptr(resid), _ptr(q), _ptr(dx),
                                      _ptr(stats, torch.float64), _ptr(slabs), B, CD, CX, H, W, _stream()),
             "dm_conv3x3_bwd_fused")
-    if pending is not None:
-        pending.append((slabs, dst))
-    else:
-        reduce_slabs(slabs, dst)
+    _queue_or_reduce(slabs, dst, pending)
     return dx, stats
 
 
@@ -458,10 +459,7 @@ def conv4x4s2_bwd_fused(dy, x, xcoef, w, dst, B, pending=None):
     d = dy.struct()
     L.check(lib.dm_conv4x4s2_bwd_fused(C.byref(d), _ptr(x), _ptr(xcoef), _ptr(w), _ptr(dx), _ptr(stats, torch.float64),
                                        _ptr(slabs), B, CD, CX, H, W, _stream()), "dm_conv4x4s2_bwd_fused")
-    if pending is not None:
-        pending.append((slabs, dst))
-    else:
-        reduce_slabs(slabs, dst)
+    _queue_or_reduce(slabs, dst, pending)
     return dx, stats
 
 
@@ -488,10 +486,7 @@ def convT_bwd_fused(S, G, w, dst, mask_relu=False, want_stats=False, pending=Non
     slabs = _new((nb, CI * CO * 16), S)
     L.check(lib.dm_convt_bwd_fused(_ptr(S), _ptr(G), _ptr(w), _ptr(gin), _ptr(stats, torch.float64), _ptr(slabs),
                                    1 if mask_relu else 0, B, CI, CO, H, W, _stream()), "dm_convt_bwd_fused")
-    if pending is not None:
-        pending.append((slabs, dst))
-    else:
-        reduce_slabs(slabs, dst)
+    _queue_or_reduce(slabs, dst, pending)
     return gin, stats
 
 

@@ -101,7 +101,37 @@ ROUTES = [
     # ---- dm_apply --------------------------------------------------------------------------------------------------
     Route("apply", "apply", "apply_kernel", (2, 16, 16, 16)),
 ]
-ROUTE = {r.name: r for r in ROUTES}
+
+# One base case per register-resident table row (DM_CONV4_ROWS, DM_CONVT_PHASE_ROWS, DM_CONV3_ROWS in conv_mfma.hip,
+# DM_WGRAD_ROWS in wgrad_mfma.hip) that no route above selects, at the smallest shape that does: two samples of one tile,
+# as wide as the row's tile.  (The rows with 64-wide tiles from 16 channels and 32-wide tiles from 32 channels cannot be
+# selected by any shape: conv3_tw caps those widths at 32 and 16.)
+def _row(name, entry, kernel, shape, base=()):
+    return Route("row_" + name, entry, kernel, shape, base=base)
+
+
+ROW_ROUTES = (
+    # dm_conv4x4s2, row (CIN, TW): output of 8 x TW
+    [_row(f"s2_c{c}_tw{tw}", "s2", f"conv4x4s2_kernel<{c},", (2, c, 16 if c == 8 else 8, 16, 2 * tw, 16))
+     for c, tw in ((3, 16), (4, 64), (4, 16), (5, 32), (5, 16), (2, 32), (2, 16), (1, 32), (1, 16), (8, 16))]
+    # dm_conv3x3 pixel shuffle on the phase kernel, row (COUT, TW): 16 rows with 16-wide tiles, else 8
+    + [_row(f"convT_phase_co{co}_tw{tw}", "pix", f"convT_phase_kernel<16, {co},", (2, 16, 4 * co, 16 if tw == 16 else 8, tw, 9))
+       for co, tw in ((8, 32), (16, 16), (16, 32))]
+    # dm_conv3x3, row (CIN, NTOT, taps, pix, TW); the 16-channel pixel-shuffle rows are reached with per-tile statistics only
+    + [_row("s1_c16_tw32", "s1", "conv3x3_kernel<16, 1, 1, 9, false", (2, 16, 16, 8, 32, 9)),
+       _row("s1_c16n2_tw16", "s1", "conv3x3_kernel<16, 2, 1, 9, false", (2, 16, 32, 16, 16, 9)),
+       _row("s1_1x1_c16n2_tw16", "s1", "conv3x3_kernel<16, 2, 1, 1, false", (2, 16, 32, 16, 16, 1)),
+       _row("pix_c16n2_tw32", "pix", "conv3x3_kernel<16, 2, 1, 9, true", (2, 16, 32, 8, 32, 9), base=("per_tile",)),
+       _row("pix_c16n4_tw32", "pix", "conv3x3_kernel<16, 2, 2, 9, true", (2, 16, 64, 8, 32, 9), base=("per_tile",)),
+       _row("pix_c8_tw32", "pix", "conv3x3_kernel<8, 1, 1, 9, true", (2, 8, 16, 8, 32, 9))]
+    # dm_wgrad, row (CS, CT, k, TW): S grid of 8 x TW
+    + [_row(f"wg_{cs}x{ct}_k{k}_tw{tw}", "wgrad", ("wgrad_ys_kernel<%d," % ct) if cs == 8 else f"wgrad_kernel<{cs}, {ct}, {k}",
+            (2, cs, ct, 8, tw, k))
+       for cs, ct, k, tw in ((8, 3, 4, 32), (8, 3, 4, 16), (8, 5, 4, 64), (8, 2, 4, 64), (8, 4, 4, 64), (8, 1, 4, 64),
+                             (16, 8, 4, 64), (16, 8, 4, 16), (16, 16, 4, 16), (16, 16, 4, 32), (16, 16, 3, 32),
+                             (32, 16, 3, 32), (16, 32, 1, 32), (8, 4, 4, 32))]
+)
+ROUTE = {r.name: r for r in ROUTES + ROW_ROUTES}
 
 # ---------------------------------------------------------------------------------------------------------- features
 MODES = ("mode0", "mode1", "mode2", "mode3", "mode4")
@@ -340,9 +370,14 @@ def persistent_B(route):
     return (cap // max(u1, 1) + 1) * 5 // 4 + 1
 
 
+def row_cases():
+    """The base case of every ROW_ROUTES entry."""
+    return [Case(r.name, normalize(r, ()), r.shape[0], "match") for r in ROW_ROUTES]
+
+
 def all_cases(env=None):
-    """Every case; env None: all, "" : in-process routes, "tiled": the child's."""
-    return [c for r in ROUTES if env is None or r.env == env for c in cases_for(r)]
+    """Every case; env None: all, "" : in-process routes (and the table-row cases), "tiled": the child's."""
+    return [c for r in ROUTES if env is None or r.env == env for c in cases_for(r)] + (row_cases() if not env else [])
 
 
 # ------------------------------------------------------------------------------------------------------------ inputs
