@@ -1811,18 +1811,181 @@ int vq2_cells()
     }();
     return v;
 }
-bool vq2_applicable(const float *z, const int64_t *idx, const float *out, const void *ws, int D, int HW)
-{
-    const uintptr_t al = (uintptr_t)z | (uintptr_t)idx | (uintptr_t)out | (uintptr_t)ws;
-    return (D == 8 || D == 16 || D == 32 || D == 64) && HW % 64 == 0 && (al & 15) == 0;
-}
-}  // namespace
 
-namespace {
+// ---- the route ----------------------------------------------------------------------------------------------------------
+// Which forward kernel takes a call, and in which of its forms.  vq_route fills it from the call's shape, the alignment of
+// its tensors and the three environment switches above; the launch, the join's shape test and its entry point all read it.
+enum { VQ_ROUTE_EXACT, VQ_ROUTE_ANY, VQ_ROUTE_MFMA, VQ_ROUTE_CELLS };   // vq_forward{,_any,_mfma}_kernel, vq_cells_kernel
+struct VqRoute {
+    int kind;
+    bool mfma_ok;               // the matrix kernels tile the call: what DM_VQ_MFMA / DM_VQ_BF16 insist on
+    bool bf;                    // bf16-split filter (DM_VQ_BF16; DM_VQ_AUTO takes it where it applies) or the f32 one (DM_VQ_MFMA)
+    bool single, inl, join;     // VQ_ROUTE_MFMA: <= 64 codes; the one-launch form (no preparation, counters as rows); its join
+    int prod;                   // VQ_ROUTE_CELLS: products of the bf16 split (3 or 4)
+};
+
+// vq_forward_mfma_kernel, one row per (D, SINGLE, MINW, WGS): embedding_dim, at most 64 codes, workgroups per CU the kernel is
+// bounded for, workgroups per CU the grid is sized for.  The forms (BF, INL, JOIN) a row is built in: vq2_launch_row.
+#define DM_VQ2_ROWS(X)                                                                                                   \
+    X(8, true, 3, 3) X(8, false, 3, 3) X(16, true, 3, 3) X(16, false, 3, 3) X(32, true, 2, 2) X(32, false, 2, 2)         \
+    X(64, true, 1, 1) X(64, false, 1, 2)
+
+// the fused residual join: the one-launch form at embedding_dim 16 (= the reference's num_hiddens: at 32 / 64 the second
+// prefetched tensor does not fit the registers)
+bool vq_join_built(int D, int K, int HW) { return K > 0 && K <= 64 && D == 16 && HW > 0 && HW % 64 == 0; }
+
+VqRoute vq_route(int variant, int D, int K, int HW, uintptr_t al /* every tensor's address, or-ed */, bool want_join)
+{
+    VqRoute r{};
+    r.mfma_ok = (D == 8 || D == 16 || D == 32 || D == 64) && HW % 64 == 0 && (al & 15) == 0;
+    r.kind = vq_dim_built(D) ? VQ_ROUTE_EXACT : VQ_ROUTE_ANY;
+    if (variant == DM_VQ_EXACT || !r.mfma_ok) return r;
+    r.bf = D % 16 == 0 && (variant == DM_VQ_BF16 || (variant == DM_VQ_AUTO && vq2_auto_bf16()));
+    r.prod = vq2_cells();
+    // BASELINE configs[4]: the cell kernel of vq_cells.h (DM_VQ_CELLS=0 keeps the streamed one, DM_VQ_CELLS_PROD=4 all four products)
+    const bool cells = r.bf && D == 16 && K > 64 && K <= VQC_MAX_K && HW % 128 == 0 && r.prod > 0;
+    r.kind = cells ? VQ_ROUTE_CELLS : VQ_ROUTE_MFMA;
+    if (cells) return r;
+    r.single = K <= 64;
+    // every configuration of the reference: the kernel prepares its own operands and writes its counters as per-workgroup rows
+    r.inl = r.single && D % 16 == 0;
+    r.join = want_join && r.inl && vq_join_built(D, K, HW);
+    return r;
+}
+
+struct VqArgs {
+    const float *z, *cb, *jh, *jcoef;      // jh, jcoef, jz: the join's block input and coefficients, the latents it writes (else NULL)
+    float *out, *jz, *ws;
+    long long *idx;
+    double *slabs;
+    int *hrep;
+    Vq2Layout L;
+    int D, K, HW, nslabs;
+    long long P;
+    hipStream_t s;
+};
+
+// A row in the form the route names.  Built: the bf16-split filter at embedding_dim 16 / 32 / 64, the one-launch form for the
+// SINGLE rows of those, its join at 16.
+template <int D, bool SINGLE, int MINW, int WGS, bool BF = false, bool INL = false, bool JOIN = false>
+void vq2_launch_row(const VqRoute &r, const VqArgs &a)
+{
+    if constexpr (!BF && D % 16 == 0) { if (r.bf) return vq2_launch_row<D, SINGLE, MINW, WGS, true, INL, JOIN>(r, a); }
+    if constexpr (!INL && SINGLE && D % 16 == 0) { if (r.inl) return vq2_launch_row<D, SINGLE, MINW, WGS, BF, true, JOIN>(r, a); }
+    if constexpr (INL && !JOIN && D == 16) { if (r.join) return vq2_launch_row<D, SINGLE, MINW, WGS, BF, true, true>(r, a); }
+    const long long groups = ((a.P >> 6) + 3) / 4;               // four chunks of 64 positions per workgroup and iteration
+    long long g = groups < 256 * WGS ? groups : 256 * WGS;
+    if (INL && g > VQ2_SLAB_ROWS) g = VQ2_SLAB_ROWS;             // one counter row per workgroup
+    hipLaunchKernelGGL((vq_forward_mfma_kernel<D, SINGLE, MINW, BF, INL, JOIN>), dim3((unsigned)g), dim3(256), 0, a.s, a.z, a.cb,
+                       a.ws + (BF ? a.L.cbB : a.L.cbA), a.ws + a.L.nrm, a.ws + a.L.cbH, a.idx, a.out, a.slabs, a.hrep, a.L.R,
+                       (int *)a.ws, a.K, a.HW, a.P, a.nslabs, a.jh, a.jcoef, a.jz);
+}
+
+void vq2_launch(const VqRoute &r, const VqArgs &a)
+{
+#define DM_V2(DD, SINGLE_, MINW_, WGS_) if (a.D == DD && r.single == SINGLE_) return vq2_launch_row<DD, SINGLE_, MINW_, WGS_>(r, a);
+    DM_VQ2_ROWS(DM_V2)
+#undef DM_V2
+}
+
+void vq_cells_launch(const VqRoute &r, const VqArgs &a)
+{
+    const long long passes = a.P >> 7;
+    long long g = (passes + 3) / 4;
+    if (g > 512) g = 512;                                        // two workgroups per CU, persistent over the passes
+    // half a pass in units of 64 cycles (s_sleep): a pass streams K / 32 chunks of 12 (16) matrix instructions of 32
+    // cycles, started 90 % of the way in; only where both slots of the CUs are taken and every wave has more than one pass
+    const long long chunk_cycles = (long long)(r.prod == 4 ? 16 : 12) * 32;
+    const int stagger = (g > 256 && passes >= 2 * g * 4) ? (int)(((a.K + 31) / 32) * chunk_cycles * 90 / 100 / 64) : 0;
+    const auto kernel = r.prod == 4 ? vq_cells_kernel<4> : vq_cells_kernel<3>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)g), dim3(256), 0, a.s, a.z, a.cb, reinterpret_cast<const vqc_u32x4 *>(a.ws + a.L.cbP),
+                       a.ws + a.L.nrmP, a.ws + a.L.nrm, a.idx, a.out, a.slabs, a.hrep, a.L.R, (int *)a.ws, a.K, a.HW, a.P, stagger);
+}
+
+void vq_any_launch(const VqArgs &a)
+{
+    long long g = (a.P + 63) / 64;
+    if (g > a.nslabs) g = a.nslabs;                              // one squared-error slab per workgroup (the rest were zeroed)
+    if (g > 4096) g = 4096;
+    hipLaunchKernelGGL(vq_forward_any_kernel, dim3((unsigned)g), dim3(64), (size_t)a.D * 64 * sizeof(float), a.s, a.z, a.cb, a.idx,
+                       a.out, a.slabs, a.hrep, a.L.R, a.K, a.D, a.HW, a.P);
+}
+
+void vq_exact_launch(const VqArgs &a)
+{
+#define DM_VQ_FWD(DD, PP_)                                                                                             \
+    hipLaunchKernelGGL((vq_forward_kernel<DD, PP_>), dim3((unsigned)((a.P + VQ_BLOCK * PP_ - 1) / (VQ_BLOCK * PP_))),   \
+                       dim3(VQ_BLOCK), 0, a.s, a.z, a.cb, a.ws + a.L.cbT, a.idx, a.out, a.slabs, a.hrep, a.L.R, a.K, a.HW, a.P)
+    switch (a.D) {
+    case 8: DM_VQ_FWD(8, VQ_PP); break;
+    case 16: DM_VQ_FWD(16, VQ_PP); break;
+    case 32: DM_VQ_FWD(32, VQ_PP); break;
+    case 64: DM_VQ_FWD(64, 1); break;
+    default: DM_VQ_FWD(128, 1); break;        // VectorQuantizer's own default embedding_dim (vq_vae.py:35)
+    }
+#undef DM_VQ_FWD
+}
+
+// Dynamic LDS beyond the 48 KB every kernel may use has to be reserved for the kernel first: per call with the call's size
+// (the backward kernels, whose window depends on K and D), or -- `once` -- once per device with a size that covers every later
+// call (the forward any-width kernel: its widest form).  The two callers' messages differ and are kept.
+int vq_reserve_lds(const char *who, const void *kernel, size_t bytes, DmPerDeviceOnce *once)
+{
+    if (bytes <= 48 * 1024 || (once && !once->need())) return 0;
+    const hipError_t ea = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (ea != hipSuccess) {
+        if (once) dm_set_error("%s: cannot reserve LDS: %s", who, hipGetErrorString(ea));
+        else dm_set_error("%s: cannot reserve %zu bytes of LDS: %s", who, bytes, hipGetErrorString(ea));
+        return (int)ea;
+    }
+    if (once) once->mark();
+    return 0;
+}
+
 int vq_forward_launch(const float *z, const float *codebook, int64_t *idx, float *out, double *sse_slabs, int32_t *hist,
                       int B, int D, int K, int H, int W, void *workspace, size_t workspace_bytes, int variant, int repeats,
-                      void *stream, const float *jh = nullptr, const float *jcoef = nullptr, float *jz = nullptr);
+                      void *stream, const float *jh = nullptr, const float *jcoef = nullptr, float *jz = nullptr)
+{
+    DM_REQUIRE(z && codebook && sse_slabs, "dm_vq_forward: NULL pointer");     // hist == NULL: the counters stay in their replicas
+    DM_REQUIRE(B > 0 && H > 0 && W > 0 && K > 0, "dm_vq_forward: bad shape B=%d K=%d H=%d W=%d", B, K, H, W);
+    DM_REQUIRE(vq_dim_supported(D), "dm_vq_forward: embedding_dim %d outside 1 .. 512", D);
+    DM_REQUIRE(workspace && workspace_bytes >= dm_vq_workspace_bytes(K, D), "dm_vq_forward: workspace too small");
+    DM_REQUIRE(variant >= DM_VQ_AUTO && variant <= DM_VQ_BF16, "dm_vq_forward: bad variant %d", variant);
+    DM_REQUIRE(variant != DM_VQ_BF16 || D % 16 == 0, "dm_vq_forward: the bf16-split filter needs embedding_dim 16, 32 or 64");
+    const uintptr_t al = (uintptr_t)z | (uintptr_t)idx | (uintptr_t)out | (uintptr_t)workspace | (uintptr_t)codebook;
+    const VqRoute r = vq_route(variant, D, K, H * W, al, jz != nullptr);
+    DM_REQUIRE((variant != DM_VQ_MFMA && variant != DM_VQ_BF16) || r.mfma_ok,
+               "dm_vq_forward: the MFMA variant needs embedding_dim 8/16/32/64, H*W %% 64 == 0 and 16-byte aligned tensors");
+    DM_REQUIRE(!jz || r.join, "dm_vq_forward_join: built for the one-launch form (<= 64 codes, embedding_dim 16, H*W %% 64 == 0)");
+    const long long P = (long long)B * H * W;
+    float *ws = (float *)workspace;
+    const Vq2Layout L = vq2_layout(K, D);
+    const VqArgs a{z, codebook, jh, jcoef, out, jz, ws, (long long *)idx, sse_slabs, reinterpret_cast<int *>(ws + L.hrep), L,
+                   D, K, H * W, dm_vq_num_blocks(P), P, (hipStream_t)stream};
+    if (!r.inl) {
+        // (vq_prep_kernel also clears the counter replicas and all slabs: there are fewer workgroups than slabs)
+        int pgrid = (int)((a.L.total + 255) / 256);
+        if (pgrid > 1024) pgrid = 1024;
+        hipLaunchKernelGGL(vq_prep_kernel, dim3(pgrid), dim3(256), 0, a.s, codebook, ws, a.L, K, D, sse_slabs, a.nslabs);
+    }
+    if (r.kind == VQ_ROUTE_ANY) {
+        // a width above 192 needs more than 48 KB for its [D][64] latents: the widest (512) is reserved, once
+        static DmPerDeviceOnce any_attr;
+        const size_t lds = (size_t)D * 64 * sizeof(float) > 48 * 1024 ? 512 * 64 * sizeof(float) : 0;
+        if (const int rc = vq_reserve_lds("dm_vq_forward", (const void *)vq_forward_any_kernel, lds, &any_attr)) return rc;
+    }
+    for (int rep = 0; rep < repeats; ++rep) {
+        switch (r.kind) {
+        case VQ_ROUTE_CELLS: vq_cells_launch(r, a); break;
+        case VQ_ROUTE_MFMA: vq2_launch(r, a); break;
+        case VQ_ROUTE_ANY: vq_any_launch(a); break;
+        default: vq_exact_launch(a); break;
+        }
+    }
+    if (hist) hipLaunchKernelGGL(vq_hist_reduce_kernel, dim3((K + 63) / 64), dim3(1024), 0, a.s, a.hrep, (int *)ws, K, (int *)hist);
+    return dm_launch_status("dm_vq_forward");
 }
+}  // namespace
 
 extern "C" int dm_vq_forward_variant(const float *z, const float *codebook, int64_t *idx, float *out,
                                      double *sse_slabs, int32_t *hist, int B, int D, int K, int H, int W,
@@ -1841,138 +2004,6 @@ extern "C" int dm_vq_forward_repeat(const float *z, const float *codebook, int64
                              repeats, stream);
 }
 
-namespace {
-int vq_forward_launch(const float *z, const float *codebook, int64_t *idx, float *out, double *sse_slabs, int32_t *hist,
-                      int B, int D, int K, int H, int W, void *workspace, size_t workspace_bytes, int variant, int repeats,
-                      void *stream, const float *jh, const float *jcoef, float *jz)
-{
-    DM_REQUIRE(z && codebook && sse_slabs, "dm_vq_forward: NULL pointer");     // hist == NULL: the counters stay in their replicas
-    DM_REQUIRE(B > 0 && H > 0 && W > 0 && K > 0, "dm_vq_forward: bad shape B=%d K=%d H=%d W=%d", B, K, H, W);
-    DM_REQUIRE(vq_dim_supported(D), "dm_vq_forward: embedding_dim %d outside 1 .. 512", D);
-    DM_REQUIRE(workspace && workspace_bytes >= dm_vq_workspace_bytes(K, D), "dm_vq_forward: workspace too small");
-    DM_REQUIRE(variant >= DM_VQ_AUTO && variant <= DM_VQ_BF16, "dm_vq_forward: bad variant %d", variant);
-    DM_REQUIRE(variant != DM_VQ_BF16 || D % 16 == 0, "dm_vq_forward: the bf16-split filter needs embedding_dim 16, 32 or 64");
-    hipStream_t s = (hipStream_t)stream;
-    const long long P = (long long)B * H * W;
-    const Vq2Layout L = vq2_layout(K, D);
-    float *ws = (float *)workspace;
-    const bool can2 = vq2_applicable(z, idx, out, workspace, D, H * W) && ((uintptr_t)codebook & 15) == 0;
-    DM_REQUIRE((variant != DM_VQ_MFMA && variant != DM_VQ_BF16) || can2,
-               "dm_vq_forward: the MFMA variant needs embedding_dim 8/16/32/64, H*W %% 64 == 0 and 16-byte aligned tensors");
-    const bool use2 = variant == DM_VQ_MFMA || variant == DM_VQ_BF16 || (variant == DM_VQ_AUTO && can2);
-    const long long n = L.total;
-    const int nslabs = dm_vq_num_blocks(P);
-    int pgrid = (int)((n + 255) / 256);
-    if (pgrid > 1024) pgrid = 1024;
-    // <= 64 codes (every configuration of the reference), embedding_dim 16 / 32 / 64: the MFMA kernel prepares its own
-    // operands and writes its counters as per-workgroup rows -- no preparation launch, no counter reduction
-    const bool inl = use2 && K <= 64 && D % 16 == 0;
-    DM_REQUIRE(!jz || (inl && D == 16), "dm_vq_forward_join: built for the one-launch form (<= 64 codes, embedding_dim 16, H*W %% 64 == 0)");
-    if (!inl) hipLaunchKernelGGL(vq_prep_kernel, dim3(pgrid), dim3(256), 0, s, codebook, ws, L, K, D, sse_slabs, nslabs);
-    // (vq_prep_kernel cleared the counter replicas and all slabs: there are fewer workgroups than slabs)
-    int *hrep = reinterpret_cast<int *>(ws + L.hrep);
-    if (use2) {
-        const long long groups = ((P >> 6) + 3) / 4;
-#define DM_VQ2K(DD, SINGLE_, MINW, WGS, BF_, INL_, JOIN_)                                                            \
-    {                                                                                                                \
-        const int wgs = (WGS);                                                                                       \
-        long long g_ = groups < 256 * wgs ? groups : 256 * wgs;                                                      \
-        if (INL_ && g_ > VQ2_SLAB_ROWS) g_ = VQ2_SLAB_ROWS;          /* one counter row per workgroup */              \
-        hipLaunchKernelGGL((vq_forward_mfma_kernel<DD, SINGLE_, MINW, BF_, INL_, JOIN_>),                            \
-                           dim3((unsigned)g_), dim3(256), 0, s, z, codebook,                                         \
-                           ws + (BF_ ? L.cbB : L.cbA), ws + L.nrm, ws + L.cbH, (long long *)idx, out, sse_slabs, hrep, \
-                           L.R, (int *)ws, K, H * W, P, nslabs, jh, jcoef, jz);                                      \
-    }
-#define DM_VQ2(DD, SINGLE_, MINW, WGS)                                                                               \
-    {                                                                                                                \
-        if constexpr (DD % 16 == 0 && SINGLE_) {                                                                     \
-            if (inl && bf && jz) DM_VQ2K(DD, SINGLE_, MINW, WGS, true, true, DD == 16)                               \
-            else if (inl && jz) DM_VQ2K(DD, SINGLE_, MINW, WGS, false, true, DD == 16)                               \
-            else if (inl && bf) DM_VQ2K(DD, SINGLE_, MINW, WGS, true, true, false)                                          \
-            else if (inl) DM_VQ2K(DD, SINGLE_, MINW, WGS, false, true, false)                                               \
-            else if (bf) DM_VQ2K(DD, SINGLE_, MINW, WGS, true, false, false)                                                \
-            else DM_VQ2K(DD, SINGLE_, MINW, WGS, false, false, false)                                                       \
-        } else if constexpr (DD % 16 == 0) {                                                                         \
-            if (bf) DM_VQ2K(DD, SINGLE_, MINW, WGS, true, false, false) else DM_VQ2K(DD, SINGLE_, MINW, WGS, false, false, false)  \
-        } else DM_VQ2K(DD, SINGLE_, MINW, WGS, false, false, false)                                                         \
-    }
-        const bool single = K <= 64;
-        // bf16-split filter (DM_VQ_BF16; DM_VQ_AUTO takes it where it applies) or the f32 one (DM_VQ_MFMA)
-        const bool bf = D % 16 == 0 && (variant == DM_VQ_BF16 || (variant == DM_VQ_AUTO && vq2_auto_bf16()));
-        // 64 < K <= 4096 at embedding_dim 16 (BASELINE configs[4]): the cell kernel of vq_cells.h -- DM_VQ_CELLS=0 keeps the
-        // streamed 16x16x32 kernel, DM_VQ_CELLS_PROD=4 all four products of the split (A/B measurements)
-        const bool cells = bf && D == 16 && K > 64 && K <= VQC_MAX_K && (H * W) % 128 == 0 && vq2_cells() > 0;
-        for (int rep = 0; rep < repeats; ++rep) {
-            if (cells) {
-                const long long passes = P >> 7;
-                long long g_ = (passes + 3) / 4;
-                if (g_ > 512) g_ = 512;                              // two workgroups per CU, persistent over the passes
-                // half a pass in units of 64 cycles (s_sleep): a pass streams K / 32 chunks of 12 (16) matrix instructions of 32
-                // cycles, started 90 % of the way in; only where both slots of the CUs are taken and every wave has more than one pass
-                const int prod = vq2_cells();
-                const long long chunk_cycles = (long long)(prod == 4 ? 16 : 12) * 32;
-                int stagger = (g_ > 256 && passes >= 2 * g_ * 4) ? (int)(((K + 31) / 32) * chunk_cycles * 90 / 100 / 64) : 0;
-                if (prod == 4)
-                    hipLaunchKernelGGL((vq_cells_kernel<4>), dim3((unsigned)g_), dim3(256), 0, s, z, codebook,
-                                       reinterpret_cast<const vqc_u32x4 *>(ws + L.cbP), ws + L.nrmP, ws + L.nrm, (long long *)idx,
-                                       out, sse_slabs, hrep, L.R, (int *)ws, K, H * W, P, stagger);
-                else
-                    hipLaunchKernelGGL((vq_cells_kernel<3>), dim3((unsigned)g_), dim3(256), 0, s, z, codebook,
-                                       reinterpret_cast<const vqc_u32x4 *>(ws + L.cbP), ws + L.nrmP, ws + L.nrm, (long long *)idx,
-                                       out, sse_slabs, hrep, L.R, (int *)ws, K, H * W, P, stagger);
-                continue;
-            }
-            switch (D) {
-            case 8: if (single) DM_VQ2(8, true, 3, 3) else DM_VQ2(8, false, 3, 3) break;
-            case 16:
-                if (single) DM_VQ2(16, true, 3, 3)
-                else DM_VQ2(16, false, 3, 3)
-                break;
-            case 32: if (single) DM_VQ2(32, true, 2, 2) else DM_VQ2(32, false, 2, 2) break;
-            default: if (single) DM_VQ2(64, true, 1, 1) else DM_VQ2(64, false, 1, 2) break;
-            }
-        }
-#undef DM_VQ2
-#undef DM_VQ2K
-        if (hist) hipLaunchKernelGGL(vq_hist_reduce_kernel, dim3((K + 63) / 64), dim3(1024), 0, s, hrep, (int *)ws, K, (int *)hist);
-        return dm_launch_status("dm_vq_forward");
-    }
-    if (!vq_dim_built(D)) {
-        long long g_ = (P + 63) / 64;
-        if (g_ > nslabs) g_ = nslabs;                            // one squared-error slab per workgroup (the rest were zeroed)
-        if (g_ > 4096) g_ = 4096;
-        const size_t lds = (size_t)D * 64 * sizeof(float);
-        static DmPerDeviceOnce any_attr;
-        if (lds > 48 * 1024 && any_attr.need()) {
-            const hipError_t ea = hipFuncSetAttribute((const void *)vq_forward_any_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 512 * 64 * 4);
-            if (ea != hipSuccess) { dm_set_error("dm_vq_forward: cannot reserve LDS: %s", hipGetErrorString(ea)); return (int)ea; }
-            any_attr.mark();
-        }
-        for (int rep = 0; rep < repeats; ++rep)
-            hipLaunchKernelGGL(vq_forward_any_kernel, dim3((unsigned)g_), dim3(64), lds, s, z, codebook, (long long *)idx, out,
-                               sse_slabs, hrep, L.R, K, D, H * W, P);
-        if (hist) hipLaunchKernelGGL(vq_hist_reduce_kernel, dim3((K + 63) / 64), dim3(1024), 0, s, hrep, (int *)ws, K, (int *)hist);
-        return dm_launch_status("dm_vq_forward");
-    }
-    const float *cbT = ws + L.cbT;
-#define DM_VQ_FWD(DD, PP_)                                                                                   \
-    hipLaunchKernelGGL((vq_forward_kernel<DD, PP_>), dim3((unsigned)((P + VQ_BLOCK * PP_ - 1) / (VQ_BLOCK * PP_))), \
-                       dim3(VQ_BLOCK), 0, s, z, codebook, cbT, (long long *)idx, out, sse_slabs, hrep, L.R, K, H * W, P)
-    for (int rep = 0; rep < repeats; ++rep) {
-        switch (D) {
-        case 8: DM_VQ_FWD(8, VQ_PP); break;
-        case 16: DM_VQ_FWD(16, VQ_PP); break;
-        case 32: DM_VQ_FWD(32, VQ_PP); break;
-        case 64: DM_VQ_FWD(64, 1); break;
-        default: DM_VQ_FWD(128, 1); break;        // VectorQuantizer's own default embedding_dim (vq_vae.py:35)
-        }
-    }
-#undef DM_VQ_FWD
-    if (hist) hipLaunchKernelGGL(vq_hist_reduce_kernel, dim3((K + 63) / 64), dim3(1024), 0, s, hrep, (int *)ws, K, (int *)hist);
-    return dm_launch_status("dm_vq_forward");
-}
-}  // namespace
-
 extern "C" int dm_vq_forward(const float *z, const float *codebook, int64_t *idx, float *out,
                              double *sse_slabs, int32_t *hist, int B, int D, int K, int H, int W,
                              void *workspace, size_t workspace_bytes, void *stream)
@@ -1983,8 +2014,7 @@ extern "C" int dm_vq_forward(const float *z, const float *codebook, int64_t *idx
 
 extern "C" int dm_vq_forward_join_supported(int D, int K, int H, int W)
 {
-    // (embedding_dim 16 = the reference's num_hiddens: at 32 / 64 the second prefetched tensor does not fit the registers)
-    return (K > 0 && K <= 64 && D == 16 && H > 0 && W > 0 && (H * W) % 64 == 0) ? 1 : 0;
+    return (H > 0 && W > 0 && vq_join_built(D, K, H * W)) ? 1 : 0;
 }
 
 extern "C" int dm_vq_forward_join(const float *rb, const float *h_in, const float *coef, float *z_out, const float *codebook,
@@ -2019,20 +2049,29 @@ extern "C" int dm_vq_finalize(const double *sse_slabs, int nslabs, const int32_t
     return dm_launch_status("dm_vq_finalize");
 }
 
+// The step's scalar launch, with or without the pairwise term (`tm`: its partial losses and weight)
+static int vq_loss_finalize_launch(const char *who, bool tm, const double *sse_slabs, int nslabs, const void *workspace, int K, int D,
+                                   int64_t positions, float commitment_cost, const double *loss_slabs, int nloss, int64_t count,
+                                   float weight_recon, float weight_commitment, const double *tm_slabs, int ntm, float weight_matching,
+                                   float *scalars_out, void *stream)
+{
+    DM_REQUIRE(sse_slabs && workspace && loss_slabs && scalars_out && (!tm || (tm_slabs && ntm > 0)) && nslabs > 0 && nloss > 0 &&
+                   K > 0 && D > 0 && positions > 0 && count > 0, "%s: bad argument", who);
+    const Vq2Layout L = vq2_layout(K, D);
+    const int *hrep = reinterpret_cast<const int *>(reinterpret_cast<const float *>(workspace) + L.hrep);
+    hipLaunchKernelGGL(vq_loss_finalize_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, sse_slabs, nslabs, hrep,
+                       reinterpret_cast<const int *>(workspace), K, (long long)positions, D, commitment_cost, loss_slabs, nloss,
+                       (long long)count, weight_recon, weight_commitment, scalars_out, tm_slabs, ntm, weight_matching);
+    return dm_launch_status(who);
+}
+
 extern "C" int dm_vq_loss_finalize(const double *sse_slabs, int nslabs, const void *workspace, int K, int D,
                                    int64_t positions, float commitment_cost, const double *loss_slabs, int nloss,
                                    int64_t count, float weight_recon, float weight_commitment, float *scalars_out,
                                    void *stream)
 {
-    DM_REQUIRE(sse_slabs && workspace && loss_slabs && scalars_out && nslabs > 0 && nloss > 0 && K > 0 && D > 0 &&
-                   positions > 0 && count > 0, "dm_vq_loss_finalize: bad argument");
-    const Vq2Layout L = vq2_layout(K, D);
-    const int *hrep = reinterpret_cast<const int *>(reinterpret_cast<const float *>(workspace) + L.hrep);
-    hipLaunchKernelGGL(vq_loss_finalize_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, sse_slabs, nslabs, hrep,
-                       reinterpret_cast<const int *>(workspace), K,
-                       (long long)positions, D, commitment_cost, loss_slabs, nloss, (long long)count, weight_recon,
-                       weight_commitment, scalars_out, (const double *)nullptr, 0, 0.f);
-    return dm_launch_status("dm_vq_loss_finalize");
+    return vq_loss_finalize_launch("dm_vq_loss_finalize", false, sse_slabs, nslabs, workspace, K, D, positions, commitment_cost,
+                                   loss_slabs, nloss, count, weight_recon, weight_commitment, nullptr, 0, 0.f, scalars_out, stream);
 }
 
 extern "C" int dm_vq_loss_finalize_tm(const double *sse_slabs, int nslabs, const void *workspace, int K, int D,
@@ -2040,15 +2079,9 @@ extern "C" int dm_vq_loss_finalize_tm(const double *sse_slabs, int nslabs, const
                                       int64_t count, float weight_recon, float weight_commitment, const double *tm_slabs,
                                       int ntm, float weight_matching, float *scalars_out, void *stream)
 {
-    DM_REQUIRE(sse_slabs && workspace && loss_slabs && scalars_out && tm_slabs && nslabs > 0 && nloss > 0 && ntm > 0 && K > 0 &&
-                   D > 0 && positions > 0 && count > 0, "dm_vq_loss_finalize_tm: bad argument");
-    const Vq2Layout L = vq2_layout(K, D);
-    const int *hrep = reinterpret_cast<const int *>(reinterpret_cast<const float *>(workspace) + L.hrep);
-    hipLaunchKernelGGL(vq_loss_finalize_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, sse_slabs, nslabs, hrep,
-                       reinterpret_cast<const int *>(workspace), K,
-                       (long long)positions, D, commitment_cost, loss_slabs, nloss, (long long)count, weight_recon,
-                       weight_commitment, scalars_out, tm_slabs, ntm, weight_matching);
-    return dm_launch_status("dm_vq_loss_finalize_tm");
+    return vq_loss_finalize_launch("dm_vq_loss_finalize_tm", true, sse_slabs, nslabs, workspace, K, D, positions, commitment_cost,
+                                   loss_slabs, nloss, count, weight_recon, weight_commitment, tm_slabs, ntm, weight_matching,
+                                   scalars_out, stream);
 }
 
 namespace {
@@ -2089,29 +2122,16 @@ int vq_backward_launch(const char *who, const float *z, const float *codebook, c
 #undef DM_VQ_BWD2
         return dm_launch_status(who);
     }
-#define DM_VQ_BWD(DD)                                                                                          \
-    if (lds > 48 * 1024) {                                                                                     \
-        const hipError_t ea = hipFuncSetAttribute((const void *)vq_backward_kernel<DD>,                        \
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);       \
-        if (ea != hipSuccess) {                                                                                \
-            dm_set_error("%s: cannot reserve %zu bytes of LDS: %s", who, (size_t)lds, hipGetErrorString(ea));  \
-            return (int)ea;                                                                                    \
-        }                                                                                                      \
-    }                                                                                                          \
-    hipLaunchKernelGGL(vq_backward_kernel<DD>, g3, dim3(VQ_BWD_BLOCK), lds, s, z, codebook,                    \
-                       (const long long *)idx, g_out, g_loss_dev, commitment_cost, dz, dw, dw_slabs, K, H * W, P, Kc)
     if (!vq_dim_built(D)) {
-        if (lds > 48 * 1024) {
-            const hipError_t ea = hipFuncSetAttribute((const void *)vq_backward_any_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (ea != hipSuccess) {
-                dm_set_error("%s: cannot reserve %zu bytes of LDS: %s", who, (size_t)lds, hipGetErrorString(ea));
-                return (int)ea;
-            }
-        }
+        if (const int rc = vq_reserve_lds(who, (const void *)vq_backward_any_kernel, lds, nullptr)) return rc;
         hipLaunchKernelGGL(vq_backward_any_kernel, g3, dim3(VQ_BWD_BLOCK), lds, s, z, codebook, (const long long *)idx, g_out,
                            g_loss_dev, commitment_cost, dz, dw, dw_slabs, K, D, H * W, P, Kc);
         return dm_launch_status(who);
     }
+#define DM_VQ_BWD(DD)                                                                                          \
+    if (const int rc = vq_reserve_lds(who, (const void *)vq_backward_kernel<DD>, lds, nullptr)) return rc;     \
+    hipLaunchKernelGGL(vq_backward_kernel<DD>, g3, dim3(VQ_BWD_BLOCK), lds, s, z, codebook,                    \
+                       (const long long *)idx, g_out, g_loss_dev, commitment_cost, dz, dw, dw_slabs, K, H * W, P, Kc)
     switch (D) {
     case 8: DM_VQ_BWD(8); break;
     case 16: DM_VQ_BWD(16); break;

@@ -263,6 +263,75 @@ def test_vq_mfma_near_ties_and_non_finite_values(ops, cvq, D, K, filt):
             assert nre >= near, (nre, near, P)
 
 
+def _vq_tie_case(D, K, H, W, B=2):
+    """Codebook with exact duplicate rows across the structures the exact re-check walks (the last code = the first; code 64 =
+    code 63: two 64-code chunks / lane strides; code 129 = code 7: two groups of 128), and latents of which a third lie
+    exactly on a duplicated code, a third on the bisector of two random codes, the rest random, one with a NaN, one with an
+    inf.  Returns (z, cb, dup, on): the positions (flat, (b, h, w) order) placed on a duplicated code and, per position, the
+    two codes (first, again) of that pair."""
+    g = np.random.default_rng(1000 * D + K + H * W)
+    cb = g.standard_normal((K, D)).astype(np.float32)
+    pairs = [(0, K - 1)] + ([(63, 64)] if K > 64 else []) + ([(7, 129)] if K > 129 else [])
+    for first, again in pairs:
+        cb[again] = cb[first]
+    pairs = [p for p in pairs if np.array_equal(cb[p[0]], cb[p[1]])]      # (K = 130: code 129 ends as code 7's copy, not code 0's)
+    z = g.standard_normal((B, D, H, W)).astype(np.float32)
+    zf = z.transpose(0, 2, 3, 1).reshape(-1, D)
+    P = zf.shape[0]
+    pick, n = g.permutation(P), P // 3
+    on = np.array(pairs)[g.integers(0, len(pairs), n)]
+    zf[pick[:n]] = cb[on[:, 0]]
+    a, b = g.integers(0, K, n), g.integers(0, K, n)
+    zf[pick[n:2 * n]] = 0.5 * (cb[a] + cb[b])
+    zf[pick[2 * n], 0] = np.nan
+    zf[pick[2 * n + 1], D - 1] = np.inf
+    z = np.ascontiguousarray(zf.reshape(B, H, W, D).transpose(0, 3, 1, 2))
+    return z, cb, pick[:n], on
+
+
+@pytest.mark.parametrize("D,K,H,W", [(16, 5, 8, 8),        # fewer codes than lanes
+                                     (8, 70, 8, 8),        # embedding_dim 8: the f32 filter only
+                                     (16, 200, 8, 8),      # streamed re-check (64 positions per sample: not the cell kernel)
+                                     (32, 130, 8, 8),      # embedding_dim 32 across groups
+                                     (16, 130, 8, 16),     # vq_cells_kernel, two codes in the last group of 128
+                                     (16, 200, 8, 16)])    # vq_cells_kernel, ragged last group
+def test_vq_exact_recheck_ties_on_every_route(ops, cvq, D, K, H, W):
+    """Exact ties where the lanes, chunks, cells and groups of the exact re-check meet (the per-lane scans and the wave-wide
+    first minimum of vq_forward_mfma_kernel and vq_cells_kernel): the smaller code wins on every route.  Indices,
+    straight-through values and counters bit-equal to DM_VQ_EXACT and to the C oracle (`out` against the oracle: the same
+    bits wherever the oracle's value is finite, and non-finite in the same places -- the position with an inf yields
+    inf - inf, whose NaN sign is the host's resp. the GPU's own); every position on a duplicated code went through the
+    re-check -- except, where vq_cells_kernel runs, a pair inside one cell of 8 consecutive codes, which the cell's own
+    exact evaluation settles (the rule of test_vq_mfma_near_ties_and_non_finite_values)."""
+    z, cb, dup, on = _vq_tie_case(D, K, H, W)
+    idx_ref = _c_oracle_idx(cvq, z, cb)
+    q = cb[idx_ref].transpose(0, 3, 1, 2)
+    with np.errstate(invalid="ignore"):
+        out_ref = z + (q - z)
+    fin = np.isfinite(out_ref)
+    hist_ref = np.bincount(idx_ref.ravel(), minlength=K)
+    # the construction: a position on a duplicated code is the earlier code's; pairs inside one cell of 8 consecutive codes
+    assert np.array_equal(idx_ref.ravel()[dup], on[:, 0])
+    in_one_cell = int((on[:, 0] // 8 == on[:, 1] // 8).sum())
+    zd, cbd = torch.from_numpy(z).to(DEV), torch.from_numpy(cb).to(DEV)
+    idx_e, out_e, _, hist_e = ops.vq_forward(zd, cbd, variant=DM_VQ_EXACT)
+    variants = [DM_VQ_AUTO, DM_VQ_EXACT] + ([DM_VQ_MFMA] if (H * W) % 64 == 0 and D in (8, 16, 32, 64) else []) + (
+        [DM_VQ_BF16] if (H * W) % 64 == 0 and D in (16, 32, 64) else [])
+    for variant in variants:
+        idx, out, _, hist, nre = ops.vq_forward(zd, cbd, variant=variant, want_rechecked=True)
+        assert np.array_equal(idx.cpu().numpy(), idx_ref), variant
+        got = out.cpu().numpy()
+        assert np.array_equal(np.isfinite(got), fin) and np.array_equal(got.view(np.int32)[fin], out_ref.view(np.int32)[fin]), variant
+        assert np.array_equal(hist.cpu().numpy(), hist_ref), variant
+        assert torch.equal(idx, idx_e) and torch.equal(out.view(torch.int32), out_e.view(torch.int32)), variant
+        assert torch.equal(hist, hist_e), variant
+        if variant != DM_VQ_EXACT:
+            # vq_cells_kernel: the bf16-split filter (AUTO takes it) at embedding_dim 16, 64 < K <= 4096, grids of 128 positions
+            cells = variant != DM_VQ_MFMA and D == 16 and 64 < K <= 4096 and (H * W) % 128 == 0
+            must = len(dup) - (in_one_cell if cells else 0)
+            assert must > 0 and int(nre.cpu()) >= must, (variant, int(nre.cpu()), must)
+
+
 @pytest.mark.parametrize("filt", [pytest.param(DM_VQ_MFMA, id="f32"), pytest.param(DM_VQ_BF16, id="bf16split")])
 def test_vq_mfma_large_sweep(ops, cvq, filt):
     """4 M random positions at the headline shape (K = 64, D = 16, 16 x 16 latents): the MFMA kernel equals the exact
