@@ -19,6 +19,7 @@
 //                      lane interleave in registers into 8 consecutive output columns
 // plus the (sum dx, sum dx * x) slabs of the BatchNorm below.
 #include "dm_common.h"
+#include "tile.h"
 
 namespace {
 
@@ -69,31 +70,28 @@ void conv4x4s2_bwd_kernel(Operand dy, const float *__restrict__ x, const float *
     // plane qp = e * NW + wave (channel qp >> 2, rows 8 (qp & 3) + (lane >> 3), columns 4 (lane & 7) ..)
     const int dq = (lane >> 2) * 16 + 4 * (lane & 3), dl = ((lane >> 2) + 1) * RS + 4 + 4 * (lane & 3);
     const int tq = (lane >> 3) * 32 + 4 * (lane & 7), tl = ((lane >> 3) + 1) * RST + 4 + 4 * (lane & 7);
+    // Every load and store of the patch loop is unconditional: the next patch's loads leave through descriptors that are empty
+    // when there is none (tile.h; the second gradient tensor's also when there is no such tensor), so the waits of the commit
+    // and of the data gradient's epilogue are counted and the stores of dx stay in flight behind them.
     f32x4 rv[2], ru[2], rx[8];
-    auto issue = [&](int b) {
-        const long long db = (long long)b * C * 256, xb = (long long)b * C * 1024;
+    auto issue = [&](int b, bool live) {
+        const __amdgpu_buffer_rsrc_t r0 = tile_rsrc(dy.p0, (long long)b * C * 256, C * 256, live);
+        const __amdgpu_buffer_rsrc_t r1 = tile_rsrc(dy.p1, (long long)b * C * 256, C * 256, live && two);
+        const __amdgpu_buffer_rsrc_t rX = tile_rsrc(x, (long long)b * C * 1024, C * 1024, live);
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-            const long long off = db + (long long)(e * NW + wave) * 256 + dq;
-            rv[e] = *reinterpret_cast<const f32x4 *>(dy.p0 + off);
-            if (two) ru[e] = *reinterpret_cast<const f32x4 *>(dy.p1 + off);
+            const int off = ((e * NW + wave) * 256 + dq) * 4;
+            rv[e] = tile_load4(r0, off);
+            ru[e] = tile_load4(r1, off);
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int qp = e * NW + wave;
-            rx[e] = *reinterpret_cast<const f32x4 *>(x + xb + (long long)(qp >> 2) * 1024 + (qp & 3) * 256 + tq);
+            rx[e] = tile_load4(rX, ((qp >> 2) * 1024 + (qp & 3) * 256 + tq) * 4);
         }
+        __builtin_amdgcn_sched_barrier(0);                       // (the requests leave here, in this order, on every path)
     };
-    int tile = blockIdx.x;
-    if (tile < ntiles) issue(tile);
-    __syncthreads();                                             // zero fill, weights and coefficient table complete
-
-    // weight-gradient B column of this lane inside N tile t = ci: tap (ky, kx) = (m >> 2, m & 3):
-    // T[ci][2y + ky - 1][2x + kx - 1] <-> sT[ci*PST + (2y + ky)*RST + 2x + kx + 3], x = 4 s + kq
-    const int wb = (m >> 2) * RST + (m & 3) + 3 + 2 * kq;
-
-    while (tile < ntiles) {
-        if (tile != (int)blockIdx.x) __syncthreads();            // the previous patch has been consumed
+    auto commit = [&]() {
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
             f32x4 v = dc0[e] * rv[e] + dc2[e];
@@ -106,10 +104,36 @@ void conv4x4s2_bwd_kernel(Operand dy, const float *__restrict__ x, const float *
             const f32x4 v = s_tc[ci][0] * rx[e] + s_tc[ci][1];
             *reinterpret_cast<f32x4 *>(sT + ci * PST + (qp & 3) * 8 * RST + tl) = dm_relu4(v);
         }
-        __syncthreads();
+    };
+    // The statistics' second factor (the raw input) for this lane's 8 output columns of a phase row is requested ONE ROW AHEAD,
+    // the first row's of a patch during the last row of the patch before it (the first patch's: here, ahead of its staging
+    // loads), so the wait for it leaves the stores of dx issued since, and the request after it, in flight.
+    const int qoff = (m * 1024 + 8 * kq) * 4;
+    f32x4 qe[2], qo[2];                                          // of an even row u (pu = 0) / of an odd one
+    auto request_q = [&](f32x4 (&q)[2], int b, bool live, int u) {
+        const __amdgpu_buffer_rsrc_t rQ = tile_rsrc(x, (long long)b * C * 1024, C * 1024, live);
+        q[0] = tile_load4(rQ, qoff + u * 128); q[1] = tile_load4(rQ, qoff + u * 128 + 16);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    int tile = blockIdx.x;
+    const bool any = tile < ntiles;
+    request_q(qe, tile, any, 2 * wave);
+    issue(tile, any);
+    __syncthreads();                                             // zero fill, weights and coefficient table complete
+
+    // weight-gradient B column of this lane inside N tile t = ci: tap (ky, kx) = (m >> 2, m & 3):
+    // T[ci][2y + ky - 1][2x + kx - 1] <-> sT[ci*PST + (2y + ky)*RST + 2x + kx + 3], x = 4 s + kq
+    const int wb = (m >> 2) * RST + (m & 3) + 3 + 2 * kq;
+
+    // The commit of patch i + 1 closes the loop body of patch i (the first one: ahead of the loop): the only way to it leads
+    // through patch i's requests and stores, so its waits are counted.  (At the head of the loop it is also reached from the
+    // prologue, where no store follows the requests, and hipcc waits for the smaller count of the two paths: vmcnt(0).)
+    if (any) commit();
+    while (any) {
+        __syncthreads();                                         // the patch images are complete
         const int b = tile;
         tile += gridDim.x;
-        if (tile < ntiles) issue(tile);                          // in flight during the products below
+        issue(tile, tile < ntiles);                              // in flight during the products below
 
         // ---- weight gradient: rows y = wave, wave + 8; four positions per step
         // (the row loops of both products stay rolled: unrolled, hipcc hoists the LDS operands of several rows and spills)
@@ -125,13 +149,9 @@ void conv4x4s2_bwd_kernel(Operand dy, const float *__restrict__ x, const float *
             }
         }
         // ---- data gradient: phase rows (Y, pu), Y = wave, wave + 8; both column phases of a row in flight
-        const float *xq = x + (long long)b * C * 1024 + (long long)m * 1024 + 8 * kq;
         float *oq = dx + (long long)b * C * 1024 + (long long)m * 1024 + 8 * kq;
-#pragma unroll 1
-        for (int it = 0; it < 4; ++it) {
-            const int Y = wave + NW * (it >> 1), pu = it & 1, u = 2 * Y + pu;
-            // the statistics' second factor (the raw input) for this lane's 8 output columns: requested now
-            const f32x4 q0 = *reinterpret_cast<const f32x4 *>(xq + u * 32), q1 = *reinterpret_cast<const f32x4 *>(xq + u * 32 + 4);
+        auto phase_row = [&](int Y, int pu, const f32x4 (&q)[2]) {
+            const int u = 2 * Y + pu;
             f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
             for (int s = 0; s < 16; ++s) {                       // (a, b, cg)
@@ -152,9 +172,24 @@ void conv4x4s2_bwd_kernel(Operand dy, const float *__restrict__ x, const float *
             *reinterpret_cast<f32x4 *>(oq + u * 32) = o0;
             *reinterpret_cast<f32x4 *>(oq + u * 32 + 4) = o1;
             s1 += (double)(((o0.x + o0.y) + (o0.z + o0.w)) + ((o1.x + o1.y) + (o1.z + o1.w)));
-            s2 += (double)(((o0.x * q0.x + o0.y * q0.y) + (o0.z * q0.z + o0.w * q0.w)) +
-                           ((o1.x * q1.x + o1.y * q1.y) + (o1.z * q1.z + o1.w * q1.w)));
+            s2 += (double)(((o0.x * q[0].x + o0.y * q[0].y) + (o0.z * q[0].z + o0.w * q[0].w)) +
+                           ((o1.x * q[1].x + o1.y * q[1].y) + (o1.z * q[1].z + o1.w * q[1].w)));
+        };
+        // (two rows per turn, each with registers of its own for q: rotating ONE pair through a copy at the end of a row would
+        //  wait for the next row's request there, and with it for every store but the row's own)
+#pragma unroll 1
+        for (int rr = 0; rr < 2; ++rr) {
+            const int Y = wave + NW * rr;
+            request_q(qo, b, true, 2 * Y + 1);
+            phase_row(Y, 0, qe);
+            __builtin_amdgcn_sched_barrier(0);
+            // the next turn's even row; in the last turn: the next patch's first one (no next patch: an empty descriptor)
+            request_q(qe, rr == 0 ? b : tile, rr == 0 || tile < ntiles, rr == 0 ? 2 * (Y + NW) : 2 * wave);
+            phase_row(Y, 1, qo);
         }
+        if (tile >= ntiles) break;
+        __syncthreads();                                         // this patch has been consumed
+        commit();
     }
 
     // ---- statistics slab: the four kq groups of a channel, then the waves in wave order

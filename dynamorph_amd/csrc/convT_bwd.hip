@@ -23,6 +23,7 @@
 //     weight gradient  M = (ci, sy) with ky = 2 sy + py, summed over position rows Y = y + sy: A = S shifted by sy rows,
 //                      N = (co, py, kx) = CO / 2 tiles -- half the instructions (the y-shift of wgrad_ys_kernel)
 #include "dm_common.h"
+#include "tile.h"
 
 namespace {
 
@@ -78,7 +79,11 @@ void convT_bwd_kernel(const float *__restrict__ S, const float *__restrict__ G, 
         }
     }
 
-    // staging: element e of thread tid = float4 number e * 256 + tid of the tile image (G: [co][row][col4]; S: [ci][row][col4])
+    // staging: element e of thread tid = float4 number e * 256 + tid of the tile image (G: [co][row][col4]; S: [ci][row][col4]).
+    // A slot past the G image (the tail of the last pass) reads 0 and is written to plane 0's padding, which nothing reads:
+    // the commit then has no lane predicate either (a predicated ds_write leaves its load's wait inside a branch, and hipcc
+    // would wait for that load again -- draining the stores behind it -- before the next issue may overwrite its register).
+    static_assert(Geo::NS4 % DM_BLOCK == 0 && PSG - Geo::PSG_RAW >= 4, "whole passes over S; a float4 of padding behind G's plane 0");
     int g_lds[EG], g_row[EG], g_col[EG], g_ch[EG];
 #pragma unroll
     for (int e = 0; e < EG; ++e) {
@@ -86,37 +91,41 @@ void convT_bwd_kernel(const float *__restrict__ S, const float *__restrict__ G, 
         const int co = i / (GROWS * C4G), rem = i - co * (GROWS * C4G), lr = rem / C4G, c4 = rem - lr * C4G;
         g_ch[e] = i < Geo::NG4 ? co : -1;
         g_row[e] = lr; g_col[e] = 4 * c4;
-        g_lds[e] = co * PSG + lr * RSG + 4 * c4;
+        g_lds[e] = i < Geo::NG4 ? co * PSG + lr * RSG + 4 * c4 : Geo::PSG_RAW;
     }
     int s_lds[ES], s_off[ES];
-    bool s_ok[ES];
 #pragma unroll
     for (int e = 0; e < ES; ++e) {
         const int i = e * DM_BLOCK + threadIdx.x;
         const int ci = i / (CT_TH * (TW / 4)), rem = i - ci * (CT_TH * (TW / 4)), lr = rem / (TW / 4), c4 = rem - lr * (TW / 4);
-        s_ok[e] = i < Geo::NS4;
         s_lds[e] = ci * PSS + lr * TW + 4 * c4;
-        s_off[e] = (ci * H + lr) * W + 4 * c4;
+        s_off[e] = ((ci * H + lr) * W + 4 * c4) * 4;             // bytes from the tile's first element
     }
     f32x4 rg[EG], rs[ES];
     auto coords = [&](int t, int &b, int &y0, int &x0) {
         x0 = (t % tiles_x) * TW; t /= tiles_x;
         y0 = (t % tiles_y) * CT_TH; b = t / tiles_y;
     };
-    auto issue = [&](int t) {
+    // every load unconditional, through the sample's descriptors (tile.h): no next tile = empty descriptors; a halo element
+    // outside the image, a slot past the G image = an offset no descriptor reaches.  All of them read 0.
+    auto issue = [&](int t, bool live) {
         int b, y0, x0;
         coords(t, b, y0, x0);
-        const float *gb = G + (long long)b * CO * OH * OW;
-        const float *sb = S + (long long)b * CI * H * W + (long long)y0 * W + x0;
+        const __amdgpu_buffer_rsrc_t rG = tile_rsrc(G, (long long)b * CO * OH * OW, CO * OH * OW, live);
+        const __amdgpu_buffer_rsrc_t rS = tile_rsrc(S, (long long)b * CI * H * W, CI * H * W, live);
+        const int so = (y0 * W + x0) * 4;
 #pragma unroll
         for (int e = 0; e < EG; ++e) {
             const int gr = 2 * y0 - 1 + g_row[e], gc = 2 * x0 - 4 + g_col[e];
             const bool ok = g_ch[e] >= 0 && (unsigned)gr < (unsigned)OH && (unsigned)gc < (unsigned)OW;
-            rg[e] = ok ? *reinterpret_cast<const f32x4 *>(gb + ((long long)g_ch[e] * OH + gr) * OW + gc) : (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
+            rg[e] = tile_load4(rG, ok ? ((g_ch[e] * OH + gr) * OW + gc) * 4 : DM_TILE_VOFF_NONE);
+            __builtin_amdgcn_sched_barrier(0);                   // the requests leave in this order, before the loop and inside it:
+        }                                                        // the commit's counted waits are the same on both paths
 #pragma unroll
-        for (int e = 0; e < ES; ++e)
-            rs[e] = s_ok[e] ? *reinterpret_cast<const f32x4 *>(sb + s_off[e]) : (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int e = 0; e < ES; ++e) {
+            rs[e] = tile_load4(rS, s_off[e] + so);
+            __builtin_amdgcn_sched_barrier(0);
+        }
     };
 
     f32x4 wacc[NWT];
@@ -141,21 +150,25 @@ void convT_bwd_kernel(const float *__restrict__ S, const float *__restrict__ G, 
         }
     }
 
+    auto commit = [&]() {
+#pragma unroll
+        for (int e = 0; e < EG; ++e) *reinterpret_cast<f32x4 *>(sG + g_lds[e]) = rg[e];
+#pragma unroll
+        for (int e = 0; e < ES; ++e) *reinterpret_cast<f32x4 *>(sS + s_lds[e]) = rs[e];
+    };
+    // The commit of tile i + 1 closes the loop body of tile i (the first one: ahead of the loop), so the only way to it leads
+    // through tile i's requests and stores and every wait in it is counted.  At the head of the loop it would also be reached
+    // from the prologue, where no store follows the requests, and hipcc waits for the smaller count of the two: vmcnt(0).
     int tile = blockIdx.x;
-    if (tile < ntiles) issue(tile);
-    while (tile < ntiles) {
-        __syncthreads();                                         // the previous tile has been consumed
-#pragma unroll
-        for (int e = 0; e < EG; ++e)
-            if (g_ch[e] >= 0) *reinterpret_cast<f32x4 *>(sG + g_lds[e]) = rg[e];
-#pragma unroll
-        for (int e = 0; e < ES; ++e)
-            if (s_ok[e]) *reinterpret_cast<f32x4 *>(sS + s_lds[e]) = rs[e];
-        __syncthreads();
+    const bool any = tile < ntiles;
+    issue(tile, any);
+    if (any) commit();
+    while (any) {
+        __syncthreads();                                         // the tile image is complete
         int b, y0, x0;
         coords(tile, b, y0, x0);
         tile += gridDim.x;
-        if (tile < ntiles) issue(tile);                          // in flight during the products below
+        issue(tile, tile < ntiles);                              // in flight during the products below
 
         // ---- weight gradient, four positions per step
         if constexpr (HALF) {
@@ -213,6 +226,9 @@ void convT_bwd_kernel(const float *__restrict__ S, const float *__restrict__ G, 
                 s1 += (double)((acc.x + acc.y) + (acc.z + acc.w));
             }
         }
+        if (tile >= ntiles) break;
+        __syncthreads();                                         // this tile has been consumed
+        commit();
     }
 
     // ---- channel sums of the input gradient (the previous layer's bias gradient): kq groups, then waves in wave order

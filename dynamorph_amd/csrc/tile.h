@@ -232,3 +232,23 @@ struct TileStage {
         }
     }
 };
+
+// ---- unconditional 16-byte loads for the persistent backward kernels (convT_bwd, conv3x3_bwd, conv4x4s2_patch) --------------
+// The same discipline as the forward family's epilogue (conv_mfma.hip): the next tile's loads leave through a descriptor of the
+// sample they belong to -- EMPTY when there is no next tile, so every lane's load then returns 0 without touching memory -- and
+// an element outside the image carries an offset no descriptor reaches.  No load sits behind a branch or a lane predicate, so
+// the number of vector-memory operations between a request and its use is static and hipcc waits with a COUNTED vmcnt: the
+// stores of the tile just finished, which are younger than the next tile's loads, stay in flight across the commit.
+constexpr int DM_TILE_VOFF_NONE = (int)0x80000000u;    // (unsigned) past every descriptor: samples are < 2^31 bytes
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const float *base, long long first_elem, int elems, bool live)
+{
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base) + (live ? first_elem : 0), 0, live ? elems * 4 : 0, 0x00020000);
+}
+__device__ __forceinline__ f32x4 tile_load4(__amdgpu_buffer_rsrc_t r, int byte_off)
+{
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0));
+}
+// A use of a staged value on the way OUT of the tile loop.  hipcc sinks a load whose only use sits in one later branch -- the
+// commit of the next tile, which the last tile skips -- into that branch, to the far side of the products; with a use on the
+// other way as well the request stays where it is written.  (No instruction; once per workgroup, the loop is over.)
+__device__ __forceinline__ void tile_keep(f32x4 v) { asm volatile("" ::"v"(v)); }
