@@ -213,12 +213,9 @@ extern "C" int dm_conv1x1_bwd_fused(const dm_operand *dy, const float *x, const 
     DM_REQUIRE(dy && dy->p0 && x && xcoef && w && dx && stats && wslabs, "dm_conv1x1_bwd_fused: NULL pointer");
     DM_REQUIRE(B > 0 && (conv1x1_bwd_shape(CD, CX, H, W) || dm_stream_conv1x1_bwd_shape(CD, CX, H, W)),
                "dm_conv1x1_bwd_fused: shape %d -> %d channels on %dx%d not built", CX, CD, H, W);
-    DM_REQUIRE(dy->mode == DM_LOAD_IDENT || dy->mode == DM_LOAD_AFFINE2, "dm_conv1x1_bwd_fused: dy operand must be IDENT or AFFINE2");
-    DM_REQUIRE(dy->mode == DM_LOAD_IDENT || dy->coef, "dm_conv1x1_bwd_fused: AFFINE2 needs coefficients");
-    DM_REQUIRE(dy->coef_bstride == 0 && !dy->ones_channel, "dm_conv1x1_bwd_fused: shared coefficients only");
+    Operand d;
+    if (dm_bwd_dy_operand(dy, "dm_conv1x1_bwd_fused", &d)) return -1;
     DM_REQUIRE((long long)B * CX * H * W < (1LL << 31), "dm_conv1x1_bwd_fused: tensor too large");
-    Operand d = to_dev(dy);
-    if (d.mode == DM_LOAD_IDENT) { d.coef = nullptr; d.p1 = nullptr; }
     if (dm_stream_conv1x1_bwd_shape(CD, CX, H, W)) {
         dm_stream_conv1x1_bwd(d, x, xcoef, w, dx, stats, wslabs, B, H, W, (hipStream_t)stream);
         return dm_launch_status("dm_conv1x1_bwd_fused");

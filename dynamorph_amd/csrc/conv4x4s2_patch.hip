@@ -53,14 +53,9 @@ void conv4x4s2_bwd_kernel(Operand dy, const float *__restrict__ x, const float *
     }
     if (threadIdx.x < C) { s_tc[threadIdx.x][0] = xcoef[threadIdx.x * 4]; s_tc[threadIdx.x][1] = xcoef[threadIdx.x * 4 + 2]; }
     // BatchNorm backward of the output gradient for the planes this wave stages (2 e + ..: planes e * NW + wave)
-    float dc0[2], dc1[2], dc2[2];
+    DyCoef dc[2];
 #pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        const int c = e * NW + wave;
-        dc0[e] = dy.coef ? dy.coef[c * 4] : 1.f;
-        dc1[e] = (dy.coef && two) ? dy.coef[c * 4 + 1] : 0.f;
-        dc2[e] = dy.coef ? dy.coef[c * 4 + 2] : 0.f;
-    }
+    for (int e = 0; e < 2; ++e) dc[e] = dy_coef(dy.coef, two, e * NW + wave);
     f32x4 wacc[C];
 #pragma unroll
     for (int t = 0; t < C; ++t) wacc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -93,11 +88,7 @@ void conv4x4s2_bwd_kernel(Operand dy, const float *__restrict__ x, const float *
     };
     auto commit = [&]() {
 #pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            f32x4 v = dc0[e] * rv[e] + dc2[e];
-            if (two) v += dc1[e] * ru[e];
-            *reinterpret_cast<f32x4 *>(sD + (e * NW + wave) * PS + dl) = v;
-        }
+        for (int e = 0; e < 2; ++e) *reinterpret_cast<f32x4 *>(sD + (e * NW + wave) * PS + dl) = dy_commit(dc[e], rv[e], ru[e], two);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int qp = e * NW + wave, ci = qp >> 2;
@@ -164,16 +155,13 @@ void conv4x4s2_bwd_kernel(Operand dy, const float *__restrict__ x, const float *
                 }
             }
             // lane (m = ci, kq): X = 4 kq .. 4 kq + 3 -> columns v = 8 kq .. 8 kq + 7 of row u
-            f32x4 o0 = {acc[0].x, acc[1].x, acc[0].y, acc[1].y}, o1 = {acc[0].z, acc[1].z, acc[0].w, acc[1].w};
             const float *pt = sT + m * PST + (u + 1) * RST + 4 + 8 * kq;
-            const f32x4 t0 = *reinterpret_cast<const f32x4 *>(pt), t1 = *reinterpret_cast<const f32x4 *>(pt + 4);
-            o0.x = t0.x > 0.f ? o0.x : 0.f; o0.y = t0.y > 0.f ? o0.y : 0.f; o0.z = t0.z > 0.f ? o0.z : 0.f; o0.w = t0.w > 0.f ? o0.w : 0.f;
-            o1.x = t1.x > 0.f ? o1.x : 0.f; o1.y = t1.y > 0.f ? o1.y : 0.f; o1.z = t1.z > 0.f ? o1.z : 0.f; o1.w = t1.w > 0.f ? o1.w : 0.f;
+            const f32x4 o0 = relu_gate4(*reinterpret_cast<const f32x4 *>(pt), (f32x4){acc[0].x, acc[1].x, acc[0].y, acc[1].y});
+            const f32x4 o1 = relu_gate4(*reinterpret_cast<const f32x4 *>(pt + 4), (f32x4){acc[0].z, acc[1].z, acc[0].w, acc[1].w});
             *reinterpret_cast<f32x4 *>(oq + u * 32) = o0;
             *reinterpret_cast<f32x4 *>(oq + u * 32 + 4) = o1;
-            s1 += (double)(((o0.x + o0.y) + (o0.z + o0.w)) + ((o1.x + o1.y) + (o1.z + o1.w)));
-            s2 += (double)(((o0.x * q[0].x + o0.y * q[0].y) + (o0.z * q[0].z + o0.w * q[0].w)) +
-                           ((o1.x * q[1].x + o1.y * q[1].y) + (o1.z * q[1].z + o1.w * q[1].w)));
+            s1 += (double)(pair_sum4(o0) + pair_sum4(o1));
+            s2 += (double)(pair_dot4(o0, q[0]) + pair_dot4(o1, q[1]));
         };
         // (two rows per turn, each with registers of its own for q: rotating ONE pair through a copy at the end of a row would
         //  wait for the next row's request there, and with it for every store but the row's own)
@@ -194,12 +182,7 @@ void conv4x4s2_bwd_kernel(Operand dy, const float *__restrict__ x, const float *
 
     // ---- statistics slab: the four kq groups of a channel, then the waves in wave order
     __syncthreads();
-    {
-        double a = s1, c = s2;
-        a += __shfl_xor(a, 16, 64); c += __shfl_xor(c, 16, 64);
-        a += __shfl_xor(a, 32, 64); c += __shfl_xor(c, 32, 64);
-        if (lane < 16) { s_stat[wave][lane][0] = a; s_stat[wave][lane][1] = c; }
-    }
+    stat_fold<C, true>(&s_stat[0][0][0], wave, lane, s1, s2);
     // ---- weight-gradient slab: the eight waves' accumulators through LDS in wave order, 8 input channels at a time
     float *red = lds4;                                           // [wave][8][64 lanes][4] = 16 384 floats (the images are free now)
     static_assert(NW * 8 * 256 <= 16 * S2_PS + 16 * S2_PST, "the slab combine reuses the tile images");
@@ -209,13 +192,7 @@ void conv4x4s2_bwd_kernel(Operand dy, const float *__restrict__ x, const float *
 #pragma unroll
         for (int t = 0; t < 8; ++t) *reinterpret_cast<f32x4 *>(red + ((wave * 8 + t) * 64 + lane) * 4) = wacc[8 * half + t];
         __syncthreads();
-        if (half == 0 && stats && threadIdx.x < C) {
-            double ta = 0.0, tc = 0.0;
-#pragma unroll
-            for (int wv = 0; wv < NW; ++wv) { ta += s_stat[wv][threadIdx.x][0]; tc += s_stat[wv][threadIdx.x][1]; }
-            stats[((long long)blockIdx.x * C + threadIdx.x) * 2 + 0] = ta;
-            stats[((long long)blockIdx.x * C + threadIdx.x) * 2 + 1] = tc;
-        }
+        if (half == 0 && stats) stat_slab<NW, C, true>(&s_stat[0][0][0], stats + (long long)blockIdx.x * C * 2);
         // element e = dW[co][ci = 8 half + t][tap]: accumulator row co = 4 kq + r of lane (m = tap, kq) in N tile t
         for (int e = threadIdx.x; e < 16 * 8 * 16; e += S2_NTH) {
             const int co = e >> 7, t = (e >> 4) & 7, tap = e & 15;
@@ -246,21 +223,10 @@ extern "C" int dm_conv4x4s2_bwd_fused(const dm_operand *dy, const float *x, cons
     DM_REQUIRE(dy && dy->p0 && x && xcoef && w && dx && stats && wslabs, "dm_conv4x4s2_bwd_fused: NULL pointer");
     DM_REQUIRE(B > 0 && conv4x4s2_bwd_shape(CD, CX, H, W), "dm_conv4x4s2_bwd_fused: shape %d -> %d channels, %dx%d output grid not built",
                CX, CD, H, W);
-    DM_REQUIRE(dy->mode == DM_LOAD_IDENT || dy->mode == DM_LOAD_AFFINE2, "dm_conv4x4s2_bwd_fused: dy operand must be IDENT or AFFINE2");
-    DM_REQUIRE(dy->mode == DM_LOAD_IDENT || dy->coef, "dm_conv4x4s2_bwd_fused: AFFINE2 needs coefficients");
-    DM_REQUIRE(dy->coef_bstride == 0 && !dy->ones_channel, "dm_conv4x4s2_bwd_fused: shared coefficients only");
-    Operand d = to_dev(dy);
-    if (d.mode == DM_LOAD_IDENT) { d.coef = nullptr; d.p1 = nullptr; }
+    Operand d;
+    if (dm_bwd_dy_operand(dy, "dm_conv4x4s2_bwd_fused", &d)) return -1;
     static DmPerDeviceOnce attr_done;
-    if (attr_done.need()) {
-        const hipError_t e = hipFuncSetAttribute((const void *)conv4x4s2_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)S2_LDS_BYTES);
-        if (e != hipSuccess) {
-            dm_set_error("dm_conv4x4s2_bwd_fused: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            return (int)e;
-        }
-        attr_done.mark();
-    }
+    if (const int rc = dm_reserve_lds(attr_done, {{(const void *)conv4x4s2_bwd_kernel, S2_LDS_BYTES}}, "dm_conv4x4s2_bwd_fused")) return rc;
     const int grid = dm_conv4x4s2_bwd_fused_num_blocks(B, CD, CX, H, W);
     hipLaunchKernelGGL(conv4x4s2_bwd_kernel, dim3(grid), dim3(S2_NTH), S2_LDS_BYTES, (hipStream_t)stream, d, x, xcoef, w, dx, stats,
                        wslabs, B);
@@ -365,42 +331,27 @@ void conv4x4s2_patch_forward_kernel(Operand in, WeightView wv, const float *__re
             f32x4 v = acc[j] + bco;
             if (relu_out) v = dm_relu4(v);
             *reinterpret_cast<f32x4 *>(ob + (wave + NW * j) * 16) = v;
-            p1 += (double)((v.x + v.y) + (v.z + v.w));
-            p2 += (double)((v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w));
+            p1 += (double)pair_sum4(v);
+            p2 += (double)pair_dot4(v, v);
         }
         if (stats && per_tile) {
             // per-sample statistics: this patch's sums to its first slab, zeros to its second
-            p1 += __shfl_xor(p1, 16, 64); p2 += __shfl_xor(p2, 16, 64);
-            p1 += __shfl_xor(p1, 32, 64); p2 += __shfl_xor(p2, 32, 64);
-            if (lane < 16) { s_stat[wave][lane][0] = p1; s_stat[wave][lane][1] = p2; }
+            stat_fold<C, true>(&s_stat[0][0][0], wave, lane, p1, p2);
             __syncthreads();
-            if (threadIdx.x < C) {
-                double ta = 0.0, tc = 0.0;
-#pragma unroll
-                for (int w8 = 0; w8 < NW; ++w8) { ta += s_stat[w8][threadIdx.x][0]; tc += s_stat[w8][threadIdx.x][1]; }
-                const int spp = nslabs / ntiles;                 // slabs the caller holds per patch
-                double *dst = stats + ((long long)b * spp * C + threadIdx.x) * 2;
-                dst[0] = ta; dst[1] = tc;
-                for (int k = 1; k < spp; ++k) { dst[(long long)k * C * 2] = 0.0; dst[(long long)k * C * 2 + 1] = 0.0; }
-            }
+            const int spp = nslabs / ntiles;                     // slabs the caller holds per patch
+            double *dst = stats + (long long)b * spp * C * 2;
+            stat_slab<NW, C, true>(&s_stat[0][0][0], dst);
+            if (threadIdx.x < C)
+                for (int k = 1; k < spp; ++k) { dst[((long long)k * C + threadIdx.x) * 2] = 0.0; dst[((long long)k * C + threadIdx.x) * 2 + 1] = 0.0; }
         } else {
             s1 += p1; s2 += p2;
         }
     }
     if (stats && !per_tile) {
         __syncthreads();
-        double a = s1, c = s2;
-        a += __shfl_xor(a, 16, 64); c += __shfl_xor(c, 16, 64);
-        a += __shfl_xor(a, 32, 64); c += __shfl_xor(c, 32, 64);
-        if (lane < 16) { s_stat[wave][lane][0] = a; s_stat[wave][lane][1] = c; }
+        stat_fold<C, true>(&s_stat[0][0][0], wave, lane, s1, s2);
         __syncthreads();
-        if (threadIdx.x < C) {
-            double ta = 0.0, tc = 0.0;
-#pragma unroll
-            for (int w8 = 0; w8 < NW; ++w8) { ta += s_stat[w8][threadIdx.x][0]; tc += s_stat[w8][threadIdx.x][1]; }
-            stats[((long long)blockIdx.x * C + threadIdx.x) * 2 + 0] = ta;
-            stats[((long long)blockIdx.x * C + threadIdx.x) * 2 + 1] = tc;
-        }
+        stat_slab<NW, C, true>(&s_stat[0][0][0], stats + (long long)blockIdx.x * C * 2);
         for (int t2 = blockIdx.x + gridDim.x; t2 < nslabs; t2 += gridDim.x)         // slabs no workgroup owns
             for (int i = threadIdx.x; i < C * 2; i += S2_NTH) stats[(long long)t2 * C * 2 + i] = 0.0;
     }
@@ -416,12 +367,7 @@ bool dm_conv4x4s2_patch_forward(const Operand &in, const WeightView &wv, float *
     if (in.mode == DM_LOAD_AFFINE2 || in.ones || ep.mask.p0 || ep.resid || ep.stat_q || ep.bias_border) return false;
     if (per_tile && (!ep.stats || nslabs % B != 0)) return false;
     static DmPerDeviceOnce attr_done;
-    if (attr_done.need()) {
-        const hipError_t e = hipFuncSetAttribute((const void *)conv4x4s2_patch_forward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)F2_LDS_BYTES);
-        if (e != hipSuccess) return false;
-        attr_done.mark();
-    }
+    if (dm_reserve_lds(attr_done, {{(const void *)conv4x4s2_patch_forward_kernel, F2_LDS_BYTES}}, nullptr)) return false;
     const int grid = B < 256 ? B : 256;
     hipLaunchKernelGGL(conv4x4s2_patch_forward_kernel, dim3(grid), dim3(S2_NTH), F2_LDS_BYTES, stream, in, wv, ep.bias, ep.relu, out,
                        ep.stats, per_tile, nslabs, B);

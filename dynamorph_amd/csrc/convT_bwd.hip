@@ -217,13 +217,9 @@ void convT_bwd_kernel(const float *__restrict__ S, const float *__restrict__ G, 
             const int ci = HALF ? (m & 7) : m, r = HALF ? 2 * rp + (m >> 3) : rp;
             if (HALF || m < CI) {
                 const int off = r * TW + 16 * cg + 4 * kq;
-                if (mask_relu) {
-                    const f32x4 sv = *reinterpret_cast<const f32x4 *>(sS + ci * PSS + off);
-                    acc.x = sv.x > 0.f ? acc.x : 0.f; acc.y = sv.y > 0.f ? acc.y : 0.f;
-                    acc.z = sv.z > 0.f ? acc.z : 0.f; acc.w = sv.w > 0.f ? acc.w : 0.f;
-                }
+                if (mask_relu) acc = relu_gate4(*reinterpret_cast<const f32x4 *>(sS + ci * PSS + off), acc);
                 *reinterpret_cast<f32x4 *>(gb + ((long long)ci * H + r) * W + 16 * cg + 4 * kq) = acc;
-                s1 += (double)((acc.x + acc.y) + (acc.z + acc.w));
+                s1 += (double)pair_sum4(acc);
             }
         }
         if (tile >= ntiles) break;
@@ -233,25 +229,13 @@ void convT_bwd_kernel(const float *__restrict__ S, const float *__restrict__ G, 
 
     // ---- channel sums of the input gradient (the previous layer's bias gradient): kq groups, then waves in wave order
     __syncthreads();
-    if (stats) {
-        double a = s1;
-        a += __shfl_xor(a, 16, 64);
-        a += __shfl_xor(a, 32, 64);
-        if (HALF) a += __shfl_xor(a, 8, 64);                     // the two output rows of a channel
-        if (lane < 16) s_stat[wave][lane] = a;
-    }
+    if (stats) stat_fold<16, false, HALF>(&s_stat[0][0], wave, lane, s1);      // (HALF: and the two output rows of a channel)
     // ---- weight-gradient slab: the four waves' accumulators through LDS in wave order
     float *red = lds;
 #pragma unroll
     for (int t = 0; t < NWT; ++t) *reinterpret_cast<f32x4 *>(red + ((wave * NWT + t) * 64 + lane) * 4) = wacc[t];
     __syncthreads();
-    if (stats && threadIdx.x < CI) {
-        double ta = 0.0;
-#pragma unroll
-        for (int wv = 0; wv < 4; ++wv) ta += s_stat[wv][threadIdx.x];
-        stats[((long long)blockIdx.x * CI + threadIdx.x) * 2 + 0] = ta;
-        stats[((long long)blockIdx.x * CI + threadIdx.x) * 2 + 1] = 0.0;
-    }
+    if (stats) stat_slab<4, 16, false>(&s_stat[0][0], stats + (long long)blockIdx.x * CI * 2, CI);
     // element i of the slab = dW[ci][co][ky][kx]: accumulator row 4 kq + r of lane (m, kq) in an N tile --
     // plain: row = ci, tile co, column m = (ky, kx);  HALF: row = (ci, sy) = ci + 8 sy, column 16 t + m = (co, py, kx), ky = 2 sy + py
     for (int i = threadIdx.x; i < CI * CO * 16; i += DM_BLOCK) {

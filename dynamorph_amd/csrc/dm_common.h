@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <initializer_list>
 #include "../../include/dynamorph_hip.h"
 
 // The split-bf16 operands of the gradient kernels (rounds 4-5: fp32 values as bf16 head + remainder pairs on the bf16
@@ -109,6 +110,18 @@ static inline int dm_check_operand(const dm_operand *o, const char *who)
     return 0;
 }
 
+// The output gradient of a fused backward entry point `who`: read as it is, or through BatchNorm's backward (AFFINE2) with one
+// coefficient row set shared by the batch.  *d: the device operand; IDENT travels as coef == p1 == nullptr.
+static inline int dm_bwd_dy_operand(const dm_operand *dy, const char *who, Operand *d)
+{
+    DM_REQUIRE(dy->mode == DM_LOAD_IDENT || dy->mode == DM_LOAD_AFFINE2, "%s: dy operand must be IDENT or AFFINE2", who);
+    DM_REQUIRE(dy->mode == DM_LOAD_IDENT || dy->coef, "%s: AFFINE2 needs coefficients", who);
+    DM_REQUIRE(dy->coef_bstride == 0 && !dy->ones_channel, "%s: shared coefficients only", who);
+    *d = to_dev(dy);
+    if (d->mode == DM_LOAD_IDENT) { d->coef = nullptr; d->p1 = nullptr; }
+    return 0;
+}
+
 #ifdef __HIPCC__
 // ReLU as torch.relu defines it: negative numbers to 0, every NaN (either sign) kept -- fmaxf / v_max_f32 would return 0
 // for a NaN and hide it from everything downstream.  gfx950 has the IEEE 754-2019 maximum, which propagates NaNs, as ONE
@@ -207,5 +220,22 @@ struct DmPerDeviceOnce {
     bool need() const { const int d = dev(); return d < 0 || !done[d]; }
     void mark() { const int d = dev(); if (d >= 0) done[d] = true; }
 };
+
+// Dynamic LDS beyond 64 KB is granted per kernel: once per device, every kernel an entry point `who` may launch with what it
+// asks for.  0, or the HIP error with the message set (no `who`: no message, for a route that falls back to another kernel).
+struct DmLdsNeed { const void *kernel; size_t bytes; };
+static inline int dm_reserve_lds(DmPerDeviceOnce &once, std::initializer_list<DmLdsNeed> needs, const char *who)
+{
+    if (!once.need()) return 0;
+    for (const DmLdsNeed &n : needs) {
+        const hipError_t e = hipFuncSetAttribute(n.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)n.bytes);
+        if (e != hipSuccess) {
+            if (who) dm_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
+            return (int)e;
+        }
+    }
+    once.mark();
+    return 0;
+}
 
 #endif

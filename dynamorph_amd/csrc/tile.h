@@ -252,3 +252,67 @@ __device__ __forceinline__ f32x4 tile_load4(__amdgpu_buffer_rsrc_t r, int byte_o
 // commit of the next tile, which the last tile skips -- into that branch, to the far side of the products; with a use on the
 // other way as well the request stays where it is written.  (No instruction; once per workgroup, the loop is over.)
 __device__ __forceinline__ void tile_keep(f32x4 v) { asm volatile("" ::"v"(v)); }
+
+// ---- the glue of the fused backward family (conv1x1_bwd, conv3x3_bwd, conv4x4s2_patch, convT_bwd), spelled once ------------------
+// BatchNorm's backward folded into the load of an output gradient: da = c0*dy + c1*y + c2 (dm_operand AFFINE2).  The host hands
+// IDENT over as coef == p1 == nullptr: (1, 0, 0) leaves the value bit-identical.
+struct DyCoef { float c0, c1, c2; };
+__device__ __forceinline__ DyCoef dy_coef(const float *coef, bool two, int c)
+{
+    return {coef ? coef[c * 4] : 1.f, (coef && two) ? coef[c * 4 + 1] : 0.f, coef ? coef[c * 4 + 2] : 0.f};
+}
+// the commit's transform of a staged float4 (v from p0, u from p1, read only where there are `two` tensors): two fused
+// multiply-adds, in this order
+__device__ __forceinline__ f32x4 dy_commit(const DyCoef &k, f32x4 v, f32x4 u, bool two)
+{
+    f32x4 r = k.c0 * v + k.c2;
+    if (two) r += k.c1 * u;
+    return r;
+}
+// ReLU's mask from what the forward multiplied: v where t > 0, else 0
+__device__ __forceinline__ f32x4 relu_gate4(f32x4 t, f32x4 v)
+{
+    return (f32x4){t.x > 0.f ? v.x : 0.f, t.y > 0.f ? v.y : 0.f, t.z > 0.f ? v.z : 0.f, t.w > 0.f ? v.w : 0.f};
+}
+// four elements in fp32, pairwise (the parentheses fix the rounding), before the one promotion to double
+__device__ __forceinline__ float pair_sum4(f32x4 v) { return (v.x + v.y) + (v.z + v.w); }
+__device__ __forceinline__ float pair_dot4(f32x4 v, f32x4 q) { return (v.x * q.x + v.y * q.y) + (v.z * q.z + v.w * q.w); }
+// the same with every product rounded on its own, whatever the compiler would contract: the 3x3 backward's statistics
+__device__ __forceinline__ float pair_dot4_rounded(f32x4 v, f32x4 q)
+{
+#pragma clang fp contract(off)
+    const f32x4 p = v * q;
+    return (p.x + p.y) + (p.z + p.w);
+}
+
+// Statistics of a persistent workgroup: lane (m, kq) holds the sums of channel m over its kq group.  stat_fold adds the
+// four kq groups (lanes l, l ^ 16, l ^ 32, l ^ 48; FOLD8: and l ^ 8, two rows of one channel side by side) and puts the wave's
+// sums into s_stat[wave][m]; stat_slab, behind a barrier, adds the waves in wave order into the workgroup's slab
+// dst[n][2] (no second column: 0.0).  s_stat: [NW][C][TWO ? 2 : 1] doubles.
+template <int C, bool TWO, bool FOLD8 = false>
+__device__ __forceinline__ void stat_fold(double *s_stat, int wave, int lane, double a, double c = 0.0)
+{
+    a += __shfl_xor(a, 16, 64); if (TWO) c += __shfl_xor(c, 16, 64);
+    a += __shfl_xor(a, 32, 64); if (TWO) c += __shfl_xor(c, 32, 64);
+    if (FOLD8) a += __shfl_xor(a, 8, 64);
+    if (lane < 16) {
+        double *p = s_stat + (wave * C + lane) * (TWO ? 2 : 1);
+        p[0] = a;
+        if (TWO) p[1] = c;
+    }
+}
+template <int NW, int C, bool TWO>
+__device__ __forceinline__ void stat_slab(const double *s_stat, double *__restrict__ dst, int n = C)
+{
+    if ((int)threadIdx.x < n) {
+        double ta = 0.0, tc = 0.0;
+#pragma unroll
+        for (int wv = 0; wv < NW; ++wv) {
+            const double *p = s_stat + (wv * C + threadIdx.x) * (TWO ? 2 : 1);
+            ta += p[0];
+            if (TWO) tc += p[1];
+        }
+        dst[threadIdx.x * 2 + 0] = ta;
+        dst[threadIdx.x * 2 + 1] = tc;
+    }
+}

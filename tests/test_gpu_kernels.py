@@ -858,7 +858,9 @@ def test_conv1x1_backward_fused_equals_the_two_kernels(ops, B, H, W, two):
                                           (300, 32, "res", (16, 16)), (4, 32, "res_noq", (16, 16)), (2, 16, "ident", (16, 16)),
                                           # 32-column latent grids (32 x 32: C5, default-width z32): bands of 8 rows with halo rows
                                           (3, 32, "res", (32, 32)), (70, 32, "res", (32, 32)), (3, 32, "res_noq", (32, 32)),
-                                          (300, 32, "res", (32, 32))])
+                                          (300, 32, "res", (32, 32)),
+                                          # the 32-channel forms without a second gradient tensor / with xcoef
+                                          (2, 32, "ident", (16, 16)), (3, 32, "enc10", (16, 16)), (3, 32, "ident", (32, 32))])
 def test_conv3x3_backward_fused_equals_the_two_kernels(ops, B, CD, form, hw):
     """dm_conv3x3_bwd_fused (data + weight gradient of enc.10 / the ResidualBlock's 3x3 convolution from one staging of the
     patch) against dm_conv3x3 + dm_wgrad and against autograd's conv2d backward in float64."""
