@@ -2,8 +2,12 @@
 
 Public surface = the reference's module surface for this path:
     VQ_VAE, VQ_VAE_z16, VQ_VAE_z32, VectorQuantizer, ResidualBlock      (dynamorph_amd.vq_vae)
-computed by hand-written gfx950 HIP kernels behind the C ABI in include/dynamorph_hip.h.
+computed by hand-written gfx950 HIP kernels behind the C ABI in include/dynamorph_hip.h, and the per-patch scoring drivers
+of the inference path:
+    score_patches, score_patches_sharded, score_VAE                     (dynamorph_amd.patch_vae)
 """
 from .vq_vae import VQ_VAE, VQ_VAE_z16, VQ_VAE_z32, VectorQuantizer, ResidualBlock  # noqa: F401
+from .patch_vae import score_patches, score_patches_sharded, score_VAE  # noqa: F401
 
-__all__ = ["VQ_VAE", "VQ_VAE_z16", "VQ_VAE_z32", "VectorQuantizer", "ResidualBlock"]
+__all__ = ["VQ_VAE", "VQ_VAE_z16", "VQ_VAE_z32", "VectorQuantizer", "ResidualBlock",
+           "score_patches", "score_patches_sharded", "score_VAE"]

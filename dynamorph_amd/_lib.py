@@ -129,6 +129,11 @@ SIGNATURES = {
     "dm_recon_loss_num_blocks": (C.c_int, [C.c_int] * 4),
     "dm_recon_loss": (C.c_int, [vp, vp, vp, C.c_int, vp, vp] + [C.c_int] * 4 + [vp]),
     "dm_recon_loss_backward": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, vp, vp] + [C.c_int] * 4 + [vp]),
+    "dm_dec_tail_score_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "dm_dec_tail_score": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_size_t] + [C.c_int] * 5 + [vp]),
+    "dm_recon_loss_per_sample": (C.c_int, [vp, vp, vp, C.c_int, vp, vp] + [C.c_int] * 4 + [vp]),
+    "dm_vq_patch_scalars": (C.c_int, [vp, vp, vp, f32, vp, vp] + [C.c_int] * 5 + [vp]),
+    "dm_score_finalize": (C.c_int, [vp, vp, f32, f32, i64, vp, C.c_int, C.c_int, vp]),
     "dm_pair_msd": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
     "dm_pair_msd_backward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
     "dm_time_matching_supported": (C.c_int, [C.c_int, C.c_int]),

@@ -121,7 +121,14 @@ __device__ __forceinline__ void convT_pair(const RowVals &P, const RowVals &C, c
 __device__ __forceinline__ f32x2 relu2(f32x2 v) { return (f32x2){dm_relu(v.x), dm_relu(v.y)}; }
 
 // =================================================================================== forward
-template <int NIN, bool WIDE>
+// SCORE (dm_dec_tail_score): the loss partials leave the workgroup per TILE and per channel -- each wave's sum over its four
+// rows of the tile goes to score_ws[tile][wave][NIN] (loss_slabs' place), so that no partial ever mixes two patches and a
+// patch's sums do not depend on where in the batch it lies or on which workgroup served it; `dec` may be NULL (not stored).
+// A lane runs the forward form's own fp32 chain over (row, channel) and credits every step's increment -- the chain after
+// the step minus the chain before it, taken in double, where that difference is exact -- to the step's channel; from there
+// on everything is added in double.  The channels of a lane therefore add up to exactly what the forward form adds to its
+// slab for that lane and tile: the scores and the batch loss are one arithmetic, not two roundings of the same sum.
+template <int NIN, bool WIDE, bool SCORE = false>
 __global__ __launch_bounds__(DM_BLOCK, 3)
 void dec_tail_forward_kernel(const float *__restrict__ d2, const float *__restrict__ w4, const float *__restrict__ b4,
                              const float *__restrict__ w6, const float *__restrict__ b6, const float *__restrict__ x,
@@ -215,6 +222,7 @@ void dec_tail_forward_kernel(const float *__restrict__ d2, const float *__restri
         __syncthreads();
         // ---- phase B: dec.6 (1x1) + loss; one wave per output row, one lane per column pair --------------------
         float tl = 0.f;
+        double tlc[SCORE ? NIN : 1] = {}, tprev = 0.0;     // SCORE: the chain's increments per channel; the chain so far
 #pragma unroll
         for (int j = 0; j < DROWS / 4; ++j) {
             const int R = wave + 4 * j;
@@ -228,7 +236,7 @@ void dec_tail_forward_kernel(const float *__restrict__ d2, const float *__restri
 #pragma unroll
                 for (int co = 0; co < TT_C; ++co) o += w6r[c][co] * dv[co];
                 const int off = ((cb * NIN + c) * OH + oy) * OW + 2 * colx;
-                if (ownl) *reinterpret_cast<f32x2 *>(dec + off) = o;
+                if (ownl && (!SCORE || dec)) *reinterpret_cast<f32x2 *>(dec + off) = o;
                 if (x && ownl) {
                     f32x2 t = o - xr[j][c];
                     if (mask) {
@@ -236,14 +244,46 @@ void dec_tail_forward_kernel(const float *__restrict__ d2, const float *__restri
                         t = o * mv - xr[j][c] * mv;
                     }
                     tl += (t.x * t.x + t.y * t.y) * ivar[c];
+                    if constexpr (SCORE && NIN > 1) {
+                        const double tnow = (double)tl;
+                        tlc[c] += tnow - tprev;
+                        tprev = tnow;
+                    }
                 }
             }
         }
-        loss += (double)tl;
+        if constexpr (SCORE) {
+            // the wave's 64 lane sums in double: inside a 16-lane row by DPP moves, the four rows by lane swaps; no barrier added
+            if constexpr (NIN == 1) tlc[0] = (double)tl;
+#pragma unroll
+            for (int c = 0; c < NIN; ++c) {
+                double v = tlc[c];
+                v += lane_xor1(v); v += lane_xor2(v); v += lane_xor4(v); v += lane_xor8(v);
+                const double ws = dm_row_sum_f64(v);
+                if (lane == 0) loss_slabs[((long long)tidx * 4 + wave) * NIN + c] = ws;
+            }
+        } else {
+            loss += (double)tl;
+        }
         tidx = next;
     }
-    const double tot = block_sum(loss, s_red);
-    if (threadIdx.x == 0 && loss_slabs) loss_slabs[blockIdx.x] = tot;
+    if constexpr (!SCORE) {
+        const double tot = block_sum(loss, s_red);
+        if (threadIdx.x == 0 && loss_slabs) loss_slabs[blockIdx.x] = tot;
+    }
+}
+
+// dm_dec_tail_score, second launch: patch_sums[b][c] = the patch's tiles in index order, each tile's waves in order.
+__global__ __launch_bounds__(DM_BLOCK)
+void dec_tail_score_reduce_kernel(const double *__restrict__ ws, double *__restrict__ patch_sums, int n, int NIN, int tiles_per_patch)
+{
+    const int i = blockIdx.x * DM_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int b = i / NIN, c = i - b * NIN;
+    const double *__restrict__ p = ws + (long long)b * tiles_per_patch * 4 * NIN + c;
+    double s = 0.0;
+    for (int k = 0; k < tiles_per_patch * 4; ++k) s += p[(long long)k * NIN];
+    patch_sums[i] = s;
 }
 
 // Weight gradient of dec.4 on the MFMA with a full 16x16 tile.  R[ci][co][ky][kx] = sum_{y,x} d2[ci][y][x] *
@@ -918,6 +958,40 @@ extern "C" int dm_dec_tail_forward(const float *d2, const float *w4, const float
     }
 #undef DM_TF
     return dm_launch_status("dm_dec_tail_forward");
+}
+
+extern "C" size_t dm_dec_tail_score_workspace_bytes(int B, int NIN, int H2, int W2)
+{
+    if (B <= 0 || NIN <= 0 || H2 < TT_TH || W2 <= 0) return 0;
+    return (size_t)B * (H2 / TT_TH) * tail_tiles_x(W2) * 4 * NIN * sizeof(double);
+}
+
+extern "C" int dm_dec_tail_score(const float *d2, const float *w4, const float *b4, const float *w6, const float *b6,
+                                 const float *x, const float *mask, int mask_channels, const float *channel_var,
+                                 float *decoded, double *patch_sums, void *workspace, size_t workspace_bytes,
+                                 int B, int C2, int NIN, int H2, int W2, void *stream)
+{
+    DM_REQUIRE(d2 && w4 && b4 && w6 && x && channel_var && patch_sums && workspace, "dm_dec_tail_score: NULL pointer");
+    DM_REQUIRE(!mask || mask_channels == 1 || mask_channels == NIN, "dm_dec_tail_score: mask channels %d", mask_channels);
+    if (tail_checks("dm_dec_tail_score", B, C2, NIN, H2, W2)) return -1;
+    DM_REQUIRE(workspace_bytes >= dm_dec_tail_score_workspace_bytes(B, NIN, H2, W2),
+               "dm_dec_tail_score: workspace of %zu bytes, %zu needed", workspace_bytes,
+               dm_dec_tail_score_workspace_bytes(B, NIN, H2, W2));
+    const int tiles_x = tail_tiles_x(W2), per_patch = (H2 / TT_TH) * tiles_x, ntiles = B * per_patch, grid = tail_grid(ntiles);
+    hipStream_t st = (hipStream_t)stream;
+    double *ws = static_cast<double *>(workspace);
+#define DM_TS(N_, W_) hipLaunchKernelGGL((dec_tail_forward_kernel<N_, W_, true>), dim3(grid), dim3(DM_BLOCK), 0, st, d2, w4, b4, w6, b6, \
+                                         x, mask, mask_channels, channel_var, decoded, ws, H2, ntiles, W2, tiles_x)
+    if (W2 == TT_W) {
+        switch (NIN) { case 1: DM_TS(1, false); break; case 2: DM_TS(2, false); break; case 3: DM_TS(3, false); break; default: DM_TS(4, false); }
+    } else {
+        switch (NIN) { case 1: DM_TS(1, true); break; case 2: DM_TS(2, true); break; case 3: DM_TS(3, true); break; default: DM_TS(4, true); }
+    }
+#undef DM_TS
+    if (const int rc = dm_launch_status("dm_dec_tail_score")) return rc;
+    hipLaunchKernelGGL(dec_tail_score_reduce_kernel, dim3((B * NIN + DM_BLOCK - 1) / DM_BLOCK), dim3(DM_BLOCK), 0, st, ws,
+                       patch_sums, B * NIN, NIN, per_patch);
+    return dm_launch_status("dm_dec_tail_score");
 }
 
 namespace {

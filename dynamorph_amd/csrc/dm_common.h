@@ -164,6 +164,20 @@ __device__ __forceinline__ f32x4 lane_xor1(f32x4 v) { return (f32x4){lane_xor1(v
 __device__ __forceinline__ f32x4 lane_xor4(f32x4 v) { return (f32x4){lane_xor4(v.x), lane_xor4(v.y), lane_xor4(v.z), lane_xor4(v.w)}; }
 __device__ __forceinline__ f32x4 lane_xor8(f32x4 v) { return (f32x4){lane_xor8(v.x), lane_xor8(v.y), lane_xor8(v.z), lane_xor8(v.w)}; }
 
+// ... of a double: its two halves make the same move
+template <float (*MOVE)(float)>
+__device__ __forceinline__ double dpp_move_f64(double v)
+{
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = __builtin_bit_cast(unsigned, MOVE(__builtin_bit_cast(float, (unsigned)(u & 0xffffffffull))));
+    const unsigned hi = __builtin_bit_cast(unsigned, MOVE(__builtin_bit_cast(float, (unsigned)(u >> 32))));
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ double lane_xor1(double v) { return dpp_move_f64<static_cast<float (*)(float)>(lane_xor1)>(v); }
+__device__ __forceinline__ double lane_xor2(double v) { return dpp_move_f64<static_cast<float (*)(float)>(lane_xor2)>(v); }
+__device__ __forceinline__ double lane_xor4(double v) { return dpp_move_f64<static_cast<float (*)(float)>(lane_xor4)>(v); }
+__device__ __forceinline__ double lane_xor8(double v) { return dpp_move_f64<static_cast<float (*)(float)>(lane_xor8)>(v); }
+
 __device__ __forceinline__ double wave_sum(double v)
 {
 #pragma unroll

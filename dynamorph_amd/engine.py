@@ -269,6 +269,14 @@ def _replay(cx, x, defer, join):
             cx.join()
 
 
+def _need_per_sample_slabs(stats, B, route):
+    """Per-sample BatchNorm statistics need the producing kernel's slabs grouped by sample (a whole number per sample); a
+    route that hands back anything else cannot serve them -- an error that names the route, never batch statistics."""
+    if stats is None or stats.shape[0] % B != 0:
+        raise NotImplementedError("%s: this kernel route has no per-sample statistics (%s slabs for %d samples)"
+                                  % (route, "no" if stats is None else stats.shape[0], B))
+
+
 def residual_forward(res_layers, h, per_sample=False, defer=None, defer_last_join=False):
     """ResidualBlock.forward (vq_vae.py:212-225) on a materialised h (B,nh,H,W).
     defer: the caller's list of postponed running-statistics updates (per-sample path); None: flushed here.
@@ -284,9 +292,13 @@ def residual_forward(res_layers, h, per_sample=False, defer=None, defer_last_joi
         nrh = ca.weight.shape[0]
         ra, st = ops.conv3x3(Op(h, DM_LOAD_RELU), weight_view(_w(ca.weight), nh * 9, 9, 3, 1), B, nh, nrh, H, W, taps=9,
                              want_stats=True, bias=_w(ca.bias), per_tile=per_sample)
+        if per_sample:
+            _need_per_sample_slabs(st, B, "residual_forward: 3x3 convolution %d -> %d at %d x %d" % (nh, nrh, H, W))
         coefa, saveda = _bn_coef(st, bna, n, per_sample, B, defer)
         rb, st = ops.conv3x3(Op(ra, DM_LOAD_AFFINE_RELU, coefa, per_sample=per_sample), weight_view(_w(cb.weight), nrh, 1, 0, 0),
                              B, nrh, nh, H, W, taps=1, want_stats=True, bias=_w(cb.bias), per_tile=per_sample)
+        if per_sample:
+            _need_per_sample_slabs(st, B, "residual_forward: 1x1 convolution %d -> %d at %d x %d" % (nrh, nh, H, W))
         coefb, savedb = _bn_coef(st, bnb, n, per_sample, B, defer)
         last = defer_last_join and ca is res_layers[-1][0]
         hn = None if last else ops.apply(Op(rb, DM_LOAD_AFFINE, coefb, per_sample=per_sample), B, nh, H, W, resid=h)
@@ -459,12 +471,8 @@ def decoder_forward(L, zq, x=None, mask=None, defer_tail=False):
     (ops.dec_tail_train); `decoded` is not produced and cx.loss_slabs is filled by decoder_backward."""
     B, nh, H3, W3 = zq.shape
     c1, c2 = nh // 2, nh // 4
-    d0, _ = ops.conv3x3(Op(zq), weight_view(_w(L.dec0.weight), 16, c1 * 16, 4, 1), B, nh, 4 * c1, H3, W3, taps=9,
-                        pixel_shuffle=True, bias=_w(L.dec0.bias), relu=True)
-    d2, _ = ops.conv3x3(Op(d0), weight_view(_w(L.dec2.weight), 16, c2 * 16, 4, 1), B, c1, 4 * c2, 2 * H3, 2 * W3, taps=9,
-                        pixel_shuffle=True, bias=_w(L.dec2.bias), relu=True)
-    # (model.dec called on its own has no loss and hence no channel variances)
-    var = _w(L.channel_var).reshape(-1) if L.channel_var is not None else torch.ones(L.dec6.weight.shape[0], device=zq.device)
+    d0, d2 = _dec_upsample(L, zq)
+    var = _dec_var(L, zq)
     fused = ops.dec_tail_supported(c2, L.dec6.weight.shape[0], 4 * H3, 4 * W3)
     if fused and defer_tail and x is not None:
         cx = SimpleNamespace(zq=zq, d0=d0, d2=d2, d4=None, dec=None, x=x, mask=mask, loss_slabs=None, deferred=True)
@@ -486,6 +494,38 @@ def decoder_forward(L, zq, x=None, mask=None, defer_tail=False):
             slabs = ops.recon_loss(dec, x, mask, var) if x is not None else None
     cx = SimpleNamespace(zq=zq, d0=d0, d2=d2, d4=d4, dec=dec, x=x, mask=mask, loss_slabs=slabs, deferred=False)
     return dec, cx
+
+
+def _dec_upsample(L, zq):
+    """dec.0 + ReLU and dec.2 + ReLU: zq (B,nh,H3,W3) -> d0 (B,nh/2,2H3,2W3), d2 (B,nh/4,4H3,4W3)."""
+    B, nh, H3, W3 = zq.shape
+    c1, c2 = nh // 2, nh // 4
+    d0, _ = ops.conv3x3(Op(zq), weight_view(_w(L.dec0.weight), 16, c1 * 16, 4, 1), B, nh, 4 * c1, H3, W3, taps=9,
+                        pixel_shuffle=True, bias=_w(L.dec0.bias), relu=True)
+    d2, _ = ops.conv3x3(Op(d0), weight_view(_w(L.dec2.weight), 16, c2 * 16, 4, 1), B, c1, 4 * c2, 2 * H3, 2 * W3, taps=9,
+                        pixel_shuffle=True, bias=_w(L.dec2.bias), relu=True)
+    return d0, d2
+
+
+def _dec_var(L, zq):
+    # (model.dec called on its own has no loss and hence no channel variances)
+    return _w(L.channel_var).reshape(-1) if L.channel_var is not None else torch.ones(L.dec6.weight.shape[0], device=zq.device)
+
+
+def decoder_score(L, zq, x, mask=None, want_decoded=False):
+    """The decoder for per-patch scores: -> (decoded or None, patch_sums (B, NIN) float64 of (dec*m - x*m)^2 / var per patch
+    and channel).  The decoder has no BatchNorm, so every patch is the reference's batch-of-one call as it stands; what
+    differs from decoder_forward is the reduction.  Where the fused tail is built (ops.dec_tail_supported) its scoring form
+    runs and `decoded` is only written when asked for; other widths run the existing forward kernels and sum the stored
+    `decoded` per patch."""
+    B, nh, H3, W3 = zq.shape
+    nin = L.dec6.weight.shape[0]
+    if not ops.dec_tail_supported(nh // 4, nin, 4 * H3, 4 * W3):
+        dec, _ = decoder_forward(L, zq)
+        return dec, ops.recon_loss_per_sample(dec, x, mask, _dec_var(L, zq))
+    _, d2 = _dec_upsample(L, zq)
+    return ops.dec_tail_score(d2, _w(L.dec4.weight), _w(L.dec4.bias), _w(L.dec6.weight), _w(L.dec6.bias), x, mask,
+                              _dec_var(L, zq), want_decoded=want_decoded)
 
 
 def _dec4_forward(L, d2):
@@ -632,14 +672,19 @@ def z32_stem_backward(conv0, bn0, conv1, bn1, cx, g_h, G, stats=None, pending=No
     return None
 
 
-def z32_tail_forward(up0, bn, up1, r, x, mask, channel_var):
-    """r (B,nh,H2,W2) -> decoded (B,NIN,4*H2,4*W2) (+ loss slabs when x is given)."""
+def z32_tail_forward(up0, bn, up1, r, x, mask, channel_var, per_sample=False, defer=None):
+    """r (B,nh,H2,W2) -> decoded (B,NIN,4*H2,4*W2) (+ loss slabs when x is given).
+    per_sample=True: the BatchNorm uses every sample's own statistics (the reference's batch-of-one call, batched), exactly
+    as z32_stem_forward does; defer: the caller's list of postponed running-statistics updates (ops.bn_running_replay)."""
     B, nh, H2, W2 = r.shape
+    ps = per_sample
     c1, NIN = up0.weight.shape[1], up1.weight.shape[1]
     d1, st = ops.conv3x3(Op(r), weight_view(_w(up0.weight), 16, c1 * 16, 4, 1), B, nh, 4 * c1, H2, W2, taps=9,
-                         pixel_shuffle=True, want_stats=True, bias=_w(up0.bias))
-    coefd, savedd = _bn_coef(st, bn, B * 4 * H2 * W2, False, B)
-    dec, _ = ops.conv3x3(Op(d1, DM_LOAD_AFFINE_RELU, coefd), weight_view(_w(up1.weight), 16, NIN * 16, 4, 1), B, c1,
+                         pixel_shuffle=True, want_stats=True, bias=_w(up0.bias), per_tile=ps)
+    if ps:
+        _need_per_sample_slabs(st, B, "z32_tail_forward: dec.1 (ConvTranspose2d %d -> %d at %d x %d)" % (nh, c1, H2, W2))
+    coefd, savedd = _bn_coef(st, bn, 4 * H2 * W2 * (1 if ps else B), ps, B, defer)
+    dec, _ = ops.conv3x3(Op(d1, DM_LOAD_AFFINE_RELU, coefd, per_sample=ps), weight_view(_w(up1.weight), 16, NIN * 16, 4, 1), B, c1,
                          4 * NIN, 2 * H2, 2 * W2, taps=9, pixel_shuffle=True, bias=_w(up1.bias))
     var = _w(channel_var).reshape(-1) if channel_var is not None else torch.ones(NIN, device=r.device)
     slabs = ops.recon_loss(dec, x, mask, var) if x is not None else None

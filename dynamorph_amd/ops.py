@@ -846,6 +846,63 @@ def recon_loss_backward(dec, x, mask, channel_var, gscale):
     return g, part
 
 
+# ------------------------------------------------------------------ per-patch scores
+@_op
+def dec_tail_score(d2, w4, b4, w6, b6, x, mask, channel_var, want_decoded=False):
+    """dec_tail_forward with the loss sums kept per patch and channel (include/dynamorph_hip.h, dm_dec_tail_score).
+    Returns (decoded or None, patch_sums (B, NIN) float64); `decoded` is not written unless asked for."""
+    lib = L.load()
+    B, C2, H2, W2 = d2.shape
+    NIN = w6.shape[0]
+    dec = _new((B, NIN, 2 * H2, 2 * W2), d2) if want_decoded else None
+    sums = _new((B, NIN), d2, torch.float64)
+    wsb = lib.dm_dec_tail_score_workspace_bytes(B, NIN, H2, W2)
+    ws = _new((max(wsb // 8, 1),), d2, torch.float64)
+    mc = mask.shape[1] if mask is not None else 0
+    L.check(lib.dm_dec_tail_score(_ptr(d2), _ptr(w4), _ptr(b4), _ptr(w6), _ptr(b6), _ptr(x), _ptr(mask), mc,
+                                  _ptr(channel_var), _ptr(dec), _ptr(sums, torch.float64), _ptr(ws, torch.float64), wsb,
+                                  B, C2, NIN, H2, W2, _stream()), "dm_dec_tail_score")
+    return dec, sums
+
+
+@_op
+def recon_loss_per_sample(dec, x, mask, channel_var):
+    """patch_sums (B, NIN) float64 of (dec*m - x*m)^2 / var from a stored `dec`; any H and W."""
+    lib = L.load()
+    B, NIN, H, W = dec.shape
+    sums = _new((B, NIN), dec, torch.float64)
+    mc = mask.shape[1] if mask is not None else 0
+    L.check(lib.dm_recon_loss_per_sample(_ptr(dec), _ptr(x), _ptr(mask), mc, _ptr(channel_var), _ptr(sums, torch.float64),
+                                         B, NIN, H, W, _stream()), "dm_recon_loss_per_sample")
+    return sums
+
+
+@_op
+def vq_patch_scalars(z, idx, codebook, commitment_cost, want_counts=False):
+    """Per patch (loss, perplexity, mse) as a (B, 3) tensor, and the (B, K) int32 code histogram on request (else None)."""
+    lib = L.load()
+    B, D, H, W = z.shape
+    K = codebook.shape[0]
+    if tuple(idx.shape) != (B, H, W) or codebook.shape[1] != D:
+        raise ValueError("dm_vq_patch_scalars: z (B, D, H, W), idx (B, H, W), codebook (K, D)")
+    scalars = _new((B, 3), z)
+    counts = _new((B, K), z, torch.int32) if want_counts else None
+    L.check(lib.dm_vq_patch_scalars(_ptr(z), _ptr(idx, torch.int64), _ptr(codebook), commitment_cost, _ptr(scalars),
+                                    _ptr(counts, torch.int32), B, D, K, H, W, _stream()), "dm_vq_patch_scalars")
+    return scalars, counts
+
+
+@_op
+def score_finalize(patch_sums, vq_scalars, weight_recon, weight_commitment, chw):
+    """(B, 4 + NIN): recon, commitment, total, perplexity, recon per channel."""
+    lib = L.load()
+    B, NIN = patch_sums.shape
+    out = _new((B, 4 + NIN), vq_scalars)
+    L.check(lib.dm_score_finalize(_ptr(patch_sums, torch.float64), _ptr(vq_scalars), weight_recon, weight_commitment, chw,
+                                  _ptr(out), B, NIN, _stream()), "dm_score_finalize")
+    return out
+
+
 # ------------------------------------------------------------------ time-matching loss
 @_op
 def pair_msd(z):

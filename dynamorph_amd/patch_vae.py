@@ -16,6 +16,116 @@ from . import engine as E
 from .train_utils import zscore_patch
 
 
+def _patch_encoder(model):
+    """(encode, codebook) for `model`: encode(x) -> (z_before, join) runs the HIP encoder on a device batch with PER-SAMPLE
+    BatchNorm statistics; join (or None) is the pending running-statistics replay the caller joins after its next launches."""
+    from .vq_vae import VQ_VAE, VQ_VAE_z32
+    if isinstance(model, VQ_VAE):
+        layers = E.Layers(model)
+        e1 = None                           # composite first-layer weights: once per call (the weights do not change here)
+
+        def encode(x):
+            nonlocal e1
+            if e1 is None:
+                e1 = E.e1_operands(layers)
+            z, cx = E.encoder_forward(layers, x, per_sample=True, e1=e1, join=False, latents_only=True)
+            return z, cx.join
+        return encode, layers.codebook.weight
+    if isinstance(model, VQ_VAE_z32):
+        enc = model.enc                     # children 0/1/3/4: conv, BatchNorm, conv, BatchNorm; 5: ResidualBlock
+
+        def encode(x):
+            h, _ = E.z32_stem_forward(enc[0], enc[1], enc[3], enc[4], x, per_sample=True)
+            return E.residual_forward(enc[5]._handles(), h, True)[0], None
+        return encode, model.vq.w.weight
+
+    def encode(x):                          # any other module: the reference's batch-of-one loop as it is
+        return torch.cat([model.enc(x[j:j + 1]) for j in range(x.shape[0])], 0), None
+    return encode, model.vq.w.weight
+
+
+def _pipelined(inputs, in_dtypes, step, device, batch_size):
+    """The three-stage pinned pipeline of the inference drivers.  inputs: host tensors with the same first dimension N > 0;
+    in_dtypes: the dtype each reaches the device in; step(batch tensors on the device) -> tuple of device tensors with first
+    dimension n, enqueued on the current stream.  Returns one host tensor (N, ...) per output, in input order.
+
+    Three stages in flight: batch i+1 crosses PCIe on a copy stream while batch i is computed, and the outputs of batch
+    i-1 go back on a second copy stream straight into the result arrays (a synchronous .cpu() per batch would leave the
+    GPU idle for both transfers: at 2 M patches/s one batch of 1024 is 0.5 ms of kernels against 134 MB in and 33 MB
+    out).  Measured on the MI355X host (tools/exp/host_alloc_probe.py): DMA from / to pinned memory 53-56 GB/s, from
+    pageable memory 10 GB/s, into freshly allocated pageable memory 5 GB/s (first-touch page faults).  Hence: hand
+    over PINNED patches for the full rate (process_VAE does: 365 k patches/s host to host, the PCIe limit); pageable
+    patches of the right dtype are copied by the runtime's own staging (this thread blocks, the queued kernels do
+    not: 120 k patches/s); patches that need a dtype conversion go through two pinned staging buffers.  The result
+    arrays are allocated pinned (25 GB/s to allocate) unless they exceed DM_PINNED_RESULT_BYTES (default 16 GiB; then
+    pageable, pre-faulted by a parallel fill, and written by blocking copies on a helper thread)."""
+    from concurrent.futures import ThreadPoolExecutor
+    N = inputs[0].shape[0]
+    bs = int(min(batch_size, N))
+    pin_cap = int(os.environ.get("DM_PINNED_RESULT_BYTES", str(16 << 30)))
+    res = None
+    with torch.no_grad(), torch.cuda.device(device), ThreadPoolExecutor(1) as helper:   # (non-zero gpu ids: patch_VAE.py:422)
+        compute = torch.cuda.current_stream()
+        s_in, s_out = torch.cuda.Stream(), torch.cuda.Stream()
+        shapes = [(bs,) + tuple(t.shape[1:]) for t in inputs]
+        x_dev = [[torch.empty(sh, dtype=dt, device=device) for sh, dt in zip(shapes, in_dtypes)] for _ in range(2)]
+        convert = [t.dtype != dt for t, dt in zip(inputs, in_dtypes)]
+        in_pin = [[torch.empty(sh, dtype=dt, pin_memory=True) if cv else None for sh, dt, cv in zip(shapes, in_dtypes, convert)]
+                  for _ in range(2)]
+        ev_in = [torch.cuda.Event() for _ in range(2)]          # the batch has reached x_dev[k]
+        ev_done = [torch.cuda.Event() for _ in range(2)]        # the kernels reading x_dev[k] have finished
+        sent = [None, None]                                     # helper's future for the batch that last used slot k
+
+        def hand_back(lo, n, outs, ev):
+            with torch.cuda.device(device), torch.cuda.stream(s_out):
+                s_out.wait_event(ev)
+                for r, o in zip(res, outs):
+                    r[lo:lo + n].copy_(o, non_blocking=True)    # asynchronous into pinned results; into pageable ones it
+                                                                # blocks, but only this helper thread
+
+        for it, lo in enumerate(range(0, N, bs)):
+            k = it & 1
+            n = min(bs, N - lo)
+            if sent[k] is not None:
+                sent[k].result()                                # at most two batches of outputs wait on the device
+            srcs = [t[lo:lo + n] for t in inputs]
+            if any(convert):
+                ev_in[k].synchronize()                          # staging buffer k has left for the device
+                for q, cv in enumerate(convert):
+                    if cv:
+                        in_pin[k][q][:n].copy_(srcs[q])         # host: the reference's .float() (patch_VAE.py:419)
+                        srcs[q] = in_pin[k][q][:n]
+            with torch.cuda.stream(s_in):
+                s_in.wait_event(ev_done[k])                     # x_dev[k] is no longer being read (no-op the first time)
+                for q, src in enumerate(srcs):
+                    x_dev[k][q][:n].copy_(src, non_blocking=True)   # (pageable source: blocks this thread until it has left)
+                ev_in[k].record(s_in)
+            compute.wait_event(ev_in[k])
+            outs = step(*[xd[:n] for xd in x_dev[k]])
+            ev_done[k].record(compute)
+            outs = tuple(o.reshape(n, -1) if o.dim() == 1 else o for o in outs)
+            if res is None:
+                pinned = sum(N * o[0].numel() * o.element_size() for o in outs) <= pin_cap
+                res = []
+                for o in outs:
+                    shape = (N,) + tuple(o.shape[1:])
+                    if pinned:
+                        try:
+                            res.append(torch.empty(shape, dtype=o.dtype, pin_memory=True))
+                            continue
+                        except RuntimeError:                    # the host refuses to pin that much: pageable results
+                            pinned = False
+                    res.append(torch.empty(shape, dtype=o.dtype).fill_(0))
+            for o in outs:
+                o.record_stream(s_out)
+            sent[k] = helper.submit(hand_back, lo, n, outs, ev_done[k])
+        for f in sent:
+            if f is not None:
+                f.result()
+        s_out.synchronize()
+    return res
+
+
 def encode_patches(model, patches, device="cuda:0", batch_size=1024, zscore_on_device=False):
     """patches: (N, C, H, W) float tensor/array on the host.  Returns (z_before, z_after) as float32
     numpy arrays of shape (N, D*H/8*W/8), in input order (patch_VAE.py:454,459).
@@ -25,108 +135,110 @@ def encode_patches(model, patches, device="cuda:0", batch_size=1024, zscore_on_d
     patches = torch.as_tensor(patches)
     if patches.dim() != 4:
         raise AssertionError("dataset tensor dimension can only be 4, not {}".format(patches.dim()))
-    from .vq_vae import VQ_VAE, VQ_VAE_z32
-    if isinstance(model, VQ_VAE):
-        layers = E.Layers(model)
-        codebook = layers.codebook.weight
-        e1 = None                           # composite first-layer weights: once per call (the weights do not change here)
-
-        def encode(x):
-            nonlocal e1
-            if e1 is None:
-                e1 = E.e1_operands(layers)
-            z, cx = E.encoder_forward(layers, x, per_sample=True, e1=e1, join=False, latents_only=True)
-            return z, cx.join
-    elif isinstance(model, VQ_VAE_z32):
-        enc = model.enc                     # children 0/1/3/4: conv, BatchNorm, conv, BatchNorm; 5: ResidualBlock
-        codebook = model.vq.w.weight
-
-        def encode(x):
-            h, _ = E.z32_stem_forward(enc[0], enc[1], enc[3], enc[4], x, per_sample=True)
-            return E.residual_forward(enc[5]._handles(), h, True)[0], None
-    else:
-        codebook = model.vq.w.weight
-
-        def encode(x):                      # any other module: the reference's batch-of-one loop as it is
-            return torch.cat([model.enc(x[j:j + 1]) for j in range(x.shape[0])], 0), None
+    encode, codebook = _patch_encoder(model)
     device = torch.device(device)
-    N = patches.shape[0]
-    if N == 0:
+    if patches.shape[0] == 0:
         return np.zeros((0, 0), np.float32), np.zeros((0, 0), np.float32)
-    # Three stages in flight: batch i+1 crosses PCIe on a copy stream while batch i is encoded, and the latents of batch
-    # i-1 go back on a second copy stream straight into the result arrays (a synchronous .cpu() per batch would leave the
-    # GPU idle for both transfers: at 2 M patches/s one batch of 1024 is 0.5 ms of kernels against 134 MB in and 33 MB
-    # out).  Measured on the MI355X host (tools/exp/host_alloc_probe.py): DMA from / to pinned memory 53-56 GB/s, from
-    # pageable memory 10 GB/s, into freshly allocated pageable memory 5 GB/s (first-touch page faults).  Hence: hand
-    # over PINNED patches for the full rate (process_VAE does: 365 k patches/s host to host, the PCIe limit); pageable
-    # patches of the right dtype are copied by the runtime's own staging (this thread blocks, the queued kernels do
-    # not: 120 k patches/s); patches that need a dtype conversion go through two pinned staging buffers.  The result
-    # arrays are allocated pinned (25 GB/s to allocate) unless they exceed DM_PINNED_RESULT_BYTES (default 16 GiB; then
-    # pageable, pre-faulted by a parallel fill, and written by blocking copies on a helper thread).
-    from concurrent.futures import ThreadPoolExecutor
-    bs = int(min(batch_size, N))
-    in_dtype = patches.dtype if zscore_on_device else torch.float32
-    pin_cap = int(os.environ.get("DM_PINNED_RESULT_BYTES", str(16 << 30)))
-    res = [None, None]
-    with torch.no_grad(), torch.cuda.device(device), ThreadPoolExecutor(1) as helper:   # (non-zero gpu ids: patch_VAE.py:422)
-        compute = torch.cuda.current_stream()
-        s_in, s_out = torch.cuda.Stream(), torch.cuda.Stream()
-        shape = (bs,) + tuple(patches.shape[1:])
-        x_dev = [torch.empty(shape, dtype=in_dtype, device=device) for _ in range(2)]
-        convert = patches.dtype != in_dtype
-        in_pin = [torch.empty(shape, dtype=in_dtype, pin_memory=True) for _ in range(2)] if convert else None
-        ev_in = [torch.cuda.Event() for _ in range(2)]          # the batch has reached x_dev[k]
-        ev_done = [torch.cuda.Event() for _ in range(2)]        # the kernels reading x_dev[k] have finished
-        sent = [None, None]                                     # helper's future for the batch that last used slot k
 
-        def hand_back(lo, n, z_b, z_a, ev):
-            with torch.cuda.device(device), torch.cuda.stream(s_out):
-                s_out.wait_event(ev)
-                res[0][lo:lo + n].copy_(z_b, non_blocking=True)     # asynchronous into pinned results; into pageable ones
-                res[1][lo:lo + n].copy_(z_a, non_blocking=True)     # it blocks, but only this helper thread
+    def step(x):
+        if zscore_on_device:
+            x = ops.zscore_patch(x)
+        z_b, join = encode(x)
+        z_a, _, _ = E.vq_forward(codebook, z_b, float(model.commitment_cost), want_scalars=False)
+        if join is not None:
+            join()                                              # the running-statistics replay ran beside the quantiser
+        n = x.shape[0]
+        return z_b.reshape(n, -1), z_a.reshape(n, -1)
+    z_b, z_a = _pipelined([patches], [patches.dtype if zscore_on_device else torch.float32], step, device, batch_size)
+    return z_b.numpy(), z_a.numpy()
 
-        for it, lo in enumerate(range(0, N, bs)):
-            k = it & 1
-            n = min(bs, N - lo)
-            if sent[k] is not None:
-                sent[k].result()                                # at most two batches of latents wait on the device
-            src = patches[lo:lo + n]
-            if convert:
-                ev_in[k].synchronize()                          # staging buffer k has left for the device
-                in_pin[k][:n].copy_(src)                        # host: the reference's .float() (patch_VAE.py:419)
-                src = in_pin[k][:n]
-            with torch.cuda.stream(s_in):
-                s_in.wait_event(ev_done[k])                     # x_dev[k] is no longer being read (no-op the first time)
-                x_dev[k][:n].copy_(src, non_blocking=True)      # (pageable source: blocks this thread until it has left)
-                ev_in[k].record(s_in)
-            compute.wait_event(ev_in[k])
-            x = x_dev[k][:n]
-            if zscore_on_device:
-                x = ops.zscore_patch(x)
-            z_b, join = encode(x)
-            z_a, _, _ = E.vq_forward(codebook, z_b, float(model.commitment_cost), want_scalars=False)
-            if join is not None:
-                join()                                          # the running-statistics replay ran beside the quantiser
-            ev_done[k].record(compute)
-            z_b, z_a = z_b.reshape(n, -1), z_a.reshape(n, -1)
-            if res[0] is None:
-                pinned = 4 * N * (z_b.shape[1] + z_a.shape[1]) <= pin_cap
-                for q, zq in enumerate((z_b, z_a)):
-                    if pinned:
-                        try:
-                            res[q] = torch.empty((N, zq.shape[1]), dtype=torch.float32, pin_memory=True)
-                            continue
-                        except RuntimeError:                    # the host refuses to pin that much: pageable results
-                            pinned = False
-                    res[q] = torch.empty((N, zq.shape[1]), dtype=torch.float32).fill_(0)
-            z_b.record_stream(s_out)
-            z_a.record_stream(s_out)
-            sent[k] = helper.submit(hand_back, lo, n, z_b, z_a, ev_done[k])
-        for f in sent:
-            if f is not None:
-                f.result()
-        s_out.synchronize()
-    return res[0].numpy(), res[1].numpy()
+
+SCORE_KEYS = ("recon_loss", "recon_loss_per_channel", "commitment_loss", "perplexity", "total_loss", "z_before", "z_after")
+
+
+def score_patches(model, patches, masks=None, device="cuda:0", batch_size=1024, zscore_on_device=False,
+                  return_decoded=False, return_code_counts=False):
+    """What the reference's `model(patches[i:i+1], batch_mask=masks[i:i+1])` returns in its loss dict, for every patch, in
+    batched passes (plot_scripts/recon_loss.py loops that call over 5000 single patches; process_VAE(save_output=True) over
+    20).  The model is in the mode it is handed: train mode = every BatchNorm with the patch's own statistics (running
+    statistics advance as N batch-of-one calls), eval mode = running statistics, as in encode_patches.
+    patches (N, C, H, W) and masks (N, 1 or C, H, W) or None: host tensors / arrays.  Returns a dict of numpy arrays in input
+    order: recon_loss (N,), recon_loss_per_channel (N, C), commitment_loss (N,), perplexity (N,), total_loss (N,) =
+    weight_recon * recon + weight_commitment * commitment (VQ_VAE_z32: recon + commitment; a batch of one carries no
+    time-matching term), z_before / z_after (N, D*h*w) exactly as encode_patches returns them, code_counts (N, K) int32
+    (return_code_counts) and decoded (N, C, H, W) (return_decoded).  Every value of a patch is the same to the bit whatever
+    batch_size, its position and its neighbours."""
+    from . import ops
+    from .vq_vae import VQ_VAE, VQ_VAE_z32
+    patches = torch.as_tensor(patches)
+    if patches.dim() != 4:
+        raise AssertionError("dataset tensor dimension can only be 4, not {}".format(patches.dim()))
+    N, C, H, W = patches.shape
+    if masks is not None:
+        masks = torch.as_tensor(masks)
+        if masks.dim() != 4 or masks.shape[0] != N or masks.shape[1] not in (1, C) or tuple(masks.shape[2:]) != (H, W):
+            raise ValueError("score_patches: masks must be (N, 1 or C, H, W) for patches (N, C, H, W); got {} for {}".format(
+                tuple(masks.shape), tuple(patches.shape)))
+    if not isinstance(model, (VQ_VAE, VQ_VAE_z32)):
+        raise TypeError("score_patches: {} is not built on the HIP path (VQ_VAE, VQ_VAE_z16, VQ_VAE_z32)".format(
+            type(model).__name__))
+    if N == 0:
+        out = {k: np.zeros((0, C) if k == "recon_loss_per_channel" else ((0, 0) if k.startswith("z_") else (0,)), np.float32)
+               for k in SCORE_KEYS}
+        if return_code_counts:
+            out["code_counts"] = np.zeros((0, model.vq.w.weight.shape[0]), np.int32)
+        if return_decoded:
+            out["decoded"] = np.zeros((0, C, H, W), np.float32)
+        return out
+    encode, codebook = _patch_encoder(model)
+    device = torch.device(device)
+    cc = float(model.commitment_cost)
+    z32 = isinstance(model, VQ_VAE_z32)
+    if z32:
+        dec = model.dec                     # children 0: ResidualBlock; 1/2/4: ConvTranspose, BatchNorm, ConvTranspose
+        w_recon = w_commit = 1.0            # vae.py:457
+    else:
+        layers = E.Layers(model)
+        w_recon, w_commit = float(model.weight_recon), float(model.weight_commitment)
+
+    def step(x, m=None):
+        if zscore_on_device:
+            x = ops.zscore_patch(x)
+        n = x.shape[0]
+        z_b, join = encode(x)
+        z_a, idx, _ = E.vq_forward(codebook, z_b, cc, want_scalars=False)
+        vqs, counts = ops.vq_patch_scalars(z_b, idx, codebook.detach(), cc, want_counts=return_code_counts)
+        if z32:
+            defer = []
+            r, _ = E.residual_forward(dec[0]._handles(), z_a, True, defer)
+            decoded, _ = E.z32_tail_forward(dec[1], dec[2], dec[4], r, None, None, model.channel_var, per_sample=True, defer=defer)
+            ops.bn_running_replay(defer)
+            sums = ops.recon_loss_per_sample(decoded, x, m, model.channel_var.detach().reshape(-1))
+        else:
+            decoded, sums = E.decoder_score(layers, z_a, x, m, want_decoded=return_decoded)
+        out = ops.score_finalize(sums, vqs, w_recon, w_commit, C * H * W)
+        if join is not None:
+            join()
+        outs = [out, z_b.reshape(n, -1), z_a.reshape(n, -1)]
+        if return_code_counts:
+            outs.append(counts)
+        if return_decoded:
+            outs.append(decoded)
+        return tuple(outs)
+    inputs, dtypes = [patches], [patches.dtype if zscore_on_device else torch.float32]
+    if masks is not None:
+        inputs.append(masks)
+        dtypes.append(torch.float32)
+    res = [r.numpy() for r in _pipelined(inputs, dtypes, step, device, batch_size)]
+    sc = res[0]
+    out = {"recon_loss": sc[:, 0].copy(), "commitment_loss": sc[:, 1].copy(), "total_loss": sc[:, 2].copy(),
+           "perplexity": sc[:, 3].copy(), "recon_loss_per_channel": sc[:, 4:].copy(), "z_before": res[1], "z_after": res[2]}
+    rest = res[3:]
+    if return_code_counts:
+        out["code_counts"], rest = rest[0], rest[1:]
+    if return_decoded:
+        out["decoded"] = rest[0]
+    return out
 
 
 def encode_patches_sharded(model, patches, device="cuda:0", batch_size=1024, zscore_on_device=False, group=None, dst=0):
@@ -143,6 +255,95 @@ def encode_patches_sharded(model, patches, device="cuda:0", batch_size=1024, zsc
     lo, hi = D.shard_range(patches.shape[0], rank, world)
     z_b, z_a = encode_patches(model, patches[lo:hi], device=device, batch_size=batch_size, zscore_on_device=zscore_on_device)
     return D.gather_shards((z_b, z_a), group=group, dst=dst) if world > 1 else (z_b, z_a)
+
+
+def score_patches_sharded(model, patches, masks=None, device="cuda:0", batch_size=1024, zscore_on_device=False,
+                          return_decoded=False, return_code_counts=False, group=None, dst=0):
+    """score_patches over a torch.distributed group, the twin of encode_patches_sharded: rank r scores the contiguous shard
+    dist.shard_range(N, r, world) (per-patch values do not depend on the batch they ran in) and the arrays are handed over on
+    the host to rank `dst` in rank order = input order; the other ranks return None."""
+    from . import dist as D
+    import torch.distributed as tdist
+    patches = torch.as_tensor(patches)
+    world = D.world_size(group)
+    rank = tdist.get_rank(group) if world > 1 else 0
+    lo, hi = D.shard_range(patches.shape[0], rank, world)
+    out = score_patches(model, patches[lo:hi], masks=None if masks is None else torch.as_tensor(masks)[lo:hi], device=device,
+                        batch_size=batch_size, zscore_on_device=zscore_on_device, return_decoded=return_decoded,
+                        return_code_counts=return_code_counts)
+    if world == 1:
+        return out
+    keys = sorted(out)
+    full = D.gather_shards(tuple(out[k] for k in keys), group=group, dst=dst)
+    return None if full is None else dict(zip(keys, full))
+
+
+def _load_well(raw_folder, sites, on_dev):
+    """(well, file paths, patches) as process_VAE reads them: z-scored on the host into pinned fp32 memory, or -- on_dev --
+    the raw float64 patches for dm_zscore_patch."""
+    assert len(set(site[:2] for site in sites)) == 1, "Sites should be from a single well/condition"
+    well = sites[0][:2]
+    with open(os.path.join(raw_folder, '%s_file_paths.pkl' % well), 'rb') as f:
+        fs = pickle.load(f)
+    with open(os.path.join(raw_folder, '%s_static_patches.pkl' % well), 'rb') as f:
+        dataset = pickle.load(f)
+    if on_dev:
+        dataset = torch.from_numpy(np.ascontiguousarray(np.squeeze(dataset)))       # raw float64; z-scored per batch on the GPU
+    else:
+        dataset = torch.from_numpy(zscore_patch(np.squeeze(dataset)))
+        try:                                        # the .float() of patch_VAE.py:419, into pinned memory: the drivers
+            dataset = torch.empty(dataset.shape, dtype=torch.float32, pin_memory=True).copy_(dataset)   # then run at the PCIe rate
+        except RuntimeError:
+            dataset = dataset.float()
+    assert dataset.dim() == 4, "dataset tensor dimension can only be 4, not {}".format(dataset.dim())
+    assert len(fs) == dataset.shape[0]
+    return well, fs, dataset
+
+
+def _load_model(config_, num_inputs, device, network_module=None):
+    le = config_.latent_encoding
+    if 'VAE' not in le.network:
+        raise ValueError('Network {} is not available'.format(le.network))
+    if network_module is None:
+        from . import vq_vae as network_module
+    model = getattr(network_module, le.network)(num_inputs=num_inputs,
+                                                num_hiddens=le.num_hiddens,
+                                                num_residual_hiddens=le.num_residual_hiddens,
+                                                num_residual_layers=2,
+                                                num_embeddings=le.num_embeddings,
+                                                gpu=True).to(device)
+    try:
+        model.load_state_dict(torch.load(os.path.join(le.weights, 'model.pt'), map_location=device))
+    except Exception as ex:
+        print(ex)
+        raise ValueError("Error in loading model weights for VQ-VAE")
+    return model
+
+
+def score_VAE(raw_folder, supp_folder, sites, config_, gpu=0, **kwargs):
+    """Per-patch losses and code usage of a well: reads what process_VAE reads (<raw>/<well>_file_paths.pkl,
+    <well>_static_patches.pkl, <weights>/model.pt) plus, with use_mask=True, <raw>/<well>_static_patches_mask.pkl (the
+    training pipeline's batch_mask source); writes <raw>/<model_name>/<well>_patch_scores.pkl: score_patches' dict of arrays
+    (protocol 4).  kwargs: use_mask, batch_size, zscore_on_device, return_decoded, return_code_counts, network_module."""
+    le = config_.latent_encoding
+    assert len(le.channels) > 0, "At least one channel must be specified"
+    output_dir = os.path.join(raw_folder, os.path.basename(le.weights))
+    os.makedirs(output_dir, exist_ok=True)
+    on_dev = bool(kwargs.get("zscore_on_device", False))
+    well, fs, dataset = _load_well(raw_folder, sites, on_dev)
+    masks = None
+    if kwargs.get("use_mask", False):
+        with open(os.path.join(raw_folder, '%s_static_patches_mask.pkl' % well), 'rb') as f:
+            masks = np.asarray(pickle.load(f))
+        masks = torch.from_numpy(np.ascontiguousarray(masks.reshape((masks.shape[0], -1) + tuple(dataset.shape[2:])))).float()
+    device = torch.device('cuda:%d' % gpu)
+    model = _load_model(config_, dataset.shape[1], device, kwargs.get("network_module"))
+    scores = score_patches(model, dataset, masks=masks, device=device, batch_size=kwargs.get("batch_size", 1024),
+                           zscore_on_device=on_dev, return_decoded=bool(kwargs.get("return_decoded", False)),
+                           return_code_counts=bool(kwargs.get("return_code_counts", False)))
+    with open(os.path.join(output_dir, '%s_patch_scores.pkl' % well), 'wb') as f:
+        pickle.dump(scores, f, protocol=4)
+    return scores
 
 
 def process_VAE(raw_folder, supp_folder, sites, config_, gpu=0, network_module=None, **kwargs):

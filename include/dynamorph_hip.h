@@ -513,6 +513,46 @@ int dm_recon_loss_backward(const float *decoded, const float *x, const float *ma
                            const float *channel_var, const float *gscale_dev, float *g_decoded,
                            double *bias_slabs, int B, int NIN, int H, int W, void *stream);
 
+/* ===== per-patch scores (what model.forward(sample) returns for ONE patch, for every patch of a batch) ==========
+ * plot_scripts/recon_loss.py and process_VAE(save_output=True) call the model on single patches and keep its loss dict; the
+ * batched kernels above keep one partial sum per persistent workgroup and one code histogram per call, which mix patches.
+ * Every value below belongs to one patch and is summed in an order fixed by the patch's own shape (no float atomics, no
+ * slab that can hold two patches): it is the same to the bit whatever the batch size, the patch's position in the batch
+ * and its neighbours.  All four entries only enqueue and never allocate. */
+
+/* dm_dec_tail_forward's arithmetic (same operands, same supported shapes: dm_dec_tail_supported) with the loss partials
+ * kept per patch and channel: patch_sums[B][NIN] doubles = sum over the patch of (decoded*m - x*m)^2 / channel_var[c].
+ * x is required.  decoded = NULL: it is never written (196 608 B/patch of traffic at 128 x 128 x 2 instead of 327 680);
+ * where given, it is bit-equal to dm_dec_tail_forward's.  Two launches: each wave's sum over its rows of a tile goes to
+ * workspace[tile][wave][NIN] doubles, then a patch's tiles are added in index order.  A lane runs dm_dec_tail_forward's own
+ * fp32 chain over its terms of the tile and credits each step's increment, taken exactly in double, to the step's channel;
+ * all further sums are double.  Summed over channels and patches, patch_sums therefore equals the sum of
+ * dm_dec_tail_forward's loss_slabs up to the order of double additions.  workspace: dm_dec_tail_score_workspace_bytes(B, NIN, H2, W2) bytes, 8-byte aligned. */
+size_t dm_dec_tail_score_workspace_bytes(int B, int NIN, int H2, int W2);
+int dm_dec_tail_score(const float *d2, const float *w4, const float *b4, const float *w6, const float *b6,
+                      const float *x, const float *mask, int mask_channels, const float *channel_var,
+                      float *decoded, double *patch_sums, void *workspace, size_t workspace_bytes,
+                      int B, int C2, int NIN, int H2, int W2, void *stream);
+
+/* The same sums from a stored `decoded` (VQ_VAE_z32 and every width the fused tail is not built for): patch_sums[B][NIN]
+ * doubles, dm_recon_loss's arithmetic per element, one workgroup per (patch, channel) plane.  Any H and W. */
+int dm_recon_loss_per_sample(const float *decoded, const float *x, const float *mask, int mask_channels,
+                             const float *channel_var, double *patch_sums, int B, int NIN, int H, int W, void *stream);
+
+/* The quantiser's scalars per patch (vq_vae.py:74-82 on a batch of one): z (B,D,H,W), idx (B,H,W) as dm_vq_forward wrote
+ * them, codebook (K,D).  scalars[B][3] = (loss = mse + cc*mse, perplexity, mse) with mse over the patch's own D*H*W
+ * latents -- sum (codebook[idx] - z)^2 in double -- and the perplexity from its own H*W codes (dm_vq_finalize's
+ * arithmetic).  counts[B][K] int32 = the patch's code histogram (NULL: not written).  Any D, K, H, W: one workgroup per
+ * patch, integer counters in LDS, codebooks beyond 4096 codes walk windows of 4096. */
+int dm_vq_patch_scalars(const float *z, const int64_t *idx, const float *codebook, float commitment_cost,
+                        float *scalars, int32_t *counts, int B, int D, int K, int H, int W, void *stream);
+
+/* out[B][4 + NIN] = (recon, commitment, total, perplexity, recon per channel) from patch_sums and dm_vq_patch_scalars'
+ * scalars: recon = sum_c S[b][c] / chw rounded to float once, recon per channel = S[b][c] / (chw / NIN), total =
+ * w_recon*recon + w_commit*commitment.  chw = NIN*H*W of one patch. */
+int dm_score_finalize(const double *patch_sums, const float *vq_scalars, float weight_recon, float weight_commitment,
+                      int64_t chw, float *out, int B, int NIN, void *stream);
+
 /* ===== time-matching loss (vq_vae.py:324-332, vae.py:322-336) ================= */
 
 /* sim[i][j] = mean_d (z[i][d] - z[j][d])^2 for the B flattened latents z (B, n) -- the reference's
