@@ -25,17 +25,10 @@ from types import SimpleNamespace
 import torch
 
 from . import ops
-from .ops import (DM_LOAD_AFFINE, DM_LOAD_AFFINE2, DM_LOAD_AFFINE_RELU, DM_LOAD_IDENT, DM_LOAD_RELU, Op,
-                  weight_view)
+from .ops import DM_LOAD_AFFINE, DM_LOAD_AFFINE2, DM_LOAD_AFFINE_RELU, DM_LOAD_IDENT, DM_LOAD_RELU, Op, weight_view
 
 
-# DM_FUSED_BACKWARD=0 in the environment: the two-kernel backward of enc.4 (A/B measurements)
-import os as _os
-LATENT_TAIL = _os.environ.get("DM_LATENT_TAIL", "1") != "0"
-# ... starting one layer earlier, at enc.7: built and tested, but measured slower (C2 0.354 vs 0.320 ms: the 46 KB input
-# tile of the strided convolution is staged twice per patch with its loads exposed, and the instantiation spills) -- opt-in
-LATENT_TAIL_E7 = _os.environ.get("DM_LATENT_TAIL_E7", "0") == "1"
-FUSED_BACKWARD = _os.environ.get("DM_FUSED_BACKWARD", "1") != "0"
+FUSED_BACKWARD = True     # False: the two-launch pairs everywhere (two tests in test_gpu_model.py monkeypatch it)
 
 
 class Layers:
@@ -109,17 +102,20 @@ class BnSync:
         self.fwd = {}                     # BatchNorm module -> its all-reduced forward payload (the global count)
 
     def forward(self, stats, bn, count):
-        momentum = 0.1 if bn.momentum is None else bn.momentum
         payload = ops.bn_sync_pack(stats, count, self.weights[0:1])
         self.exchange(payload)
         self.fwd[bn] = payload
         return ops.bn_finalize_payload(payload, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var,
-                                       bn.num_batches_tracked, momentum, bn.eps)
+                                       bn.num_batches_tracked, _momentum(bn), bn.eps)
 
     def backward(self, stats, bn, saved, G):
         payload = ops.bn_backward_pack(stats, saved, self.weights[1:2], G(bn.weight), G(bn.bias))
         self.exchange(payload)
         return ops.bn_backward_payload(payload, self.fwd[bn], bn.weight.detach(), saved, self.weights[1:2])
+
+
+def _momentum(bn):
+    return 0.1 if bn.momentum is None else bn.momentum
 
 
 def _bn_coef(stats, bn, count, per_sample, nbatch, defer=None):
@@ -136,10 +132,9 @@ def _bn_coef(stats, bn, count, per_sample, nbatch, defer=None):
         if per_sample:
             return coef, None
         return coef, torch.stack([bn.running_mean, invstd], 1).contiguous()     # what _bn_backward takes in eval() mode
-    momentum = 0.1 if bn.momentum is None else bn.momentum
     spg = stats.shape[0] // nbatch if per_sample else 1
     return ops.bn_finalize(stats, count, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var,
-                           bn.num_batches_tracked, momentum, bn.eps, per_sample=per_sample, slabs_per_group=spg,
+                           bn.num_batches_tracked, _momentum(bn), bn.eps, per_sample=per_sample, slabs_per_group=spg,
                            defer=defer if per_sample else None)
 
 
@@ -147,12 +142,41 @@ def _w(p):
     return p.detach()
 
 
-def _bn_backward(stats, count, bn, saved, G):
-    """native_batch_norm_backward's reductions for `bn` from the (sum dy, sum dy * a) slabs -> the AFFINE2 coefficients of
-    da; eval() mode (fixed statistics: count 0) keeps only da = gamma * invstd * dy."""
+def view_strides(shape, swapped):
+    """(sn, sc, sky, skx, off) of the dm_weight_view of a contiguous weight (A, Bc, k, k), k = 4, 3 or 1.  Stored order: the
+    output index is dim 0 (a Conv2d forward, a ConvTranspose2d's data gradient).  Swapped: the output index is dim 1 (a
+    Conv2d's data gradient, a ConvTranspose2d forward); the 3x3 taps are then flipped, the 4x4 ones are not -- the
+    phase-decomposed kernels do that themselves."""
+    _, bc, k, _ = shape
+    d0, d1 = bc * k * k, k * k
+    sky, skx = (k, 1) if k > 1 else (0, 0)
+    if not swapped:
+        return d0, d1, sky, skx, 0
+    if k == 3:
+        return d1, d0, -sky, -skx, 8
+    return d1, d0, sky, skx, 0
+
+
+def _view(w):
+    return weight_view(_w(w), *view_strides(w.shape, False))
+
+
+def _view_swapped(w):
+    return weight_view(_w(w), *view_strides(w.shape, True))
+
+
+def _bn_backward(stats, count, bn, saved, g, a, G, gbias=None, zero=True):
+    """One BatchNorm-backward step: native_batch_norm_backward's reductions for `bn` from the (sum g, sum g * a) slabs ->
+    da = BatchNorm backward of g as an AFFINE2 operand over the raw conv output a (its .coef: the coefficients); eval()
+    mode (fixed statistics: count 0) keeps only da = gamma * invstd * g.  gbias: the gradient of the conv bias that feeds
+    `bn`, written here (_fed_bias; None: the caller writes it where its launch belongs)."""
     if _bn_sync is not None and bn.training:
-        return _bn_sync.backward(stats, bn, saved, G)
-    return ops.bn_backward_finalize(stats, count if bn.training else 0, _w(bn.weight), saved, G(bn.weight), G(bn.bias))
+        c = _bn_sync.backward(stats, bn, saved, G)
+    else:
+        c = ops.bn_backward_finalize(stats, count if bn.training else 0, _w(bn.weight), saved, G(bn.weight), G(bn.bias))
+    if gbias is not None:
+        _fed_bias(gbias, bn, c, G, zero)
+    return Op(g, DM_LOAD_AFFINE2, c, p1=a)
 
 
 # ------------------------------------------------------------------------------- encoder
@@ -179,7 +203,7 @@ def encoder_forward(L, x, per_sample=False, e1=None, join=True, latents_only=Fal
     e1: e1_operands(L) computed by the caller (inference: once per call).
     latents_only (per_sample only): the caller wants z and the running statistics, nothing to differentiate through --
     the 16 x 16 part of the encoder (enc.10 .. enc.12) then is ONE launch that keeps a patch on its CU
-    (ops.latent_tail_forward; DM_LATENT_TAIL=0 in the environment keeps the layer-by-layer kernels).
+    (ops.latent_tail_forward) where that kernel is built.
     defer_last_join = K (training step only): when the quantiser can do it (ops.vq_forward_join_supported for K codes), the
     LAST residual join is left to the VectorQuantizer kernel's load path: the return value is then (None, cx) and
     cx.pending_join = (rb, h_in, coef) goes to vq_forward_joined, which also produces z.
@@ -195,57 +219,40 @@ def encoder_forward(L, x, per_sample=False, e1=None, join=True, latents_only=Fal
     # forward: K = 16*NIN; the ones channel of the composite is folded into a per-position bias table (bias_border)
     weff, border = e1 if e1 is not None else e1_operands(L)
     H1, W1 = H // 2, W // 2
-    a1, st = ops.conv4x4s2(Op(x), weight_view(weff, (NIN + 1) * 16, 16, 4, 1), B, NIN, c1, H, W,
-                           want_stats=True, bias_border=border, per_tile=ps)
+    a1, st = ops.conv4x4s2(Op(x), _view(weff), B, NIN, c1, H, W, want_stats=True, bias_border=border, per_tile=ps)
     coef1, saved1 = _bn_coef(st, L.bn1, H1 * W1 * (1 if ps else B), ps, B, defer)
 
     H2, W2 = H1 // 2, W1 // 2
-    a2, st = ops.conv4x4s2(Op(a1, DM_LOAD_AFFINE_RELU, coef1, per_sample=ps), weight_view(_w(L.enc4.weight), c1 * 16, 16, 4, 1),
-                           B, c1, nh, H1, W1, want_stats=True, bias=_w(L.enc4.bias), per_tile=ps)
+    a2, st = ops.conv4x4s2(Op(a1, DM_LOAD_AFFINE_RELU, coef1, per_sample=ps), _view(L.enc4.weight), B, c1, nh, H1, W1,
+                           want_stats=True, bias=_w(L.enc4.bias), per_tile=ps)
     coef2, saved2 = _bn_coef(st, L.bn2, H2 * W2 * (1 if ps else B), ps, B, defer)
 
     H3, W3 = H2 // 2, W2 // 2
     n3 = H3 * W3 * (1 if ps else B)
-    fuse_tail = (ps and latents_only and LATENT_TAIL and L.bn3.training and L.bn4.training
+    fuse_tail = (ps and latents_only and L.bn3.training and L.bn4.training
                  and all(bna.training and bnb.training for _, bna, _, bnb in L.res)
                  and ops.latent_tail_supported(nh, nrh, H3, W3, len(L.res)))
-    mom = lambda bn: 0.1 if bn.momentum is None else bn.momentum
-    res_args = lambda: [(_w(ca.weight), _w(ca.bias), _w(bna.weight), _w(bna.bias), bna.eps, _w(cb.weight), _w(cb.bias),
-                         _w(bnb.weight), _w(bnb.bias), bnb.eps) for ca, bna, cb, bnb in L.res]
-
-    def defer_tail(st4, sts):
-        defer.append((st4, 1, n3, L.bn4.running_mean, L.bn4.running_var, L.bn4.num_batches_tracked, mom(L.bn4)))
-        for (sa, sb), (_, bna, _, bnb) in zip(sts, L.res):
-            defer.append((sa, 1, n3, bna.running_mean, bna.running_var, bna.num_batches_tracked, mom(bna)))
-            defer.append((sb, 1, n3, bnb.running_mean, bnb.running_var, bnb.num_batches_tracked, mom(bnb)))
-    if fuse_tail and LATENT_TAIL_E7:
-        # enc.7 .. enc.12 of a patch in one workgroup, from a2 (csrc/latent_tail.hip, E7 form)
-        z, st4, sts, st3 = ops.latent_tail_forward(
-            None, None, _w(L.enc10.weight), _w(L.enc10.bias), _w(L.bn4.weight), _w(L.bn4.bias), L.bn4.eps, res_args(),
-            enc7=(a2, coef2, _w(L.enc7.weight), _w(L.enc7.bias), _w(L.bn3.weight), _w(L.bn3.bias), L.bn3.eps))
-        defer.append((st3, 1, n3, L.bn3.running_mean, L.bn3.running_var, L.bn3.num_batches_tracked, mom(L.bn3)))
-        defer_tail(st4, sts)
-        cx.__dict__.update(a1=a1, a2=a2, coef1=coef1, coef2=coef2, saved1=None, dims=(H1, W1, H2, W2, H3, W3))
-        _replay(cx, x, defer, join)
-        return z, cx
-    a3, st = ops.conv4x4s2(Op(a2, DM_LOAD_AFFINE_RELU, coef2, per_sample=ps), weight_view(_w(L.enc7.weight), nh * 16, 16, 4, 1),
-                           B, nh, nh, H2, W2, want_stats=True, bias=_w(L.enc7.bias), per_tile=ps)
+    a3, st = ops.conv4x4s2(Op(a2, DM_LOAD_AFFINE_RELU, coef2, per_sample=ps), _view(L.enc7.weight), B, nh, nh, H2, W2,
+                           want_stats=True, bias=_w(L.enc7.bias), per_tile=ps)
     coef3, saved3 = _bn_coef(st, L.bn3, n3, ps, B, defer)
+    cx.__dict__.update(a1=a1, a2=a2, a3=a3, coef1=coef1, coef2=coef2, coef3=coef3, saved1=None, dims=(H1, W1, H2, W2, H3, W3))
 
     if fuse_tail:
-        z, st4, sts = ops.latent_tail_forward(a3, coef3, _w(L.enc10.weight), _w(L.enc10.bias), _w(L.bn4.weight), _w(L.bn4.bias),
-                                              L.bn4.eps, res_args())
-        defer_tail(st4, sts)
-        cx.__dict__.update(a1=a1, a2=a2, a3=a3, coef1=coef1, coef2=coef2, coef3=coef3, saved1=None, dims=(H1, W1, H2, W2, H3, W3))
+        z, st4, sts = ops.latent_tail_forward(
+            a3, coef3, _w(L.enc10.weight), _w(L.enc10.bias), _w(L.bn4.weight), _w(L.bn4.bias), L.bn4.eps,
+            [(_w(ca.weight), _w(ca.bias), _w(bna.weight), _w(bna.bias), bna.eps, _w(cb.weight), _w(cb.bias),
+              _w(bnb.weight), _w(bnb.bias), bnb.eps) for ca, bna, cb, bnb in L.res])
+        bns = [L.bn4] + [bn for _, bna, _, bnb in L.res for bn in (bna, bnb)]
+        for slabs, bn in zip([st4] + [s for pair in sts for s in pair], bns):
+            defer.append((slabs, 1, n3, bn.running_mean, bn.running_var, bn.num_batches_tracked, _momentum(bn)))
         _replay(cx, x, defer, join)
         return z, cx
-    a4, st = ops.conv3x3(Op(a3, DM_LOAD_AFFINE_RELU, coef3, per_sample=ps), weight_view(_w(L.enc10.weight), nh * 9, 9, 3, 1),
-                         B, nh, nh, H3, W3, taps=9, want_stats=True, bias=_w(L.enc10.bias), per_tile=ps)
+    a4, st = ops.conv3x3(Op(a3, DM_LOAD_AFFINE_RELU, coef3, per_sample=ps), _view(L.enc10.weight), B, nh, nh, H3, W3,
+                         taps=9, want_stats=True, bias=_w(L.enc10.bias), per_tile=ps)
     coef4, saved4 = _bn_coef(st, L.bn4, n3, ps, B, defer)
     h = ops.apply(Op(a4, DM_LOAD_AFFINE, coef4, per_sample=ps), B, nh, H3, W3)
 
-    cx.__dict__.update(a1=a1, a2=a2, a3=a3, a4=a4, coef1=coef1, coef2=coef2, coef3=coef3, coef4=coef4,
-                       saved1=saved1, saved2=saved2, saved3=saved3, saved4=saved4, dims=(H1, W1, H2, W2, H3, W3))
+    cx.__dict__.update(a4=a4, coef4=coef4, saved1=saved1, saved2=saved2, saved3=saved3, saved4=saved4)
     fuse = bool(defer_last_join) and not ps and len(L.res) > 0 and L.res[-1][3].training and \
         ops.vq_forward_join_supported(nh, int(defer_last_join), H3, W3)
     z, cx.res = residual_forward(L.res, h, ps, defer, defer_last_join=fuse)
@@ -290,13 +297,13 @@ def residual_forward(res_layers, h, per_sample=False, defer=None, defer_last_joi
         defer = []
     for ca, bna, cb, bnb in res_layers:
         nrh = ca.weight.shape[0]
-        ra, st = ops.conv3x3(Op(h, DM_LOAD_RELU), weight_view(_w(ca.weight), nh * 9, 9, 3, 1), B, nh, nrh, H, W, taps=9,
-                             want_stats=True, bias=_w(ca.bias), per_tile=per_sample)
+        ra, st = ops.conv3x3(Op(h, DM_LOAD_RELU), _view(ca.weight), B, nh, nrh, H, W, taps=9, want_stats=True, bias=_w(ca.bias),
+                             per_tile=per_sample)
         if per_sample:
             _need_per_sample_slabs(st, B, "residual_forward: 3x3 convolution %d -> %d at %d x %d" % (nh, nrh, H, W))
         coefa, saveda = _bn_coef(st, bna, n, per_sample, B, defer)
-        rb, st = ops.conv3x3(Op(ra, DM_LOAD_AFFINE_RELU, coefa, per_sample=per_sample), weight_view(_w(cb.weight), nrh, 1, 0, 0),
-                             B, nrh, nh, H, W, taps=1, want_stats=True, bias=_w(cb.bias), per_tile=per_sample)
+        rb, st = ops.conv3x3(Op(ra, DM_LOAD_AFFINE_RELU, coefa, per_sample=per_sample), _view(cb.weight), B, nrh, nh, H, W,
+                             taps=1, want_stats=True, bias=_w(cb.bias), per_tile=per_sample)
         if per_sample:
             _need_per_sample_slabs(st, B, "residual_forward: 1x1 convolution %d -> %d at %d x %d" % (nrh, nh, H, W))
         coefb, savedb = _bn_coef(st, bnb, n, per_sample, B, defer)
@@ -320,9 +327,18 @@ def _fed_bias(gbias, bn, coef_bwd, G, zero=True):
         torch.mul(coef_bwd[:, 0], G(bn.bias), out=gbias)
 
 
-def _zero(t, do=True):
-    if do:
-        t.zero_()
+def _conv_backward_pair(dy, x, xcoef, w, gw, B, CD, CX, H, W, k, pending, like, stat_q, resid=None, want_stats=True,
+                        between=lambda: None):
+    """The two-launch backward of a Conv2d CX -> CD (k = 3, 1: same size; k = 4: stride 2), for the shapes its fused kernel is
+    not built for: the weight gradient of dy (B,CD,H,W) against the conv's input relu(BN(x)) (xcoef None: relu(x)), then the
+    data gradient with that ReLU's mask, the residual branch `resid` and the (sum, sum * stat_q) slabs for the BatchNorm
+    below.  between: a bias gradient whose launch sits between the two.  Returns (dx, stats)."""
+    xin, mask = (Op(x, DM_LOAD_RELU), Op(x)) if xcoef is None else (Op(x, DM_LOAD_AFFINE_RELU, xcoef), Op(x, DM_LOAD_AFFINE, xcoef))
+    ops.wgrad(dy, xin, gw, B, CD, CX, H, W, k, pending=pending)
+    between()
+    # (stride 2 backwards is the phase-decomposed transposed convolution: 4 phases x CX outputs, pixel-shuffled)
+    return ops.conv3x3(dy, _view_swapped(w), B, CD, 4 * CX if k == 4 else CX, H, W, taps=9 if k == 4 else k * k, pixel_shuffle=k == 4,
+                       want_stats=want_stats, like=like, mask=mask, resid=resid, stat_q=stat_q)
 
 
 def residual_backward(res_layers, saved, g_h, G, q_below, pending=None, zero_fed_biases=True):
@@ -340,28 +356,22 @@ def residual_backward(res_layers, saved, g_h, G, q_below, pending=None, zero_fed
         nrh = ca.weight.shape[0]
         if s.savedb is None or s.coefb.dim() != 2:
             raise NotImplementedError("backward needs batch-statistics BatchNorm (train mode, per_sample=False)")
-        cb_bwd = _bn_backward(stats, cnt, bnb, s.savedb, G)
-        da_rb = Op(g_h, DM_LOAD_AFFINE2, cb_bwd, p1=s.rb)
-        _fed_bias(G(cb.bias), bnb, cb_bwd, G, zero_fed_biases)
+        da_rb = _bn_backward(stats, cnt, bnb, s.savedb, g_h, s.rb, G, G(cb.bias), zero_fed_biases)
         if FUSED_BACKWARD and s.coefa.dim() == 2 and ops.conv1x1_bwd_fused_supported(nh, nrh, H, W):
             # the 1x1 convolution's data and weight gradient from ONE staging of (g_h, rb, ra) -- csrc/conv1x1_bwd.hip
             dy_ra, st = ops.conv1x1_bwd_fused(da_rb, s.ra, s.coefa, _w(cb.weight), G(cb.weight), B, nh, nrh, H, W, pending=pending)
         else:
-            ops.wgrad(da_rb, Op(s.ra, DM_LOAD_AFFINE_RELU, s.coefa), G(cb.weight), B, nh, nrh, H, W, 1, pending=pending)
-            dy_ra, st = ops.conv3x3(da_rb, weight_view(_w(cb.weight), 1, nrh, 0, 0), B, nh, nrh, H, W, taps=1, want_stats=True,
-                                    like=g_h, mask=Op(s.ra, DM_LOAD_AFFINE, s.coefa), stat_q=s.ra)
-        ca_bwd = _bn_backward(st, cnt, bna, s.saveda, G)
-        da_ra = Op(dy_ra, DM_LOAD_AFFINE2, ca_bwd, p1=s.ra)
-        _fed_bias(G(ca.bias), bna, ca_bwd, G, zero_fed_biases)
+            dy_ra, st = _conv_backward_pair(da_rb, s.ra, s.coefa, cb.weight, G(cb.weight), B, nh, nrh, H, W, 1, pending, like=g_h,
+                                            stat_q=s.ra)
+        da_ra = _bn_backward(st, cnt, bna, s.saveda, dy_ra, s.ra, G, G(ca.bias), zero_fed_biases)
         q = saved[i - 1].rb if i > 0 else q_below
         if FUSED_BACKWARD and ops.conv3x3_bwd_fused_supported(nrh, nh, H, W):
             # the 3x3 convolution's data and weight gradient from ONE staging of the patch -- csrc/conv3x3_bwd.hip
             g_h, stats = ops.conv3x3_bwd_fused(da_ra, s.h_in, None, _w(ca.weight), G(ca.weight), B, nrh, resid=g_h, q=q,
                                                want_stats=q is not None, pending=pending)
         else:
-            ops.wgrad(da_ra, Op(s.h_in, DM_LOAD_RELU), G(ca.weight), B, nrh, nh, H, W, 3, pending=pending)
-            g_h, stats = ops.conv3x3(da_ra, weight_view(_w(ca.weight), 9, nh * 9, -3, -1, off=8), B, nrh, nh, H, W, taps=9,
-                                     want_stats=q is not None, like=g_h, mask=Op(s.h_in), resid=g_h, stat_q=q)
+            g_h, stats = _conv_backward_pair(da_ra, s.h_in, None, ca.weight, G(ca.weight), B, nrh, nh, H, W, 3, pending, like=g_h,
+                                             stat_q=q, resid=g_h, want_stats=q is not None)
     return g_h, stats
 
 
@@ -381,62 +391,54 @@ def encoder_backward(L, cx, g_z, G, zero_fed_biases=True, pending_extra=(), want
 
     g_h, stats = residual_backward(L.res, cx.res, g_z, G, cx.a4, pending=pending, zero_fed_biases=zero_fed_biases)
     cnt3 = B * H3 * W3
-    c4b = _bn_backward(stats, cnt3, L.bn4, cx.saved4, G)
-    da4 = Op(g_h, DM_LOAD_AFFINE2, c4b, p1=cx.a4)
-    _fed_bias(G(L.enc10.bias), L.bn4, c4b, G, zero_fed_biases)
+    da4 = _bn_backward(stats, cnt3, L.bn4, cx.saved4, g_h, cx.a4, G, G(L.enc10.bias), zero_fed_biases)
     if FUSED_BACKWARD and cx.coef3.dim() == 2 and ops.conv3x3_bwd_fused_supported(nh, nh, H3, W3):
         # enc.10: data and weight gradient from ONE staging of the patch -- csrc/conv3x3_bwd.hip
-        dy3, st = ops.conv3x3_bwd_fused(da4, cx.a3, cx.coef3, _w(L.enc10.weight), G(L.enc10.weight), B, nh, q=cx.a3,
-                                        pending=pending)
+        dy3, st = ops.conv3x3_bwd_fused(da4, cx.a3, cx.coef3, _w(L.enc10.weight), G(L.enc10.weight), B, nh, q=cx.a3, pending=pending)
     else:
-        ops.wgrad(da4, Op(cx.a3, DM_LOAD_AFFINE_RELU, cx.coef3), G(L.enc10.weight), B, nh, nh, H3, W3, 3, pending=pending)
-        dy3, st = ops.conv3x3(da4, weight_view(_w(L.enc10.weight), 9, nh * 9, -3, -1, off=8), B, nh, nh, H3, W3, taps=9,
-                              want_stats=True, like=g_h, mask=Op(cx.a3, DM_LOAD_AFFINE, cx.coef3), stat_q=cx.a3)
+        dy3, st = _conv_backward_pair(da4, cx.a3, cx.coef3, L.enc10.weight, G(L.enc10.weight), B, nh, nh, H3, W3, 3, pending,
+                                      like=g_h, stat_q=cx.a3)
 
-    c3b = _bn_backward(st, cnt3, L.bn3, cx.saved3, G)
-    da3 = Op(dy3, DM_LOAD_AFFINE2, c3b, p1=cx.a3)
-    _fed_bias(G(L.enc7.bias), L.bn3, c3b, G, zero_fed_biases)
+    da3 = _bn_backward(st, cnt3, L.bn3, cx.saved3, dy3, cx.a3, G, G(L.enc7.bias), zero_fed_biases)
     if FUSED_BACKWARD and cx.coef2.dim() == 2 and ops.conv4x4s2_bwd_fused_supported(nh, nh, H3, W3):
         # enc.7: data and weight gradient from ONE staging of the patch -- csrc/conv4x4s2_patch.hip
         dy2, st = ops.conv4x4s2_bwd_fused(da3, cx.a2, cx.coef2, _w(L.enc7.weight), G(L.enc7.weight), B, pending=pending)
     else:
-        ops.wgrad(da3, Op(cx.a2, DM_LOAD_AFFINE_RELU, cx.coef2), G(L.enc7.weight), B, nh, nh, H3, W3, 4, pending=pending)
-        dy2, st = ops.conv3x3(da3, weight_view(_w(L.enc7.weight), 16, nh * 16, 4, 1), B, nh, 4 * nh, H3, W3, taps=9,
-                              pixel_shuffle=True, want_stats=True, like=g_h, mask=Op(cx.a2, DM_LOAD_AFFINE, cx.coef2),
-                              stat_q=cx.a2)
+        dy2, st = _conv_backward_pair(da3, cx.a2, cx.coef2, L.enc7.weight, G(L.enc7.weight), B, nh, nh, H3, W3, 4, pending,
+                                      like=g_h, stat_q=cx.a2)
 
-    c2b = _bn_backward(st, B * H2 * W2, L.bn2, cx.saved2, G)
-    da2 = Op(dy2, DM_LOAD_AFFINE2, c2b, p1=cx.a2)
-    _fed_bias(G(L.enc4.bias), L.bn2, c2b, G, zero_fed_biases)
+    da2 = _bn_backward(st, B * H2 * W2, L.bn2, cx.saved2, dy2, cx.a2, G, G(L.enc4.bias), zero_fed_biases)
     if FUSED_BACKWARD and ops.conv_bwd_s2_fused_supported(nh, c1, H2, W2):
         # enc.4: data gradient + weight gradient from ONE staging of (dy2, a2, a1) -- csrc/conv_mfma.hip, kernel D
-        dy1, st = ops.conv_bwd_s2_fused(da2, Op(cx.a1, DM_LOAD_AFFINE_RELU, cx.coef1), weight_view(_w(L.enc4.weight), 16, c1 * 16, 4, 1),
+        dy1, st = ops.conv_bwd_s2_fused(da2, Op(cx.a1, DM_LOAD_AFFINE_RELU, cx.coef1), _view_swapped(L.enc4.weight),
                                         G(L.enc4.weight), B, nh, c1, H2, W2, mask=Op(cx.a1, DM_LOAD_AFFINE, cx.coef1),
                                         stat_q=cx.a1, pending=pending)
     else:
-        ops.wgrad(da2, Op(cx.a1, DM_LOAD_AFFINE_RELU, cx.coef1), G(L.enc4.weight), B, nh, c1, H2, W2, 4, pending=pending)
-        dy1, st = ops.conv3x3(da2, weight_view(_w(L.enc4.weight), 16, c1 * 16, 4, 1), B, nh, 4 * c1, H2, W2, taps=9,
-                              pixel_shuffle=True, want_stats=True, like=g_h, mask=Op(cx.a1, DM_LOAD_AFFINE, cx.coef1),
-                              stat_q=cx.a1)
+        dy1, st = _conv_backward_pair(da2, cx.a1, cx.coef1, L.enc4.weight, G(L.enc4.weight), B, nh, c1, H2, W2, 4, pending,
+                                      like=g_h, stat_q=cx.a1)
 
-    c1b = _bn_backward(st, B * H1 * W1, L.bn1, cx.saved1, G)
-    da1 = Op(dy1, DM_LOAD_AFFINE2, c1b, p1=cx.a1)
+    da1 = _bn_backward(st, B * H1 * W1, L.bn1, cx.saved1, dy1, cx.a1, G)
     dweff = torch.empty((c1, NIN + 1, 4, 4), device=x.device, dtype=torch.float32)
     ops.wgrad(da1, Op(x, ones=True), dweff, B, c1, NIN + 1, H1, W1, 4, pending=pending)
     ops.reduce_slabs_multi(pending)                  # all encoder weight gradients in one launch
-    ops.e1_chain(dweff, _w(L.enc0.weight), _w(L.enc0.bias), _w(L.enc1.weight),
-                 G(L.enc0.weight), G(L.enc0.bias), G(L.enc1.weight))
-    _fed_bias(G(L.enc1.bias), L.bn1, c1b, G, zero_fed_biases)
+    ops.e1_chain(dweff, _w(L.enc0.weight), _w(L.enc0.bias), _w(L.enc1.weight), G(L.enc0.weight), G(L.enc0.bias), G(L.enc1.weight))
+    _fed_bias(G(L.enc1.bias), L.bn1, da1.coef, G, zero_fed_biases)
     if want_dx:
         # a1 = conv(x, Weff[:, :NIN]) + border bias: dx = ConvTranspose(da1, Weff[:, :NIN]) (phase-decomposed kernel family;
         # the ones channel of the composite carries no gradient to x)
         weff, _ = e1_operands(L)
-        dx, _ = ops.conv3x3(da1, weight_view(weff, 16, (NIN + 1) * 16, 4, 1), B, c1, 4 * NIN, H1, W1, taps=9, pixel_shuffle=True)
+        dx, _ = ops.conv3x3(da1, _view_swapped(weff), B, c1, 4 * NIN, H1, W1, taps=9, pixel_shuffle=True)
         return dx
     return None
 
 
 # ------------------------------------------------------------------------------------ VQ
+def _vq_state(codebook, shape, slabs, ws, commitment_cost):
+    """What ops.vq_loss_finalize needs to produce the quantiser's scalars at the end of the step."""
+    B, D, H, W = shape
+    return SimpleNamespace(slabs=slabs, ws=ws, K=codebook.shape[0], D=D, positions=B * H * W, cc=commitment_cost)
+
+
 def vq_forward(codebook, z, commitment_cost, want_out=True, defer_scalars=False, want_scalars=True):
     """defer_scalars (training pass): no scalar launches here; the third return value is the state
     ops.vq_loss_finalize needs to produce them together with the reconstruction loss at the end of the step.
@@ -448,7 +450,7 @@ def vq_forward(codebook, z, commitment_cost, want_out=True, defer_scalars=False,
         return out, idx, None
     if defer_scalars:
         idx, out, slabs, ws = ops.vq_forward(z, _w(codebook), want_out=want_out, want_hist=False)
-        return out, idx, SimpleNamespace(slabs=slabs, ws=ws, K=codebook.shape[0], D=D, positions=B * H * W, cc=commitment_cost)
+        return out, idx, _vq_state(codebook, z.shape, slabs, ws, commitment_cost)
     idx, out, slabs, hist = ops.vq_forward(z, _w(codebook), want_out=want_out)
     scalars = ops.vq_finalize(slabs, hist, B * H * W, D, commitment_cost)     # (loss, perplexity, mse)
     return out, idx, scalars
@@ -459,9 +461,8 @@ def vq_forward_joined(codebook, pending_join, commitment_cost):
     it and writes both.  Returns (z, out, idx, state for ops.vq_loss_finalize) -- vq_forward(defer_scalars=True)'s contract
     plus the latents."""
     rb, h_in, coef = pending_join
-    B, D, H, W = rb.shape
     idx, out, slabs, ws, z = ops.vq_forward_join(rb, h_in, coef, _w(codebook))
-    return z, out, idx, SimpleNamespace(slabs=slabs, ws=ws, K=codebook.shape[0], D=D, positions=B * H * W, cc=commitment_cost)
+    return z, out, idx, _vq_state(codebook, rb.shape, slabs, ws, commitment_cost)
 
 
 # -------------------------------------------------------------------------------- decoder
@@ -480,8 +481,7 @@ def decoder_forward(L, zq, x=None, mask=None, defer_tail=False):
     if fused:
         # dec.4 + ReLU + dec.6 (+ loss) in one kernel; the 4 x 128 x 128 tensor d4 is never stored
         d4 = None
-        dec, slabs = ops.dec_tail_forward(d2, _w(L.dec4.weight), _w(L.dec4.bias), _w(L.dec6.weight), _w(L.dec6.bias),
-                                          x, mask, var)
+        dec, slabs = ops.dec_tail_forward(d2, _w(L.dec4.weight), _w(L.dec4.bias), _w(L.dec6.weight), _w(L.dec6.bias), x, mask, var)
     else:
         d4 = _dec4_forward(L, d2)
         if ops.head_supported(c2, L.dec6.weight.shape[0]):
@@ -489,8 +489,7 @@ def decoder_forward(L, zq, x=None, mask=None, defer_tail=False):
         else:
             # widths without a fused head: dec.6 as a plain 1x1 convolution, the loss as its own pass
             nin = L.dec6.weight.shape[0]
-            dec, _ = ops.conv3x3(Op(d4), weight_view(_w(L.dec6.weight), c2, 1, 0, 0), B, c2, nin, 8 * H3, 8 * W3, taps=1,
-                                 bias=_w(L.dec6.bias))
+            dec, _ = ops.conv3x3(Op(d4), _view(L.dec6.weight), B, c2, nin, 8 * H3, 8 * W3, taps=1, bias=_w(L.dec6.bias))
             slabs = ops.recon_loss(dec, x, mask, var) if x is not None else None
     cx = SimpleNamespace(zq=zq, d0=d0, d2=d2, d4=d4, dec=dec, x=x, mask=mask, loss_slabs=slabs, deferred=False)
     return dec, cx
@@ -500,16 +499,20 @@ def _dec_upsample(L, zq):
     """dec.0 + ReLU and dec.2 + ReLU: zq (B,nh,H3,W3) -> d0 (B,nh/2,2H3,2W3), d2 (B,nh/4,4H3,4W3)."""
     B, nh, H3, W3 = zq.shape
     c1, c2 = nh // 2, nh // 4
-    d0, _ = ops.conv3x3(Op(zq), weight_view(_w(L.dec0.weight), 16, c1 * 16, 4, 1), B, nh, 4 * c1, H3, W3, taps=9,
-                        pixel_shuffle=True, bias=_w(L.dec0.bias), relu=True)
-    d2, _ = ops.conv3x3(Op(d0), weight_view(_w(L.dec2.weight), 16, c2 * 16, 4, 1), B, c1, 4 * c2, 2 * H3, 2 * W3, taps=9,
-                        pixel_shuffle=True, bias=_w(L.dec2.bias), relu=True)
+    d0, _ = ops.conv3x3(Op(zq), _view_swapped(L.dec0.weight), B, nh, 4 * c1, H3, W3, taps=9, pixel_shuffle=True,
+                        bias=_w(L.dec0.bias), relu=True)
+    d2, _ = ops.conv3x3(Op(d0), _view_swapped(L.dec2.weight), B, c1, 4 * c2, 2 * H3, 2 * W3, taps=9, pixel_shuffle=True,
+                        bias=_w(L.dec2.bias), relu=True)
     return d0, d2
 
 
-def _dec_var(L, zq):
+def _var(channel_var, nin, device):
     # (model.dec called on its own has no loss and hence no channel variances)
-    return _w(L.channel_var).reshape(-1) if L.channel_var is not None else torch.ones(L.dec6.weight.shape[0], device=zq.device)
+    return _w(channel_var).reshape(-1) if channel_var is not None else torch.ones(nin, device=device)
+
+
+def _dec_var(L, zq):
+    return _var(L.channel_var, L.dec6.weight.shape[0], zq.device)
 
 
 def decoder_score(L, zq, x, mask=None, want_decoded=False):
@@ -530,9 +533,30 @@ def decoder_score(L, zq, x, mask=None, want_decoded=False):
 
 def _dec4_forward(L, d2):
     B, c2, H, W = d2.shape
-    d4, _ = ops.conv3x3(Op(d2), weight_view(_w(L.dec4.weight), 16, c2 * 16, 4, 1), B, c2, 4 * c2, H, W, taps=9,
-                        pixel_shuffle=True, bias=_w(L.dec4.bias), relu=True)
+    d4, _ = ops.conv3x3(Op(d2), _view_swapped(L.dec4.weight), B, c2, 4 * c2, H, W, taps=9, pixel_shuffle=True, bias=_w(L.dec4.bias),
+                        relu=True)
     return d4
+
+
+def _pending(pending):
+    """-> (the caller's list of (slabs, dst) pairs for the ONE slab reduction of its whole backward pass, a no-op), or for None
+    (a list of our own, its reduction launch): what to append to and what to call after the last append."""
+    if pending is not None:
+        return pending, lambda: None
+    own = []
+    return own, lambda: ops.reduce_slabs_multi(own)
+
+
+def _loss_gradient(dec, x, mask, var, gscale, gdec_ext):
+    """The gradient w.r.t. decoded -- of the reconstruction loss (gscale; None: no loss term) plus the upstream one (gdec_ext;
+    None: none) -- and the slabs of its channel sums (the last layer's bias gradient)."""
+    if gscale is None:
+        g, part = gdec_ext.contiguous(), None
+    else:
+        g, part = ops.recon_loss_backward(dec, x, mask, var, gscale)
+        if gdec_ext is not None:
+            g, part = g + gdec_ext, None
+    return g, part if part is not None else ops.channel_stats(g)
 
 
 def _head_backward_unfused(L, cx, d4, var, gscale, gdec_ext, G, pending):
@@ -540,16 +564,10 @@ def _head_backward_unfused(L, cx, d4, var, gscale, gdec_ext, G, pending):
     and the input gradient (masked by dec.4's ReLU, its channel sums = dec.4's bias gradient) as separate launches."""
     B, c2, H, W = d4.shape
     NIN = L.dec6.weight.shape[0]
-    if gscale is not None:
-        g, part = ops.recon_loss_backward(cx.dec, cx.x, cx.mask, var, gscale)
-        if gdec_ext is not None:
-            g, part = g + gdec_ext, None
-    else:
-        g, part = gdec_ext.contiguous(), None
-    ops.sum_slabs(part if part is not None else ops.channel_stats(g), G(L.dec6.bias))
+    g, sums = _loss_gradient(cx.dec, cx.x, cx.mask, var, gscale, gdec_ext)
+    ops.sum_slabs(sums, G(L.dec6.bias))
     ops.wgrad(Op(g), Op(d4), G(L.dec6.weight), B, NIN, c2, H, W, 1, pending=pending)
-    g4, st = ops.conv3x3(Op(g), weight_view(_w(L.dec6.weight), 1, c2, 0, 0), B, NIN, c2, H, W, taps=1, want_stats=True,
-                         mask=Op(d4))
+    g4, st = ops.conv3x3(Op(g), _view_swapped(L.dec6.weight), B, NIN, c2, H, W, taps=1, want_stats=True, mask=Op(d4))
     ops.sum_slabs(st, G(L.dec4.bias))
     return g4
 
@@ -563,10 +581,8 @@ def decoder_backward(L, cx, gscale, gdec_ext, G, want_gz=True, pending=None):
     B, nh, H3, W3 = zq.shape
     c1, c2 = nh // 2, nh // 4
     NIN = L.dec6.weight.shape[0]
-    var = _w(L.channel_var).reshape(-1) if L.channel_var is not None else torch.ones(NIN, device=zq.device)
-    own_pending = pending is None
-    if own_pending:
-        pending = []
+    var = _dec_var(L, zq)
+    pending, reduce = _pending(pending)
     if cx.deferred:
         if gdec_ext is not None or gscale is None:
             raise ValueError("decoder_backward: a deferred tail takes the reconstruction-loss gradient only")
@@ -588,8 +604,7 @@ def decoder_backward(L, cx, gscale, gdec_ext, G, want_gz=True, pending=None):
         else:
             g4 = _head_backward_unfused(L, cx, d4, var, gscale, gdec_ext, G, pending)
         ops.wgrad(Op(cx.d2), Op(g4), G(L.dec4.weight), B, c2, c2, 4 * H3, 4 * W3, 4, pending=pending)
-        g2, st = ops.conv4x4s2(Op(g4), weight_view(_w(L.dec4.weight), c2 * 16, 16, 4, 1), B, c2, c2, 8 * H3, 8 * W3,
-                               want_stats=True, mask=Op(cx.d2))
+        g2, st = ops.conv4x4s2(Op(g4), _view(L.dec4.weight), B, c2, c2, 8 * H3, 8 * W3, want_stats=True, mask=Op(cx.d2))
         ops.pend_stats(pending, st, [G(L.dec2.bias)])
     g2 = g2.contiguous()
     if FUSED_BACKWARD and ops.convT_bwd_fused_supported(c1, c2, 2 * H3, 2 * W3):
@@ -598,20 +613,18 @@ def decoder_backward(L, cx, gscale, gdec_ext, G, want_gz=True, pending=None):
                                      pending=pending)
     else:
         ops.wgrad(Op(cx.d0), Op(g2), G(L.dec2.weight), B, c1, c2, 2 * H3, 2 * W3, 4, pending=pending)
-        g0, st = ops.conv4x4s2(Op(g2), weight_view(_w(L.dec2.weight), c2 * 16, 16, 4, 1), B, c2, c1, 4 * H3, 4 * W3,
-                               want_stats=True, mask=Op(cx.d0))
+        g0, st = ops.conv4x4s2(Op(g2), _view(L.dec2.weight), B, c2, c1, 4 * H3, 4 * W3, want_stats=True, mask=Op(cx.d0))
     ops.pend_stats(pending, st, [G(L.dec0.bias)])         # bias gradients ride in the one slab reduction below
     g_zq = None
     if want_gz and FUSED_BACKWARD and ops.convT_bwd_fused_supported(nh, c1, H3, W3):
         g_zq, _ = ops.convT_bwd_fused(zq.contiguous(), g0, _w(L.dec0.weight), G(L.dec0.weight), pending=pending)     # dec.0 likewise
     else:
         ops.wgrad(Op(zq), Op(g0), G(L.dec0.weight), B, nh, c1, H3, W3, 4, pending=pending)
-    if own_pending:
-        ops.reduce_slabs_multi(pending)              # all decoder weight gradients in one launch
+    reduce()                                         # all decoder weight gradients in one launch
     if not want_gz:
         return None
     if g_zq is None:
-        g_zq, _ = ops.conv4x4s2(Op(g0), weight_view(_w(L.dec0.weight), c1 * 16, 16, 4, 1), B, c1, nh, 2 * H3, 2 * W3)
+        g_zq, _ = ops.conv4x4s2(Op(g0), _view(L.dec0.weight), B, c1, nh, 2 * H3, 2 * W3)
     return g_zq
 
 
@@ -627,11 +640,10 @@ def z32_stem_forward(conv0, bn0, conv1, bn1, x, per_sample=False):
     ps = per_sample
     c1, nh = conv0.weight.shape[0], conv1.weight.shape[0]
     H1, W1, H2, W2 = H // 2, W // 2, H // 4, W // 4
-    a1, st = ops.conv4x4s2(Op(x), weight_view(_w(conv0.weight), NIN * 16, 16, 4, 1), B, NIN, c1, H, W,
-                           want_stats=True, bias=_w(conv0.bias), per_tile=ps)
+    a1, st = ops.conv4x4s2(Op(x), _view(conv0.weight), B, NIN, c1, H, W, want_stats=True, bias=_w(conv0.bias), per_tile=ps)
     coef1, saved1 = _bn_coef(st, bn0, H1 * W1 * (1 if ps else B), ps, B)
-    a2, st = ops.conv4x4s2(Op(a1, DM_LOAD_AFFINE_RELU, coef1, per_sample=ps), weight_view(_w(conv1.weight), c1 * 16, 16, 4, 1),
-                           B, c1, nh, H1, W1, want_stats=True, bias=_w(conv1.bias), per_tile=ps)
+    a2, st = ops.conv4x4s2(Op(a1, DM_LOAD_AFFINE_RELU, coef1, per_sample=ps), _view(conv1.weight), B, c1, nh, H1, W1,
+                           want_stats=True, bias=_w(conv1.bias), per_tile=ps)
     coef2, saved2 = _bn_coef(st, bn1, H2 * W2 * (1 if ps else B), ps, B)
     h = ops.apply(Op(a2, DM_LOAD_AFFINE, coef2, per_sample=ps), B, nh, H2, W2)
     cx = SimpleNamespace(x=x, a1=a1, a2=a2, coef1=coef1, coef2=coef2, saved1=saved1, saved2=saved2, per_sample=ps,
@@ -648,26 +660,18 @@ def z32_stem_backward(conv0, bn0, conv1, bn1, cx, g_h, G, stats=None, pending=No
         raise NotImplementedError("backward through per-sample BatchNorm statistics with B > 1")
     B, NIN, c1, nh, H1, W1, H2, W2 = cx.dims
     g_h = g_h.contiguous()
-    own = pending is None
-    if own:
-        pending = []
+    pending, reduce = _pending(pending)
     if stats is None:
         stats = ops.channel_stats(g_h, cx.a2)
-    c2b = _bn_backward(stats, B * H2 * W2, bn1, cx.saved2, G)
-    da2 = Op(g_h, DM_LOAD_AFFINE2, c2b, p1=cx.a2)
-    ops.wgrad(da2, Op(cx.a1, DM_LOAD_AFFINE_RELU, cx.coef1), G(conv1.weight), B, nh, c1, H2, W2, 4, pending=pending)
-    _fed_bias(G(conv1.bias), bn1, c2b, G, zero_fed_biases)
-    dy1, st = ops.conv3x3(da2, weight_view(_w(conv1.weight), 16, c1 * 16, 4, 1), B, nh, 4 * c1, H2, W2, taps=9,
-                          pixel_shuffle=True, want_stats=True, like=g_h, mask=Op(cx.a1, DM_LOAD_AFFINE, cx.coef1),
-                          stat_q=cx.a1)
-    c1b = _bn_backward(st, B * H1 * W1, bn0, cx.saved1, G)
-    da1 = Op(dy1, DM_LOAD_AFFINE2, c1b, p1=cx.a1)
+    da2 = _bn_backward(stats, B * H2 * W2, bn1, cx.saved2, g_h, cx.a2, G)
+    dy1, st = _conv_backward_pair(da2, cx.a1, cx.coef1, conv1.weight, G(conv1.weight), B, nh, c1, H2, W2, 4, pending, like=g_h,
+                                  stat_q=cx.a1, between=lambda: _fed_bias(G(conv1.bias), bn1, da2.coef, G, zero_fed_biases))
+    da1 = _bn_backward(st, B * H1 * W1, bn0, cx.saved1, dy1, cx.a1, G)
     ops.wgrad(da1, Op(cx.x), G(conv0.weight), B, c1, NIN, H1, W1, 4, pending=pending)
-    _fed_bias(G(conv0.bias), bn0, c1b, G, zero_fed_biases)
-    if own:
-        ops.reduce_slabs_multi(pending)
+    _fed_bias(G(conv0.bias), bn0, da1.coef, G, zero_fed_biases)
+    reduce()
     if want_dx:          # the gradient w.r.t. the input patches: conv0's data gradient (see encoder_backward)
-        dx, _ = ops.conv3x3(da1, weight_view(_w(conv0.weight), 16, NIN * 16, 4, 1), B, c1, 4 * NIN, H1, W1, taps=9, pixel_shuffle=True)
+        dx, _ = ops.conv3x3(da1, _view_swapped(conv0.weight), B, c1, 4 * NIN, H1, W1, taps=9, pixel_shuffle=True)
         return dx
     return None
 
@@ -679,14 +683,14 @@ def z32_tail_forward(up0, bn, up1, r, x, mask, channel_var, per_sample=False, de
     B, nh, H2, W2 = r.shape
     ps = per_sample
     c1, NIN = up0.weight.shape[1], up1.weight.shape[1]
-    d1, st = ops.conv3x3(Op(r), weight_view(_w(up0.weight), 16, c1 * 16, 4, 1), B, nh, 4 * c1, H2, W2, taps=9,
-                         pixel_shuffle=True, want_stats=True, bias=_w(up0.bias), per_tile=ps)
+    d1, st = ops.conv3x3(Op(r), _view_swapped(up0.weight), B, nh, 4 * c1, H2, W2, taps=9, pixel_shuffle=True,
+                         want_stats=True, bias=_w(up0.bias), per_tile=ps)
     if ps:
         _need_per_sample_slabs(st, B, "z32_tail_forward: dec.1 (ConvTranspose2d %d -> %d at %d x %d)" % (nh, c1, H2, W2))
     coefd, savedd = _bn_coef(st, bn, 4 * H2 * W2 * (1 if ps else B), ps, B, defer)
-    dec, _ = ops.conv3x3(Op(d1, DM_LOAD_AFFINE_RELU, coefd, per_sample=ps), weight_view(_w(up1.weight), 16, NIN * 16, 4, 1), B, c1,
-                         4 * NIN, 2 * H2, 2 * W2, taps=9, pixel_shuffle=True, bias=_w(up1.bias))
-    var = _w(channel_var).reshape(-1) if channel_var is not None else torch.ones(NIN, device=r.device)
+    dec, _ = ops.conv3x3(Op(d1, DM_LOAD_AFFINE_RELU, coefd, per_sample=ps), _view_swapped(up1.weight), B, c1, 4 * NIN,
+                         2 * H2, 2 * W2, taps=9, pixel_shuffle=True, bias=_w(up1.bias))
+    var = _var(channel_var, NIN, r.device)
     slabs = ops.recon_loss(dec, x, mask, var) if x is not None else None
     cx = SimpleNamespace(r=r, d1=d1, coefd=coefd, savedd=savedd, dec=dec, x=x, mask=mask, var=var, loss_slabs=slabs,
                          dims=(B, nh, c1, NIN, H2, W2))
@@ -697,33 +701,22 @@ def z32_tail_backward(up0, bn, up1, cx, gscale, gdec_ext, G, want_gr=True, pendi
     """gscale: 1-element device tensor d(total)/d(recon_loss) or None; gdec_ext: upstream gradient w.r.t. decoded or None.
     pending / zero_fed_biases: as in z32_stem_backward."""
     B, nh, c1, NIN, H2, W2 = cx.dims
-    own = pending is None
-    if own:
-        pending = []
-    if gscale is not None:
-        g, part = ops.recon_loss_backward(cx.dec, cx.x, cx.mask, cx.var, gscale)
-        if gdec_ext is not None:
-            g = g + gdec_ext
-            part = None
-    else:
-        g, part = gdec_ext.contiguous(), None
-    # the last layer's bias gradient (channel sums of g) rides in the slab reduction
-    ops.pend_stats(pending, part if part is not None else ops.channel_stats(g), [G(up1.bias)])
-    ops.wgrad(Op(cx.d1, DM_LOAD_AFFINE_RELU, cx.coefd), Op(g), G(up1.weight), B, c1, NIN, 2 * H2, 2 * W2, 4,
-              pending=pending)
-    dy, st = ops.conv4x4s2(Op(g), weight_view(_w(up1.weight), NIN * 16, 16, 4, 1), B, NIN, c1, 4 * H2, 4 * W2,
-                           want_stats=True, mask=Op(cx.d1, DM_LOAD_AFFINE, cx.coefd), stat_q=cx.d1)
-    cdb = _bn_backward(st, B * 4 * H2 * W2, bn, cx.savedd, G)
+    pending, reduce = _pending(pending)
+    g, sums = _loss_gradient(cx.dec, cx.x, cx.mask, cx.var, gscale, gdec_ext)
+    ops.pend_stats(pending, sums, [G(up1.bias)])         # the last layer's bias gradient rides in the slab reduction
+    ops.wgrad(Op(cx.d1, DM_LOAD_AFFINE_RELU, cx.coefd), Op(g), G(up1.weight), B, c1, NIN, 2 * H2, 2 * W2, 4, pending=pending)
+    dy, st = ops.conv4x4s2(Op(g), _view(up1.weight), B, NIN, c1, 4 * H2, 4 * W2, want_stats=True,
+                           mask=Op(cx.d1, DM_LOAD_AFFINE, cx.coefd), stat_q=cx.d1)
     # da = BatchNorm backward of dy.  The weight-gradient kernels take that transform on their S operand; as the T operand only
     # where the one-pass kernel prefetches both tensors (the example widths) -- elsewhere da is materialised here
-    da = Op(dy, DM_LOAD_AFFINE2, cdb, p1=cx.d1)
+    da = _bn_backward(st, B * 4 * H2 * W2, bn, cx.savedd, dy, cx.d1, G)
+    cdb = da.coef
     if not ops.wgrad_t_affine2_supported(nh, c1, H2, W2, 4):
         da = Op(ops.apply(da, B, c1, 2 * H2, 2 * W2))
     ops.wgrad(Op(cx.r), da, G(up0.weight), B, nh, c1, H2, W2, 4, pending=pending)
     _fed_bias(G(up0.bias), bn, cdb, G, zero_fed_biases)
     g_r = None
     if want_gr:
-        g_r, _ = ops.conv4x4s2(da, weight_view(_w(up0.weight), c1 * 16, 16, 4, 1), B, c1, nh, 2 * H2, 2 * W2)
-    if own:
-        ops.reduce_slabs_multi(pending)
+        g_r, _ = ops.conv4x4s2(da, _view(up0.weight), B, c1, nh, 2 * H2, 2 * W2)
+    reduce()
     return g_r

@@ -34,8 +34,7 @@ from . import ops
 from .train_utils import EarlyStopping
 
 LOSS_KEYS = ("recon_loss", "commitment_loss", "total_loss", "perplexity")
-# DM_VQ_JOIN=0 in the environment: the last residual join as its own launch (dm_apply) in front of the quantiser (A/B runs)
-JOIN_IN_VQ = os.environ.get("DM_VQ_JOIN", "1") != "0"
+JOIN_IN_VQ = True     # False: the last residual join as its own launch (dm_apply); two tests in test_gpu_model.py monkeypatch it
 
 
 class _Marks:

@@ -79,7 +79,7 @@ K_SIGMA = 32.0
 # chain lengths: a 3x3 product over 16 channels is 36 matrix steps of four products (144) and the bias; the 1x1 over 32
 # channels 8 steps (32) + 1; enc.7 (4x4, 16 channels) 64 steps (256) + 1.  BatchNorm application scale v + shift: scale 2,
 # mean 1, shift 2, product and sum 2, the residual join 1 = 8 (glue_reference.C_BWD), relative to the terms.
-C_LT_CONV3, C_LT_CONV1, C_LT_CONV7, C_LT_BN = 145.0, 33.0, 257.0, 8.0
+C_LT_CONV3, C_LT_CONV1, C_LT_BN = 145.0, 33.0, 8.0
 # composition kernels: a double sum stored once (an exact count: held to <= 1)
 C_E1 = 1.0
 
@@ -564,26 +564,16 @@ def _lt_conv(t, e, w, b, cnt, **kw):
     return v, torch.sqrt(var)
 
 
-def latent_tail_ref(a3, coef3, w10, b10, gamma4, beta4, eps4, res, enc7=None, mut=None, dtype=torch.float64):
-    """enc.7 .. enc.12 of EVERY patch of the batch at once, each BatchNorm with that patch's own statistics (by hand in
-    float64, no loop of batch-of-one calls).  Both entry forms: (a3, coef3), or enc7 = (a2, coef2, w7, b7, gamma3, beta3,
-    eps3).  res: per residual layer (wa, ba, gamma_a, beta_a, eps_a, wb, bb, gamma_b, beta_b, eps_b), 0 .. 4 of them.
-    Returns dict(z, b_z, stats=[(name, sums (B, C, 2), bound)]) in the order the wrapper returns the slabs: [stats3,]
-    stats4, then (stats_a, stats_b) per residual layer."""
+def latent_tail_ref(a3, coef3, w10, b10, gamma4, beta4, eps4, res, mut=None, dtype=torch.float64):
+    """enc.10 .. enc.12 of EVERY patch of the batch at once, each BatchNorm with that patch's own statistics (by hand in
+    float64, no loop of batch-of-one calls).  res: per residual layer (wa, ba, gamma_a, beta_a, eps_a, wb, bb, gamma_b,
+    beta_b, eps_b), 0 .. 4 of them.
+    Returns dict(z, b_z, stats=[(name, sums (B, C, 2), bound)]) in the order the wrapper returns the slabs: stats4, then
+    (stats_a, stats_b) per residual layer."""
     stats = []
-    if enc7 is not None:
-        a2, coef2, w7, b7, g3, be3, eps3 = enc7
-        A2, C2 = d(a2).to(dtype), d(coef2).to(dtype)
-        c0, c2 = C2[:, :, 0, None, None], C2[:, :, 2, None, None]
-        t, e = (c0 * A2 + c2).clamp(min=0), U * ((c0 * A2).abs() + c2.abs())
-        v, e = _lt_conv(t, e, w7, b7, C_LT_CONV7, stride=2, padding=1)
-        y, e, s, bs = _lt_bn(v, e, g3, be3, eps3, mut)
-        stats.append(("stats3", s, bs))
-        t = y.clamp(min=0)
-    else:
-        A3, C3 = d(a3).to(dtype), d(coef3).to(dtype)
-        c0, c2 = C3[:, :, 0, None, None], C3[:, :, 2, None, None]
-        t, e = (c0 * A3 + c2).clamp(min=0), U * ((c0 * A3).abs() + c2.abs())
+    A3, C3 = d(a3).to(dtype), d(coef3).to(dtype)
+    c0, c2 = C3[:, :, 0, None, None], C3[:, :, 2, None, None]
+    t, e = (c0 * A3 + c2).clamp(min=0), U * ((c0 * A3).abs() + c2.abs())
     v, e = _lt_conv(t, e, w10, b10, C_LT_CONV3, padding=1)
     h, eh, s, bs = _lt_bn(v, e, gamma4, beta4, eps4, mut)
     stats.append(("stats4", s, bs))
@@ -603,9 +593,9 @@ LT_BATCHES = (1, 2, 511, 512, 513, 600, 1025)
 
 
 def lt_cases():
-    """B x nres 0 .. 4 x both entry forms (the grid is min(B, 512): 511 / 512 / 513 and 1025 lie around one and two full
-    passes).  Every patch is compared."""
-    return [(B, nres, e7) for B in LT_BATCHES for nres in range(5) for e7 in (False, True)]
+    """B x nres 0 .. 4 (the grid is min(B, 512): 511 / 512 / 513 and 1025 lie around one and two full passes).  Every patch
+    is compared."""
+    return [(B, nres) for B in LT_BATCHES for nres in range(5)]
 
 
 def lt_patch_scale(B):
@@ -614,7 +604,7 @@ def lt_patch_scale(B):
     return 4.0 ** ((3 * torch.arange(B) % 5) - 2).double()
 
 
-def lt_inputs(B, nres, e7):
+def lt_inputs(B, nres):
     """The kernel's arguments on the host.  The input channels get |mean| / std of 0, 3 and 30 (with_mean_over_std) and the
     patches scales from 1 / 16 to 16; a conv bias of the scale of the layer's spread keeps |mean| / std of the deeper layers
     around 1 .. 10; eps 1e-5 against variances down to ~1e-3 (the smallest patches)."""
@@ -622,11 +612,10 @@ def lt_inputs(B, nres, e7):
     C, CR = 16, 32
     r = lambda *s, k=1.0: torch.randn(*s, generator=gen) * k                              # noqa: E731
     scale = lt_patch_scale(B).float().reshape(B, 1, 1, 1)
-    side = 32 if e7 else 16
-    a = torch.randn(B, C, side, side, generator=gen)
+    a = torch.randn(B, C, 16, 16, generator=gen)
     ratio = torch.tensor([0.0, 3.0, 30.0]).repeat(6)[:C].reshape(1, C, 1, 1)
     a = (with_mean_over_std(a, 0.0) + ratio) * scale
-    # the on-load affine undoes most of the offset (as enc.5 / enc.8's BatchNorm would): c2 = -c0 mean + noise
+    # the on-load affine undoes most of the offset (as enc.8's BatchNorm would): c2 = -c0 mean + noise
     c0 = r(B, C).abs() + 0.5
     c2 = (-c0 * ratio.reshape(1, C) + r(B, C, k=0.3)) * scale.reshape(B, 1)
     coef = torch.stack([c0, torch.zeros(B, C), c2, torch.zeros(B, C)], 2).contiguous()
@@ -639,13 +628,7 @@ def lt_inputs(B, nres, e7):
         gb, beb = bn(C)
         res.append((r(CR, C, 3, 3, k=0.15), r(CR, k=1.0 if i % 3 == 1 else 0.2), ga, bea, 1e-5,
                     r(C, CR, k=0.2), r(C, k=0.2), gb, beb, 1e-5))
-    out = dict(a3=None, coef3=None, w10=w10, b10=b10, gamma4=g4, beta4=be4, eps4=1e-5, res=res, enc7=None)
-    if e7:
-        g3, be3 = bn(C)
-        out["enc7"] = (a, coef, r(C, C, 4, 4, k=0.1), r(C, k=0.2), g3, be3, 1e-5)
-    else:
-        out["a3"], out["coef3"] = a, coef
-    return out
+    return dict(a3=a, coef3=coef, w10=w10, b10=b10, gamma4=g4, beta4=be4, eps4=1e-5, res=res)
 
 
 # ================================================================================================= enc.0 o enc.1

@@ -358,7 +358,7 @@ def test_fused_trainer_equals_autograd_path(golden):
 @pytest.mark.parametrize("use_graph", [False, True])
 def test_fused_trainer_join_in_the_quantiser_changes_no_bit(golden, monkeypatch, use_graph):
     """The last residual join inside the quantiser's load path (dm_vq_forward_join, the default) against the join as its
-    own launch (DM_VQ_JOIN=0): same losses, parameters and BatchNorm buffers bit for bit over three steps."""
+    own launch (train.JOIN_IN_VQ = False): same losses, parameters and BatchNorm buffers bit for bit over three steps."""
     import dynamorph_amd.train as T
     x = torch.from_numpy(golden("g2_input.npz")["x"]).to(DEV)
     res = {}
@@ -378,7 +378,7 @@ def test_fused_trainer_join_in_the_quantiser_changes_no_bit(golden, monkeypatch,
                                             ("VQ_VAE", dict(num_inputs=4, num_embeddings=512, channel_var=np.ones(4)), 256)])
 def test_fused_backward_kernels_against_the_two_kernel_path(monkeypatch, cls_name, kw, hw):
     """Round 4's one-staging backward kernels (conv1x1 / conv3x3 / conv4x4s2 / transposed) against the data-gradient +
-    weight-gradient pairs they replace (DM_FUSED_BACKWARD=0), through the whole model: same losses, every parameter
+    weight-gradient pairs they replace (engine.FUSED_BACKWARD = False), through the whole model: same losses, every parameter
     gradient equal to accumulation-order tolerance -- on the default 16 x 16 latents (all five kernels), on VQ_VAE_z32 and on
     256-pixel patches (32 x 32 latents: only the shapes they are built for switch over, the rest keeps the pairs)."""
     import dynamorph_amd

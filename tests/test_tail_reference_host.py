@@ -263,26 +263,19 @@ def test_border_table_mutation_is_caught():
 
 
 # =========================================================================== latent tail
-@pytest.mark.parametrize("nres,e7", [(0, False), (2, True), (4, False), (1, True)])
-def test_latent_tail_reference_matches_batch_of_one_batchnorm(nres, e7):
+# (ids as they were while a second entry form, from enc.4's output, existed: "-False" is the (a3, coef3) form)
+@pytest.mark.parametrize("nres", [0, 4, 2, 1], ids=lambda nres: f"{nres}-False")
+def test_latent_tail_reference_matches_batch_of_one_batchnorm(nres):
     B, C = 5, 16
-    a = T.lt_inputs(B, nres, e7)
+    a = T.lt_inputs(B, nres)
     ref = T.latent_tail_ref(**a)
     dd = T.d
     bn = lambda v, g, b, eps: F.batch_norm(v, None, None, dd(g), dd(b), True, 0.1, T.f32(eps))   # noqa: E731
     for i in range(B):
-        per = []
-        if e7:
-            a2, coef2, w7, b7, g3, be3, eps3 = a["enc7"]
-            t2 = torch.relu(dd(coef2)[i, :, 0].reshape(1, C, 1, 1) * dd(a2)[i:i + 1] + dd(coef2)[i, :, 2].reshape(1, C, 1, 1))
-            a3i = F.conv2d(t2, dd(w7), dd(b7), stride=2, padding=1)
-            per.append(a3i)
-            t = torch.relu(bn(a3i, g3, be3, eps3))
-        else:
-            c3 = dd(a["coef3"])
-            t = torch.relu(c3[i, :, 0].reshape(1, C, 1, 1) * dd(a["a3"])[i:i + 1] + c3[i, :, 2].reshape(1, C, 1, 1))
+        c3 = dd(a["coef3"])
+        t = torch.relu(c3[i, :, 0].reshape(1, C, 1, 1) * dd(a["a3"])[i:i + 1] + c3[i, :, 2].reshape(1, C, 1, 1))
         a4 = F.conv2d(t, dd(a["w10"]), dd(a["b10"]), padding=1)
-        per.append(a4)
+        per = [a4]
         h = bn(a4, a["gamma4"], a["beta4"], a["eps4"])
         for wa, ba, ga, bea, ea, wb, bb, gb, beb, eb in a["res"]:
             ra = F.conv2d(torch.relu(h), dd(wa), dd(ba), padding=1)
@@ -296,20 +289,20 @@ def test_latent_tail_reference_matches_batch_of_one_batchnorm(nres, e7):
             torch.testing.assert_close(s[i], want, rtol=1e-10, atol=1e-11 * float(want.abs().max()))
 
 
-LT_HOST = [(2, 0, False), (2, 4, True), (513, 4, False), (600, 2, True), (1025, 1, False)]
+LT_HOST = [(2, 0), (2, 4), (513, 4), (600, 2), (1025, 1)]
 
 
 def test_latent_tail_bounds_hold_an_fp32_evaluation_to_a_quarter_and_stay_a_check():
     worst = {}
-    for (B, nres, e7) in LT_HOST:
-        a = T.lt_inputs(B, nres, e7)
+    for (B, nres) in LT_HOST:
+        a = T.lt_inputs(B, nres)
         ref, got = T.latent_tail_ref(**a), T.latent_tail_ref(**a, dtype=torch.float32)
         worst["z"] = max(worst.get("z", 0.0), ratio(got["z"], ref["z"], ref["b_z"]))
         for (name, s, bs), (_, s32, _) in zip(ref["stats"], got["stats"]):
             worst["statistics"] = max(worst.get("statistics", 0.0), ratio(s32, s, bs))
         # the bound stays a check for every patch, the small ones included: well under a percent of the patch's own z
         rel = float((ref["b_z"].amax((1, 2, 3)) / ref["z"].abs().amax((1, 2, 3))).max())
-        print(f"[tail bound] latent tail B={B} nres={nres} e7={e7}: bound / max|z| per patch up to {rel:.1e}")
+        print(f"[tail bound] latent tail B={B} nres={nres}: bound / max|z| per patch up to {rel:.1e}")
         assert rel < 5e-3, rel
         # patch b and patch b + 512 differ in scale
         if B > 512:
@@ -321,15 +314,15 @@ def test_latent_tail_bounds_hold_an_fp32_evaluation_to_a_quarter_and_stay_a_chec
 
 @pytest.mark.parametrize("mut", T.LT_MUTATIONS)
 def test_latent_tail_mutations_are_caught(mut):
-    for (B, nres, e7) in LT_HOST:
-        a = T.lt_inputs(B, nres, e7)
+    for (B, nres) in LT_HOST:
+        a = T.lt_inputs(B, nres)
         ref, bad = T.latent_tail_ref(**a), T.latent_tail_ref(**a, mut=mut)
         hit = "z" if ratio(bad["z"], ref["z"], ref["b_z"]) > T.MUTATION_MARGIN else None
         for (name, s, bs), (_, sb, _) in zip(ref["stats"], bad["stats"]):
             if ratio(sb, s, bs) > T.MUTATION_MARGIN:
                 hit = hit or name
         if hit:
-            print(f"[tail mutation] latent tail {mut}: caught by B={B} nres={nres} e7={e7} on {hit}")
+            print(f"[tail mutation] latent tail {mut}: caught by B={B} nres={nres} on {hit}")
             return
     pytest.fail(f"no latent-tail case tells the wrong kernel '{mut}' from the reference")
 
@@ -351,7 +344,7 @@ def test_grids_cross_every_cap():
         assert "below" in per[key] and "above_768" in per[key], (key, per[key])
         if key[1] == 2:
             assert "above_bwd" in per[key] and "ownerless" in per[key], (key, per[key])
-    assert {b for b, _, _ in T.lt_cases()} >= {1, 2, 511, 512, 513, 600, 1025} and len(T.lt_cases()) == 70
+    assert {b for b, _ in T.lt_cases()} >= {1, 2, 511, 512, 513, 600, 1025} and len(T.lt_cases()) == 35
     # an impulse in a LATER tile of a workgroup, per tiling and per launch
     later = set()
     for case in T.tail_impulse_cases():
