@@ -5,9 +5,10 @@ Public surface = the reference's module surface for this path:
 computed by hand-written gfx950 HIP kernels behind the C ABI in include/dynamorph_hip.h, and the per-patch scoring drivers
 of the inference path:
     score_patches, score_patches_sharded, score_VAE                     (dynamorph_amd.patch_vae)
+    patch_gradients, patch_gradients_sharded                            (dynamorph_amd.patch_vae)
 """
 from .vq_vae import VQ_VAE, VQ_VAE_z16, VQ_VAE_z32, VectorQuantizer, ResidualBlock  # noqa: F401
-from .patch_vae import score_patches, score_patches_sharded, score_VAE  # noqa: F401
+from .patch_vae import score_patches, score_patches_sharded, score_VAE, patch_gradients, patch_gradients_sharded  # noqa: F401
 
 __all__ = ["VQ_VAE", "VQ_VAE_z16", "VQ_VAE_z32", "VectorQuantizer", "ResidualBlock",
-           "score_patches", "score_patches_sharded", "score_VAE"]
+           "score_patches", "score_patches_sharded", "score_VAE", "patch_gradients", "patch_gradients_sharded"]

@@ -54,6 +54,15 @@ class LatentTailArgs(C.Structure):
                 ("res", LatentTailRes * 4)]
 
 
+class LatentTailBwdRes(C.Structure):
+    _fields_ = [(k, vp) for k in ("ra", "rb", "h_in", "coefa", "saveda", "savedb", "gamma_a", "gamma_b", "wa", "wb")]
+
+
+class LatentTailBwdArgs(C.Structure):
+    _fields_ = [(k, vp) for k in ("g_z", "a3", "coef3", "a4", "saved4", "gamma4", "w10", "dy3", "stats3")] + \
+               [(k, i32) for k in ("B", "C", "CR", "H", "W", "nres")] + [("res", LatentTailBwdRes * 4)]
+
+
 OP, WV, EP = C.POINTER(Operand), C.POINTER(WeightView), C.POINTER(Epilogue)
 
 # name -> (restype, argtypes); every symbol include/dynamorph_hip.h declares
@@ -101,6 +110,7 @@ SIGNATURES = {
     "dm_wgrad": (C.c_int, [OP, OP, vp, vp] + [C.c_int] * 6 + [vp]),
     "dm_bn_finalize": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64, vp, vp, vp, vp, vp, f32, f32, vp, vp, C.c_int, vp]),
     "dm_bn_backward_finalize": (C.c_int, [vp, C.c_int, C.c_int, i64, vp, vp, vp, vp, vp, vp]),
+    "dm_bn_backward_finalize_per_sample": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64, vp, vp, vp, vp, vp, vp]),
     "dm_bn_sync_pack": (C.c_int, [vp, C.c_int, C.c_int, i64, vp, vp, vp]),
     "dm_bn_finalize_payload": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp]),
     "dm_bn_backward_pack": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
@@ -108,12 +118,14 @@ SIGNATURES = {
     "dm_apply": (C.c_int, [OP, vp, vp] + [C.c_int] * 4 + [vp]),
     "dm_channel_stats_num_blocks": (C.c_int, [C.c_int] * 4),
     "dm_channel_stats": (C.c_int, [vp, vp, vp] + [C.c_int] * 4 + [vp]),
+    "dm_channel_stats_per_sample": (C.c_int, [vp, vp, vp] + [C.c_int] * 4 + [vp]),
     "dm_sum_slabs": (C.c_int, [vp, C.c_int, C.c_int, f32, vp, vp]),
     "dm_sum_slabs_scatter": (C.c_int, [vp, C.c_int, C.c_int, f32, C.POINTER(Scatter), vp]),
     "dm_reduce_slabs_multi": (C.c_int, [C.POINTER(ReduceSeg), C.c_int, vp]),
     "dm_bn_running_replay": (C.c_int, [C.POINTER(ReplaySeg), C.c_int, vp]),
     "dm_latent_tail_supported": (C.c_int, [C.c_int] * 5),
     "dm_latent_tail_forward": (C.c_int, [C.POINTER(LatentTailArgs), vp]),
+    "dm_latent_tail_backward": (C.c_int, [C.POINTER(LatentTailBwdArgs), vp]),
     "dm_head_supported": (C.c_int, [C.c_int] * 2),
     "dm_head_num_blocks": (C.c_int, [C.c_int] * 3),
     "dm_head_forward": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp, vp, vp] + [C.c_int] * 5 + [vp]),

@@ -256,6 +256,65 @@ __global__ __launch_bounds__(256) void bn_backward_finalize_kernel(
     }
 }
 
+// Per-sample form of bn_backward_finalize_kernel (every patch is its own batch: the backward of process_VAE's batch-of-one
+// calls, batched), ONE launch:
+//   blocks [0, nb): one thread per (patch, channel) adds that patch's slabs_per_group slabs in slab order and writes the
+//     patch's coefficients -- bn_backward_finalize_kernel's arithmetic, in double, with the patch's own mean, invstd and count;
+//   blocks [nb, nb + C) (only when dgamma or dbeta is asked for): channel c's parameter gradients, the per-patch terms
+//     (sum dy, invstd_b * (sum dy*a - mean_b * sum dy)) added over the patches IN INDEX ORDER in double and rounded once.
+//     256 patches at a time are put into LDS by the workgroup and added by thread 0: no atomics, one order whatever the grid.
+__global__ __launch_bounds__(256) void bn_backward_finalize_per_sample_kernel(
+    const double *__restrict__ stats, int B, int spg, int C, long long count, const float *__restrict__ gamma,
+    const float *__restrict__ saved, float *__restrict__ dgamma, float *__restrict__ dbeta, float *__restrict__ coef_bwd, int nb)
+{
+    if ((int)blockIdx.x >= nb) {
+        __shared__ double s_dy[256], s_dyxh[256];
+        const int c = blockIdx.x - nb;
+        double tb = 0.0, tg = 0.0;
+        for (int b0 = 0; b0 < B; b0 += 256) {
+            const int b = b0 + (int)threadIdx.x;
+            double s1 = 0.0, s2 = 0.0, xh = 0.0;
+            if (b < B) {
+                for (int i = 0; i < spg; ++i) {
+                    s1 += stats[((long long)(b * spg + i) * C + c) * 2 + 0];
+                    s2 += stats[((long long)(b * spg + i) * C + c) * 2 + 1];
+                }
+                const double mean = (double)saved[((long long)b * C + c) * 2 + 0], invstd = (double)saved[((long long)b * C + c) * 2 + 1];
+                xh = invstd * (s2 - mean * s1);
+            }
+            __syncthreads();
+            s_dy[threadIdx.x] = s1;
+            s_dyxh[threadIdx.x] = xh;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                const int n = B - b0 < 256 ? B - b0 : 256;
+                for (int j = 0; j < n; ++j) { tb += s_dy[j]; tg += s_dyxh[j]; }
+            }
+        }
+        if (threadIdx.x == 0) {
+            if (dgamma) dgamma[c] = (float)tg;
+            if (dbeta) dbeta[c] = (float)tb;
+        }
+        return;
+    }
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= B * C) return;
+    const int b = idx / C, c = idx - b * C;
+    double sum_dy = 0.0, sum_dya = 0.0;
+    for (int i = 0; i < spg; ++i) {
+        sum_dy += stats[((long long)(b * spg + i) * C + c) * 2 + 0];
+        sum_dya += stats[((long long)(b * spg + i) * C + c) * 2 + 1];
+    }
+    const double inv_n = 1.0 / (double)count;
+    const double mean = (double)saved[(long long)idx * 2 + 0], invstd = (double)saved[(long long)idx * 2 + 1];
+    const double g = gamma ? (double)gamma[c] : 1.0;
+    const double sum_dyxh = invstd * (sum_dya - mean * sum_dy);
+    const double scale = g * invstd;
+    const double c1 = sum_dy * inv_n, c2 = sum_dyxh * inv_n;
+    const double Bc = -scale * invstd * c2;
+    *reinterpret_cast<f32x4 *>(coef_bwd + (long long)idx * 4) = (f32x4){(float)scale, (float)Bc, (float)(-scale * c1 - Bc * mean), 0.f};
+}
+
 // ------------------------------------------------------------------ synchronized BatchNorm (data parallel)
 // A layer's statistics leave the rank as ONE payload of doubles that the ranks add up (all-reduce, SUM) between two
 // launches; the global count and the gradient weight live in device memory, so a captured graph keyed on the LOCAL shape
@@ -398,6 +457,30 @@ __global__ __launch_bounds__(256) void channel_stats_kernel(const float *__restr
     }
 }
 
+// Per-sample form: one workgroup per patch, stats[b][c] = (sum p, sum p*q) over that patch's H*W positions.  Wave w takes
+// channels w, w + 4, ...; a lane adds its float4 groups in channel_stats_kernel's arithmetic (four elements in fp32, then one
+// promotion) and the wave's 64 partial sums are added by wave_sum: one order whatever the batch.
+__global__ __launch_bounds__(256) void channel_stats_per_sample_kernel(const float *__restrict__ p, const float *__restrict__ q,
+                                                                       double *__restrict__ stats, int C, int HW4)
+{
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int c = wave; c < C; c += 4) {
+        const long long base = ((long long)b * C + c) * HW4 * 4;
+        double s1 = 0.0, s2 = 0.0;
+        for (int i = lane; i < HW4; i += 64) {
+            const f32x4 a = *reinterpret_cast<const f32x4 *>(p + base + (long long)i * 4);
+            const f32x4 w = q ? *reinterpret_cast<const f32x4 *>(q + base + (long long)i * 4) : a;
+            s1 += (double)((a.x + a.y) + (a.z + a.w));
+            s2 += (double)((a.x * w.x + a.y * w.y) + (a.z * w.z + a.w * w.w));
+        }
+        const double t1 = wave_sum(s1), t2 = wave_sum(s2);
+        if (lane == 0) {
+            stats[((long long)b * C + c) * 2 + 0] = t1;
+            stats[((long long)b * C + c) * 2 + 1] = t2;
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void sum_slabs_kernel(const double *__restrict__ stats, int nslabs, int N,
                                                         float scale, float *__restrict__ dst)
 {
@@ -501,6 +584,23 @@ extern "C" int dm_bn_backward_finalize(const double *stats, int nslabs, int C, i
     return dm_launch_status("dm_bn_backward_finalize");
 }
 
+extern "C" int dm_bn_backward_finalize_per_sample(const double *stats, int nslabs, int slabs_per_group, int C,
+                                                  int64_t count_per_group, const float *gamma, const float *saved,
+                                                  float *dgamma, float *dbeta, float *coef_bwd, void *stream)
+{
+    DM_REQUIRE(stats && saved && coef_bwd, "dm_bn_backward_finalize_per_sample: NULL pointer");
+    DM_REQUIRE(nslabs > 0 && C > 0 && count_per_group > 0, "dm_bn_backward_finalize_per_sample: bad sizes");
+    DM_REQUIRE(slabs_per_group > 0 && nslabs % slabs_per_group == 0,
+               "dm_bn_backward_finalize_per_sample: nslabs %d not a multiple of slabs_per_group %d", nslabs, slabs_per_group);
+    const int B = nslabs / slabs_per_group;
+    DM_REQUIRE((long long)B * C < (1LL << 30), "dm_bn_backward_finalize_per_sample: too many (sample, channel) pairs");
+    const int nb = (B * C + 255) / 256;
+    const int pb = dgamma || dbeta ? C : 0;
+    hipLaunchKernelGGL(bn_backward_finalize_per_sample_kernel, dim3(nb + pb), dim3(256), 0, (hipStream_t)stream, stats, B,
+                       slabs_per_group, C, (long long)count_per_group, gamma, saved, dgamma, dbeta, coef_bwd, nb);
+    return dm_launch_status("dm_bn_backward_finalize_per_sample");
+}
+
 extern "C" int dm_apply(const dm_operand *in, const float *resid, float *out, int B, int C, int H, int W, void *stream)
 {
     if (dm_check_operand(in, "dm_apply")) return -1;
@@ -528,6 +628,15 @@ extern "C" int dm_channel_stats(const float *p, const float *q, double *stats, i
     hipLaunchKernelGGL(channel_stats_kernel, dim3(chunks * C), dim3(256), 0, (hipStream_t)stream, p, q, stats, B, C,
                        H * W / 4, STATS_BCHUNK);
     return dm_launch_status("dm_channel_stats");
+}
+
+extern "C" int dm_channel_stats_per_sample(const float *p, const float *q, double *stats, int B, int C, int H, int W, void *stream)
+{
+    DM_REQUIRE(p && stats, "dm_channel_stats_per_sample: NULL pointer");
+    DM_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "dm_channel_stats_per_sample: bad sizes");
+    DM_REQUIRE((H * W) % 4 == 0, "dm_channel_stats_per_sample: H*W must be a multiple of 4");
+    hipLaunchKernelGGL(channel_stats_per_sample_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, p, q, stats, C, H * W / 4);
+    return dm_launch_status("dm_channel_stats_per_sample");
 }
 
 extern "C" int dm_sum_slabs_scatter(const double *stats, int nslabs, int N, float scale, const dm_scatter *sc, void *stream)

@@ -129,8 +129,6 @@ def _bn_coef(stats, bn, count, per_sample, nbatch, defer=None):
         scale = bn.weight.detach() * invstd
         coef = torch.stack([scale, torch.zeros_like(scale), bn.bias.detach() - bn.running_mean * scale,
                             torch.zeros_like(scale)], 1).contiguous()
-        if per_sample:
-            return coef, None
         return coef, torch.stack([bn.running_mean, invstd], 1).contiguous()     # what _bn_backward takes in eval() mode
     spg = stats.shape[0] // nbatch if per_sample else 1
     return ops.bn_finalize(stats, count, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var,
@@ -165,18 +163,29 @@ def _view_swapped(w):
     return weight_view(_w(w), *view_strides(w.shape, True))
 
 
-def _bn_backward(stats, count, bn, saved, g, a, G, gbias=None, zero=True):
+def _no_grads(p):
+    """G of a data-only backward pass (want_param_grads=False): no parameter has a gradient buffer, nothing is written."""
+    return None
+
+
+def _bn_backward(stats, count, bn, saved, g, a, G, gbias=None, zero=True, nbatch=0):
     """One BatchNorm-backward step: native_batch_norm_backward's reductions for `bn` from the (sum g, sum g * a) slabs ->
     da = BatchNorm backward of g as an AFFINE2 operand over the raw conv output a (its .coef: the coefficients); eval()
     mode (fixed statistics: count 0) keeps only da = gamma * invstd * g.  gbias: the gradient of the conv bias that feeds
-    `bn`, written here (_fed_bias; None: the caller writes it where its launch belongs)."""
-    if _bn_sync is not None and bn.training:
+    `bn`, written here (_fed_bias; None: the caller writes it where its launch belongs).
+    nbatch = B > 0: per-sample statistics -- `stats` holds a whole number of slabs per patch, `count` is ONE patch's positions
+    and `saved` (B, C, 2); patch b's da comes from patch b's own sums, the parameter gradients are the sums over the patches
+    (ops.bn_backward_finalize_per_sample).  eval() mode shares its statistics and takes the batch form either way."""
+    if nbatch and bn.training:
+        c = ops.bn_backward_finalize_per_sample(stats, stats.shape[0] // nbatch, count, _w(bn.weight), saved,
+                                                G(bn.weight), G(bn.bias))
+    elif _bn_sync is not None and bn.training:
         c = _bn_sync.backward(stats, bn, saved, G)
     else:
         c = ops.bn_backward_finalize(stats, count if bn.training else 0, _w(bn.weight), saved, G(bn.weight), G(bn.bias))
     if gbias is not None:
         _fed_bias(gbias, bn, c, G, zero)
-    return Op(g, DM_LOAD_AFFINE2, c, p1=a)
+    return Op(g, DM_LOAD_AFFINE2, c, p1=a, per_sample=bool(nbatch))
 
 
 # ------------------------------------------------------------------------------- encoder
@@ -197,7 +206,7 @@ def e1_operands(L):
     return ops.e1_compose_border(_w(L.enc0.weight), _w(L.enc0.bias), _w(L.enc1.weight), _w(L.enc1.bias))
 
 
-def encoder_forward(L, x, per_sample=False, e1=None, join=True, latents_only=False, defer_last_join=0):
+def encoder_forward(L, x, per_sample=False, e1=None, join=True, latents_only=False, defer_last_join=0, replay_as_latents=False):
     """x (B,NIN,H,W) -> z_before (B,nh,H/8,W/8).  per_sample=True normalises every BatchNorm with
     that sample's own statistics = pipeline/patch_VAE.py:445-452 (batch-of-one calls in train mode).
     e1: e1_operands(L) computed by the caller (inference: once per call).
@@ -207,6 +216,10 @@ def encoder_forward(L, x, per_sample=False, e1=None, join=True, latents_only=Fal
     defer_last_join = K (training step only): when the quantiser can do it (ops.vq_forward_join_supported for K codes), the
     LAST residual join is left to the VectorQuantizer kernel's load path: the return value is then (None, cx) and
     cx.pending_join = (rb, h_in, coef) goes to vq_forward_joined, which also produces z.
+    replay_as_latents (per_sample only, a context to differentiate through): where latents_only would take the one-launch
+    latent tail, that kernel ALSO runs, for its per-patch sums alone: they, not the layer-by-layer slabs (equal up to the order
+    of the additions), feed the running-statistics replay of enc.11 / enc.12, so the running statistics advance to the same
+    bits as under encode_patches / score_patches.  The forward values and everything kept for backward are the chain's.
     join=False (per_sample only): the running-statistics replay -- a side effect no kernel of the path reads -- is left
     running on a helper stream beside whatever the caller launches next (the VectorQuantizer); the caller MUST call
     cx.join() before it hands the stream back (a HIP-graph capture cannot end with unjoined work)."""
@@ -229,15 +242,16 @@ def encoder_forward(L, x, per_sample=False, e1=None, join=True, latents_only=Fal
 
     H3, W3 = H2 // 2, W2 // 2
     n3 = H3 * W3 * (1 if ps else B)
-    fuse_tail = (ps and latents_only and L.bn3.training and L.bn4.training
-                 and all(bna.training and bnb.training for _, bna, _, bnb in L.res)
-                 and ops.latent_tail_supported(nh, nrh, H3, W3, len(L.res)))
+    tail_built = (ps and (latents_only or replay_as_latents) and L.bn3.training and L.bn4.training
+                  and all(bna.training and bnb.training for _, bna, _, bnb in L.res)
+                  and ops.latent_tail_supported(nh, nrh, H3, W3, len(L.res)))
+    fuse_tail = tail_built and latents_only
     a3, st = ops.conv4x4s2(Op(a2, DM_LOAD_AFFINE_RELU, coef2, per_sample=ps), _view(L.enc7.weight), B, nh, nh, H2, W2,
                            want_stats=True, bias=_w(L.enc7.bias), per_tile=ps)
     coef3, saved3 = _bn_coef(st, L.bn3, n3, ps, B, defer)
     cx.__dict__.update(a1=a1, a2=a2, a3=a3, coef1=coef1, coef2=coef2, coef3=coef3, saved1=None, dims=(H1, W1, H2, W2, H3, W3))
 
-    if fuse_tail:
+    if tail_built:
         z, st4, sts = ops.latent_tail_forward(
             a3, coef3, _w(L.enc10.weight), _w(L.enc10.bias), _w(L.bn4.weight), _w(L.bn4.bias), L.bn4.eps,
             [(_w(ca.weight), _w(ca.bias), _w(bna.weight), _w(bna.bias), bna.eps, _w(cb.weight), _w(cb.bias),
@@ -245,17 +259,19 @@ def encoder_forward(L, x, per_sample=False, e1=None, join=True, latents_only=Fal
         bns = [L.bn4] + [bn for _, bna, _, bnb in L.res for bn in (bna, bnb)]
         for slabs, bn in zip([st4] + [s for pair in sts for s in pair], bns):
             defer.append((slabs, 1, n3, bn.running_mean, bn.running_var, bn.num_batches_tracked, _momentum(bn)))
+    if fuse_tail:
         _replay(cx, x, defer, join)
         return z, cx
+    tail_defer = [] if tail_built else defer         # replay_as_latents: the chain's own updates of these layers are dropped
     a4, st = ops.conv3x3(Op(a3, DM_LOAD_AFFINE_RELU, coef3, per_sample=ps), _view(L.enc10.weight), B, nh, nh, H3, W3,
                          taps=9, want_stats=True, bias=_w(L.enc10.bias), per_tile=ps)
-    coef4, saved4 = _bn_coef(st, L.bn4, n3, ps, B, defer)
+    coef4, saved4 = _bn_coef(st, L.bn4, n3, ps, B, tail_defer)
     h = ops.apply(Op(a4, DM_LOAD_AFFINE, coef4, per_sample=ps), B, nh, H3, W3)
 
     cx.__dict__.update(a4=a4, coef4=coef4, saved1=saved1, saved2=saved2, saved3=saved3, saved4=saved4)
     fuse = bool(defer_last_join) and not ps and len(L.res) > 0 and L.res[-1][3].training and \
         ops.vq_forward_join_supported(nh, int(defer_last_join), H3, W3)
-    z, cx.res = residual_forward(L.res, h, ps, defer, defer_last_join=fuse)
+    z, cx.res = residual_forward(L.res, h, ps, tail_defer, defer_last_join=fuse)
     cx.pending_join = (cx.res[-1].rb, cx.res[-1].h_in, cx.res[-1].coefb) if fuse else None
     _replay(cx, x, defer, join)
     return z, cx
@@ -309,7 +325,8 @@ def residual_forward(res_layers, h, per_sample=False, defer=None, defer_last_joi
         coefb, savedb = _bn_coef(st, bnb, n, per_sample, B, defer)
         last = defer_last_join and ca is res_layers[-1][0]
         hn = None if last else ops.apply(Op(rb, DM_LOAD_AFFINE, coefb, per_sample=per_sample), B, nh, H, W, resid=h)
-        saved.append(SimpleNamespace(h_in=h, ra=ra, rb=rb, coefa=coefa, saveda=saveda, coefb=coefb, savedb=savedb))
+        saved.append(SimpleNamespace(h_in=h, ra=ra, rb=rb, coefa=coefa, saveda=saveda, coefb=coefb, savedb=savedb,
+                                     per_sample=per_sample))
         h = hn
     if own and defer:
         ops.bn_running_replay(defer)
@@ -320,6 +337,8 @@ def _fed_bias(gbias, bn, coef_bwd, G, zero=True):
     """Gradient of a convolution bias that feeds the BatchNorm `bn`: identically zero in train mode (the batch mean removes a
     constant; zero=False: the caller's buffer holds the zero already); in eval() mode the sum of the BatchNorm's input
     gradient over the positions, gamma / sqrt(running_var + eps) * dbeta."""
+    if gbias is None:                                # a data-only pass
+        return
     if bn.training:
         if zero:
             gbias.zero_()
@@ -328,101 +347,153 @@ def _fed_bias(gbias, bn, coef_bwd, G, zero=True):
 
 
 def _conv_backward_pair(dy, x, xcoef, w, gw, B, CD, CX, H, W, k, pending, like, stat_q, resid=None, want_stats=True,
-                        between=lambda: None):
+                        between=lambda: None, per_sample=False):
     """The two-launch backward of a Conv2d CX -> CD (k = 3, 1: same size; k = 4: stride 2), for the shapes its fused kernel is
     not built for: the weight gradient of dy (B,CD,H,W) against the conv's input relu(BN(x)) (xcoef None: relu(x)), then the
     data gradient with that ReLU's mask, the residual branch `resid` and the (sum, sum * stat_q) slabs for the BatchNorm
-    below.  between: a bias gradient whose launch sits between the two.  Returns (dx, stats)."""
-    xin, mask = (Op(x, DM_LOAD_RELU), Op(x)) if xcoef is None else (Op(x, DM_LOAD_AFFINE_RELU, xcoef), Op(x, DM_LOAD_AFFINE, xcoef))
-    ops.wgrad(dy, xin, gw, B, CD, CX, H, W, k, pending=pending)
+    below.  between: a bias gradient whose launch sits between the two.  Returns (dx, stats).
+    per_sample: xcoef is per patch and the slabs come back grouped by patch; gw None (a data-only pass): no weight gradient."""
+    ps = per_sample
+    xin, mask = (Op(x, DM_LOAD_RELU), Op(x)) if xcoef is None else (Op(x, DM_LOAD_AFFINE_RELU, xcoef, per_sample=ps),
+                                                                   Op(x, DM_LOAD_AFFINE, xcoef, per_sample=ps))
+    if gw is not None:
+        ops.wgrad(dy, xin, gw, B, CD, CX, H, W, k, pending=pending)
     between()
     # (stride 2 backwards is the phase-decomposed transposed convolution: 4 phases x CX outputs, pixel-shuffled)
-    return ops.conv3x3(dy, _view_swapped(w), B, CD, 4 * CX if k == 4 else CX, H, W, taps=9 if k == 4 else k * k, pixel_shuffle=k == 4,
-                       want_stats=want_stats, like=like, mask=mask, resid=resid, stat_q=stat_q)
+    per_tile = ps and want_stats
+    dx, stats = ops.conv3x3(dy, _view_swapped(w), B, CD, 4 * CX if k == 4 else CX, H, W, taps=9 if k == 4 else k * k,
+                            pixel_shuffle=k == 4, want_stats=want_stats, like=like, mask=mask, resid=resid, stat_q=stat_q,
+                            **({"per_tile": True} if per_tile else {}))
+    if per_tile:
+        _need_per_sample_slabs(stats, B, "backward of the %d x %d convolution %d -> %d at %d x %d" % (k, k, CX, CD, H, W))
+    return dx, stats
 
 
-def residual_backward(res_layers, saved, g_h, G, q_below, pending=None, zero_fed_biases=True):
+def residual_backward(res_layers, saved, g_h, G, q_below, pending=None, zero_fed_biases=True, want_param_grads=True,
+                      per_sample=None):
     """Gradient of the residual stack.  g_h: gradient w.r.t. its output.  q_below: the raw conv output
     whose BatchNorm produced the stack's input (None if there is none); when given, the returned stats
-    are the (sum g, sum g*q_below) slabs that BatchNorm's backward needs.  Returns (g_in, stats)."""
+    are the (sum g, sum g*q_below) slabs that BatchNorm's backward needs.  Returns (g_in, stats).
+    A stack that ran with per_sample=True (its saved contexts say so; per_sample: for a stack without layers) goes backward
+    per patch: every BatchNorm's backward takes that patch's own sums and count, the slabs are grouped by patch, and the
+    fused kernels -- one coefficient set and one slab per persistent workgroup -- are not reached.
+    want_param_grads=False: the data gradient alone; G is not called, no weight gradient is launched."""
+    ps = bool(saved[0].per_sample if saved else per_sample)
+    chan_stats = ops.channel_stats_per_sample if ps else ops.channel_stats
+    if not want_param_grads:
+        G = _no_grads
     if not saved:
-        return g_h, (ops.channel_stats(g_h, q_below) if q_below is not None else None)
+        return g_h, (chan_stats(g_h, q_below) if q_below is not None else None)
     B, nh, H, W = g_h.shape
-    cnt = B * H * W
-    stats = ops.channel_stats(g_h, saved[-1].rb)
+    cnt = H * W * (1 if ps else B)
+    nb = B if ps else 0
+    fused = FUSED_BACKWARD and not ps and want_param_grads
+    stats = chan_stats(g_h, saved[-1].rb)
     for i in range(len(saved) - 1, -1, -1):
         ca, bna, cb, bnb = res_layers[i]
         s = saved[i]
         nrh = ca.weight.shape[0]
-        if s.savedb is None or s.coefb.dim() != 2:
-            raise NotImplementedError("backward needs batch-statistics BatchNorm (train mode, per_sample=False)")
-        da_rb = _bn_backward(stats, cnt, bnb, s.savedb, g_h, s.rb, G, G(cb.bias), zero_fed_biases)
-        if FUSED_BACKWARD and s.coefa.dim() == 2 and ops.conv1x1_bwd_fused_supported(nh, nrh, H, W):
+        da_rb = _bn_backward(stats, cnt, bnb, s.savedb, g_h, s.rb, G, G(cb.bias), zero_fed_biases, nbatch=nb)
+        if fused and s.coefa.dim() == 2 and ops.conv1x1_bwd_fused_supported(nh, nrh, H, W):
             # the 1x1 convolution's data and weight gradient from ONE staging of (g_h, rb, ra) -- csrc/conv1x1_bwd.hip
             dy_ra, st = ops.conv1x1_bwd_fused(da_rb, s.ra, s.coefa, _w(cb.weight), G(cb.weight), B, nh, nrh, H, W, pending=pending)
         else:
             dy_ra, st = _conv_backward_pair(da_rb, s.ra, s.coefa, cb.weight, G(cb.weight), B, nh, nrh, H, W, 1, pending, like=g_h,
-                                            stat_q=s.ra)
-        da_ra = _bn_backward(st, cnt, bna, s.saveda, dy_ra, s.ra, G, G(ca.bias), zero_fed_biases)
+                                            stat_q=s.ra, per_sample=ps)
+        da_ra = _bn_backward(st, cnt, bna, s.saveda, dy_ra, s.ra, G, G(ca.bias), zero_fed_biases, nbatch=nb)
         q = saved[i - 1].rb if i > 0 else q_below
-        if FUSED_BACKWARD and ops.conv3x3_bwd_fused_supported(nrh, nh, H, W):
+        if fused and ops.conv3x3_bwd_fused_supported(nrh, nh, H, W):
             # the 3x3 convolution's data and weight gradient from ONE staging of the patch -- csrc/conv3x3_bwd.hip
             g_h, stats = ops.conv3x3_bwd_fused(da_ra, s.h_in, None, _w(ca.weight), G(ca.weight), B, nrh, resid=g_h, q=q,
                                                want_stats=q is not None, pending=pending)
         else:
             g_h, stats = _conv_backward_pair(da_ra, s.h_in, None, ca.weight, G(ca.weight), B, nrh, nh, H, W, 3, pending, like=g_h,
-                                             stat_q=q, resid=g_h, want_stats=q is not None)
+                                             stat_q=q, resid=g_h, want_stats=q is not None, per_sample=ps)
     return g_h, stats
 
 
-def encoder_backward(L, cx, g_z, G, zero_fed_biases=True, pending_extra=(), want_dx=False):
+def latent_stage_backward(L, cx, g_z, G, pending=None, zero_fed_biases=True, want_param_grads=True, fused=True):
+    """The 16 x 16 stage of encoder_backward (on a 128 px patch), enc.12 .. enc.10: g_z (B,nh,H3,W3), the gradient at the
+    encoder's output -> (dy3, stats): the gradient at enc.7's raw output a3, masked by relu(BN3(a3)), and its
+    (sum dy3, sum dy3 * a3) slabs for enc.8's backward (grouped by patch on a per_sample context).  encoder_backward's own
+    first step; also what the stage's tests and tools/gradbench.py call.
+    A data-only pass on a per_sample context in train mode is ONE launch that keeps a patch on its CU
+    (ops.latent_tail_backward) where that kernel is built; fused=False: the layer-by-layer launches there too."""
+    if not hasattr(cx, "a4"):
+        raise NotImplementedError("encoder_backward: this context was made with latents_only=True (nothing was kept to "
+                                  "differentiate through)")
+    if not want_param_grads:
+        G = _no_grads
+    B, nh = cx.B, L.nh
+    H3, W3 = cx.dims[4:]
+    ps = bool(cx.per_sample)
+    if (fused and ps and not want_param_grads and L.bn3.training and L.bn4.training
+            and all(bna.training and bnb.training for _, bna, _, bnb in L.res)
+            and ops.latent_tail_supported(nh, L.nrh, H3, W3, len(L.res))):
+        return ops.latent_tail_backward(
+            g_z.contiguous(), cx.a3, cx.coef3, cx.a4, cx.saved4, _w(L.bn4.weight), _w(L.enc10.weight),
+            [(s.ra, s.rb, s.h_in, s.coefa, s.saveda, s.savedb, _w(bna.weight), _w(bnb.weight), _w(ca.weight), _w(cb.weight))
+             for s, (ca, bna, cb, bnb) in zip(cx.res, L.res)])
+    g_h, stats = residual_backward(L.res, cx.res, g_z.contiguous(), G, cx.a4, pending=pending, zero_fed_biases=zero_fed_biases,
+                                   want_param_grads=want_param_grads, per_sample=ps)
+    da4 = _bn_backward(stats, H3 * W3 * (1 if ps else B), L.bn4, cx.saved4, g_h, cx.a4, G, G(L.enc10.bias), zero_fed_biases,
+                       nbatch=B if ps else 0)
+    if FUSED_BACKWARD and not ps and want_param_grads and cx.coef3.dim() == 2 and ops.conv3x3_bwd_fused_supported(nh, nh, H3, W3):
+        # enc.10: data and weight gradient from ONE staging of the patch -- csrc/conv3x3_bwd.hip
+        return ops.conv3x3_bwd_fused(da4, cx.a3, cx.coef3, _w(L.enc10.weight), G(L.enc10.weight), B, nh, q=cx.a3, pending=pending)
+    return _conv_backward_pair(da4, cx.a3, cx.coef3, L.enc10.weight, G(L.enc10.weight), B, nh, nh, H3, W3, 3, pending,
+                               like=g_h, stat_q=cx.a3, per_sample=ps)
+
+
+def encoder_backward(L, cx, g_z, G, zero_fed_biases=True, pending_extra=(), want_dx=False, want_param_grads=True):
     """Accumulates nothing: every parameter gradient G(p) is overwritten.  want_dx: also returns the gradient w.r.t. the input
     patches (the reference's training never asks for it; autograd there would answer) -- the data gradient of the composite
     enc.0 o enc.1 convolution, a transposed convolution with the composite weights' image channels.
     zero_fed_biases=False skips writing the (identically zero) gradients of the conv biases that feed a
-    BatchNorm -- for callers whose gradient buffer is zero there already (FusedTrainer)."""
+    BatchNorm -- for callers whose gradient buffer is zero there already (FusedTrainer).
+    A context made with per_sample=True goes backward per patch at any B (the reference's batch-of-one calls, batched): patch
+    b's BatchNorm backward takes patch b's own (sum dy, sum dy * a), mean, invstd and count H * W, so g_z[b] -> dx[b] is what a
+    batch of that one patch gives; the parameter gradients are the sums over the patches.  Every operand then carries
+    per-sample coefficients and every data-gradient launch writes its slabs per patch; the fused backward kernels (one
+    coefficient set in registers, one slab per persistent workgroup) are not reached.
+    want_param_grads=False: the data gradient only -- G is not called; no weight-gradient launch, no e1_chain, no slab
+    reduction, no dgamma / dbeta."""
     pending = list(pending_extra)                    # (slabs, dst) pairs that ride along in the one slab reduction
-    if cx.per_sample and cx.B > 1:
-        raise NotImplementedError("backward through per-sample BatchNorm statistics with B > 1")
+    if not want_param_grads:
+        G = _no_grads
     B, x = cx.B, cx.x
+    ps = bool(cx.per_sample)
+    nb = B if ps else 0
+    fused = FUSED_BACKWARD and not ps and want_param_grads
     NIN, nh, c1 = L.nin, L.nh, L.nh // 2
     H1, W1, H2, W2, H3, W3 = cx.dims
-    g_z = g_z.contiguous()
+    dy3, st = latent_stage_backward(L, cx, g_z, G, pending, zero_fed_biases, want_param_grads)
 
-    g_h, stats = residual_backward(L.res, cx.res, g_z, G, cx.a4, pending=pending, zero_fed_biases=zero_fed_biases)
-    cnt3 = B * H3 * W3
-    da4 = _bn_backward(stats, cnt3, L.bn4, cx.saved4, g_h, cx.a4, G, G(L.enc10.bias), zero_fed_biases)
-    if FUSED_BACKWARD and cx.coef3.dim() == 2 and ops.conv3x3_bwd_fused_supported(nh, nh, H3, W3):
-        # enc.10: data and weight gradient from ONE staging of the patch -- csrc/conv3x3_bwd.hip
-        dy3, st = ops.conv3x3_bwd_fused(da4, cx.a3, cx.coef3, _w(L.enc10.weight), G(L.enc10.weight), B, nh, q=cx.a3, pending=pending)
-    else:
-        dy3, st = _conv_backward_pair(da4, cx.a3, cx.coef3, L.enc10.weight, G(L.enc10.weight), B, nh, nh, H3, W3, 3, pending,
-                                      like=g_h, stat_q=cx.a3)
-
-    da3 = _bn_backward(st, cnt3, L.bn3, cx.saved3, dy3, cx.a3, G, G(L.enc7.bias), zero_fed_biases)
-    if FUSED_BACKWARD and cx.coef2.dim() == 2 and ops.conv4x4s2_bwd_fused_supported(nh, nh, H3, W3):
+    da3 = _bn_backward(st, H3 * W3 * (1 if ps else B), L.bn3, cx.saved3, dy3, cx.a3, G, G(L.enc7.bias), zero_fed_biases, nbatch=nb)
+    if fused and cx.coef2.dim() == 2 and ops.conv4x4s2_bwd_fused_supported(nh, nh, H3, W3):
         # enc.7: data and weight gradient from ONE staging of the patch -- csrc/conv4x4s2_patch.hip
         dy2, st = ops.conv4x4s2_bwd_fused(da3, cx.a2, cx.coef2, _w(L.enc7.weight), G(L.enc7.weight), B, pending=pending)
     else:
         dy2, st = _conv_backward_pair(da3, cx.a2, cx.coef2, L.enc7.weight, G(L.enc7.weight), B, nh, nh, H3, W3, 4, pending,
-                                      like=g_h, stat_q=cx.a2)
+                                      like=dy3, stat_q=cx.a2, per_sample=ps)
 
-    da2 = _bn_backward(st, B * H2 * W2, L.bn2, cx.saved2, dy2, cx.a2, G, G(L.enc4.bias), zero_fed_biases)
-    if FUSED_BACKWARD and ops.conv_bwd_s2_fused_supported(nh, c1, H2, W2):
+    da2 = _bn_backward(st, H2 * W2 * (1 if ps else B), L.bn2, cx.saved2, dy2, cx.a2, G, G(L.enc4.bias), zero_fed_biases, nbatch=nb)
+    if fused and cx.coef1.dim() == 2 and ops.conv_bwd_s2_fused_supported(nh, c1, H2, W2):
         # enc.4: data gradient + weight gradient from ONE staging of (dy2, a2, a1) -- csrc/conv_mfma.hip, kernel D
         dy1, st = ops.conv_bwd_s2_fused(da2, Op(cx.a1, DM_LOAD_AFFINE_RELU, cx.coef1), _view_swapped(L.enc4.weight),
                                         G(L.enc4.weight), B, nh, c1, H2, W2, mask=Op(cx.a1, DM_LOAD_AFFINE, cx.coef1),
                                         stat_q=cx.a1, pending=pending)
     else:
         dy1, st = _conv_backward_pair(da2, cx.a1, cx.coef1, L.enc4.weight, G(L.enc4.weight), B, nh, c1, H2, W2, 4, pending,
-                                      like=g_h, stat_q=cx.a1)
+                                      like=dy3, stat_q=cx.a1, per_sample=ps)
 
-    da1 = _bn_backward(st, B * H1 * W1, L.bn1, cx.saved1, dy1, cx.a1, G)
-    dweff = torch.empty((c1, NIN + 1, 4, 4), device=x.device, dtype=torch.float32)
-    ops.wgrad(da1, Op(x, ones=True), dweff, B, c1, NIN + 1, H1, W1, 4, pending=pending)
-    ops.reduce_slabs_multi(pending)                  # all encoder weight gradients in one launch
-    ops.e1_chain(dweff, _w(L.enc0.weight), _w(L.enc0.bias), _w(L.enc1.weight), G(L.enc0.weight), G(L.enc0.bias), G(L.enc1.weight))
-    _fed_bias(G(L.enc1.bias), L.bn1, da1.coef, G, zero_fed_biases)
+    da1 = _bn_backward(st, H1 * W1 * (1 if ps else B), L.bn1, cx.saved1, dy1, cx.a1, G, nbatch=nb)
+    if want_param_grads:
+        dweff = torch.empty((c1, NIN + 1, 4, 4), device=x.device, dtype=torch.float32)
+        ops.wgrad(da1, Op(x, ones=True), dweff, B, c1, NIN + 1, H1, W1, 4, pending=pending)
+        ops.reduce_slabs_multi(pending)                  # all encoder weight gradients in one launch
+        ops.e1_chain(dweff, _w(L.enc0.weight), _w(L.enc0.bias), _w(L.enc1.weight), G(L.enc0.weight), G(L.enc0.bias), G(L.enc1.weight))
+        _fed_bias(G(L.enc1.bias), L.bn1, da1.coef, G, zero_fed_biases)
     if want_dx:
         # a1 = conv(x, Weff[:, :NIN]) + border bias: dx = ConvTranspose(da1, Weff[:, :NIN]) (phase-decomposed kernel family;
         # the ones channel of the composite carries no gradient to x)
@@ -547,16 +618,16 @@ def _pending(pending):
     return own, lambda: ops.reduce_slabs_multi(own)
 
 
-def _loss_gradient(dec, x, mask, var, gscale, gdec_ext):
+def _loss_gradient(dec, x, mask, var, gscale, gdec_ext, want_sums=True):
     """The gradient w.r.t. decoded -- of the reconstruction loss (gscale; None: no loss term) plus the upstream one (gdec_ext;
-    None: none) -- and the slabs of its channel sums (the last layer's bias gradient)."""
+    None: none) -- and the slabs of its channel sums (the last layer's bias gradient; want_sums=False: not reduced)."""
     if gscale is None:
         g, part = gdec_ext.contiguous(), None
     else:
         g, part = ops.recon_loss_backward(dec, x, mask, var, gscale)
         if gdec_ext is not None:
             g, part = g + gdec_ext, None
-    return g, part if part is not None else ops.channel_stats(g)
+    return g, part if (part is not None or not want_sums) else ops.channel_stats(g)
 
 
 def _head_backward_unfused(L, cx, d4, var, gscale, gdec_ext, G, pending):
@@ -651,25 +722,32 @@ def z32_stem_forward(conv0, bn0, conv1, bn1, x, per_sample=False):
     return h, cx
 
 
-def z32_stem_backward(conv0, bn0, conv1, bn1, cx, g_h, G, stats=None, pending=None, zero_fed_biases=True, want_dx=False):
+def z32_stem_backward(conv0, bn0, conv1, bn1, cx, g_h, G, stats=None, pending=None, zero_fed_biases=True, want_dx=False,
+                      want_param_grads=True):
     """stats: the (sum g, sum g*a2) slabs when the caller's last kernel already produced them (residual_backward with
     q_below = cx.a2); pending: the caller's list for ONE slab reduction of the whole backward pass (None: reduced here);
     zero_fed_biases=False: the gradient buffer is zero already (FusedTrainer) -- the identically zero gradients of the
-    conv biases that feed a BatchNorm are not written."""
-    if getattr(cx, "per_sample", False) and cx.dims[0] > 1:
-        raise NotImplementedError("backward through per-sample BatchNorm statistics with B > 1")
+    conv biases that feed a BatchNorm are not written.
+    A context made with per_sample=True goes backward per patch and want_param_grads=False returns the data gradient only,
+    both as in encoder_backward (`stats` then is grouped by patch: residual_backward's per-sample slabs)."""
     B, NIN, c1, nh, H1, W1, H2, W2 = cx.dims
+    ps = bool(getattr(cx, "per_sample", False))
+    nb = B if ps else 0
+    if not want_param_grads:
+        G = _no_grads
     g_h = g_h.contiguous()
     pending, reduce = _pending(pending)
     if stats is None:
-        stats = ops.channel_stats(g_h, cx.a2)
-    da2 = _bn_backward(stats, B * H2 * W2, bn1, cx.saved2, g_h, cx.a2, G)
+        stats = (ops.channel_stats_per_sample if ps else ops.channel_stats)(g_h, cx.a2)
+    da2 = _bn_backward(stats, H2 * W2 * (1 if ps else B), bn1, cx.saved2, g_h, cx.a2, G, nbatch=nb)
     dy1, st = _conv_backward_pair(da2, cx.a1, cx.coef1, conv1.weight, G(conv1.weight), B, nh, c1, H2, W2, 4, pending, like=g_h,
-                                  stat_q=cx.a1, between=lambda: _fed_bias(G(conv1.bias), bn1, da2.coef, G, zero_fed_biases))
-    da1 = _bn_backward(st, B * H1 * W1, bn0, cx.saved1, dy1, cx.a1, G)
-    ops.wgrad(da1, Op(cx.x), G(conv0.weight), B, c1, NIN, H1, W1, 4, pending=pending)
-    _fed_bias(G(conv0.bias), bn0, da1.coef, G, zero_fed_biases)
-    reduce()
+                                  stat_q=cx.a1, between=lambda: _fed_bias(G(conv1.bias), bn1, da2.coef, G, zero_fed_biases),
+                                  per_sample=ps)
+    da1 = _bn_backward(st, H1 * W1 * (1 if ps else B), bn0, cx.saved1, dy1, cx.a1, G, nbatch=nb)
+    if want_param_grads:
+        ops.wgrad(da1, Op(cx.x), G(conv0.weight), B, c1, NIN, H1, W1, 4, pending=pending)
+        _fed_bias(G(conv0.bias), bn0, da1.coef, G, zero_fed_biases)
+        reduce()
     if want_dx:          # the gradient w.r.t. the input patches: conv0's data gradient (see encoder_backward)
         dx, _ = ops.conv3x3(da1, _view_swapped(conv0.weight), B, c1, 4 * NIN, H1, W1, taps=9, pixel_shuffle=True)
         return dx
@@ -693,30 +771,41 @@ def z32_tail_forward(up0, bn, up1, r, x, mask, channel_var, per_sample=False, de
     var = _var(channel_var, NIN, r.device)
     slabs = ops.recon_loss(dec, x, mask, var) if x is not None else None
     cx = SimpleNamespace(r=r, d1=d1, coefd=coefd, savedd=savedd, dec=dec, x=x, mask=mask, var=var, loss_slabs=slabs,
-                         dims=(B, nh, c1, NIN, H2, W2))
+                         per_sample=ps, dims=(B, nh, c1, NIN, H2, W2))
     return dec, cx
 
 
-def z32_tail_backward(up0, bn, up1, cx, gscale, gdec_ext, G, want_gr=True, pending=None, zero_fed_biases=True):
+def z32_tail_backward(up0, bn, up1, cx, gscale, gdec_ext, G, want_gr=True, pending=None, zero_fed_biases=True,
+                      want_param_grads=True):
     """gscale: 1-element device tensor d(total)/d(recon_loss) or None; gdec_ext: upstream gradient w.r.t. decoded or None.
-    pending / zero_fed_biases: as in z32_stem_backward."""
+    pending / zero_fed_biases / a per_sample context / want_param_grads: as in z32_stem_backward."""
     B, nh, c1, NIN, H2, W2 = cx.dims
+    ps = bool(getattr(cx, "per_sample", False))
+    nb = B if ps else 0
+    if not want_param_grads:
+        G = _no_grads
     pending, reduce = _pending(pending)
-    g, sums = _loss_gradient(cx.dec, cx.x, cx.mask, cx.var, gscale, gdec_ext)
-    ops.pend_stats(pending, sums, [G(up1.bias)])         # the last layer's bias gradient rides in the slab reduction
-    ops.wgrad(Op(cx.d1, DM_LOAD_AFFINE_RELU, cx.coefd), Op(g), G(up1.weight), B, c1, NIN, 2 * H2, 2 * W2, 4, pending=pending)
-    dy, st = ops.conv4x4s2(Op(g), _view(up1.weight), B, NIN, c1, 4 * H2, 4 * W2, want_stats=True,
-                           mask=Op(cx.d1, DM_LOAD_AFFINE, cx.coefd), stat_q=cx.d1)
+    g, sums = _loss_gradient(cx.dec, cx.x, cx.mask, cx.var, gscale, gdec_ext, want_sums=want_param_grads)
+    d1_in, d1_mask = (Op(cx.d1, DM_LOAD_AFFINE_RELU, cx.coefd, per_sample=ps), Op(cx.d1, DM_LOAD_AFFINE, cx.coefd, per_sample=ps))
+    if want_param_grads:
+        ops.pend_stats(pending, sums, [G(up1.bias)])         # the last layer's bias gradient rides in the slab reduction
+        ops.wgrad(d1_in, Op(g), G(up1.weight), B, c1, NIN, 2 * H2, 2 * W2, 4, pending=pending)
+    dy, st = ops.conv4x4s2(Op(g), _view(up1.weight), B, NIN, c1, 4 * H2, 4 * W2, want_stats=True, mask=d1_mask, stat_q=cx.d1,
+                           **({"per_tile": True} if ps else {}))
+    if ps:
+        _need_per_sample_slabs(st, B, "z32_tail_backward: dec.4 (ConvTranspose2d %d -> %d at %d x %d)" % (c1, NIN, 2 * H2, 2 * W2))
     # da = BatchNorm backward of dy.  The weight-gradient kernels take that transform on their S operand; as the T operand only
     # where the one-pass kernel prefetches both tensors (the example widths) -- elsewhere da is materialised here
-    da = _bn_backward(st, B * 4 * H2 * W2, bn, cx.savedd, dy, cx.d1, G)
+    da = _bn_backward(st, 4 * H2 * W2 * (1 if ps else B), bn, cx.savedd, dy, cx.d1, G, nbatch=nb)
     cdb = da.coef
-    if not ops.wgrad_t_affine2_supported(nh, c1, H2, W2, 4):
-        da = Op(ops.apply(da, B, c1, 2 * H2, 2 * W2))
-    ops.wgrad(Op(cx.r), da, G(up0.weight), B, nh, c1, H2, W2, 4, pending=pending)
-    _fed_bias(G(up0.bias), bn, cdb, G, zero_fed_biases)
+    if want_param_grads:
+        if not ops.wgrad_t_affine2_supported(nh, c1, H2, W2, 4):
+            da = Op(ops.apply(da, B, c1, 2 * H2, 2 * W2))
+        ops.wgrad(Op(cx.r), da, G(up0.weight), B, nh, c1, H2, W2, 4, pending=pending)
+        _fed_bias(G(up0.bias), bn, cdb, G, zero_fed_biases)
     g_r = None
     if want_gr:
         g_r, _ = ops.conv4x4s2(da, _view(up0.weight), B, c1, nh, 2 * H2, 2 * W2)
-    reduce()
+    if want_param_grads:
+        reduce()
     return g_r

@@ -609,12 +609,57 @@ def latent_tail_forward(a3, coef3, w10, b10, gamma4, beta4, eps4, res):
 
 
 @_op
+def latent_tail_backward(g_z, a3, coef3, a4, saved4, gamma4, w10, res):
+    """The data-only backward of enc.12 .. enc.10 of every patch with that patch's own BatchNorm sums, one launch
+    (csrc/latent_tail_bwd.hip; latent_tail_supported is its gate).  res: per residual layer (ra, rb, h_in, coefa, saveda, savedb,
+    gamma_a, gamma_b, wa, wb) as the per-sample forward saved them.  Returns (dy3 (B, C, H, W), already masked by
+    relu(BN3(a3)), stats3 (B, C, 2) float64 = (sum dy3, sum dy3 * a3) per patch)."""
+    lib = L.load()
+    B, Cn, H, W = g_z.shape
+    if coef3.dim() != 3 or saved4.dim() != 3:
+        raise ValueError("dm_latent_tail_backward: per-sample coefficients (B, C, 4) and saved statistics (B, C, 2)")
+    dy3 = torch.empty_like(g_z)
+    st3 = _new((B, Cn, 2), g_z, torch.float64)
+    args = L.LatentTailBwdArgs()
+    args.g_z, args.a3, args.coef3, args.a4, args.saved4 = _ptr(g_z), _ptr(a3), _ptr(coef3), _ptr(a4), _ptr(saved4)
+    args.gamma4, args.w10, args.dy3, args.stats3 = _ptr(gamma4), _ptr(w10), _ptr(dy3), _ptr(st3, torch.float64)
+    args.B, args.C, args.H, args.W, args.nres = B, Cn, H, W, len(res)
+    args.CR = res[0][0].shape[1] if res else 32
+    for i, layer in enumerate(res):
+        ra, rb, h_in, coefa, saveda, savedb = layer[:6]
+        if coefa.dim() != 3 or saveda.dim() != 3 or savedb.dim() != 3 or tuple(rb.shape) != tuple(g_z.shape) or \
+                tuple(h_in.shape) != tuple(g_z.shape) or ra.shape[0] != B:
+            raise ValueError("dm_latent_tail_backward: residual layer %d: per-sample tensors of the batch's shape" % i)
+        for k, t in zip(("ra", "rb", "h_in", "coefa", "saveda", "savedb", "gamma_a", "gamma_b", "wa", "wb"), layer):
+            setattr(args.res[i], k, _ptr(t))
+    L.check(lib.dm_latent_tail_backward(C.byref(args), _stream()), "dm_latent_tail_backward")
+    return dy3, st3
+
+
+@_op
 def bn_backward_finalize(stats, count, gamma, saved, dgamma, dbeta):
     lib = L.load()
     nslabs, Cn = stats.shape[0], stats.shape[1]
     coef_bwd = _new((Cn, 4), gamma)
     L.check(lib.dm_bn_backward_finalize(_ptr(stats, torch.float64), nslabs, Cn, count, _ptr(gamma), _ptr(saved),
                                         _ptr(dgamma), _ptr(dbeta), _ptr(coef_bwd), _stream()), "dm_bn_backward_finalize")
+    return coef_bwd
+
+
+@_op
+def bn_backward_finalize_per_sample(stats, slabs_per_group, count_per_group, gamma, saved, dgamma=None, dbeta=None):
+    """bn_backward_finalize with every patch its own batch: stats (B * slabs_per_group, C, 2) grouped by patch, saved
+    (B, C, 2) from bn_finalize(per_sample=True), count_per_group the positions of one patch.  Returns the (B, C, 4) AFFINE2
+    coefficients; dgamma / dbeta (or None: not computed) get the sums over the patches, in index order."""
+    lib = L.load()
+    nslabs, Cn = stats.shape[0], stats.shape[1]
+    if slabs_per_group <= 0 or nslabs % slabs_per_group or tuple(saved.shape) != (nslabs // slabs_per_group, Cn, 2):
+        raise ValueError(f"dm_bn_backward_finalize_per_sample: {nslabs} slabs in groups of {slabs_per_group} against saved "
+                         f"statistics {tuple(saved.shape)}")
+    coef_bwd = _new((nslabs // slabs_per_group, Cn, 4), gamma)
+    L.check(lib.dm_bn_backward_finalize_per_sample(_ptr(stats, torch.float64), nslabs, slabs_per_group, Cn, count_per_group,
+                                                   _ptr(gamma), _ptr(saved), _ptr(dgamma), _ptr(dbeta), _ptr(coef_bwd),
+                                                   _stream()), "dm_bn_backward_finalize_per_sample")
     return coef_bwd
 
 
@@ -685,6 +730,17 @@ def channel_stats(p, q=None):
     nb = lib.dm_channel_stats_num_blocks(B, Cn, H, W)
     stats = _new((nb, Cn, 2), p, torch.float64)
     L.check(lib.dm_channel_stats(_ptr(p), _ptr(q), _ptr(stats, torch.float64), B, Cn, H, W, _stream()), "dm_channel_stats")
+    return stats
+
+
+@_op
+def channel_stats_per_sample(p, q=None):
+    """(B, C, 2) float64: (sum p, sum p*q) of every patch on its own -- the slabs bn_backward_finalize_per_sample takes."""
+    lib = L.load()
+    B, Cn, H, W = p.shape
+    stats = _new((B, Cn, 2), p, torch.float64)
+    L.check(lib.dm_channel_stats_per_sample(_ptr(p), _ptr(q), _ptr(stats, torch.float64), B, Cn, H, W, _stream()),
+            "dm_channel_stats_per_sample")
     return stats
 
 

@@ -241,6 +241,204 @@ def score_patches(model, patches, masks=None, device="cuda:0", batch_size=1024, 
     return out
 
 
+GRADIENT_KEYS = ("total_loss", "recon_loss", "commitment_loss")
+
+
+def _pow2_chunks(n):
+    """[(lo, hi), ...]: 0 .. n cut into runs whose lengths are the powers of two of n's binary expansion, largest first."""
+    out, lo = [], 0
+    while lo < n:
+        size = 1 << ((n - lo).bit_length() - 1)
+        out.append((lo, lo + size))
+        lo += size
+    return out
+
+
+def _latent_shape(model, H, W):
+    """(D, h, w) of z_before for patches of H x W."""
+    from .vq_vae import VQ_VAE_z32
+    f = 4 if isinstance(model, VQ_VAE_z32) else 8
+    return int(model.num_hiddens), H // f, W // f
+
+
+def patch_gradients(model, patches, masks=None, of="total_loss", device="cuda:0", batch_size=1024, zscore_on_device=False):
+    """The gradient of every patch's own loss with respect to its pixels, in batched passes: patch i's array is what the
+    reference's batch-of-one call leaves in x.grad for x = patches[i:i+1].requires_grad_() after
+    model(x, batch_mask=masks[i:i+1])[1][of].backward().  The model is in the mode it is handed, as in score_patches: train
+    mode = every BatchNorm with the patch's own statistics, forward and backward (running statistics advance as N
+    batch-of-one calls), eval mode = running statistics.
+    of: "total_loss" (VQ_VAE_z32: recon + commitment, as score_patches), "recon_loss", "commitment_loss", or a cotangent on
+    z_before -- an array (D*h*w,) shared by all patches or (N, D*h*w) in encode_patches' flattened layout: the result is then
+    the gradient of <of_i, z_before(x_i)>, the encoder alone (neither quantiser nor decoder runs).
+    zscore_on_device: `patches` are the raw patches and the gradient is with respect to the z-scored patch.
+    Returns float32 (N, C, H, W) in input order.  No parameter and no .grad of the model is touched; every patch's gradient is
+    the same to the bit whatever batch_size, its position and its neighbours."""
+    from . import ops
+    from .vq_vae import VQ_VAE, VQ_VAE_z32, _GradBag
+    patches = torch.as_tensor(patches)
+    if patches.dim() != 4:
+        raise AssertionError("dataset tensor dimension can only be 4, not {}".format(patches.dim()))
+    N, C, H, W = patches.shape
+    if masks is not None:
+        masks = torch.as_tensor(masks)
+        if masks.dim() != 4 or masks.shape[0] != N or masks.shape[1] not in (1, C) or tuple(masks.shape[2:]) != (H, W):
+            raise ValueError("patch_gradients: masks must be (N, 1 or C, H, W) for patches (N, C, H, W); got {} for {}".format(
+                tuple(masks.shape), tuple(patches.shape)))
+    if not isinstance(model, (VQ_VAE, VQ_VAE_z32)):
+        raise TypeError("patch_gradients: {} is not built on the HIP path (VQ_VAE, VQ_VAE_z16, VQ_VAE_z32)".format(
+            type(model).__name__))
+    D, h, w = _latent_shape(model, H, W)
+    cot = None
+    if isinstance(of, str):
+        if of not in GRADIENT_KEYS:
+            raise ValueError("patch_gradients: of must be one of {} or a cotangent on z_before; got {!r}".format(GRADIENT_KEYS, of))
+    else:
+        cot = torch.as_tensor(of)
+        if tuple(cot.shape) not in ((D * h * w,), (N, D * h * w)):
+            raise ValueError("patch_gradients: a cotangent on z_before must be ({0},) or (N, {0}) for patches {1}; got {2}".format(
+                D * h * w, tuple(patches.shape), tuple(cot.shape)))
+    if N == 0:
+        return np.zeros((0, C, H, W), np.float32)
+    device = torch.device(device)
+    cc = float(model.commitment_cost)
+    z32 = isinstance(model, VQ_VAE_z32)
+    codebook = model.vq.w.weight
+    if z32:
+        enc, dec = model.enc, model.dec
+        w_recon = w_commit = 1.0            # vae.py:457
+    else:
+        layers = E.Layers(model)
+        w_recon, w_commit = float(model.weight_recon), float(model.weight_commitment)
+    if cot is None and of == "recon_loss":
+        w_recon, w_commit = 1.0, 0.0
+    elif cot is None and of == "commitment_loss":
+        w_recon, w_commit = 0.0, 1.0
+    var = model.channel_var.detach().reshape(1, -1, 1, 1)
+    shared_cot = None
+    if cot is not None and cot.dim() == 1:
+        shared_cot = cot.to(device=device, dtype=torch.float32).reshape(1, D, h, w)
+    e1 = None
+    scalars = {}
+
+    def scalar(v):
+        """The 1-element device tensor holding v (one fill per distinct value and call)."""
+        if v not in scalars:
+            scalars[v] = torch.full((1,), v, dtype=torch.float32, device=device)
+        return scalars[v]
+
+    def loss_gradient(z_b, x, m, decode):
+        """d(sum_i loss_i) / d z_before and the part of d / d x that does not pass through the encoder.  Per batch of n
+        patches the scalar is n x the batched mean, so the loss kernels take n * weight; they form (2 / count) * scale in
+        fp32, which is the same number for every n that is a power of two, so they run on power-of-two runs of the batch."""
+        z_a, idx, _ = E.vq_forward(codebook, z_b, cc, want_scalars=False)
+        n = x.shape[0]
+        chunks = _pow2_chunks(n)
+        g_zq = g_dir = None
+        if w_recon != 0.0:
+            g_zq, g_dir = decode(z_a, x, m, chunks)
+        if w_commit == 0.0:
+            return g_zq, g_dir                                  # the quantiser's straight-through gradient as it is
+        g_z = torch.empty_like(z_b)
+        for lo, hi in chunks:
+            g_z[lo:hi], _ = ops.vq_backward_slabs(z_b[lo:hi], codebook.detach(), idx[lo:hi], None if g_zq is None else g_zq[lo:hi],
+                                                  scalar((hi - lo) * w_commit), cc)
+        return g_z, g_dir
+
+    def direct(x, decoded, m):
+        """d(recon_loss_i) / d x_i at fixed decoded: vq_vae.py:320-322 has the patch itself in the loss."""
+        g = (x - decoded) * (2.0 / (C * H * W))
+        if m is not None:
+            g = g * (m * m)
+        return (g / var) * scalar(w_recon).reshape(())
+
+    def decode_default(z_a, x, m, chunks):
+        g_zq, g_dir = torch.empty_like(z_a), torch.empty_like(x)
+        for lo, hi in chunks:                                   # (no BatchNorm in this decoder: a run of patches is a batch)
+            mm = None if m is None else m[lo:hi]
+            decoded, dcx = E.decoder_forward(layers, z_a[lo:hi], x[lo:hi], mm)
+            g_zq[lo:hi] = E.decoder_backward(layers, dcx, scalar((hi - lo) * w_recon), None, _GradBag())
+            g_dir[lo:hi] = direct(x[lo:hi], decoded, mm)
+        return g_zq, g_dir
+
+    def decode_z32(z_a, x, m, chunks):
+        defer = []
+        hs = dec[0]._handles()
+        r, saved = E.residual_forward(hs, z_a, True, defer)
+        decoded, tcx = E.z32_tail_forward(dec[1], dec[2], dec[4], r, None, None, model.channel_var, per_sample=True, defer=defer)
+        ops.bn_running_replay(defer)
+        g = torch.empty_like(decoded)
+        for lo, hi in chunks:
+            g[lo:hi], _ = ops.recon_loss_backward(decoded[lo:hi], x[lo:hi], None if m is None else m[lo:hi], tcx.var,
+                                                  scalar((hi - lo) * w_recon))
+        g_r = E.z32_tail_backward(dec[1], dec[2], dec[4], tcx, None, g, None, want_param_grads=False)
+        g_zq, _ = E.residual_backward(hs, saved, g_r, None, None, want_param_grads=False, per_sample=True)
+        return g_zq, direct(x, decoded, m)
+
+    def step(x, *rest):
+        nonlocal e1
+        rest = list(rest)
+        m = rest.pop(0) if masks is not None else None
+        wt = rest.pop(0) if (cot is not None and shared_cot is None) else None
+        if zscore_on_device:
+            x = ops.zscore_patch(x)
+        n = x.shape[0]
+        if z32:
+            hh, scx = E.z32_stem_forward(enc[0], enc[1], enc[3], enc[4], x, per_sample=True)
+            hs = enc[5]._handles()
+            z_b, saved = E.residual_forward(hs, hh, True)
+            join = None
+        else:
+            if e1 is None:
+                e1 = E.e1_operands(layers)
+            z_b, cx = E.encoder_forward(layers, x, per_sample=True, e1=e1, join=False, replay_as_latents=True)
+            join = cx.join
+        g_dir = None
+        if cot is not None:
+            g_z = (shared_cot.expand(n, D, h, w) if wt is None else wt.reshape(n, D, h, w)).contiguous()
+        else:
+            g_z, g_dir = loss_gradient(z_b, x, m, decode_z32 if z32 else decode_default)
+        if join is not None:
+            join()                                              # the running-statistics replay ran beside the loss kernels
+        if z32:
+            g_h, st = E.residual_backward(hs, saved, g_z, None, scx.a2, want_param_grads=False, per_sample=True)
+            dx = E.z32_stem_backward(enc[0], enc[1], enc[3], enc[4], scx, g_h, None, stats=st, want_dx=True, want_param_grads=False)
+        else:
+            dx = E.encoder_backward(layers, cx, g_z, None, want_dx=True, want_param_grads=False)
+        if g_dir is not None:
+            dx += g_dir
+        return (dx,)
+    inputs, dtypes = [patches], [patches.dtype if zscore_on_device else torch.float32]
+    if masks is not None:
+        inputs.append(masks)
+        dtypes.append(torch.float32)
+    if cot is not None and shared_cot is None:
+        inputs.append(cot)
+        dtypes.append(torch.float32)
+    return _pipelined(inputs, dtypes, step, device, batch_size)[0].numpy()
+
+
+def patch_gradients_sharded(model, patches, masks=None, of="total_loss", device="cuda:0", batch_size=1024,
+                            zscore_on_device=False, group=None, dst=0):
+    """patch_gradients over a torch.distributed group, the twin of score_patches_sharded: rank r takes the contiguous shard
+    dist.shard_range(N, r, world) (a patch's gradient does not depend on the batch it ran in; a per-patch cotangent is cut the
+    same way) with no collective on the data path, and the arrays are handed over on the host to rank `dst` in rank order =
+    input order; the other ranks return None."""
+    from . import dist as D
+    import torch.distributed as tdist
+    patches = torch.as_tensor(patches)
+    world = D.world_size(group)
+    rank = tdist.get_rank(group) if world > 1 else 0
+    N = patches.shape[0]
+    lo, hi = D.shard_range(N, rank, world)
+    if not isinstance(of, str):
+        of = torch.as_tensor(of)
+        if of.dim() == 2 and of.shape[0] == N:
+            of = of[lo:hi]
+    out = patch_gradients(model, patches[lo:hi], masks=None if masks is None else torch.as_tensor(masks)[lo:hi], of=of,
+                          device=device, batch_size=batch_size, zscore_on_device=zscore_on_device)
+    return D.gather_shards((out,), group=group, dst=dst)[0] if world > 1 else out
+
+
 def encode_patches_sharded(model, patches, device="cuda:0", batch_size=1024, zscore_on_device=False, group=None, dst=0):
     """encode_patches over a torch.distributed group: patches are independent (per-sample BatchNorm statistics), so rank r
     encodes the contiguous shard dist.shard_range(N, r, world) with no collective on the data path, and the (N, D*h*w)

@@ -377,12 +377,41 @@ typedef struct dm_latent_tail_args {
 int dm_latent_tail_supported(int C, int CR, int H, int W, int nres);
 int dm_latent_tail_forward(const dm_latent_tail_args *args, void *stream);
 
+/* ----- the data-only backward of the same stage, per-sample statistics, one kernel (csrc/latent_tail_bwd.hip) -----------
+ * g_z (B,16,16,16), the gradient at the encoder's output, goes back through enc.12, enc.11 and enc.10 with every patch's own
+ * BatchNorm sums (count 256) to dy3 (B,16,16,16): the gradient at enc.7's raw output a3, already masked by relu(BN3(a3)), and
+ * stats3 (B,16,2) doubles = (sum dy3, sum dy3 * a3) per patch, what dm_bn_backward_finalize_per_sample takes for enc.8
+ * (slabs_per_group 1).  Inputs: what the per-sample forward saved -- a3 with coef3 (B,16,4); a4 with saved4 (B,16,2) and gamma4;
+ * per residual layer ra (B,32,16,16) with coefa (B,32,4) and saveda (B,32,2), rb and h_in (B,16,16,16), savedb (B,16,2),
+ * gamma_a (32) / gamma_b (16) or NULL (1), wa (32,16,3,3), wb (16,32[,1,1]); w10 (16,16,3,3).  No parameter gradient.
+ * Same gate as the forward kernel: dm_latent_tail_supported(). */
+typedef struct dm_latent_tail_bwd_res {
+    const float *ra, *rb, *h_in, *coefa, *saveda, *savedb, *gamma_a, *gamma_b, *wa, *wb;
+} dm_latent_tail_bwd_res;
+typedef struct dm_latent_tail_bwd_args {
+    const float *g_z, *a3, *coef3, *a4, *saved4, *gamma4, *w10;
+    float *dy3;
+    double *stats3;
+    int32_t B, C, CR, H, W, nres;
+    dm_latent_tail_bwd_res res[4];
+} dm_latent_tail_bwd_args;
+int dm_latent_tail_backward(const dm_latent_tail_bwd_args *args, void *stream);
+
 /* Backward finalize: slabs hold (sum dy, sum dy*a).  Writes dgamma, dbeta and the
  * AFFINE2 coefficients (A,B,C) with da = A*dy + B*a + C.  count == 0: fixed statistics (eval() mode; saved = running mean and
  * 1 / sqrt(running_var + eps)): da = gamma * invstd * dy, dgamma / dbeta as always. */
 int dm_bn_backward_finalize(const double *stats, int nslabs, int C, int64_t count,
                             const float *gamma, const float *saved, float *dgamma, float *dbeta,
                             float *coef_bwd, void *stream);
+
+/* Per-sample form (every patch is its own batch, as dm_bn_finalize(per_sample = 1) normalised it): the nslabs slabs are
+ * nslabs / slabs_per_group patches of slabs_per_group consecutive slabs each, saved is (B,C,2), count_per_group the positions
+ * of ONE patch (> 0: eval() mode shares its statistics and takes the batch form).  coef_bwd (B,C,4): patch b's AFFINE2
+ * coefficients from patch b's own sums, in double.  dgamma / dbeta (C) or NULL: the per-patch terms added over the patches
+ * in index order in double, rounded once -- no atomics, the same bits at every launch. */
+int dm_bn_backward_finalize_per_sample(const double *stats, int nslabs, int slabs_per_group, int C, int64_t count_per_group,
+                                       const float *gamma, const float *saved, float *dgamma, float *dbeta,
+                                       float *coef_bwd, void *stream);
 
 /* ----- synchronized BatchNorm (data parallel): a layer's statistics as ONE float64 payload the ranks all-reduce (SUM)
  * between two launches.  The count and the weights are device values, so a graph captured for the local shape replays for
@@ -409,6 +438,9 @@ int dm_apply(const dm_operand *in, const float *resid, float *out, int B, int C,
 /* stats[block][c] = (sum p, sum p*q) over a (B,C,H,W) pair; blocks = dm_channel_stats_num_blocks. */
 int dm_channel_stats_num_blocks(int B, int C, int H, int W);
 int dm_channel_stats(const float *p, const float *q, double *stats, int B, int C, int H, int W, void *stream);
+
+/* Per-sample form: stats[b][c] = (sum p, sum p*q) over patch b alone, B slabs of [C][2] doubles in patch order. */
+int dm_channel_stats_per_sample(const float *p, const float *q, double *stats, int B, int C, int H, int W, void *stream);
 
 /* dst[n] = scale * sum_over_slabs stats[slab][n][0]   (bias gradients from epilogue stats). */
 int dm_sum_slabs(const double *stats, int nslabs, int N, float scale, float *dst, void *stream);
