@@ -83,6 +83,10 @@ SIGNATURES = {
     "dm_vq_backward": (C.c_int, [vp, vp, vp, vp, vp, f32, vp, vp] + [C.c_int] * 5 + [vp]),
     "dm_vq_backward_num_slabs": (C.c_int, [i64, C.c_int, C.c_int]),
     "dm_vq_backward_slabs": (C.c_int, [vp, vp, vp, vp, vp, f32, vp, vp] + [C.c_int] * 5 + [vp]),
+    "dm_vq_backward_stats": (C.c_int, [vp, vp, vp, vp, vp, f32, vp, vp] + [C.c_int] * 5 + [vp]),
+    "dm_vq_ema_apply": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp]),
+    "dm_vq_finalize_ema": (C.c_int, [vp, C.c_int, vp, C.c_int, i64, C.c_int, f32, vp, vp]),
+    "dm_vq_loss_finalize_ema": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, i64, f32, vp, C.c_int, i64, f32, f32, vp, C.c_int, f32, vp, vp]),
     "dm_conv4x4s2": (C.c_int, [OP, WV, vp, EP] + [C.c_int] * 5 + [vp]),
     "dm_conv4x4s2_num_blocks": (C.c_int, [C.c_int] * 6),
     "dm_conv4x4s2_scratch_floats": (i64, [C.c_int] * 5),
@@ -144,6 +148,7 @@ SIGNATURES = {
     "dm_dec_tail_score": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_size_t] + [C.c_int] * 5 + [vp]),
     "dm_recon_loss_per_sample": (C.c_int, [vp, vp, vp, C.c_int, vp, vp] + [C.c_int] * 4 + [vp]),
     "dm_vq_patch_scalars": (C.c_int, [vp, vp, vp, f32, vp, vp] + [C.c_int] * 5 + [vp]),
+    "dm_vq_patch_scalars_ema": (C.c_int, [vp, vp, vp, f32, vp, vp] + [C.c_int] * 5 + [vp]),
     "dm_score_finalize": (C.c_int, [vp, vp, f32, f32, i64, vp, C.c_int, C.c_int, vp]),
     "dm_pair_msd": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
     "dm_pair_msd_backward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),

@@ -62,6 +62,8 @@ void recon_loss_per_sample_kernel(const float *__restrict__ dec, const float *__
 
 // One workgroup per patch: scalars[b] = (loss, perplexity, mse) of vq_finalize_kernel's arithmetic over the patch's own
 // H*W positions, counts[b][k] on request.  q = codebook[idx] is gathered (K*D floats: cache-resident), z is read once.
+// EMA: the loss of the EMA codebook mode, cc * mse (no q_latent_loss term).
+template <bool EMA = false>
 __global__ __launch_bounds__(DM_BLOCK)
 void vq_patch_scalars_kernel(const float *__restrict__ z, const long long *__restrict__ idx, const float *__restrict__ cb,
                              float cc, float *__restrict__ scalars, int *__restrict__ counts, int B, int D, int K, int HW)
@@ -105,7 +107,7 @@ void vq_patch_scalars_kernel(const float *__restrict__ z, const long long *__res
         const double ent = block_sum(e, s_red);
         if (threadIdx.x == 0) {
             const float mse = (float)(tsse / ((double)HW * (double)D));
-            scalars[3 * b + 0] = mse + cc * mse;
+            scalars[3 * b + 0] = EMA ? cc * mse : mse + cc * mse;
             scalars[3 * b + 1] = expf(-(float)ent);
             scalars[3 * b + 2] = mse;
         }
@@ -164,9 +166,21 @@ extern "C" int dm_vq_patch_scalars(const float *z, const int64_t *idx, const flo
     DM_REQUIRE(z && idx && codebook && scalars, "dm_vq_patch_scalars: NULL pointer");
     DM_REQUIRE(B > 0 && D > 0 && K > 0 && H > 0 && W > 0, "dm_vq_patch_scalars: bad shape (%d, %d, %d, %d, %d)", B, D, K, H, W);
     DM_REQUIRE((long long)H * W < (1LL << 31), "dm_vq_patch_scalars: latent too large for 32-bit offsets");
-    hipLaunchKernelGGL(vq_patch_scalars_kernel, dim3(B < SC_MAX_GRID ? B : SC_MAX_GRID), dim3(DM_BLOCK), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(vq_patch_scalars_kernel<>, dim3(B < SC_MAX_GRID ? B : SC_MAX_GRID), dim3(DM_BLOCK), 0, (hipStream_t)stream,
                        z, reinterpret_cast<const long long *>(idx), codebook, commitment_cost, scalars, counts, B, D, K, H * W);
     return dm_launch_status("dm_vq_patch_scalars");
+}
+
+extern "C" int dm_vq_patch_scalars_ema(const float *z, const int64_t *idx, const float *codebook, float commitment_cost,
+                                       float *scalars, int32_t *counts, int B, int D, int K, int H, int W, void *stream)
+{
+    DM_REQUIRE(z && idx && codebook && scalars, "dm_vq_patch_scalars_ema: NULL pointer");
+    DM_REQUIRE(B > 0 && D > 0 && K > 0 && H > 0 && W > 0, "dm_vq_patch_scalars_ema: bad shape (%d, %d, %d, %d, %d)", B, D, K, H, W);
+    DM_REQUIRE((long long)H * W < (1LL << 31), "dm_vq_patch_scalars_ema: latent too large for 32-bit offsets");
+    hipLaunchKernelGGL(vq_patch_scalars_kernel<true>, dim3(B < SC_MAX_GRID ? B : SC_MAX_GRID), dim3(DM_BLOCK), 0,
+                       (hipStream_t)stream, z, reinterpret_cast<const long long *>(idx), codebook, commitment_cost, scalars,
+                       counts, B, D, K, H * W);
+    return dm_launch_status("dm_vq_patch_scalars_ema");
 }
 
 extern "C" int dm_score_finalize(const double *patch_sums, const float *vq_scalars, float weight_recon,

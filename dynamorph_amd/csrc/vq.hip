@@ -1317,6 +1317,9 @@ __global__ void vq_decode_kernel(const long long *__restrict__ idx, const float 
     for (int d = 0; d < D; ++d) q[(b * D + d) * HW + p] = cb[k * D + d];
 }
 
+// (EMA: the quantiser's loss of the EMA codebook mode, cc * mse -- the codebook is not trained by a gradient, so there is no
+// q_latent_loss term; everything else is the same arithmetic)
+template <bool EMA = false>
 __global__ void vq_finalize_kernel(const double *__restrict__ sse_slabs, int nslabs,
                                    const int *__restrict__ hist, int K, long long P, int D,
                                    float cc, float *__restrict__ scalars)
@@ -1333,7 +1336,7 @@ __global__ void vq_finalize_kernel(const double *__restrict__ sse_slabs, int nsl
     const double ent = block_sum(e, s_red);
     if (threadIdx.x == 0) {
         const float mse = (float)(sse / ((double)P * (double)D));
-        scalars[0] = mse + cc * mse;           // q_latent_loss + commitment_cost * e_latent_loss
+        scalars[0] = EMA ? cc * mse : mse + cc * mse;   // q_latent_loss + commitment_cost * e_latent_loss
         scalars[1] = expf(-(float)ent);
         scalars[2] = mse;
     }
@@ -1342,6 +1345,8 @@ __global__ void vq_finalize_kernel(const double *__restrict__ sse_slabs, int nsl
 // The training step's last scalar launch: vq_finalize_kernel + the reconstruction-loss finaliser in one, reading the
 // code counters straight from their replicas (no vq_hist_reduce launch before it).  out = (recon, commitment, total,
 // perplexity), same arithmetic as dm_vq_finalize followed by dm_loss_finalize.
+// (EMA: a step in the EMA codebook mode, commitment = cc * mse)
+template <bool EMA = false>
 __global__ __launch_bounds__(1024) void vq_loss_finalize_kernel(const double *__restrict__ sse_slabs, int nslabs, const int *__restrict__ hrep,
                                         const int *__restrict__ hdr,
                                         int K, long long P, int D, float cc, const double *__restrict__ loss_slabs, int nloss,
@@ -1402,7 +1407,7 @@ __global__ __launch_bounds__(1024) void vq_loss_finalize_kernel(const double *__
     const double tml = ntm > 0 ? block_sum(m, s_red) : 0.0;
     if (threadIdx.x == 0) {
         const float mse = (float)(sse / ((double)P * (double)D));
-        const float commit = mse + cc * mse;
+        const float commit = EMA ? cc * mse : mse + cc * mse;
         const float recon = (float)(tot / (double)count);
         out[0] = recon;
         out[1] = commit;
@@ -1429,7 +1434,13 @@ constexpr int VQ_BWD_LDS = 136 * 1024;     // codebook-gradient window per workg
 __host__ __device__ constexpr int vq_bwd_row(int D) { return D + 1; }
 // grid (x: positions, grid stride; y: windows of Kc codes).  A workgroup only touches the positions whose code falls
 // into its window, so z / g_out / dz are still streamed once; idx is read once per window.
-template <int D>
+//
+// STATS (the EMA codebook mode, dm_vq_backward_stats): the same walk with another payload.  A cell takes z[p][d] instead of
+// sw * (e - z), so the window ends up as s[k][d] = sum_{p: idx[p] = k} z[p][d]; the row's pad word, which the gradient form
+// never touches, counts the code's positions as an integer (wave 0 adds 1 per position).  A slab is then K * (D + 1) floats:
+// [K][D] sums, then [K] counts converted to float (exact: a workgroup holds far fewer than 2^24 positions).  dz is formed by
+// the same instructions as in the gradient form; there is no atomic form (dw_slabs is required).
+template <int D, bool STATS = false>
 __global__ __launch_bounds__(VQ_BWD_BLOCK) void vq_backward_kernel(
     const float *__restrict__ z, const float *__restrict__ cb, const long long *__restrict__ idx,
     const float *__restrict__ g_out, const float *__restrict__ g_loss_dev, float cc,
@@ -1523,7 +1534,12 @@ __global__ __launch_bounds__(VQ_BWD_BLOCK) void vq_backward_kernel(
                 if (hit[c]) {
                     const int d = d_lo + j;
                     if (dz) dz[S.base[c] + (long long)d * HW] = S.gv[j][c] + sz * (S.zv[j][c] - qd[c][j]);
-                    atomicAdd(&s_dw[kl[c] * RS + d], sw * (qd[c][j] - S.zv[j][c]));
+                    if constexpr (STATS) {
+                        atomicAdd(&s_dw[kl[c] * RS + d], S.zv[j][c]);
+                        if (j == 0 && wave == 0) atomicAdd(reinterpret_cast<int *>(&s_dw[kl[c] * RS + D]), 1);
+                    } else {
+                        atomicAdd(&s_dw[kl[c] * RS + d], sw * (qd[c][j] - S.zv[j][c]));
+                    }
                 }
     };
     if (d_lo < D) {
@@ -1540,6 +1556,13 @@ __global__ __launch_bounds__(VQ_BWD_BLOCK) void vq_backward_kernel(
         }
     }
     __syncthreads();
+    if constexpr (STATS) {
+        float *__restrict__ slab = dw_slabs + (long long)blockIdx.x * K * RS;
+        for (int i = threadIdx.x; i < kn * D; i += VQ_BWD_BLOCK) slab[k_lo * D + i] = s_dw[(i / D) * RS + i % D];
+        for (int k = threadIdx.x; k < kn; k += VQ_BWD_BLOCK)
+            slab[(long long)K * D + k_lo + k] = (float)__float_as_int(s_dw[k * RS + D]);
+        return;
+    }
     for (int i = threadIdx.x; i < kn * D; i += VQ_BWD_BLOCK) {
         const float v = s_dw[(i / D) * RS + i % D];
         if (dw_slabs) dw_slabs[(long long)blockIdx.x * K * D + k_lo * D + i] = v;   // dm_reduce_slabs adds them in slab order
@@ -1547,8 +1570,11 @@ __global__ __launch_bounds__(VQ_BWD_BLOCK) void vq_backward_kernel(
     }
 }
 
+
 // Any embedding_dim: vq_backward_kernel with the width at run time (the same LDS window of code gradients, the same
 // arithmetic per element; a coverage path for widths without an instantiation).
+// STATS: the statistics form, as in vq_backward_kernel (cells take z, wave 0 counts in the rows' pad word).
+template <bool STATS = false>
 __global__ __launch_bounds__(VQ_BWD_BLOCK) void vq_backward_any_kernel(
     const float *__restrict__ z, const float *__restrict__ cb, const long long *__restrict__ idx,
     const float *__restrict__ g_out, const float *__restrict__ g_loss_dev, float cc,
@@ -1580,16 +1606,27 @@ __global__ __launch_bounds__(VQ_BWD_BLOCK) void vq_backward_any_kernel(
                 const long long o = base + (long long)d * HW;
                 const float zv = z[o], qv = q[d], gv = g_out ? g_out[o] : 0.f;
                 if (dz) dz[o] = gv + sz * (zv - qv);
-                atomicAdd(&s_dw[kl * RS + d], sw * (qv - zv));
+                if constexpr (STATS) atomicAdd(&s_dw[kl * RS + d], zv);
+                else atomicAdd(&s_dw[kl * RS + d], sw * (qv - zv));
             }
+            if constexpr (STATS)
+                if (wave == 0) atomicAdd(reinterpret_cast<int *>(&s_dw[kl * RS + D]), 1);
         }
     __syncthreads();
+    if constexpr (STATS) {
+        float *__restrict__ slab = dw_slabs + (long long)blockIdx.x * K * RS;
+        for (int i = threadIdx.x; i < kn * D; i += VQ_BWD_BLOCK) slab[k_lo * D + i] = s_dw[(i / D) * RS + i % D];
+        for (int k = threadIdx.x; k < kn; k += VQ_BWD_BLOCK)
+            slab[(long long)K * D + k_lo + k] = (float)__float_as_int(s_dw[k * RS + D]);
+        return;
+    }
     for (int i = threadIdx.x; i < kn * D; i += VQ_BWD_BLOCK) {
         const float v = s_dw[(i / D) * RS + i % D];
         if (dw_slabs) dw_slabs[(long long)blockIdx.x * K * D + k_lo * D + i] = v;
         else if (v != 0.f) atomicAdd(&dw[k_lo * D + i], v);
     }
 }
+
 
 
 // ---- codebooks of at most 64 codes (every configuration of the reference): the codebook gradient as a one-hot product
@@ -1600,8 +1637,13 @@ __global__ __launch_bounds__(VQ_BWD_BLOCK) void vq_backward_any_kernel(
 // writes ONE slab, so the sum over positions has a fixed order: no float atomics anywhere (the LDS-atomic kernel
 // above stays for larger codebooks, where a one-hot product would cost K/16 matrix instructions per four positions).
 // Lane (i = lane & 15, g = lane >> 4) holds row d = 16 dt + i of four position quads: z[d][16 u + 4 g .. + 3].
+//
+// STATS (the EMA codebook mode): the same product with B[kk = position][j = d] = z itself, so the accumulators end up as
+// s[k][d] = sum_{p: idx[p] = k} z[p][d] in the same fixed order.  The counts are integers in the pad word of the codebook's
+// LDS rows (one ds_add_u32 per wave and chunk; the combine below never writes that word), so no second LDS object and no
+// extra column of matrix instructions.  The slab is K * (D + 1) floats: [K][D] sums, then [K] counts as floats.
 constexpr int VQ_BWD2_BLOCK = 512;
-template <int D, int WGS>
+template <int D, int WGS, bool STATS = false>
 __global__ __launch_bounds__(VQ_BWD2_BLOCK, WGS) void vq_backward_mfma_kernel(
     const float *__restrict__ z, const float *__restrict__ cb, const long long *__restrict__ idx,
     const float *__restrict__ g_out, const float *__restrict__ g_loss_dev, float cc,
@@ -1656,6 +1698,8 @@ __global__ __launch_bounds__(VQ_BWD2_BLOCK, WGS) void vq_backward_mfma_kernel(
         const int k = e / D, d = e - k * D;
         s_cb[k * HROW + d] = k < K ? cb[e] : 0.f;
     }
+    if constexpr (STATS)
+        if (threadIdx.x < 64) s_cb[threadIdx.x * HROW + D] = 0.f;      // the rows' pad words: the codes' counters
     __syncthreads();
     for (; chunk < NC; chunk += step) {
         const unsigned b = chunk / cps, cw = chunk - b * cps;
@@ -1665,6 +1709,8 @@ __global__ __launch_bounds__(VQ_BWD2_BLOCK, WGS) void vq_backward_mfma_kernel(
             if (g_out) load(gr, g_out, b, cw);
             kv = idx32[2 * ((long long)chunk * 64 + lane)];
         }
+        if constexpr (STATS)     // lane = position of the chunk; clamped like the gather below
+            atomicAdd(reinterpret_cast<int *>(&s_cb[((unsigned)kv < 64u ? kv : 63) * HROW + D]), 1);
         if constexpr (PF) {
             // the next chunk's rows are in flight during this one's products (past the end: the last chunk again, from L2 --
             // an unconditional load keeps the wait counts exact)
@@ -1707,7 +1753,7 @@ __global__ __launch_bounds__(VQ_BWD2_BLOCK, WGS) void vq_backward_mfma_kernel(
                 for (int dt = 0; dt < DT; ++dt) {
                     const float zc = zr[dt][u][t], gc = gr[dt][u][t];
                     const float diff = ev[dt][u][t] - zc;
-                    bv[dt] = sw * diff;
+                    bv[dt] = STATS ? zc : sw * diff;
                     gr[dt][u][t] = gc - sz * diff;            // g + sz * (z - e), the bits of the kernel above
                 }
                 // (all four code tiles: a tile past K holds no index, its products are zeros)
@@ -1767,11 +1813,47 @@ __global__ __launch_bounds__(VQ_BWD2_BLOCK, WGS) void vq_backward_mfma_kernel(
         }
         __syncthreads();
     }
-    float *slab = dw_slabs + (long long)blockIdx.x * K * D;
+    float *slab = dw_slabs + (long long)blockIdx.x * K * (STATS ? HROW : D);
     for (int e = threadIdx.x; e < K * D; e += VQ_BWD2_BLOCK) {
         const int k = e / D, d = e - k * D;
         slab[e] = s_sum[k * HROW + d];
     }
+    if constexpr (STATS)
+        if (threadIdx.x < K) slab[K * D + threadIdx.x] = (float)__float_as_int(s_sum[threadIdx.x * HROW + D]);
+}
+
+
+// ---- the EMA codebook update ("Neural Discrete Representation Learning", appendix A.1), one launch, in place:
+//   N <- g N + (1 - g) n;   m <- g m + (1 - g) s;   Nt[k] = (N[k] + eps) / (sum N + K eps) * sum N;   e[k] <- m[k] / Nt[k]
+// stats = [K][D] sums s, then [K] counts n (the reduced slabs of dm_vq_backward_stats, summed over the ranks).  K (D + 1)
+// elements are too few to matter: ONE workgroup, the arithmetic in double from the fp32 inputs, every stored value rounded
+// once.  The new N are formed twice from the old ones (for their sum, then per element) and stored last, so nothing reads
+// a value this launch has written.
+__global__ __launch_bounds__(1024) void vq_ema_apply_kernel(const float *__restrict__ stats, float *__restrict__ N,
+                                                            float *__restrict__ m, float *__restrict__ e, int K, int D,
+                                                            double decay, double eps)
+{
+    __shared__ double s_red[16];
+    __shared__ double s_tot;
+    const double g = decay, h = 1.0 - decay;
+    const float *__restrict__ cnt = stats + (long long)K * D;
+    double part = 0.0;
+    for (int k = threadIdx.x; k < K; k += 1024) part += g * (double)N[k] + h * (double)cnt[k];
+    const double t = block_sum(part, s_red);
+    if (threadIdx.x == 0) s_tot = t;
+    __syncthreads();
+    const double tot = s_tot, den = tot + (double)K * eps;
+    const long long KD = (long long)K * D;
+    for (long long i = threadIdx.x; i < KD; i += 1024) {
+        const int k = (int)(i / D);
+        const double nk = g * (double)N[k] + h * (double)cnt[k];
+        const double mk = g * (double)m[i] + h * (double)stats[i];
+        const double nt = (nk + eps) / den * tot;
+        m[i] = (float)mk;
+        e[i] = (float)(mk / nt);
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < K; k += 1024) N[k] = (float)(g * (double)N[k] + h * (double)cnt[k]);
 }
 
 // widths with register-resident instantiations of the exact kernels; every other width 1 .. 512 takes vq_forward_any_kernel /
@@ -2044,25 +2126,46 @@ extern "C" int dm_vq_finalize(const double *sse_slabs, int nslabs, const int32_t
                               int64_t positions, int D, float commitment_cost, float *scalars, void *stream)
 {
     DM_REQUIRE(sse_slabs && hist && scalars && nslabs > 0 && K > 0 && positions > 0, "dm_vq_finalize: bad argument");
-    hipLaunchKernelGGL(vq_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(vq_finalize_kernel<>, dim3(1), dim3(256), 0, (hipStream_t)stream,
                        sse_slabs, nslabs, (const int *)hist, K, (long long)positions, D, commitment_cost, scalars);
     return dm_launch_status("dm_vq_finalize");
+}
+
+extern "C" int dm_vq_finalize_ema(const double *sse_slabs, int nslabs, const int32_t *hist, int K,
+                                  int64_t positions, int D, float commitment_cost, float *scalars, void *stream)
+{
+    DM_REQUIRE(sse_slabs && hist && scalars && nslabs > 0 && K > 0 && positions > 0, "dm_vq_finalize_ema: bad argument");
+    hipLaunchKernelGGL(vq_finalize_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream,
+                       sse_slabs, nslabs, (const int *)hist, K, (long long)positions, D, commitment_cost, scalars);
+    return dm_launch_status("dm_vq_finalize_ema");
 }
 
 // The step's scalar launch, with or without the pairwise term (`tm`: its partial losses and weight)
 static int vq_loss_finalize_launch(const char *who, bool tm, const double *sse_slabs, int nslabs, const void *workspace, int K, int D,
                                    int64_t positions, float commitment_cost, const double *loss_slabs, int nloss, int64_t count,
                                    float weight_recon, float weight_commitment, const double *tm_slabs, int ntm, float weight_matching,
-                                   float *scalars_out, void *stream)
+                                   float *scalars_out, void *stream, bool ema = false)
 {
     DM_REQUIRE(sse_slabs && workspace && loss_slabs && scalars_out && (!tm || (tm_slabs && ntm > 0)) && nslabs > 0 && nloss > 0 &&
                    K > 0 && D > 0 && positions > 0 && count > 0, "%s: bad argument", who);
     const Vq2Layout L = vq2_layout(K, D);
     const int *hrep = reinterpret_cast<const int *>(reinterpret_cast<const float *>(workspace) + L.hrep);
-    hipLaunchKernelGGL(vq_loss_finalize_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, sse_slabs, nslabs, hrep,
+    hipLaunchKernelGGL(ema ? vq_loss_finalize_kernel<true> : vq_loss_finalize_kernel<>, dim3(1), dim3(1024), 0, (hipStream_t)stream,
+                       sse_slabs, nslabs, hrep,
                        reinterpret_cast<const int *>(workspace), K, (long long)positions, D, commitment_cost, loss_slabs, nloss,
                        (long long)count, weight_recon, weight_commitment, scalars_out, tm_slabs, ntm, weight_matching);
     return dm_launch_status(who);
+}
+
+extern "C" int dm_vq_loss_finalize_ema(const double *sse_slabs, int nslabs, const void *workspace, int K, int D,
+                                       int64_t positions, float commitment_cost, const double *loss_slabs, int nloss,
+                                       int64_t count, float weight_recon, float weight_commitment, const double *tm_slabs,
+                                       int ntm, float weight_matching, float *scalars_out, void *stream)
+{
+    const bool tm = tm_slabs != nullptr;
+    return vq_loss_finalize_launch("dm_vq_loss_finalize_ema", tm, sse_slabs, nslabs, workspace, K, D, positions, commitment_cost,
+                                   loss_slabs, nloss, count, weight_recon, weight_commitment, tm_slabs, tm ? ntm : 0,
+                                   tm ? weight_matching : 0.f, scalars_out, stream, true);
 }
 
 extern "C" int dm_vq_loss_finalize(const double *sse_slabs, int nslabs, const void *workspace, int K, int D,
@@ -2095,11 +2198,14 @@ int vq_backward_grid(long long P, int K, int D)
     return (int)(want < cap ? want : cap);
 }
 
+// stats: the slabs take dm_vq_backward_stats' payload (K * (D + 1) floats each) instead of the codebook gradient; the routes
+// and their conditions are the same
 int vq_backward_launch(const char *who, const float *z, const float *codebook, const int64_t *idx, const float *g_out,
                        const float *g_loss_dev, float commitment_cost, float *dz, float *dw, float *dw_slabs,
-                       int B, int D, int K, int H, int W, void *stream)
+                       int B, int D, int K, int H, int W, void *stream, bool stats = false)
 {
     DM_REQUIRE(z && codebook && idx && (dw || dw_slabs), "%s: NULL pointer", who);
+    DM_REQUIRE(!stats || (dw_slabs && !dw), "%s: the statistics come as slabs", who);
     DM_REQUIRE(vq_dim_supported(D), "%s: embedding_dim %d outside 1 .. 512", who, D);
     const long long P = (long long)B * H * W;
     int Kc = VQ_BWD_LDS / (vq_bwd_row(D) * (int)sizeof(float));
@@ -2111,24 +2217,39 @@ int vq_backward_launch(const char *who, const float *z, const float *codebook, c
     const uintptr_t al = (uintptr_t)z | (uintptr_t)g_out | (uintptr_t)dz;
     if (dw_slabs && K <= 64 && (D == 16 || D == 32 || D == 64) && (H * W) % 64 == 0 && (al & 15) == 0) {
         const unsigned NC = (unsigned)(P >> 6);
+#define DM_VQ_BWD2_ARGS dim3((unsigned)grid), dim3(VQ_BWD2_BLOCK), 0, s, z, codebook, (const long long *)idx, g_out, g_loss_dev, \
+                        commitment_cost, dz, dw_slabs, K, H * W, NC
 #define DM_VQ_BWD2(DD, WGS)                                                                                    \
-    hipLaunchKernelGGL((vq_backward_mfma_kernel<DD, WGS>), dim3((unsigned)grid), dim3(VQ_BWD2_BLOCK), 0, s, z, codebook, \
-                       (const long long *)idx, g_out, g_loss_dev, commitment_cost, dz, dw_slabs, K, H * W, NC)
+    if (stats) hipLaunchKernelGGL((vq_backward_mfma_kernel<DD, WGS, true>), DM_VQ_BWD2_ARGS);                  \
+    else hipLaunchKernelGGL((vq_backward_mfma_kernel<DD, WGS>), DM_VQ_BWD2_ARGS)
         switch (D) {
         case 16: DM_VQ_BWD2(16, 4); break;
         case 32: DM_VQ_BWD2(32, 2); break;
         default: DM_VQ_BWD2(64, 2); break;
         }
 #undef DM_VQ_BWD2
+#undef DM_VQ_BWD2_ARGS
         return dm_launch_status(who);
     }
     if (!vq_dim_built(D)) {
-        if (const int rc = vq_reserve_lds(who, (const void *)vq_backward_any_kernel, lds, nullptr)) return rc;
-        hipLaunchKernelGGL(vq_backward_any_kernel, g3, dim3(VQ_BWD_BLOCK), lds, s, z, codebook, (const long long *)idx, g_out,
+        if (stats) {
+            if (const int rc = vq_reserve_lds(who, (const void *)vq_backward_any_kernel<true>, lds, nullptr)) return rc;
+            hipLaunchKernelGGL(vq_backward_any_kernel<true>, g3, dim3(VQ_BWD_BLOCK), lds, s, z, codebook, (const long long *)idx,
+                               g_out, g_loss_dev, commitment_cost, dz, nullptr, dw_slabs, K, D, H * W, P, Kc);
+            return dm_launch_status(who);
+        }
+        if (const int rc = vq_reserve_lds(who, (const void *)vq_backward_any_kernel<>, lds, nullptr)) return rc;
+        hipLaunchKernelGGL(vq_backward_any_kernel<>, g3, dim3(VQ_BWD_BLOCK), lds, s, z, codebook, (const long long *)idx, g_out,
                            g_loss_dev, commitment_cost, dz, dw, dw_slabs, K, D, H * W, P, Kc);
         return dm_launch_status(who);
     }
 #define DM_VQ_BWD(DD)                                                                                          \
+    if (stats) {                                                                                               \
+        if (const int rc = vq_reserve_lds(who, (const void *)(vq_backward_kernel<DD, true>), lds, nullptr)) return rc; \
+        hipLaunchKernelGGL((vq_backward_kernel<DD, true>), g3, dim3(VQ_BWD_BLOCK), lds, s, z, codebook,        \
+                           (const long long *)idx, g_out, g_loss_dev, commitment_cost, dz, nullptr, dw_slabs, K, H * W, P, Kc); \
+        break;                                                                                                 \
+    }                                                                                                          \
     if (const int rc = vq_reserve_lds(who, (const void *)vq_backward_kernel<DD>, lds, nullptr)) return rc;     \
     hipLaunchKernelGGL(vq_backward_kernel<DD>, g3, dim3(VQ_BWD_BLOCK), lds, s, z, codebook,                    \
                        (const long long *)idx, g_out, g_loss_dev, commitment_cost, dz, dw, dw_slabs, K, H * W, P, Kc)
@@ -2164,4 +2285,24 @@ extern "C" int dm_vq_backward_slabs(const float *z, const float *codebook, const
 {
     return vq_backward_launch("dm_vq_backward_slabs", z, codebook, idx, g_out, g_loss_dev, commitment_cost, dz, nullptr,
                               dw_slabs, B, D, K, H, W, stream);
+}
+
+extern "C" int dm_vq_backward_stats(const float *z, const float *codebook, const int64_t *idx,
+                                    const float *g_out, const float *g_loss_dev, float commitment_cost,
+                                    float *dz, float *stat_slabs, int B, int D, int K, int H, int W, void *stream)
+{
+    DM_REQUIRE(B > 0 && D > 0 && K > 0 && H > 0 && W > 0, "dm_vq_backward_stats: bad shape (%d, %d, %d, %d, %d)", B, D, K, H, W);
+    return vq_backward_launch("dm_vq_backward_stats", z, codebook, idx, g_out, g_loss_dev, commitment_cost, dz, nullptr,
+                              stat_slabs, B, D, K, H, W, stream, true);
+}
+
+extern "C" int dm_vq_ema_apply(const float *stats, float *cluster_size, float *ema_w, float *codebook, int K, int D,
+                               double decay, double epsilon, void *stream)
+{
+    DM_REQUIRE(stats && cluster_size && ema_w && codebook, "dm_vq_ema_apply: NULL pointer");
+    DM_REQUIRE(K > 0 && D > 0, "dm_vq_ema_apply: bad shape (%d, %d)", K, D);
+    DM_REQUIRE(decay >= 0.0 && decay < 1.0 && epsilon >= 0.0, "dm_vq_ema_apply: decay in [0, 1), epsilon >= 0");
+    hipLaunchKernelGGL(vq_ema_apply_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, stats, cluster_size, ema_w, codebook,
+                       K, D, decay, epsilon);
+    return dm_launch_status("dm_vq_ema_apply");
 }

@@ -143,16 +143,21 @@ def gather_rank_values(value, device=None, group=None):
 
 
 class FlatParams:
-    """All trainable tensors of a module as views of ONE flat buffer, gradients as views of a second one."""
+    """All trainable tensors of a module as views of ONE flat buffer, gradients as views of a second one.
+    tail: that many extra elements behind the gradients in the same allocation (`bucket` = gradients + tail, `tail` the
+    view) for per-step values that travel in the step's one all-reduce but are no gradients: plain sums over the ranks that
+    neither the gradient weight nor the optimizer touches (the EMA codebook statistics).  0: bucket is grad."""
 
-    def __init__(self, params):
+    def __init__(self, params, tail=0):
         self.params = [p for p in params if p.requires_grad]
         if not self.params:
             raise ValueError("no trainable parameters")
         dev, dt = self.params[0].device, self.params[0].dtype
         n = sum(p.numel() for p in self.params)
         self.flat = torch.empty(n, device=dev, dtype=dt)
-        self.grad = torch.zeros(n, device=dev, dtype=dt)
+        self.bucket = torch.zeros(n + int(tail), device=dev, dtype=dt)
+        self.grad = self.bucket[:n] if tail else self.bucket
+        self.tail = self.bucket[n:] if tail else None
         self._gview = {}
         off = 0
         for p in self.params:

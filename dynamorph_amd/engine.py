@@ -510,8 +510,9 @@ def _vq_state(codebook, shape, slabs, ws, commitment_cost):
     return SimpleNamespace(slabs=slabs, ws=ws, K=codebook.shape[0], D=D, positions=B * H * W, cc=commitment_cost)
 
 
-def vq_forward(codebook, z, commitment_cost, want_out=True, defer_scalars=False, want_scalars=True):
-    """defer_scalars (training pass): no scalar launches here; the third return value is the state
+def vq_forward(codebook, z, commitment_cost, want_out=True, defer_scalars=False, want_scalars=True, ema=False):
+    """ema: the scalar launch reports the loss of the EMA codebook mode, cc * mse (the quantisation itself is the same).
+    defer_scalars (training pass): no scalar launches here; the third return value is the state
     ops.vq_loss_finalize needs to produce them together with the reconstruction loss at the end of the step.
     want_scalars=False (inference latents, patch_VAE.py:445-452 discards loss and perplexity): no counter reduction and no
     scalar launch at all; the third return value is None."""
@@ -523,7 +524,7 @@ def vq_forward(codebook, z, commitment_cost, want_out=True, defer_scalars=False,
         idx, out, slabs, ws = ops.vq_forward(z, _w(codebook), want_out=want_out, want_hist=False)
         return out, idx, _vq_state(codebook, z.shape, slabs, ws, commitment_cost)
     idx, out, slabs, hist = ops.vq_forward(z, _w(codebook), want_out=want_out)
-    scalars = ops.vq_finalize(slabs, hist, B * H * W, D, commitment_cost)     # (loss, perplexity, mse)
+    scalars = ops.vq_finalize(slabs, hist, B * H * W, D, commitment_cost, ema=ema)     # (loss, perplexity, mse)
     return out, idx, scalars
 
 

@@ -196,20 +196,29 @@ def vq_forward_repeat(z, codebook, repeats, variant=L.DM_VQ_AUTO, bufs=None, wan
 
 
 @_op
-def vq_finalize(slabs, hist, positions, D, commitment_cost):
+def vq_finalize(slabs, hist, positions, D, commitment_cost, ema=False):
+    """(loss, perplexity, mse); ema: the loss of the EMA codebook mode, cc * mse (dm_vq_finalize_ema)."""
     lib = L.load()
     scalars = _new((3,), slabs)
-    L.check(lib.dm_vq_finalize(_ptr(slabs, torch.float64), slabs.numel(), _ptr(hist, torch.int32), hist.numel(),
-                               positions, D, commitment_cost, _ptr(scalars), _stream()), "dm_vq_finalize")
+    fn, who = (lib.dm_vq_finalize_ema, "dm_vq_finalize_ema") if ema else (lib.dm_vq_finalize, "dm_vq_finalize")
+    L.check(fn(_ptr(slabs, torch.float64), slabs.numel(), _ptr(hist, torch.int32), hist.numel(),
+               positions, D, commitment_cost, _ptr(scalars), _stream()), who)
     return scalars
 
 
 @_op
-def vq_loss_finalize(sse_slabs, ws, K, D, positions, commitment_cost, loss_slabs, count, weight_recon, weight_commitment):
+def vq_loss_finalize(sse_slabs, ws, K, D, positions, commitment_cost, loss_slabs, count, weight_recon, weight_commitment,
+                     ema=False):
     """(recon, commitment, total, perplexity) in one launch: vq_finalize + loss_finalize on the counter replicas that
-    vq_forward(..., want_hist=False) left in its workspace `ws`."""
+    vq_forward(..., want_hist=False) left in its workspace `ws`.  ema: commitment = cc * mse (dm_vq_loss_finalize_ema)."""
     lib = L.load()
     out = _new((4,), sse_slabs)
+    if ema:
+        L.check(lib.dm_vq_loss_finalize_ema(_ptr(sse_slabs, torch.float64), sse_slabs.numel(), _ptr(ws), K, D, positions,
+                                            commitment_cost, _ptr(loss_slabs, torch.float64), loss_slabs.numel(), count,
+                                            weight_recon, weight_commitment, None, 0, 0.0, _ptr(out), _stream()),
+                "dm_vq_loss_finalize_ema")
+        return out
     L.check(lib.dm_vq_loss_finalize(_ptr(sse_slabs, torch.float64), sse_slabs.numel(), _ptr(ws), K, D, positions,
                                     commitment_cost, _ptr(loss_slabs, torch.float64), loss_slabs.numel(), count,
                                     weight_recon, weight_commitment, _ptr(out), _stream()), "dm_vq_loss_finalize")
@@ -218,15 +227,16 @@ def vq_loss_finalize(sse_slabs, ws, K, D, positions, commitment_cost, loss_slabs
 
 @_op
 def vq_loss_finalize_tm(sse_slabs, ws, K, D, positions, commitment_cost, loss_slabs, count, weight_recon, weight_commitment,
-                        tm_slabs, weight_matching):
+                        tm_slabs, weight_matching, ema=False):
     """vq_loss_finalize with the pairwise term: (recon, commitment, total + weight_matching * tm, perplexity, tm) in one
     launch from the partial losses time_matching_forward(..., want_slabs=True) left."""
     lib = L.load()
     out = _new((5,), sse_slabs)
-    L.check(lib.dm_vq_loss_finalize_tm(_ptr(sse_slabs, torch.float64), sse_slabs.numel(), _ptr(ws), K, D, positions,
-                                       commitment_cost, _ptr(loss_slabs, torch.float64), loss_slabs.numel(), count,
-                                       weight_recon, weight_commitment, _ptr(tm_slabs, torch.float64), tm_slabs.shape[0],
-                                       weight_matching, _ptr(out), _stream()), "dm_vq_loss_finalize_tm")
+    fn = lib.dm_vq_loss_finalize_ema if ema else lib.dm_vq_loss_finalize_tm
+    L.check(fn(_ptr(sse_slabs, torch.float64), sse_slabs.numel(), _ptr(ws), K, D, positions,
+               commitment_cost, _ptr(loss_slabs, torch.float64), loss_slabs.numel(), count,
+               weight_recon, weight_commitment, _ptr(tm_slabs, torch.float64), tm_slabs.shape[0],
+               weight_matching, _ptr(out), _stream()), "dm_vq_loss_finalize_ema" if ema else "dm_vq_loss_finalize_tm")
     return out
 
 
@@ -272,6 +282,36 @@ def vq_backward_slabs(z, codebook, idx, g_out, g_loss, commitment_cost, want_dz=
                                      commitment_cost, _ptr(dz), _ptr(slabs), B, D, K, H, W, _stream()),
             "dm_vq_backward_slabs")
     return dz, slabs
+
+
+@_op
+def vq_backward_stats(z, codebook, idx, g_out, g_loss, commitment_cost, want_dz=True):
+    """The quantiser's backward in the EMA codebook mode (include/dynamorph_hip.h, dm_vq_backward_stats): dz as
+    vq_backward_slabs writes it, and per-workgroup slabs (nslabs, K * (D + 1)) of the update's statistics -- K * D sums of the
+    assigned z, then K counts as floats -- for reduce_slabs / reduce_slabs_multi.  The order of the additions is fixed on
+    every route.  want_dz=False (and g_out, g_loss None): the statistics alone."""
+    lib = L.load()
+    B, D, H, W = z.shape
+    K = codebook.shape[0]
+    if tuple(idx.shape) != (B, H, W) or tuple(codebook.shape) != (K, D):
+        raise ValueError("dm_vq_backward_stats: z (B, D, H, W), idx (B, H, W), codebook (K, D)")
+    dz = torch.empty_like(z) if want_dz else None
+    slabs = _new((lib.dm_vq_backward_num_slabs(B * H * W, K, D), K * (D + 1)), z)
+    L.check(lib.dm_vq_backward_stats(_ptr(z), _ptr(codebook), _ptr(idx, torch.int64), _ptr(g_out), _ptr(g_loss),
+                                     commitment_cost, _ptr(dz), _ptr(slabs), B, D, K, H, W, _stream()),
+            "dm_vq_backward_stats")
+    return dz, slabs
+
+
+@_op
+def vq_ema_apply(stats, cluster_size, ema_w, codebook, decay, epsilon):
+    """The EMA codebook update in place, one launch (dm_vq_ema_apply): stats = (K * (D + 1),) sums then counts."""
+    lib = L.load()
+    K, D = codebook.shape
+    if stats.numel() != K * (D + 1) or cluster_size.numel() != K or tuple(ema_w.shape) != (K, D):
+        raise ValueError("dm_vq_ema_apply: stats (K * (D + 1),), cluster_size (K,), ema_w and codebook (K, D)")
+    L.check(lib.dm_vq_ema_apply(_ptr(stats), _ptr(cluster_size), _ptr(ema_w), _ptr(codebook), K, D, float(decay),
+                                float(epsilon), _stream()), "dm_vq_ema_apply")
 
 
 # ---------------------------------------------------------------------- convolutions
@@ -920,8 +960,9 @@ def recon_loss_per_sample(dec, x, mask, channel_var):
 
 
 @_op
-def vq_patch_scalars(z, idx, codebook, commitment_cost, want_counts=False):
-    """Per patch (loss, perplexity, mse) as a (B, 3) tensor, and the (B, K) int32 code histogram on request (else None)."""
+def vq_patch_scalars(z, idx, codebook, commitment_cost, want_counts=False, ema=False):
+    """Per patch (loss, perplexity, mse) as a (B, 3) tensor, and the (B, K) int32 code histogram on request (else None).
+    ema: the loss of the EMA codebook mode, cc * mse (dm_vq_patch_scalars_ema)."""
     lib = L.load()
     B, D, H, W = z.shape
     K = codebook.shape[0]
@@ -929,8 +970,9 @@ def vq_patch_scalars(z, idx, codebook, commitment_cost, want_counts=False):
         raise ValueError("dm_vq_patch_scalars: z (B, D, H, W), idx (B, H, W), codebook (K, D)")
     scalars = _new((B, 3), z)
     counts = _new((B, K), z, torch.int32) if want_counts else None
-    L.check(lib.dm_vq_patch_scalars(_ptr(z), _ptr(idx, torch.int64), _ptr(codebook), commitment_cost, _ptr(scalars),
-                                    _ptr(counts, torch.int32), B, D, K, H, W, _stream()), "dm_vq_patch_scalars")
+    fn = lib.dm_vq_patch_scalars_ema if ema else lib.dm_vq_patch_scalars
+    L.check(fn(_ptr(z), _ptr(idx, torch.int64), _ptr(codebook), commitment_cost, _ptr(scalars),
+               _ptr(counts, torch.int32), B, D, K, H, W, _stream()), "dm_vq_patch_scalars_ema" if ema else "dm_vq_patch_scalars")
     return scalars, counts
 
 

@@ -207,7 +207,8 @@ def score_patches(model, patches, masks=None, device="cuda:0", batch_size=1024, 
         n = x.shape[0]
         z_b, join = encode(x)
         z_a, idx, _ = E.vq_forward(codebook, z_b, cc, want_scalars=False)
-        vqs, counts = ops.vq_patch_scalars(z_b, idx, codebook.detach(), cc, want_counts=return_code_counts)
+        # (a model in the EMA codebook mode reports that mode's commitment, cc * mse, and the total built on it)
+        vqs, counts = ops.vq_patch_scalars(z_b, idx, codebook.detach(), cc, want_counts=return_code_counts, ema=model.vq.ema)
         if z32:
             defer = []
             r, _ = E.residual_forward(dec[0]._handles(), z_a, True, defer)

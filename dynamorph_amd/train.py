@@ -72,8 +72,15 @@ class FusedTrainer:
         params = [p for p in model.parameters() if p.requires_grad]
         if params[0].device.type != "cuda":
             raise RuntimeError("FusedTrainer: move the model to the GPU first (no CPU fallback)")
-        self.fp = D.FlatParams(params)
+        # EMA codebook mode (read from the model): the codebook is frozen -- no Adam parameter, no slot in the
+        # flat buffers -- and the quantiser's backward leaves the update's statistics, K * D sums and K counts, in a tail of
+        # the gradient bucket: they ride the step's one all-reduce as plain sums (neither grad_weight nor Adam's 1 / world
+        # touches them) and the update is one launch next to Adam.  fp32 counts: exact up to 2^24 positions per code and step.
+        self._ema = bool(model.vq.ema)
+        K, Dm = model.vq.w.weight.shape
+        self.fp = D.FlatParams(params, tail=K * (Dm + 1) if self._ema else 0)
         self.params, self.flat, self.grad = self.fp.params, self.fp.flat, self.fp.grad
+        self._bucket, self._ema_stats = self.fp.bucket, self.fp.tail
         dev, n = self.flat.device, self.flat.numel()
         self.m = torch.zeros(n, device=dev)
         self.v = torch.zeros(n, device=dev)
@@ -98,7 +105,8 @@ class FusedTrainer:
         self._graphs = {}            # input shapes -> {inputs: static (x, mask, tm); train / eval: (_Segments, static output)}
         self._static_x = None        # input tensor of the program replayed last
         self._labels = None          # the extra losses' labels of the step being taken
-        D.broadcast_(self.flat, list(model.buffers()), group=self.group)    # same replica everywhere
+        # same replica everywhere (the frozen codebook of the EMA mode is in neither the flat buffer nor the buffers)
+        D.broadcast_(self.flat, list(model.buffers()) + ([model.vq.w.weight.data] if self._ema else []), group=self.group)
 
     # ------------------------------------------------------------------------------------------
     def G(self, p):
@@ -161,9 +169,18 @@ class FusedTrainer:
         g_zq = E.decoder_backward(st.L, st.cx, self.w_recon, None, self.G, pending=st.pending)
         # codebook gradient as slabs, added in the encoder's single slab reduction: nothing to zero, no global atomics
         # (K <= 64: an ordered one-hot product on the matrix cores, bit-reproducible; larger K: LDS adds in arrival order)
-        dz, cb_slabs = ops.vq_backward_slabs(st.z, st.cb.detach(), st.idx, g_zq, self.w_commit, st.cc)
-        st.pending.insert(0, (cb_slabs, self.G(st.cb)))
+        dz, cb_seg = self._vq_backward(st, g_zq)
+        st.pending.insert(0, cb_seg)
         return dz
+
+    def _vq_backward(self, st, g):
+        """The quantiser's backward: (dz, the (slabs, destination) pair for the step's one slab reduction) -- the codebook
+        gradient, or in the EMA mode the update's statistics (dm_vq_backward_stats: the same dz, another slab payload)."""
+        if self._ema:
+            dz, slabs = ops.vq_backward_stats(st.z, st.cb.detach(), st.idx, g, self.w_commit, st.cc)
+            return dz, (slabs, self._ema_stats)
+        dz, slabs = ops.vq_backward_slabs(st.z, st.cb.detach(), st.idx, g, self.w_commit, st.cc)
+        return dz, (slabs, self.G(st.cb))
 
     def _backward_from_latent(self, st, g):
         """From the gradient at the latent: the rest of the backward (VQ_VAE_z32: the quantiser's straight-through backward,
@@ -173,8 +190,8 @@ class FusedTrainer:
             E.encoder_backward(st.L, st.ecx, g, self.G, zero_fed_biases=False, pending_extra=st.pending)
             return
         enc = self.model.enc
-        dz, cb_slabs = ops.vq_backward_slabs(st.z, st.cb.detach(), st.idx, g, self.w_commit, st.cc)
-        st.pending.append((cb_slabs, self.G(st.cb)))
+        dz, cb_seg = self._vq_backward(st, g)
+        st.pending.append(cb_seg)
         g_h, stats = E.residual_backward(st.er, st.esaved, dz, self.G, st.scx.a2, pending=st.pending, zero_fed_biases=False)
         E.z32_stem_backward(enc[0], enc[1], enc[3], enc[4], st.scx, g_h, self.G, stats=stats, pending=st.pending,
                             zero_fed_biases=False)
@@ -191,8 +208,9 @@ class FusedTrainer:
             _with_global sums over the ranks."""
         m = self.model
         fin = (st.vqs.slabs, st.vqs.ws, st.vqs.K, st.vqs.D, st.vqs.positions, st.vqs.cc, st.cx.loss_slabs, st.n) + st.w
+        ema = {"ema": True} if self._ema else {}          # (the EMA mode's commitment, cc * mse, from the same launch)
         if tm is None:
-            return ops.vq_loss_finalize(*fin), g, None
+            return ops.vq_loss_finalize(*fin, **ema), g, None
         B, n = st.lat.shape
         wm, args = float(m.weight_matching), _tm_args(m, self._z32)
         tm = tm.to(torch.float32).contiguous()
@@ -203,16 +221,16 @@ class FusedTrainer:
                 # the bucket is multiplied by grad_weight = B * world / Bg before the exchange and by 1 / world in Adam's
                 # load: the rows' gradient carries world / grad_weight (self._tm_gscale), so what arrives is the global term's
                 g = ops.time_matching_backward_rows(zg, S, self._tm_gscale, wm, add=g).reshape(g.shape)
-            return ops.vq_loss_finalize(*fin), g, part
+            return ops.vq_loss_finalize(*fin, **ema), g, part
         if ops.time_matching_supported(B, n):
             tm_slabs, S = ops.time_matching_forward(st.lat, tm, *args, want_slabs=True)
             if g is not None:
                 g = ops.time_matching_backward(st.lat, S, None, wm, add=g).reshape(g.shape)
-            return ops.vq_loss_finalize_tm(*fin, tm_slabs, wm), g, None
+            return ops.vq_loss_finalize_tm(*fin, tm_slabs, wm, **ema), g, None
         tml, g_sim = self._time_matching(ops.pair_msd(st.lat), tm, args[0] == 1)
         if g is not None:
             g = g + ops.pair_msd_backward(st.lat, (g_sim * wm).contiguous()).reshape(g.shape)
-        return _with_matching(ops.vq_loss_finalize(*fin), tml, wm), g, None
+        return _with_matching(ops.vq_loss_finalize(*fin, **ema), tml, wm), g, None
 
     def _time_matching(self, sim, tm, z16_form=None):
         """(loss, d loss / d sim) of the pairwise term on the (B, B) matrix of mean-squared latent distances:
@@ -345,14 +363,16 @@ class FusedTrainer:
         if self.world == 1:
             return
         if weight != 1.0:
-            self.grad.mul_(float(weight))
-        torch.distributed.all_reduce(self.grad, op=torch.distributed.ReduceOp.SUM, group=self.group)
+            self.grad.mul_(float(weight))                 # (the gradients only: the EMA statistics behind them are plain sums)
+        torch.distributed.all_reduce(self._bucket, op=torch.distributed.ReduceOp.SUM, group=self.group)
 
     def _adam(self):
         a, b = self._step_slot, 1 - self._step_slot
         ops.adam_counted(self.flat, self.grad, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps,
                          self.step_dev[a:a + 1], self.step_dev[b:b + 1], grad_scale=1.0 / self.world)
         self._step_slot = b
+        if self._ema:            # the codebook's own update, from the global batch's statistics (after the exchange)
+            self.model.vq.ema_apply(self._ema_stats)
 
     # ------------------------------------------------------------------------------------------ public steps
     def _fwd_bwd(self, x, mask, tm, grad_weight=1.0, labels=None, replay=True):
@@ -398,7 +418,7 @@ class FusedTrainer:
                 self._bn_without_data(sample_shape, global_rows, training=True)
             elif self.global_tm and global_rows is not None:
                 self._join_without_data(global_rows)
-            self.grad.zero_()
+            self._bucket.zero_()         # (with the EMA mode's statistics: this rank adds nothing and still applies the update)
             self._allreduce()
             self._adam()
 
@@ -614,6 +634,10 @@ class GraphedTrainer:
     small batches and busy hosts.  Single process (no gradient exchange)."""
 
     def __init__(self, model, lr=1e-3, betas=(.9, .999), eps=1e-8):
+        if _ema_mode(model):
+            raise ValueError("GraphedTrainer: the EMA codebook update is not built into the captured autograd step (its "
+                             "in-place update of the frozen codebook sits between forward and backward); train an EMA model "
+                             "with FusedTrainer (fused=True) or the eager autograd route (fused=False)")
         params = [p for p in model.parameters() if p.requires_grad]
         if not params or params[0].device.type != "cuda":
             raise RuntimeError("GraphedTrainer: move the model to the GPU first (no CPU fallback)")
@@ -785,11 +809,23 @@ class _EpochLosses:
         return {k: v / max(tot[-1], 1.0) for k, v in zip(keys, tot[:-1])}
 
 
+def _ema_mode(model):
+    """The model's quantiser learns its codebook by the EMA update (VectorQuantizer(ema_decay=...))."""
+    return bool(getattr(getattr(model, "vq", None), "ema", False))
+
+
 def _make_optimizer(model, lr, fused, global_time_matching=False, sync_batchnorm=False):
     from .vq_vae import VQ_VAE
     from .vq_vae import VQ_VAE_z32
     # (a model with caller-supplied extra losses, vae.py:463-469, runs arbitrary torch code per step: the autograd path)
     fusable = isinstance(model, (VQ_VAE, VQ_VAE_z32)) and getattr(model, "extra_loss", None) is None
+    if _ema_mode(model) and fused == "graph":
+        raise ValueError("fused='graph' (GraphedTrainer) does not take a model with the EMA codebook update; use fused=True "
+                         "(FusedTrainer) or, in one process, fused=False")
+    if _ema_mode(model) and D.world_size() > 1 and not (fused and fusable):
+        raise ValueError("the EMA codebook update with more than one rank needs the fused step (FusedTrainer: fused=True and a "
+                         "VQ_VAE / VQ_VAE_z16 / VQ_VAE_z32 without extra_loss): the autograd route forms the update's "
+                         "statistics on each rank's shard only")
     if global_time_matching and not (fused and fused != "graph" and fusable):
         raise ValueError("global_time_matching=True needs the fused step (FusedTrainer: fused=True and a VQ_VAE / VQ_VAE_z16 / "
                          "VQ_VAE_z32 without extra_loss); the autograd route forms the time-matching term on each rank's "

@@ -89,9 +89,11 @@ class _ResidualFn(torch.autograd.Function):
 
 class _VQFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, z, codebook, commitment_cost):
-        out, idx, scalars = E.vq_forward(codebook, z, commitment_cost)
-        ctx.save_for_backward(z, codebook, idx)
+    def forward(ctx, z, codebook, commitment_cost, ema=False):
+        """ema (the EMA codebook mode): loss = cc * mse; the codebook is frozen and updated in place right after this
+        forward (VectorQuantizer._quantize), so the backward keeps its own copy of the K x D values it quantised with."""
+        out, idx, scalars = E.vq_forward(codebook, z, commitment_cost, ema=ema)
+        ctx.save_for_backward(z, codebook.detach().clone() if ema else codebook, idx)
         ctx.cc = commitment_cost
         ctx.mark_non_differentiable(idx)
         ctx.set_materialize_grads(False)
@@ -106,7 +108,7 @@ class _VQFn(torch.autograd.Function):
             g_loss = torch.zeros(1, device=z.device)
         dz, dw = ops.vq_backward(z, codebook.detach(), idx, g_out, g_loss.reshape(1).contiguous(), ctx.cc,
                                  want_dz=ctx.needs_input_grad[0])
-        return dz, (dw if ctx.needs_input_grad[1] else None), None
+        return dz, (dw if ctx.needs_input_grad[1] else None), None, None
 
 
 def _recon_input_grad(cx, channel_var, gscale):
@@ -212,20 +214,79 @@ def time_matching_loss(latents, time_matching_mat, z16_form, w_a=0.0, w_t=0.0, w
 
 
 class VectorQuantizer(nn.Module):
-    """Vector quantizer of "Neural Discrete Representation Learning" (reference vq_vae.py:25-116)."""
+    """Vector quantizer of "Neural Discrete Representation Learning" (reference vq_vae.py:25-116).
 
-    def __init__(self, embedding_dim=128, num_embeddings=128, commitment_cost=0.25, device='cuda:0'):
+    ema_decay (None: the reference's module, the codebook trained by the gradient of q_latent_loss): a decay in [0, 1) turns
+    on the paper's exponential-moving-average codebook update (appendix A.1).  The codebook `w.weight` is then
+    a frozen parameter under its old name, the buffers `ema_cluster_size` N (K) and `ema_w` m (K, D) start at N = 1, m = e,
+    the loss is commitment_cost * mse(q.detach(), z), and in train() mode every forward with gradients enabled ends with
+        n[k] = #{p: idx[p] = k};  s[k] = sum of the z assigned to k
+        N <- g N + (1 - g) n;  m <- g m + (1 - g) s;  e[k] <- m[k] / ((N[k] + eps) / (sum N + K eps) * sum N)
+    in place under no_grad.  Nothing is updated in eval() mode, under torch.no_grad() or by encode_inputs / decode_inputs.  The counts travel as
+    fp32: exact up to 2^24 positions per code and step."""
+
+    def __init__(self, embedding_dim=128, num_embeddings=128, commitment_cost=0.25, device='cuda:0',
+                 ema_decay=None, ema_epsilon=1e-5):
         super(VectorQuantizer, self).__init__()
         self.embedding_dim = embedding_dim
         self.num_embeddings = num_embeddings
         self.commitment_cost = commitment_cost
         self.device = device
         self.w = nn.Embedding(num_embeddings, embedding_dim)
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"VectorQuantizer: ema_decay must be None or in [0, 1), got {ema_decay}")
+        if float(ema_epsilon) < 0.0:
+            raise ValueError(f"VectorQuantizer: ema_epsilon must be >= 0, got {ema_epsilon}")
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_epsilon = float(ema_epsilon)
+        if self.ema:
+            self.w.weight.requires_grad_(False)
+            self.register_buffer("ema_cluster_size", torch.ones(num_embeddings))
+            self.register_buffer("ema_w", self.w.weight.detach().clone())
+
+    @property
+    def ema(self):
+        return getattr(self, "ema_decay", None) is not None      # (a module pickled before the mode existed has no attribute)
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        """A checkpoint without the two EMA buffers (the reference's format, or a gradient-trained model of this package)
+        loads into an EMA module: the buffers take the initial state of the loaded codebook, N = 1 and m = e."""
+        if self.ema:
+            w = state_dict.get(prefix + "w.weight")
+            if w is not None and tuple(w.shape) == tuple(self.w.weight.shape):
+                if prefix + "ema_cluster_size" not in state_dict and prefix + "ema_w" not in state_dict:
+                    state_dict[prefix + "ema_cluster_size"] = torch.ones_like(self.ema_cluster_size)
+                    state_dict[prefix + "ema_w"] = w.detach().clone()
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+
+    def ema_statistics(self, z, idx):
+        """(K * (D + 1),) device tensor: the K * D sums of the z assigned to each code, then the K counts (as floats), of
+        this batch -- the new backward kernel without its dz, its slabs reduced in slab order."""
+        _, slabs = ops.vq_backward_stats(z, self.w.weight.detach(), idx, None, None, float(self.commitment_cost), want_dz=False)
+        return ops.reduce_slabs(slabs, torch.empty(slabs.shape[1], device=z.device))
+
+    def ema_apply(self, stats):
+        """The update from a batch's (global) statistics, in place, one launch."""
+        ops.vq_ema_apply(stats, self.ema_cluster_size, self.ema_w, self.w.weight.data, self.ema_decay, self.ema_epsilon)
+
+    def _quantize(self, z, commitment_cost=None):
+        """(output_quantized, loss, perplexity, idx) of a prepared z.  In the EMA mode a training forward -- train() mode
+        with gradients enabled; the validation pass of the training loop runs under no_grad -- ends with the update."""
+        cc = float(self.commitment_cost if commitment_cost is None else commitment_cost)
+        out, loss, perplexity, idx = _VQFn.apply(z, self.w.weight, cc, self.ema)
+        if self.ema and self.training and torch.is_grad_enabled():
+            if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+                raise ValueError("VectorQuantizer: the EMA codebook update on the autograd route forms its statistics from "
+                                 "this process's batch only; with more than one rank train with FusedTrainer (fused=True), "
+                                 "whose statistics ride the step's all-reduce")
+            with torch.no_grad():
+                self.ema_apply(self.ema_statistics(z.detach(), idx))
+        return out, loss, perplexity, idx
 
     def forward(self, inputs):
         """inputs (B, D, H, W) -> (output_quantized, loss, perplexity)   [vq_vae.py:52-84]"""
         _require_gpu(inputs, "VectorQuantizer.forward")
-        out, loss, perplexity, _ = _VQFn.apply(_prep(inputs), self.w.weight, float(self.commitment_cost))
+        out, loss, perplexity, _ = self._quantize(_prep(inputs))
         assert out.shape == inputs.shape
         return out, loss, perplexity
 
@@ -337,6 +398,8 @@ class VQ_VAE(nn.Module):
                  w_t=0.1,
                  w_n=-0.5,
                  margin=0.5,
+                 ema_decay=None,
+                 ema_epsilon=1e-5,
                  **kwargs):
         # callers pass gpu=True (pipeline/patch_VAE.py:431) or alpha/gpu (plot_scripts/recon_loss.py:18);
         # the reference forwards them to nn.Module.__init__ and crashes on current torch -- swallow them.
@@ -371,7 +434,8 @@ class VQ_VAE(nn.Module):
             _Conv2d(nh, nh, 3, padding=1),
             _BatchNorm2d(nh),
             ResidualBlock(nh, num_residual_hiddens, num_residual_layers))
-        self.vq = VectorQuantizer(nh, num_embeddings, commitment_cost=commitment_cost, device=device)
+        self.vq = VectorQuantizer(nh, num_embeddings, commitment_cost=commitment_cost, device=device,
+                                  ema_decay=ema_decay, ema_epsilon=ema_epsilon)
         self.dec = _HipDecoder(
             _ConvTranspose2d(nh, nh // 2, 4, stride=2, padding=1),
             _ReLU(),
@@ -392,7 +456,10 @@ class VQ_VAE(nn.Module):
         x = _prep(inputs)
         layers = E.Layers(self)
         z_before = _EncoderFn.apply(x, layers, self.enc.per_sample_stats, *layers.encoder_params())
-        z_after, c_loss, perplexity, _ = _VQFn.apply(z_before, self.vq.w.weight, float(self.commitment_cost))
+        if self.vq.ema:        # (the update follows in train() mode)
+            z_after, c_loss, perplexity, _ = self.vq._quantize(z_before, self.commitment_cost)
+        else:
+            z_after, c_loss, perplexity, _ = _VQFn.apply(z_before, self.vq.w.weight, float(self.commitment_cost))
         mask = _prep(batch_mask) if batch_mask is not None else None
         decoded, recon_loss = _DecoderFn.apply(z_after, x, mask, layers, *layers.decoder_params())
         total_loss = self.weight_recon * recon_loss + self.weight_commitment * c_loss
@@ -500,7 +567,7 @@ class VQ_VAE_z32(nn.Module):
 
     def __init__(self, num_inputs=2, num_hiddens=16, num_residual_hiddens=32, num_residual_layers=2, num_embeddings=64,
                  commitment_cost=0.25, channel_var=np.ones(2), weight_matching=0.005, w_a=1.1, w_t=0.1, w_n=-0.5,
-                 margin=0.5, extra_loss=None, device="cuda:0", **kwargs):
+                 margin=0.5, extra_loss=None, device="cuda:0", ema_decay=None, ema_epsilon=1e-5, **kwargs):
         kwargs.pop("gpu", None)
         alpha = kwargs.pop("alpha", None)
         super(VQ_VAE_z32, self).__init__(**kwargs)
@@ -530,7 +597,8 @@ class VQ_VAE_z32(nn.Module):
             _Conv2d(nh // 2, nh, 4, stride=2, padding=1),
             _BatchNorm2d(nh),
             ResidualBlock(nh, num_residual_hiddens, num_residual_layers))
-        self.vq = VectorQuantizer(nh, num_embeddings, commitment_cost=commitment_cost, device=device)
+        self.vq = VectorQuantizer(nh, num_embeddings, commitment_cost=commitment_cost, device=device,
+                                  ema_decay=ema_decay, ema_epsilon=ema_epsilon)
         self.dec = _Z32Decoder(
             ResidualBlock(nh, num_residual_hiddens, num_residual_layers),
             _ConvTranspose2d(nh, nh // 2, 4, stride=2, padding=1),

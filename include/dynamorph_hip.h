@@ -193,6 +193,36 @@ int dm_vq_backward_slabs(const float *z, const float *codebook, const int64_t *i
                          const float *g_out, const float *g_loss_dev, float commitment_cost,
                          float *dz, float *dw_slabs, int B, int D, int K, int H, int W, void *stream);
 
+/* ----- EMA codebook update (opt-in; "Neural Discrete Representation Learning", appendix A.1) -----
+ * With decay g and epsilon eps the quantiser holds N (K) and m (K, D) beside the codebook e (K, D); initially N = 1, m = e.
+ * A training step quantises with e as it stands, then
+ *     n[k] = #{p: idx[p] = k},  s[k] = sum_{p: idx[p] = k} z[p]          (over the global batch)
+ *     N <- g N + (1 - g) n;   m <- g m + (1 - g) s;   Nt[k] = (N[k] + eps) / (sum N + K eps) * sum N;   e[k] <- m[k] / Nt[k].
+ * The quantiser's loss in this mode is cc * mse(q.detach(), z): no q_latent_loss, no codebook gradient; dz is unchanged.
+ *
+ * dm_vq_backward_stats: dm_vq_backward_slabs with the statistics as the slab payload.  dz is written by the same
+ * instructions (bit-equal to dm_vq_backward_slabs' for the same inputs); a slab is K * (D + 1) floats -- [K][D] sums s, then
+ * [K] counts n as floats -- and there are dm_vq_backward_num_slabs(P, K, D) of them; dm_reduce_slabs(_multi) over slabs of
+ * K * (D + 1) columns gives the batch's statistics.  The three routes and their conditions are dm_vq_backward_slabs'; on each
+ * the order of the additions is fixed (two launches give equal bits) and the counts are integers (LDS integer adds),
+ * exact in the fp32 result up to 2^24 positions per code.  dz may be NULL (statistics only), g_out may be NULL. */
+int dm_vq_backward_stats(const float *z, const float *codebook, const int64_t *idx,
+                         const float *g_out, const float *g_loss_dev, float commitment_cost,
+                         float *dz, float *stat_slabs, int B, int D, int K, int H, int W, void *stream);
+/* The update itself, ONE launch, in place: stats = [K][D] sums then [K] counts (the reduced slabs above, summed over the
+ * ranks); cluster_size = N, ema_w = m, codebook = e.  Arithmetic in double from the fp32 inputs, every stored value rounded
+ * once.  Any K and D. */
+int dm_vq_ema_apply(const float *stats, float *cluster_size, float *ema_w, float *codebook, int K, int D,
+                    double decay, double epsilon, void *stream);
+/* The scalar launches in this mode: dm_vq_finalize / dm_vq_loss_finalize(_tm) with loss = commitment = cc * mse.
+ * dm_vq_loss_finalize_ema: tm_slabs NULL = no pairwise term (four values), else dm_vq_loss_finalize_tm's five. */
+int dm_vq_finalize_ema(const double *sse_slabs, int nslabs, const int32_t *hist, int K,
+                       int64_t positions, int D, float commitment_cost, float *scalars, void *stream);
+int dm_vq_loss_finalize_ema(const double *sse_slabs, int nslabs, const void *workspace, int K, int D, int64_t positions,
+                            float commitment_cost, const double *loss_slabs, int nloss, int64_t count, float weight_recon,
+                            float weight_commitment, const double *tm_slabs, int ntm, float weight_matching,
+                            float *scalars_out, void *stream);
+
 /* ===== convolutions (nn.Conv2d / nn.ConvTranspose2d, vq_vae.py:276-298) ======= */
 
 /* 4x4, stride 2, padding 1 implicit-GEMM convolution on MFMA f32 16x16x4.
@@ -572,6 +602,9 @@ int dm_recon_loss_per_sample(const float *decoded, const float *x, const float *
  * patch, integer counters in LDS, codebooks beyond 4096 codes walk windows of 4096. */
 int dm_vq_patch_scalars(const float *z, const int64_t *idx, const float *codebook, float commitment_cost,
                         float *scalars, int32_t *counts, int B, int D, int K, int H, int W, void *stream);
+/* ... for a model in the EMA codebook mode: loss = cc*mse. */
+int dm_vq_patch_scalars_ema(const float *z, const int64_t *idx, const float *codebook, float commitment_cost,
+                            float *scalars, int32_t *counts, int B, int D, int K, int H, int W, void *stream);
 
 /* out[B][4 + NIN] = (recon, commitment, total, perplexity, recon per channel) from patch_sums and dm_vq_patch_scalars'
  * scalars: recon = sum_c S[b][c] / chw rounded to float once, recon per channel = S[b][c] / (chw / NIN), total =
