@@ -1,0 +1,603 @@
+// knn.hip -- the exact k-nearest-neighbour graph of the latents (the n_neighbors graph umap.UMAP takes as precomputed_knn;
+// run_dim_reduction.py:143-207 fit_umap builds it inside umap-learn on the CPU).
+//
+// X (M x F fp32, row-major, leading dimension ldx) is the point set, Q (R x F) the queries -- foreign rows, or rows
+// r0 .. r0 + R - 1 of X itself (the pair (i, i) is then excluded by index).  One call handles one panel of R queries:
+//   norms     |x - s|^2 of every row in float64 (the squares of fp32 numbers are exact there), and their maximum.
+//   gram      g = |q - s|^2 + |x - s|^2 - 2 (q - s).(x - s): 128 x 128 tiles on v_mfma_f32_32x32x2_f32, fp32 within a slab of
+//             KN_SLAB features, slabs added in float64 registers, the result rounded to the fp32 panel (R x M).  A FILTER.
+//   select    per panel row: the K = k + slack smallest by radix select on the value's bits (ties: the lowest columns), and
+//             the smallest value left out.
+//   refine    per row: the candidates' distances in the exact form -- differences and squares in fp32, four squares added in
+//             fp32, those sums in float64 in a fixed order, one wave per pair, the root rounded to fp32 once -- sorted by
+//             (distance, column); the first k are written.  The row is CERTIFIED when the k-th distance squared, times
+//             1 + 2^-20, lies below (smallest rejected - A)(1 - rho), A the proven error bound of the filter (DESIGN.md
+//             section 3.5b): then every row left out has a strictly larger fp32 distance.  The other rows go onto a list.
+//   fallback  the listed rows, KN_FB_ROWS at a time: exact-form distances to all M columns, the same select (K = k: ties by
+//             the lowest column, the order of the result) and the same refine without a certificate.  The host does not
+//             know how many rows are listed: the launches are always made and leave at once when the list is shorter (no
+//             read-back, capture-free).
+// No atomics on floating-point data and no dependence on the launch shape in any value: results are a function of the inputs.
+#include "dm_common.h"
+#include <math.h>
+
+namespace {
+
+constexpr int KN_T = 128;               // tile edge of the Gram panel kernel
+constexpr int KN_CH = 16;               // features per LDS stage (8 k-steps of the 32x32x2 instruction)
+constexpr int KN_LW = KN_T + 32;        // LDS row stride: the two lane halves of a read (features k, k + 1) land 32 banks apart
+constexpr int KN_SLAB = 256;            // features accumulated in fp32 before the partial sum is added in float64
+static_assert(KN_SLAB % KN_CH == 0, "a slab is a whole number of LDS stages");
+constexpr int KN_CAND = DM_KNN_MAX_K + DM_KNN_MAX_SLACK;        // 512 candidates at most: the sort's LDS
+constexpr int KN_FB_ROWS = 256;         // rows of the fallback panel
+
+// The 16-byte form of every kernel: rows start on 16 bytes and are a whole number of float4s.
+bool vec4_ok(const float *p, long long ld, int F) { return ld % 4 == 0 && F % 4 == 0 && ((uintptr_t)p & 15) == 0; }
+
+// Four consecutive features f .. f + 3 of a row, f < F, zero past F (V4: F % 4 == 0, nothing lies past it).
+template <bool V4>
+__device__ __forceinline__ f32x4 row_load4(const float *__restrict__ row, int f, int F)
+{
+    if (V4) return *(const f32x4 *)(row + f);
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (f + e < F) v[e] = row[f + e];
+    return v;
+}
+
+__device__ __forceinline__ f32x4 shift_load4(const float *__restrict__ shift, int f, int F)
+{
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    if (shift) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (f + e < F) s[e] = shift[f + e];
+    }
+    return s;
+}
+
+// The same four features without a branch, for loads that must not be waited for where they are issued: addresses past F
+// are clamped into the row and the caller discards those elements.
+template <bool V4>
+__device__ __forceinline__ f32x4 row_load4_clamped(const float *__restrict__ row, int f, int F)
+{
+    if (V4) return *(const f32x4 *)(row + (f < F ? f : F - 4));
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = row[f + e < F ? f + e : F - 1];
+    return v;
+}
+
+// --------------------------------------------------------------------------------------------------------- norms
+// One wave per row: sum_f fl(x_f - s_f)^2, the squares and the sum in float64, lanes added in a butterfly.
+template <bool V4>
+__global__ __launch_bounds__(256) void knn_norms_kernel(const float *__restrict__ X, long long rows, int F, long long ld,
+                                                        const float *__restrict__ shift, double *__restrict__ out)
+{
+    const int lane = threadIdx.x & 63;
+    const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const float *__restrict__ row = X + r * ld;
+    double acc = 0.0;
+    for (int f = 4 * lane; f < F; f += 256) {
+        const f32x4 v = row_load4<V4>(row, f, F) - shift_load4(shift, f, F);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc += (double)v[e] * (double)v[e];
+    }
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if (lane == 0) out[r] = acc;
+}
+
+// The largest of n norms (one workgroup); thread 0 also clears the call's fallback counter.
+__global__ __launch_bounds__(256) void knn_max_kernel(const double *__restrict__ v, long long n, double *__restrict__ out,
+                                                      int *__restrict__ counter)
+{
+    __shared__ double s[256];
+    double m = 0.0;
+    for (long long i = threadIdx.x; i < n; i += 256) m = fmax(m, v[i]);
+    s[threadIdx.x] = m;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) s[threadIdx.x] = fmax(s[threadIdx.x], s[threadIdx.x + o]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { *out = s[0]; *counter = 0; }
+}
+
+// ---------------------------------------------------------------------------------------------------- Gram panel
+// Workgroup id = column tile * row_tiles + row tile: the workgroups resident together share a few column tiles of X, which
+// crosses HBM once per panel, and the panel's queries stay in the caches.  4 waves, wave w owns the 64 x 64 quarter
+// (w >> 1, w & 1) as 2 x 2 accumulators of the 32x32x2 instruction.  A thread stages features 4 (tid >> 6) .. + 3 of rows
+// (tid & 63) and (tid & 63) + 64 of both operands and stores them transposed ([feature][row]: a wave's 64 rows are 64
+// consecutive words of one LDS row).  `shift` is never NULL here (the host passes zeros).  Two stages of loads are in flight during a stage's products: a fetch only loads -- the
+// shift is subtracted when the registers go to LDS, so nothing waits for a load before the products are issued -- and it is
+// unconditional (past the end it repeats the last stage), so the wait in front of the LDS stores counts one fetch as
+// outstanding.  Rows past the matrices repeat the last row: their products are never stored.
+template <bool V4>
+__global__ __launch_bounds__(256) void knn_gram_kernel(const float *__restrict__ Q, int R, long long ldq,
+                                                       const float *__restrict__ X, int M, long long ldx, int F,
+                                                       const float *__restrict__ shift, const double *__restrict__ nq,
+                                                       const double *__restrict__ nx, int self_r0,
+                                                       float *__restrict__ panel, long long ldp, int row_tiles)
+{
+    __shared__ __attribute__((aligned(16))) float lds[2][2][KN_CH * KN_LW];
+    const int I = (int)(blockIdx.x % row_tiles) * KN_T, J = (int)(blockIdx.x / row_tiles) * KN_T;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int wm = w >> 1, wn = w & 1;
+    const int sr = tid & 63, sf = 4 * (tid >> 6);
+
+    const float *qrow[2], *xrow[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const int rq = I + sr + 64 * q, rx = J + sr + 64 * q;
+        qrow[q] = Q + (long long)(rq < R ? rq : R - 1) * ldq;
+        xrow[q] = X + (long long)(rx < M ? rx : M - 1) * ldx;
+    }
+    const int nstages = (F + KN_CH - 1) / KN_CH;
+
+    f32x4 ra[2][2], rb[2][2], rs[2];
+    auto fetch = [&](int stage, int slot) {
+        const int f = (stage < nstages ? stage : nstages - 1) * KN_CH + sf;
+        rs[slot] = row_load4_clamped<V4>(shift, f, F);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            ra[slot][q] = row_load4_clamped<V4>(qrow[q], f, F);
+            rb[slot][q] = row_load4_clamped<V4>(xrow[q], f, F);
+        }
+    };
+    auto stash = [&](int stage, int slot, int buf) {
+        const int f = stage * KN_CH + sf;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const f32x4 va = ra[slot][q] - rs[slot], vb = rb[slot][q] - rs[slot];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {       // features past F: zeros
+                lds[buf][0][(sf + e) * KN_LW + sr + 64 * q] = f + e < F ? va[e] : 0.f;
+                lds[buf][1][(sf + e) * KN_LW + sr + 64 * q] = f + e < F ? vb[e] : 0.f;
+            }
+        }
+    };
+
+    typedef float f32x16 __attribute__((ext_vector_type(16)));
+    f32x16 acc[2][2];
+    double dacc[2][2][16];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            acc[i][j] = (f32x16){};
+#pragma unroll
+            for (int e = 0; e < 16; ++e) dacc[i][j][e] = 0.0;
+        }
+
+    fetch(0, 0);
+    fetch(1, 1);
+    stash(0, 0, 0);
+    __syncthreads();
+    constexpr int STAGES_PER_SLAB = KN_SLAB / KN_CH;
+    for (int st0 = 0; st0 < nstages; st0 += 2) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {           // stage st lives in register slot u and LDS buffer u
+            const int st = st0 + u;
+            if (st >= nstages) break;
+            fetch(st + 2, u);                   // (slot u went to LDS one stage ago)
+            __builtin_amdgcn_sched_barrier(0);  // the loads are issued here, not after the products
+            const float *A = lds[u][0], *B = lds[u][1];
+            const int koff = (lane >> 5) * KN_LW + (lane & 31);
+#pragma unroll
+            for (int kk = 0; kk < KN_CH / 2; ++kk) {
+                const int o = 2 * kk * KN_LW + koff;
+                const float a0 = A[o + wm * 64], a1 = A[o + wm * 64 + 32];
+                const float b0 = B[o + wn * 64], b1 = B[o + wn * 64 + 32];
+                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+            }
+            stash(st + 1, u ^ 1, u ^ 1);        // (unconditional like the fetch: past the end nobody reads it)
+            __syncthreads();
+            if ((st + 1) % STAGES_PER_SLAB == 0 || st + 1 == nstages) {     // slab done: fold it into fp64, feature order
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+#pragma unroll
+                        for (int e = 0; e < 16; ++e) dacc[i][j][e] += (double)acc[i][j][e];
+                        acc[i][j] = (f32x16){};
+                    }
+            }
+        }
+    }
+    // C/D map of the 32x32 instructions: column lane & 31, row (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int col = J + wn * 64 + j * 32 + (lane & 31);
+        if (col >= M) continue;
+        const double ncol = nx[col];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int row = I + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
+                if (row >= R) continue;
+                float g = (float)(nq[row] + ncol - 2.0 * dacc[i][j][e]);
+                if (self_r0 >= 0 && self_r0 + row == col) g = INFINITY;      // the pair (i, i): excluded by index
+                panel[(long long)row * ldp + col] = g;
+            }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ the exact form
+// d^2 of one pair by one wave: lane l takes features 4 l + 256 t .. + 3; differences and squares in fp32, the four squares of
+// a step added in fp32 as (x^2 + y^2) + (z^2 + w^2), the steps in float64 in order, the lanes in a butterfly (every lane gets
+// the sum).  No contraction: the vector and the scalar load forms, and every kernel that calls this, produce the same bits.
+template <bool V4>
+__device__ __forceinline__ double knn_exact_d2(const float *__restrict__ a, const float *__restrict__ b, int F, int lane)
+{
+#pragma clang fp contract(off)
+    double acc = 0.0;
+    for (int f = 4 * lane; f < F; f += 256) {
+        const f32x4 df = row_load4<V4>(a, f, F) - row_load4<V4>(b, f, F);
+        const float x2 = df.x * df.x, y2 = df.y * df.y, z2 = df.z * df.z, w2 = df.w * df.w;
+        acc += (double)((x2 + y2) + (z2 + w2));
+    }
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    return acc;
+}
+
+// The exact-form distance: the float64 sum's root, rounded to fp32 once.  It is the sort key AND the reported number.
+__device__ __forceinline__ float knn_dist_of(double d2) { return (float)sqrt(d2); }
+
+// The rows a workgroup serves: slot s is row s of the panel, or (fallback) entry base + s of the list of uncertified rows.
+struct RowList { const int *rows; const int *count; int base; };
+
+__device__ __forceinline__ int row_of_slot(const RowList &rl, int slot)
+{
+    if (!rl.rows) return slot;
+    return rl.base + slot < *rl.count ? rl.rows[rl.base + slot] : -1;
+}
+
+// Fallback panel: D[slot][j] = exact-form distance of the slot's row to every column j, one wave per pair.
+template <bool V4>
+__global__ __launch_bounds__(256) void knn_exact_panel_kernel(const float *__restrict__ Q, long long ldq,
+                                                              const float *__restrict__ X, int M, long long ldx, int F,
+                                                              int self_r0, float *__restrict__ D, long long ldd, RowList rl)
+{
+    const int slot = blockIdx.y;
+    const int row = row_of_slot(rl, slot);
+    if (row < 0) return;
+    const int lane = threadIdx.x & 63;
+    const float *__restrict__ q = Q + (long long)row * ldq;
+    for (long long j = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); j < M; j += (long long)gridDim.x * 4) {
+        float d = knn_dist_of(knn_exact_d2<V4>(q, X + j * ldx, F, lane));
+        if (self_r0 >= 0 && self_r0 + row == j) d = INFINITY;
+        if (lane == 0) D[(long long)slot * ldd + j] = d;
+    }
+}
+
+// ----------------------------------------------------------------------------------------------------- selection
+// Order-preserving unsigned key of an fp32 value (negative numbers below positive ones, +inf above every finite one).
+typedef unsigned int KnnKey;
+__device__ __forceinline__ KnnKey knn_key(float v)
+{
+    const KnnKey b = __float_as_uint(v);
+    return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+}
+__device__ __forceinline__ float knn_key_value(KnnKey k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
+
+// One workgroup per panel row: the K smallest of its M values by (value, column), K <= M.  Radix select, most significant
+// byte first: a pass counts the byte among the values that share the prefix found so far (integer LDS counters) and fixes
+// the byte in which the K-th smallest lies.  Afterwards T is the K-th smallest key: every value below T is a candidate, and
+// of those equal to T the `need` lowest columns.  cand[slot][0 .. K) (unordered below T), rej[slot] = the smallest value
+// not taken (+inf when none is left).
+__global__ __launch_bounds__(256) void knn_select_kernel(const float *__restrict__ panel, long long ldp, int M, int K,
+                                                         int *__restrict__ cand, int ldc, double *__restrict__ rej, RowList rl)
+{
+    typedef KnnKey U;
+    constexpr int NB = (int)sizeof(U);
+    __shared__ int hist[256];
+    __shared__ int s_digit, s_need, s_ties, s_nlt, s_neq;
+    __shared__ U s_rejmin;
+    const int slot = blockIdx.x, tid = threadIdx.x;
+    if (row_of_slot(rl, slot) < 0) return;
+    const float *__restrict__ row = panel + (long long)slot * ldp;
+    int *__restrict__ out = cand + (long long)slot * ldc;
+
+    // the row in 16-byte steps (rows start on 128 bytes); fn(column, key) for every column below M
+    auto scan = [&](auto fn) {
+        for (int j = 4 * tid; j < M; j += 1024) {
+            if (j + 3 < M) {
+                const f32x4 v = *(const f32x4 *)(row + j);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) fn(j + e, knn_key(v[e]));
+            } else {
+                for (int e = 0; j + e < M; ++e) fn(j + e, knn_key(row[j + e]));
+            }
+        }
+    };
+
+    U prefix = 0;
+    int need = K;                       // the need-th smallest among the values that share the prefix
+    for (int p = NB - 1; p >= 0; --p) {
+        hist[tid] = 0;
+        __syncthreads();
+        const int sh = 8 * p;
+        // a thread adds a run of equal bytes at once: in the first pass nearly every value of a row has the same byte
+        // (sign and exponent), and 256 threads adding ones to one LDS word would take turns
+        int cur = -1, run = 0;
+        scan([&](int, U u) {
+            if (p != NB - 1 && (u >> (sh + 8)) != (prefix >> (sh + 8))) return;
+            const int d = (int)((u >> sh) & 255);
+            if (d == cur) { ++run; return; }
+            if (run) atomicAdd(&hist[cur], run);
+            cur = d;
+            run = 1;
+        });
+        if (run) atomicAdd(&hist[cur], run);
+        __syncthreads();
+        if (tid == 0) {
+            int c = 0, d = 0;
+            for (; d < 255; ++d) {
+                if (c + hist[d] >= need) break;
+                c += hist[d];
+            }
+            s_digit = d;
+            s_need = need - c;
+            s_ties = hist[d];
+        }
+        __syncthreads();
+        prefix |= (U)s_digit << sh;
+        need = s_need;
+    }
+    const int ties = s_ties;            // values equal to T; `need` of them (>= 1) are taken
+    const bool all_ties = ties == need;
+    if (tid == 0) { s_nlt = 0; s_neq = 0; s_rejmin = ~(U)0; }
+    __syncthreads();
+    const int eq0 = K - need;           // the values below T fill cand[0 .. eq0)
+    U mymin = ~(U)0;
+    scan([&](int j, U u) {
+        if (u < prefix) out[atomicAdd(&s_nlt, 1)] = j;
+        else if (u > prefix) mymin = u < mymin ? u : mymin;
+        else if (all_ties) out[eq0 + atomicAdd(&s_neq, 1)] = j;
+    });
+    if (mymin != ~(U)0) atomicMin(&s_rejmin, mymin);
+    if (!all_ties && tid < 64) {        // more ties than places: one wave walks the row in column order
+        int taken = 0;
+        for (int j0 = 0; j0 < M && taken < need; j0 += 64) {
+            const int j = j0 + tid;
+            const bool is = j < M && knn_key(row[j]) == prefix;
+            const unsigned long long b = __ballot(is);
+            const int rank = taken + __popcll(b & ((1ull << tid) - 1ull));
+            if (is && rank < need) out[eq0 + rank] = j;
+            taken += __popcll(b);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const U r = all_ties ? s_rejmin : prefix;
+        rej[slot] = r == ~(U)0 ? (double)INFINITY : (double)knn_key_value(r);
+    }
+}
+
+// ------------------------------------------------------------------------------------------ refine and certificate
+__device__ __forceinline__ bool pair_less(float da, int ia, float db, int ib) { return da < db || (da == db && ia < ib); }
+
+// One workgroup per row: exact-form distances of its K candidates (a wave per pair), bitonic sort by (distance, column) in
+// LDS, the first kk written behind the optional self column.  certify: the row goes onto the list unless
+//     d[kk - 1]^2 (1 + 2^-20) < (rej - cbound (|q|^2 + max |x|^2) - tiny) (1 - 2^-21):
+// the right side is a lower bound of the float64 sum of every row left out, and a sum above d^2 (1 + 2^-20) has a root above
+// d (1 + 2^-22), more than one fp32 step past d: its rounded distance is strictly larger.
+template <bool V4>
+__global__ __launch_bounds__(256) void knn_refine_kernel(const float *__restrict__ Q, long long ldq, const float *__restrict__ X,
+                                                         long long ldx, int F, const int *__restrict__ cand, int ldc, int K,
+                                                         int kk, int include_self, int self_r0, const double *__restrict__ rej,
+                                                         const double *__restrict__ nq, const double *__restrict__ nxmax,
+                                                         double cbound, int certify, int *__restrict__ idx_out,
+                                                         float *__restrict__ dist_out, int *__restrict__ fail_list,
+                                                         int *__restrict__ n_fail, RowList rl)
+{
+    __shared__ float s_d[KN_CAND];
+    __shared__ int s_i[KN_CAND];
+    const int slot = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int row = row_of_slot(rl, slot);
+    if (row < 0) return;
+    int P = 2;
+    while (P < K) P <<= 1;
+    const float *__restrict__ q = Q + (long long)row * ldq;
+    for (int c = w; c < P; c += 4) {
+        float d = INFINITY;
+        int j = 0x7fffffff;
+        if (c < K) {
+            j = cand[(long long)slot * ldc + c];
+            d = knn_dist_of(knn_exact_d2<V4>(q, X + (long long)j * ldx, F, lane));
+        }
+        if (lane == 0) { s_d[c] = d; s_i[c] = j; }
+    }
+    __syncthreads();
+    for (int size = 2; size <= P; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            const int pos = 2 * tid - (tid & (stride - 1));
+            if (pos + stride < P) {
+                const bool up = (pos & size) == 0;
+                const float da = s_d[pos], db = s_d[pos + stride];
+                const int ia = s_i[pos], ib = s_i[pos + stride];
+                if (pair_less(db, ib, da, ia) == up) {
+                    s_d[pos] = db; s_i[pos] = ib;
+                    s_d[pos + stride] = da; s_i[pos + stride] = ia;
+                }
+            }
+            __syncthreads();
+        }
+    const int k = kk + include_self;
+    int *__restrict__ io = idx_out + (long long)row * k;
+    float *__restrict__ dn = dist_out + (long long)row * k;
+    if (include_self && tid == 0) { io[0] = self_r0 + row; dn[0] = 0.f; }
+    for (int c = tid; c < kk; c += 256) {
+        io[include_self + c] = s_i[c];
+        dn[include_self + c] = s_d[c];
+    }
+    if (certify && tid == 0) {
+        const double a = cbound * (nq[row] + *nxmax) + 1e-30;
+        const double dk = (double)s_d[kk - 1];
+        const bool ok = dk * dk * (1.0 + 0x1p-20) < (rej[slot] - a) * (1.0 - 0x1p-21);
+        if (!ok) fail_list[atomicAdd(n_fail, 1)] = row;
+    }
+}
+
+// include_self with k = 1: the graph is the self column alone.
+__global__ __launch_bounds__(256) void knn_self_only_kernel(int R, int self_r0, int *__restrict__ idx_out,
+                                                            float *__restrict__ dist_out, int *__restrict__ counter)
+{
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r == 0) *counter = 0;
+    if (r < R) { idx_out[r] = self_r0 + r; dist_out[r] = 0.f; }
+}
+
+// ------------------------------------------------------------------------------------------------------- host
+// The filter's error bound per unit of |q - s|^2 + |x - s|^2: a slab of KN_SLAB products and their
+// sums, each operation with relative error <= 2^-23 (round-to-nearest or truncation inside the matrix instruction), is off
+// by at most gamma = n u / (1 - n u), n = KN_SLAB + 2, times sum |a b| <= (|a|^2 + |b|^2) / 2, and g takes -2 of it; the
+// slab sums, the norms and g itself are float64 (< 2^-36 together); the rounding of g to fp32 (<= 2^-23 (1 + ...)) and of
+// the shifted operands (<= (4 u + ...) = 2^-22 (1 + ...)) fit into 2^-21.
+double filter_bound()
+{
+    const double n = KN_SLAB + 2, u = 0x1p-23;
+    return n * u / (1.0 - n * u) + 0x1p-21;
+}
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+struct KnnPlan {
+    int kk, K, fb_rows, rounds;
+    long long ldp, ldd;
+    size_t o_panel, o_nx, o_nq, o_max, o_zero, o_cand, o_rej, o_list, o_fb, total;
+};
+
+// 0, or the reason the shape is refused.
+const char *knn_plan(long long R, long long M, int F, int k, int slack, int self_form, int include_self, KnnPlan *p)
+{
+    if (R < 1 || M < 1) return "R and M must be >= 1";
+    if (R > 0x7fffffffLL || M > 0x7fffffffLL) return "R and M must fit 31 bits";
+    if (((R + KN_T - 1) / KN_T) * ((M + KN_T - 1) / KN_T) > 0x7fffffffLL) return "more than 2^31 tiles in one panel: split R";
+    if (F < 1 || F > DM_KNN_MAX_FEATURES) return "F outside 1 .. DM_KNN_MAX_FEATURES";
+    if (k < 1 || k > DM_KNN_MAX_K) return "k outside 1 .. DM_KNN_MAX_K";
+    if (slack < 0 || slack > DM_KNN_MAX_SLACK) return "slack outside 0 .. DM_KNN_MAX_SLACK";
+    if (include_self && !self_form) return "include_self needs the self form";
+    const long long eligible = M - (self_form ? 1 : 0);
+    p->kk = k - (include_self ? 1 : 0);
+    if (p->kk > eligible) return "k exceeds the number of eligible rows";
+    p->K = (int)(p->kk + slack < eligible ? p->kk + slack : eligible);
+    p->fb_rows = (int)(R < KN_FB_ROWS ? R : KN_FB_ROWS);
+    p->rounds = (int)((R + p->fb_rows - 1) / p->fb_rows);
+    p->ldp = (M + 31) / 32 * 32;
+    p->ldd = p->ldp;
+    const int ldc = p->K > 0 ? p->K : 1;
+    size_t o = 0;
+    p->o_panel = o; o += align256((size_t)R * p->ldp * sizeof(float));
+    p->o_nx = o;    o += align256((size_t)M * sizeof(double));
+    p->o_nq = o;    o += align256((size_t)R * sizeof(double));
+    p->o_max = o;   o += 256;
+    p->o_zero = o;  o += align256((size_t)F * sizeof(float));
+    p->o_cand = o;  o += align256((size_t)R * ldc * sizeof(int));
+    p->o_rej = o;   o += align256((size_t)R * sizeof(double));
+    p->o_list = o;  o += align256((size_t)R * sizeof(int));
+    p->o_fb = o;    o += align256((size_t)p->fb_rows * p->ldd * sizeof(float));
+    p->total = o;
+    return nullptr;
+}
+
+template <bool V4>
+void knn_launch(const KnnPlan &p, const float *X, int M, int F, long long ldx, const float *Q, int R, long long ldq,
+                int self_r0, int include_self, const float *shift, int *idx, float *dist, int *n_fallback, char *ws,
+                hipStream_t s)
+{
+    float *panel = (float *)(ws + p.o_panel);
+    double *nx = (double *)(ws + p.o_nx), *nq = (double *)(ws + p.o_nq), *nmax = (double *)(ws + p.o_max);
+    int *cand = (int *)(ws + p.o_cand), *list = (int *)(ws + p.o_list);
+    double *rej = (double *)(ws + p.o_rej);
+    float *fb = (float *)(ws + p.o_fb);
+    const float *gram_shift = shift ? shift : (const float *)(ws + p.o_zero);   // (zeros: dm_knn cleared them)
+    const RowList all = {nullptr, nullptr, 0};
+
+    hipLaunchKernelGGL(knn_norms_kernel<V4>, dim3((M + 3) / 4), dim3(256), 0, s, X, (long long)M, F, ldx, shift, nx);
+    if (self_r0 >= 0) nq = nx + self_r0;
+    else hipLaunchKernelGGL(knn_norms_kernel<V4>, dim3((R + 3) / 4), dim3(256), 0, s, Q, (long long)R, F, ldq, shift, nq);
+    hipLaunchKernelGGL(knn_max_kernel, dim3(1), dim3(256), 0, s, (const double *)nx, (long long)M, nmax, n_fallback);
+    const int row_tiles = (R + KN_T - 1) / KN_T;
+    hipLaunchKernelGGL(knn_gram_kernel<V4>, dim3((unsigned)((long long)row_tiles * ((M + KN_T - 1) / KN_T))), dim3(256), 0, s,
+                       Q, R, ldq, X, M, ldx, F, gram_shift, (const double *)nq, (const double *)nx, self_r0, panel, p.ldp, row_tiles);
+    hipLaunchKernelGGL(knn_select_kernel, dim3(R), dim3(256), 0, s, (const float *)panel, p.ldp, M, p.K, cand, p.K, rej,
+                       all);
+    hipLaunchKernelGGL(knn_refine_kernel<V4>, dim3(R), dim3(256), 0, s, Q, ldq, X, ldx, F, (const int *)cand, p.K, p.K, p.kk,
+                       include_self, self_r0, (const double *)rej, (const double *)nq, (const double *)nmax, filter_bound(), 1,
+                       idx, dist, list, n_fallback, all);
+    const unsigned gx = (unsigned)(M / 4 + 1 < 64 ? M / 4 + 1 : 64);      // (a round without listed rows costs a launch, not a grid)
+    for (int b = 0; b < p.rounds; ++b) {
+        const RowList rl = {list, n_fallback, b * p.fb_rows};
+        hipLaunchKernelGGL(knn_exact_panel_kernel<V4>, dim3(gx, p.fb_rows), dim3(256), 0, s, Q, ldq, X, M, ldx, F, self_r0, fb,
+                           p.ldd, rl);
+        hipLaunchKernelGGL(knn_select_kernel, dim3(p.fb_rows), dim3(256), 0, s, (const float *)fb, p.ldd, M, p.kk,
+                           cand, p.K, rej, rl);
+        hipLaunchKernelGGL(knn_refine_kernel<V4>, dim3(p.fb_rows), dim3(256), 0, s, Q, ldq, X, ldx, F, (const int *)cand, p.K,
+                           p.kk, p.kk, include_self, self_r0, (const double *)rej, (const double *)nq, (const double *)nmax,
+                           0.0, 0, idx, dist, list, n_fallback, rl);
+    }
+}
+
+}  // namespace
+
+extern "C" int64_t dm_knn_workspace_bytes(int64_t R, int64_t M, int F, int k, int slack)
+{
+    KnnPlan p;
+    // the larger of the two forms: the foreign form keeps K = k + slack up to M
+    if (knn_plan(R, M, F, k, slack, 0, 0, &p)) return -1;
+    return (int64_t)p.total;
+}
+
+extern "C" int dm_knn(const float *X, int64_t M, int F, int64_t ldx, const float *Q, int64_t R, int64_t ldq, int64_t self_r0,
+                      int k, int slack, int include_self, const float *shift, int32_t *indices, float *distances,
+                      int32_t *n_fallback, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    DM_REQUIRE(X, "dm_knn: X is NULL");
+    DM_REQUIRE(indices && distances && n_fallback, "dm_knn: indices / distances / n_fallback is NULL");
+    DM_REQUIRE(workspace, "dm_knn: workspace is NULL");
+    const int self_form = Q == nullptr;
+    KnnPlan p;
+    const char *why = knn_plan(R, M, F, k, slack, self_form, include_self, &p);
+    DM_REQUIRE(!why, "dm_knn: R = %lld, M = %lld, F = %d, k = %d, slack = %d, %s form: %s", (long long)R, (long long)M, F, k,
+               slack, self_form ? "self" : "foreign", why ? why : "");
+    DM_REQUIRE(ldx >= F, "dm_knn: leading dimension of X %lld < F = %d", (long long)ldx, F);
+    if (self_form) {
+        DM_REQUIRE(self_r0 >= 0 && self_r0 + R <= M, "dm_knn: rows %lld .. %lld of the self form lie outside X (M = %lld)",
+                   (long long)self_r0, (long long)(self_r0 + R - 1), (long long)M);
+        Q = X + self_r0 * ldx;
+        ldq = ldx;
+    } else {
+        DM_REQUIRE(ldq >= F, "dm_knn: leading dimension of Q %lld < F = %d", (long long)ldq, F);
+        self_r0 = -1;
+    }
+    DM_REQUIRE(workspace_bytes >= (int64_t)p.total, "dm_knn: workspace of %lld bytes, need %lld", (long long)workspace_bytes,
+               (long long)p.total);
+    DM_REQUIRE(((uintptr_t)workspace & 255) == 0, "dm_knn: workspace is not 256-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    if (p.kk == 0) {
+        hipLaunchKernelGGL(knn_self_only_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, (int)R, (int)self_r0,
+                           indices, distances, n_fallback);
+        return dm_launch_status("dm_knn");
+    }
+    if (!shift) {                           // the Gram kernel's loads are unconditional: no shift = a vector of zeros
+        const hipError_t e = hipMemsetAsync((char *)workspace + p.o_zero, 0, (size_t)F * sizeof(float), s);
+        if (e != hipSuccess) {
+            dm_set_error("dm_knn: hipMemsetAsync: %s", hipGetErrorString(e));
+            return (int)e;
+        }
+    }
+    if (vec4_ok(X, ldx, F) && vec4_ok(Q, ldq, F) && ((uintptr_t)shift & 15) == 0)
+        knn_launch<true>(p, X, (int)M, F, ldx, Q, (int)R, ldq, (int)self_r0, include_self ? 1 : 0, shift, indices, distances,
+                         n_fallback, (char *)workspace, s);
+    else
+        knn_launch<false>(p, X, (int)M, F, ldx, Q, (int)R, ldq, (int)self_r0, include_self ? 1 : 0, shift, indices, distances,
+                          n_fallback, (char *)workspace, s);
+    return dm_launch_status("dm_knn");
+}

@@ -10,6 +10,7 @@ import pickle
 
 import numpy as np
 
+from . import knn as _knn
 from .pca import PCA
 
 
@@ -85,24 +86,62 @@ def process_PCA(input_dir, output_dir, weights_dir, prefix, suffix='_after', pca
     return dats_
 
 
-def dim_reduction_pca(input_dirs, output_dirs, weights_dir, prefixes, fit_model, conditions=None, **kw):
-    """The PCA branch of run_dim_reduction.py::dim_reduction.  fit_model: pool <prefix>_latent_space_after.pkl of every
-    directory and prefix, in that order, one label per file, and fit (returns the PCA); else transform every (directory,
-    prefix) with the saved model (returns the list of outputs)."""
+def _prefix_list(prefixes):
     if isinstance(prefixes, str):
         prefixes = [prefixes]
     if not prefixes:
         raise ValueError("latent space vector file name must contain a prefix: '<prefix>_latent_space.pkl'")
+    return prefixes
+
+
+def pool_latents(input_dirs, prefixes):
+    """The training matrix of run_dim_reduction.py::dim_reduction (fit_model): <prefix>_latent_space_after.pkl of every directory and prefix, in that order, stacked;
+    one label per file.  Returns (vectors (N, F), labels)."""
+    vectors, labels = [], []
+    for label, (d, p) in enumerate((d, p) for d in input_dirs for p in _prefix_list(prefixes)):
+        with open(os.path.join(d, '{}_latent_space_after.pkl'.format(p)), 'rb') as f:
+            vec = pickle.load(f)
+        vectors.append(np.asarray(vec))
+        labels += [label] * vec.shape[0]
+    return np.concatenate(vectors, axis=0), labels
+
+
+def dim_reduction_pca(input_dirs, output_dirs, weights_dir, prefixes, fit_model, conditions=None, **kw):
+    """The PCA branch of run_dim_reduction.py::dim_reduction.  fit_model: pool <prefix>_latent_space_after.pkl of every
+    directory and prefix, in that order, one label per file, and fit (returns the PCA); else transform every (directory,
+    prefix) with the saved model (returns the list of outputs)."""
+    prefixes = _prefix_list(prefixes)
     if conditions is None:
         conditions = [os.path.basename(d) for d in input_dirs]
     if fit_model:
         weights_output = os.path.dirname(weights_dir) if os.path.isfile(weights_dir) else weights_dir
-        vectors, labels = [], []
-        for label, (d, p) in enumerate((d, p) for d in input_dirs for p in prefixes):
-            with open(os.path.join(d, '{}_latent_space_after.pkl'.format(p)), 'rb') as f:
-                vec = pickle.load(f)
-            vectors.append(np.asarray(vec))
-            labels += [label] * vec.shape[0]
-        return fit_PCA(np.concatenate(vectors, axis=0), weights_output, labels=labels, conditions=conditions, **kw)
+        vectors, labels = pool_latents(input_dirs, prefixes)
+        return fit_PCA(vectors, weights_output, labels=labels, conditions=conditions, **kw)
     pca = load_model(weights_dir)
     return [process_PCA(d, o, weights_dir, p, pca=pca) for d, o in zip(input_dirs, output_dirs) for p in prefixes]
+
+
+def fit_knn(train_data, weights_dir, n_nbrs=(15, 50, 200), **kw):
+    """The neighbour graphs fit_umap's three umap.UMAP(n_neighbors=n) fits start from (run_dim_reduction.py:143-207): ONE
+    exact graph at max(n_nbrs) with the row itself in column 0, written as <weights_dir>/knn_nbr<n>.pkl (protocol 4,
+    [knn_indices int64, knn_dists float32]) for every n -- the first n columns of that graph, which is sorted.  Returns
+    {n: (knn_indices, knn_dists)}.  umap.UMAP(n_neighbors=n, precomputed_knn=tuple(pickle.load(f))) takes a file as it is."""
+    n_nbrs = sorted(set(int(n) for n in n_nbrs))
+    if not n_nbrs or n_nbrs[0] < 1:
+        raise ValueError(f"n_nbrs={n_nbrs!r}: need at least one neighbour count >= 1")
+    os.makedirs(weights_dir, exist_ok=True)
+    indices, dists = _knn.knn_graph(train_data, n_nbrs[-1], include_self=True, **kw)
+    out = {}
+    for n in n_nbrs:
+        out[n] = (np.ascontiguousarray(indices[:, :n]), np.ascontiguousarray(dists[:, :n]))
+        with open(os.path.join(weights_dir, 'knn_nbr{}.pkl'.format(n)), 'wb') as f:
+            pickle.dump([out[n][0], out[n][1]], f, protocol=4)
+    return out
+
+
+def dim_reduction_knn(input_dirs, weights_dir, prefixes, n_nbrs=(15, 50, 200), **kw):
+    """The pooling of the UMAP branch of run_dim_reduction.py::dim_reduction (fit_model=True), followed by fit_knn: the same
+    files in the same order as dim_reduction_pca pools them, so row i of the graph is row i of the PCA's training matrix."""
+    weights_output = os.path.dirname(weights_dir) if os.path.isfile(weights_dir) else weights_dir
+    vectors, _ = pool_latents(input_dirs, prefixes)
+    return fit_knn(vectors, weights_output, n_nbrs=n_nbrs, **kw)

@@ -1,0 +1,146 @@
+"""The exact k-nearest-neighbour graph of the latents on the GPU: what umap.UMAP(n_neighbors=n) computes first, and takes
+ready-made as precomputed_knn=(knn_indices, knn_dists) (run_dim_reduction.py:143-207 fit_umap fits three of them, n = 15, 50,
+200, on the pooled (N, 4096) latents; one sorted exact graph at k = 200 holds all three as its first columns).
+
+dm_knn (csrc/knn.hip) works on one panel of query rows against all of X; this module keeps X resident, computes the shift
+(the fp32 column mean: distances are translation invariant, the filter's error bound is not), walks the panels and returns
+numpy (indices int64, distances float32).  The distance matrix is never formed."""
+import numpy as np
+import torch
+
+from . import ops
+
+MAX_FEATURES = 16384           # DM_KNN_MAX_FEATURES
+MAX_K = ops.KNN_MAX_K
+DEFAULT_CHUNK_ROWS = 2048
+
+
+def _device(X, device):
+    if torch.is_tensor(X) and X.is_cuda:
+        return X.device
+    return torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+
+
+def _resident(X, device):
+    """X as a 2-D fp32 device matrix with unit column stride: a CUDA tensor is used in place, host data move there once."""
+    if torch.is_tensor(X) and X.is_cuda:
+        x = X if X.dtype == torch.float32 else X.float()
+    else:
+        if not torch.is_tensor(X):
+            X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32))
+        x = X.to(_device(X, device), dtype=torch.float32)
+    if x.dim() != 2:
+        raise ValueError(f"knn expects a 2-D (samples, features) array, got shape {tuple(x.shape)}")
+    if x.shape[1] > 1 and x.stride(1) != 1:
+        x = x.contiguous()
+    return x
+
+
+def _check(M, F, k, eligible):
+    if F < 1 or F > MAX_FEATURES:
+        raise ValueError(f"knn on the GPU supports 1 .. {MAX_FEATURES} features, got {F}")
+    if k < 1 or k > MAX_K:
+        raise ValueError(f"k = {k} is outside 1 .. {MAX_K}")
+    if k > eligible:
+        raise ValueError(f"k = {k} exceeds the {eligible} rows a query can have as neighbours (M = {M})")
+
+
+def column_shift(x):
+    """fp32 column mean of a device matrix (dm_pca_colsum: float64 sums in a fixed order)."""
+    return (ops.pca_colsum(x) / x.shape[0]).float()
+
+
+def _panel_state(x, R, k, cr, slack, shift):
+    """What every panel of a call shares: the shift, the slack, one workspace for panels of cr rows, the outputs."""
+    s = column_shift(x) if isinstance(shift, str) else shift
+    sl = ops.KNN_DEFAULT_SLACK if slack is None else int(slack)
+    ws = ops.knn_workspace(cr, x.shape[0], x.shape[1], k, sl, x)
+    idx = torch.empty((R, k), dtype=torch.int32, device=x.device)
+    dist = torch.empty((R, k), dtype=torch.float32, device=x.device)
+    return s, sl, ws, idx, dist, []
+
+
+def _result(idx, dist, counts, return_fallback):
+    """numpy (indices int64, distances float32[, rows redone exactly]): the dtypes umap-learn's precomputed_knn takes."""
+    res = idx.cpu().numpy().astype(np.int64), dist.cpu().numpy()
+    return res + (int(torch.cat(counts).sum().item()),) if return_fallback else res
+
+
+def knn_graph(X, k, include_self=True, rows=None, chunk_rows=DEFAULT_CHUNK_ROWS, device=None, slack=None, shift="mean",
+              return_fallback=False):
+    """The k-NN graph of the rows of X (M, F): numpy (indices (R, k) int64, distances (R, k) float32), sorted by (distance,
+    index).  include_self=True: column 0 is the row itself at 0.0 and k - 1 other rows follow (umap-learn's layout).
+    rows=(r0, R): only those rows of the graph (a data-parallel caller passes its dist.shard_range).  X: a CUDA tensor (used
+    in place) or host data, moved to the device once.  shift: "mean" (computed here), None, or an (F,) fp32 device tensor.
+    return_fallback: also the number of rows that were redone exactly."""
+    x = _resident(X, device)
+    M, F = x.shape
+    k = int(k)
+    _check(M, F, k, M - 1 + (1 if include_self else 0))
+    r0, R = (0, M) if rows is None else (int(rows[0]), int(rows[1]))
+    if r0 < 0 or R < 1 or r0 + R > M:
+        raise ValueError(f"rows=({r0}, {R}) lie outside X with {M} rows")
+    cr = max(1, min(int(chunk_rows), R))
+    with torch.no_grad(), torch.cuda.device(x.device):
+        s, sl, ws, idx, dist, counts = _panel_state(x, R, k, cr, slack, shift)
+        for lo in range(0, R, cr):
+            m = min(cr, R - lo)
+            _, _, c = ops.knn(x, k=k, rows=(r0 + lo, m), shift=s, slack=sl, include_self=include_self,
+                              out=(idx[lo:lo + m], dist[lo:lo + m]), workspace=ws)
+            counts.append(c)
+        return _result(idx, dist, counts, return_fallback)
+
+
+def knn_query(X, Q, k, chunk_rows=DEFAULT_CHUNK_ROWS, device=None, slack=None, shift="mean", return_fallback=False):
+    """The k nearest rows of X for every row of Q (no row is excluded; k <= M).  Q on the device is used in place; host Q is
+    streamed in chunks of chunk_rows rows through pinned staging, the next chunk's copy overlapping the current chunk's
+    kernels.  Returns numpy (indices (R, k) int64, distances (R, k) float32)."""
+    x = _resident(X, device)
+    M, F = x.shape
+    k = int(k)
+    _check(M, F, k, M)
+    on_device = torch.is_tensor(Q) and Q.is_cuda
+    if not torch.is_tensor(Q):
+        Q = torch.from_numpy(np.asarray(Q))
+    if Q.dim() != 2 or Q.shape[1] != F:
+        raise ValueError(f"Q has shape {tuple(Q.shape)}, expected (n, {F})")
+    R = Q.shape[0]
+    if R < 1:
+        raise ValueError("Q has no rows")
+    cr = max(1, min(int(chunk_rows), R))
+    with torch.no_grad(), torch.cuda.device(x.device):
+        s, sl, ws, idx, dist, counts = _panel_state(x, R, k, cr, slack, shift)
+        if on_device:
+            q = Q if Q.dtype == torch.float32 else Q.float()
+            if F > 1 and q.stride(1) != 1:
+                q = q.contiguous()
+            for lo in range(0, R, cr):
+                m = min(cr, R - lo)
+                counts.append(ops.knn(x, q[lo:lo + m], k=k, shift=s, slack=sl, out=(idx[lo:lo + m], dist[lo:lo + m]),
+                                      workspace=ws)[2])
+        else:
+            compute = torch.cuda.current_stream()
+            s_in = torch.cuda.Stream()
+            s_in.wait_stream(compute)
+            direct = Q.dtype == torch.float32 and Q.is_contiguous() and Q.is_pinned()
+            stage = None if direct else [torch.empty((cr, F), dtype=torch.float32, pin_memory=True) for _ in range(2)]
+            q_dev = [torch.empty((cr, F), dtype=torch.float32, device=x.device) for _ in range(2)]
+            ev_in = [torch.cuda.Event() for _ in range(2)]       # chunk has reached q_dev[b] (staging b is free again)
+            ev_done = [torch.cuda.Event() for _ in range(2)]     # kernels reading q_dev[b] are done
+            for it, lo in enumerate(range(0, R, cr)):
+                b = it & 1
+                m = min(cr, R - lo)
+                src = Q[lo:lo + m]
+                if not direct:
+                    ev_in[b].synchronize()
+                    stage[b][:m].copy_(src)
+                    src = stage[b][:m]
+                with torch.cuda.stream(s_in):
+                    s_in.wait_event(ev_done[b])
+                    q_dev[b][:m].copy_(src, non_blocking=True)
+                    ev_in[b].record(s_in)
+                compute.wait_event(ev_in[b])
+                counts.append(ops.knn(x, q_dev[b][:m], k=k, shift=s, slack=sl, out=(idx[lo:lo + m], dist[lo:lo + m]),
+                                      workspace=ws)[2])
+                ev_done[b].record(compute)
+        return _result(idx, dist, counts, return_fallback)

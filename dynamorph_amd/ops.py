@@ -1372,3 +1372,63 @@ def pca_transform(X, V, shift=None, out=None):
         raise ValueError(f"dm_pca_transform: out has shape {tuple(out.shape)}, need ({N}, {k})")
     L.check(lib.dm_pca_transform(p, N, F, ld, _ptr(shift), _ptr(V), k, _ptr(out), _stream()), "dm_pca_transform")
     return out
+
+
+# ----------------------------------------------------------------------------- exact k-NN graph of the latents
+KNN_MAX_K = 256                # DM_KNN_MAX_K
+KNN_MAX_SLACK = 256            # DM_KNN_MAX_SLACK
+KNN_DEFAULT_SLACK = 64
+
+
+def knn_workspace(R, M, F, k, slack, like):
+    """A workspace dm_knn accepts for panels of up to R queries (uint8, 256-byte aligned by the allocator)."""
+    nbytes = L.load().dm_knn_workspace_bytes(R, M, F, k, slack)
+    if nbytes < 0:
+        raise ValueError(f"dm_knn: bad shape R = {R}, M = {M}, F = {F}, k = {k}, slack = {slack}")
+    return torch.empty(int(nbytes), device=like.device, dtype=torch.uint8)
+
+
+@_op
+def knn(X, Q=None, k=15, rows=None, shift=None, slack=None, include_self=False, out=None, workspace=None):
+    """The k nearest rows of X (M, F) for every query, exact with respect to the fp32-difference / float64-sum distance
+    (dm_knn): (indices (R, k) int32, distances (R, k) fp32 sorted by (distance, index), n_fallback_rows (1,) int32 on the
+    device).  Queries: Q (R, F), or Q=None -- the rows of X itself, all of them or rows=(r0, R), each row excluded from its
+    own list by index (include_self=True: column 0 is the row itself at distance 0.0, umap-learn's layout).  shift (F,) fp32:
+    subtracted in the filter's operand load (the results do not depend on it); slack: extra candidates the filter keeps
+    (0 .. 256, the results do not depend on it either; 0 sends nearly every row of uncentred data through the fallback)."""
+    lib = L.load()
+    px, M, F, ldx = _rows(X)
+    if Q is not None:
+        if rows is not None or include_self:
+            raise ValueError("dm_knn: rows= and include_self belong to the self form (Q=None)")
+        pq, R, Fq, ldq = _rows(Q)
+        if Fq != F:
+            raise ValueError(f"dm_knn: Q has {Fq} features, X has {F}")
+        r0 = -1
+    else:
+        r0, R = (0, M) if rows is None else (int(rows[0]), int(rows[1]))
+        if r0 < 0 or R < 1 or r0 + R > M:
+            raise ValueError(f"dm_knn: rows=({r0}, {R}) lie outside X with {M} rows")
+        pq, ldq = None, 0
+    k = int(k)
+    if k < 1 or k > KNN_MAX_K:
+        raise ValueError(f"dm_knn: k outside 1 .. {KNN_MAX_K}, got {k}")
+    slack = KNN_DEFAULT_SLACK if slack is None else int(slack)
+    if shift is not None and shift.numel() != F:
+        raise ValueError(f"dm_knn: shift has {shift.numel()} entries, F = {F}")
+    if out is None:
+        idx, dist = _new((R, k), X, torch.int32), _new((R, k), X)
+    else:
+        idx, dist = out
+        if tuple(idx.shape) != (R, k) or tuple(dist.shape) != (R, k):
+            raise ValueError(f"dm_knn: out has shapes {tuple(idx.shape)}, {tuple(dist.shape)}, need ({R}, {k}) twice")
+    nfb = _new((1,), X, torch.int32)
+    nbytes = lib.dm_knn_workspace_bytes(R, M, F, k, slack)
+    if nbytes >= 0 and (workspace is None or workspace.numel() * workspace.element_size() < nbytes):
+        workspace = torch.empty(int(nbytes), device=X.device, dtype=torch.uint8)
+    if workspace is None:       # a bad shape: dm_knn names it (nothing is launched)
+        workspace = torch.empty(256, device=X.device, dtype=torch.uint8)
+    L.check(lib.dm_knn(px, M, F, ldx, pq, R, ldq, r0, k, slack, 1 if include_self else 0, _ptr(shift), _ptr(idx, torch.int32),
+                       _ptr(dist), _ptr(nfb, torch.int32), _ptr(workspace, workspace.dtype),
+                       workspace.numel() * workspace.element_size(), _stream()), "dm_knn")
+    return idx, dist, nfb

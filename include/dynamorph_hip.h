@@ -790,6 +790,28 @@ int dm_pca_gram(const float *X, int64_t N, int F, int64_t ld, const float *shift
 int dm_pca_transform(const float *X, int64_t N, int F, int64_t ld, const float *shift, const float *V, int k, float *Y,
                      void *stream);
 
+/* ===== exact k-nearest-neighbour graph of the latents (the graph umap.UMAP takes as precomputed_knn) ==== */
+/* X: M x F fp32 row-major, leading dimension ldx >= F, 1 <= F <= DM_KNN_MAX_FEATURES: the point set.  Queries: Q (R x F,
+ * leading dimension ldq) -- or Q == NULL, the SELF form: rows self_r0 .. self_r0 + R - 1 of X, the pair (i, i) excluded by
+ * index.  Per query the k rows of X of smallest Euclidean distance, sorted by (distance, index) ascending: indices (R x k
+ * int32) and distances (R x k fp32, not squared).  include_self (self form only): column 0 is (i, 0.0) and k - 1 others
+ * follow, the layout of umap-learn and scikit-learn.  Every distance is the pair's exact-form value sqrt(sum_f (q_f - x_f)^2)
+ * -- differences and squares in fp32, sums in float64 in a fixed order -- and the list is exact with respect to it; the
+ * shifted Gram product on the f32 matrix instruction only filters (k + slack candidates per row, 0 <= slack <=
+ * DM_KNN_MAX_SLACK), and a row whose filter result cannot be certified by the proven error bound is redone from exact
+ * distances to all M rows.  *n_fallback (device int) counts those rows; it is cleared by the call.  Results depend on the
+ * inputs only -- not on slack, shift, R or the launch.  shift: F floats (e.g. the fp32 column mean) or NULL. */
+#define DM_KNN_MAX_FEATURES 16384
+#define DM_KNN_MAX_K 256
+#define DM_KNN_MAX_SLACK 256
+/* HOST: bytes of device workspace dm_knn needs for a panel of R queries (-1 for a bad shape; k > M included). */
+int64_t dm_knn_workspace_bytes(int64_t R, int64_t M, int F, int k, int slack);
+/* Negative return + dm_last_error() text for NULL or bad arguments (k > eligible rows, workspace too small or not 256-byte
+ * aligned, ...) before any launch; asynchronous on `stream`, no read-back, capture-free. */
+int dm_knn(const float *X, int64_t M, int F, int64_t ldx, const float *Q, int64_t R, int64_t ldq, int64_t self_r0, int k,
+           int slack, int include_self, const float *shift, int32_t *indices, float *distances, int32_t *n_fallback,
+           void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
