@@ -145,3 +145,38 @@ def dim_reduction_knn(input_dirs, weights_dir, prefixes, n_nbrs=(15, 50, 200), *
     weights_output = os.path.dirname(weights_dir) if os.path.isfile(weights_dir) else weights_dir
     vectors, _ = pool_latents(input_dirs, prefixes)
     return fit_knn(vectors, weights_output, n_nbrs=n_nbrs, **kw)
+
+
+def fit_umap_embedding(train_data, weights_dir, labels=None, n_nbrs=(15, 50, 200), a_s=(1.58,), b_s=(0.9,), **kw):
+    """fit_umap of run_dim_reduction.py:143-207 without umap-learn: ONE exact graph at max(n_nbrs) through fit_knn (the
+    knn_nbr<n>.pkl files are still written), then one embedding per (n, a, b) from its first n columns by
+    umap_layout.UMAPEmbedding, written as <weights_dir>/embedding_umap_nbr<n>_a<a>_b<b>.pkl
+    (protocol 4, [embedding (N, 2) float32, labels]).  The name does not start with 'umap': the reference's umap_transform
+    lists umap*.pkl there and calls .transform on what it unpickles.  kw: UMAPEmbedding's (n_epochs, negative_sample_rate,
+    gamma, init, seed, device).  Returns {(n, a, b): embedding}."""
+    from .umap_layout import UMAPEmbedding, pca_coordinates
+    init = kw.pop("init", "pca")
+    device = kw.get("device")
+    x = _knn._resident(train_data, device)
+    graphs = fit_knn(x, weights_dir, n_nbrs=n_nbrs)
+    if isinstance(init, str):
+        if init != "pca":
+            raise ValueError(f"init={init!r}: 'pca' or an (N, 2) array")
+        init = pca_coordinates(x).cpu().numpy()
+    out = {}
+    for n in sorted(graphs):
+        for a in a_s:
+            for b in b_s:
+                emb = UMAPEmbedding(n_neighbors=n, a=a, b=b, **kw).fit_graph(graphs[n][0], graphs[n][1], init).embedding_
+                out[(n, a, b)] = emb
+                with open(os.path.join(weights_dir, 'embedding_umap_nbr{}_a{}_b{}.pkl'.format(n, a, b)), 'wb') as f:
+                    pickle.dump([emb, labels], f, protocol=4)
+    return out
+
+
+def dim_reduction_umap_embedding(input_dirs, weights_dir, prefixes, n_nbrs=(15, 50, 200), a_s=(1.58,), b_s=(0.9,), **kw):
+    """The pooling of the UMAP branch of run_dim_reduction.py::dim_reduction (fit_model=True) -- the same files in the same
+    order as dim_reduction_knn and dim_reduction_pca pool them, one label per file -- followed by fit_umap_embedding."""
+    weights_output = os.path.dirname(weights_dir) if os.path.isfile(weights_dir) else weights_dir
+    vectors, labels = pool_latents(input_dirs, prefixes)
+    return fit_umap_embedding(vectors, weights_output, labels=labels, n_nbrs=n_nbrs, a_s=a_s, b_s=b_s, **kw)

@@ -1432,3 +1432,56 @@ def knn(X, Q=None, k=15, rows=None, shift=None, slack=None, include_self=False, 
                        _ptr(dist), _ptr(nfb, torch.int32), _ptr(workspace, workspace.dtype),
                        workspace.numel() * workspace.element_size(), _stream()), "dm_knn")
     return idx, dist, nfb
+
+
+# ----------------------------------------------------------------------------- UMAP behind the k-NN graph
+UMAP_MAX_K = 256               # DM_UMAP_MAX_K
+
+
+def _umap_graph(dists, indices=None):
+    if dists.dim() != 2 or (indices is not None and tuple(indices.shape) != tuple(dists.shape)):
+        raise ValueError("dm_umap: knn_dists must be (N, k) and knn_indices of the same shape")
+    N, k = dists.shape
+    if k < 2 or k > UMAP_MAX_K or k > N:
+        raise ValueError(f"dm_umap: k = {k} outside 2 .. min({UMAP_MAX_K}, N = {N})")
+    return N, k
+
+
+@_op
+def umap_smooth(dists):
+    """(rho (N,) fp32, sigma (N,) fp32, row_mean (N,) float64, global_mean (1,) float64) of the (N, k) fp32 distances of a
+    k-NN graph with the row itself in column 0 (dm_umap_smooth)."""
+    N, k = _umap_graph(dists)
+    rho, sigma = _new((N,), dists), _new((N,), dists)
+    row_mean, global_mean = _new((N,), dists, torch.float64), _new((1,), dists, torch.float64)
+    L.check(L.load().dm_umap_smooth(_ptr(dists), N, k, _ptr(rho), _ptr(sigma), _ptr(row_mean, torch.float64),
+                                    _ptr(global_mean, torch.float64), _stream()), "dm_umap_smooth")
+    return rho, sigma, row_mean, global_mean
+
+
+@_op
+def umap_membership(indices, dists, rho, sigma):
+    """The (N, k) fp32 membership strengths of the directed graph (dm_umap_membership); indices int32."""
+    N, k = _umap_graph(dists, indices)
+    if rho.numel() != N or sigma.numel() != N:
+        raise ValueError(f"dm_umap_membership: rho / sigma need {N} entries")
+    out = _new((N, k), dists)
+    L.check(L.load().dm_umap_membership(_ptr(indices, torch.int32), _ptr(dists), N, k, _ptr(rho), _ptr(sigma), _ptr(out),
+                                        _stream()), "dm_umap_membership")
+    return out
+
+
+@_op
+def umap_epoch(indptr, cols, eps, eps_neg, nxt, nxt_neg, y_in, y_out, epoch, n_epochs, a, b, gamma, seed, group=0):
+    """One epoch of the layout (dm_umap_epoch): y_out from y_in, the schedule state nxt / nxt_neg advanced in place.  The
+    columns must lie in [0, N): the caller has checked them."""
+    N, nnz = indptr.numel() - 1, cols.numel()
+    if tuple(y_in.shape) != (N, 2) or tuple(y_out.shape) != (N, 2):
+        raise ValueError(f"dm_umap_epoch: y_in / y_out must be ({N}, 2)")
+    if not (eps.numel() == eps_neg.numel() == nxt.numel() == nxt_neg.numel() == nnz):
+        raise ValueError(f"dm_umap_epoch: eps / eps_neg / next / next_neg need {nnz} entries")
+    L.check(L.load().dm_umap_epoch(_ptr(indptr, torch.int64), _ptr(cols, torch.int32), N, nnz, _ptr(eps), _ptr(eps_neg),
+                                   _ptr(nxt), _ptr(nxt_neg), _ptr(y_in), _ptr(y_out), int(epoch), int(n_epochs), float(a),
+                                   float(b), float(gamma), int(seed) & 0xFFFFFFFFFFFFFFFF, int(group), _stream()),
+            "dm_umap_epoch")
+    return y_out

@@ -812,6 +812,31 @@ int dm_knn(const float *X, int64_t M, int F, int64_t ldx, const float *Q, int64_
            int slack, int include_self, const float *shift, int32_t *indices, float *distances, int32_t *n_fallback,
            void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ===== UMAP behind the exact k-NN graph: smooth distances, membership strengths, one layout epoch ==== */
+/* dists / indices: the N x k graph dm_knn returns with include_self (column 0 the row itself at 0.0, rows sorted),
+ * 2 <= k <= DM_UMAP_MAX_K, k <= N < 2^31.  Negative return + dm_last_error() text for NULL or bad arguments before any
+ * launch; asynchronous on `stream`, no read-back. */
+#define DM_UMAP_MAX_K 256
+/* Per row over columns 1 .. k - 1: rho = the smallest strictly positive distance (0 if none); sigma = the bisection of
+ * sum_j (d_j - rho > 0 ? exp(-(d_j - rho) / sigma) : 1) against log2(k) from lo = 0, hi = inf, mid = 1 (mid doubles while
+ * hi = inf; stop at |S - log2 k| < 1e-5 or after 64 steps), in float64, then floored at 1e-3 * row_mean (rho > 0) or
+ * 1e-3 * global_mean (rho = 0); both stored as fp32.  row_mean (N float64): mean of a row, column 0 included;
+ * *global_mean: mean of the row means.  Sums in float64 in a fixed order. */
+int dm_umap_smooth(const float *dists, int64_t N, int k, float *rho, float *sigma, double *row_mean, double *global_mean,
+                   void *stream);
+/* membership (N x k fp32): 0 where indices[i][j] == i; 1 where d - rho_i <= 0 or sigma_i == 0; else
+ * expf(-((d - rho_i) / sigma_i)) -- one fp32 subtraction, one fp32 division, the exponential. */
+int dm_umap_membership(const int32_t *indices, const float *dists, int64_t N, int k, const float *rho, const float *sigma,
+                       float *membership, void *stream);
+/* One epoch of the layout: y_out (N x 2 fp32) from y_in and the CSR graph (indptr N + 1 int64, cols nnz int32, every column
+ * in [0, N): the caller checks), advancing the schedule state next / next_neg (nnz fp32 each) by eps / eps_neg in place.
+ * Vertex i owns row i, y_out[i] and its entries' state: no two threads write one address, there are no atomics, and the
+ * result is a function of the inputs, `seed` and `epoch` only.  alpha = 1 - epoch / n_epochs in fp32.  group: lanes per
+ * vertex, 1, 8 or 32, or 0 = the library's choice (8); the result does not depend on it.  y_in != y_out. */
+int dm_umap_epoch(const int64_t *indptr, const int32_t *cols, int64_t N, int64_t nnz, const float *eps, const float *eps_neg,
+                  float *next, float *next_neg, const float *y_in, float *y_out, int epoch, int n_epochs, float a, float b,
+                  float gamma, uint64_t seed, int group, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
