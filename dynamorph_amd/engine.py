@@ -36,9 +36,13 @@ class Layers:
     halves: `model.enc` / `model.dec` called on their own build Layers(enc=self) / Layers(dec=self) -- no back-reference
     to the parent, so copy.deepcopy(model) and pickling give an independent, working module."""
 
+    latent_stride = 8            # patch pixels per latent position: three stride-2 convolutions
+    latent_after_vq = False      # the latents of the pairwise term and of the inference drivers' cotangents: z_before
+
     def __init__(self, model=None, enc=None, dec=None):
         if model is not None:
             enc, dec = model.enc, model.dec
+            self.loss_weights = (float(model.weight_recon), float(model.weight_commitment))     # of (recon, commitment) in total
         self.codebook = model.vq.w if model is not None else None
         self.channel_var = model.channel_var if model is not None else None
         if enc is not None:
@@ -46,9 +50,8 @@ class Layers:
             self.enc4, self.bn2 = enc[4], enc[5]
             self.enc7, self.bn3 = enc[7], enc[8]
             self.enc10, self.bn4 = enc[10], enc[11]
-            self.res = [(l[1], l[2], l[4], l[5]) for l in enc[12].layers]
-            self.nin = self.enc0.weight.shape[1]
-            self.nh = self.enc10.weight.shape[0]
+            self.res = enc[12]._handles()
+            self.nin, self.nh = self.enc0.weight.shape[1], self.enc10.weight.shape[0]
             self.nrh = self.res[0][0].weight.shape[0] if self.res else 0
         if dec is not None:
             self.dec0, self.dec2, self.dec4, self.dec6 = dec[0], dec[2], dec[4], dec[6]
@@ -67,6 +70,46 @@ class Layers:
     def decoder_params(self):
         return [self.dec0.weight, self.dec0.bias, self.dec2.weight, self.dec2.bias,
                 self.dec4.weight, self.dec4.bias, self.dec6.weight, self.dec6.bias]
+
+
+class Z32Layers:
+    """The twin of Layers for VQ_VAE_z32 (vae.py:348-474), again without a back-reference to the parent.  The child indices of
+    its two nn.Sequentials are spelled here and nowhere else: enc = conv0 bn0 ReLU conv1 bn1 enc_block, dec = dec_block up0 bn_up
+    ReLU up1.  enc_block / dec_block: the ResidualBlock modules; enc_res / dec_res: their handles (residual_forward / _backward)."""
+
+    latent_stride = 4            # two stride-2 convolutions
+    latent_after_vq = True       # the pairwise term acts on z_after (vae.py:441-455)
+    loss_weights = (1.0, 1.0)    # total = recon + commitment (vae.py:457)
+
+    def __init__(self, model=None, enc=None, dec=None):
+        if model is not None:
+            enc, dec = model.enc, model.dec
+        self.codebook = model.vq.w if model is not None else None
+        self.channel_var = model.channel_var if model is not None else None
+        if enc is not None:
+            self.conv0, self.bn0, self.conv1, self.bn1, self.enc_block = enc[0], enc[1], enc[3], enc[4], enc[5]
+            self.enc_res = self.enc_block._handles()
+            self.nin, self.nh = self.conv0.weight.shape[1], self.conv1.weight.shape[0]
+        if dec is not None:
+            self.dec_block, self.up0, self.bn_up, self.up1 = dec[0], dec[1], dec[2], dec[4]
+            self.dec_res = self.dec_block._handles()
+            if enc is None:
+                self.nin, self.nh = self.up1.weight.shape[1], self.up0.weight.shape[0]
+
+    def stem_params(self):
+        return [p for m in (self.conv0, self.bn0, self.conv1, self.bn1) for p in (m.weight, m.bias)]
+
+    def tail_params(self):
+        return [p for m in (self.up0, self.bn_up, self.up1) for p in (m.weight, m.bias)]
+
+
+def layers_of(model, who=None):
+    """The Layers object of a model of either family (the models name their class: VQ_VAE._layers_class).  Any other module:
+    TypeError in the name of the caller `who`; who=None: None (encode_patches runs such a module as it is)."""
+    cls = getattr(model, "_layers_class", None)
+    if cls is None and who is not None:
+        raise TypeError("{}: {} is not built on the HIP path (VQ_VAE, VQ_VAE_z16, VQ_VAE_z32)".format(who, type(model).__name__))
+    return None if cls is None else cls(model)
 
 
 # ------------------------------------------------------------------------- BatchNorm glue
@@ -702,12 +745,15 @@ def decoder_backward(L, cx, gscale, gdec_ext, G, want_gz=True, pending=None):
 
 # ======================================================================== VQ_VAE_z32 (vae.py:348-474)
 # 32x32 latent: enc = Conv(4,2,1) BN ReLU Conv(4,2,1) BN ResidualBlock; dec = ResidualBlock ConvT BN ReLU ConvT.
-# The residual stacks are the ResidualBlock module itself (residual_forward/backward); these four functions are the
-# two conv "stems" around them.  Same conventions as above: raw conv outputs + statistics slabs, BatchNorm applied by
+# L: a Z32Layers.  The residual stacks are the ResidualBlock module itself (residual_forward/backward); the four z32_stem_* /
+# z32_tail_* functions are the two conv "stems" around them (the autograd path runs them as nodes of their own, beside the
+# ResidualBlock's), the four z32_encoder_* / z32_decoder_* functions the whole stages, with the calling conventions of
+# encoder_forward .. decoder_backward.  Same conventions as above: raw conv outputs + statistics slabs, BatchNorm applied by
 # the consumer's operand load, BatchNorm backward as an AFFINE2 operand.
-def z32_stem_forward(conv0, bn0, conv1, bn1, x, per_sample=False):
+def z32_stem_forward(L, x, per_sample=False):
     """x (B,NIN,H,W) -> h = BN(conv1(relu(BN(conv0(x))))) (B,nh,H/4,W/4), materialised for the residual stack.
     per_sample=True: every BatchNorm uses that sample's own statistics (process_VAE's batch-of-one calls, batched)."""
+    conv0, bn0, conv1, bn1 = L.conv0, L.bn0, L.conv1, L.bn1
     B, NIN, H, W = x.shape
     ps = per_sample
     c1, nh = conv0.weight.shape[0], conv1.weight.shape[0]
@@ -723,7 +769,7 @@ def z32_stem_forward(conv0, bn0, conv1, bn1, x, per_sample=False):
     return h, cx
 
 
-def z32_stem_backward(conv0, bn0, conv1, bn1, cx, g_h, G, stats=None, pending=None, zero_fed_biases=True, want_dx=False,
+def z32_stem_backward(L, cx, g_h, G, stats=None, pending=None, zero_fed_biases=True, want_dx=False,
                       want_param_grads=True):
     """stats: the (sum g, sum g*a2) slabs when the caller's last kernel already produced them (residual_backward with
     q_below = cx.a2); pending: the caller's list for ONE slab reduction of the whole backward pass (None: reduced here);
@@ -731,6 +777,7 @@ def z32_stem_backward(conv0, bn0, conv1, bn1, cx, g_h, G, stats=None, pending=No
     conv biases that feed a BatchNorm are not written.
     A context made with per_sample=True goes backward per patch and want_param_grads=False returns the data gradient only,
     both as in encoder_backward (`stats` then is grouped by patch: residual_backward's per-sample slabs)."""
+    conv0, bn0, conv1, bn1 = L.conv0, L.bn0, L.conv1, L.bn1
     B, NIN, c1, nh, H1, W1, H2, W2 = cx.dims
     ps = bool(getattr(cx, "per_sample", False))
     nb = B if ps else 0
@@ -755,10 +802,11 @@ def z32_stem_backward(conv0, bn0, conv1, bn1, cx, g_h, G, stats=None, pending=No
     return None
 
 
-def z32_tail_forward(up0, bn, up1, r, x, mask, channel_var, per_sample=False, defer=None):
+def z32_tail_forward(L, r, x, mask, per_sample=False, defer=None):
     """r (B,nh,H2,W2) -> decoded (B,NIN,4*H2,4*W2) (+ loss slabs when x is given).
     per_sample=True: the BatchNorm uses every sample's own statistics (the reference's batch-of-one call, batched), exactly
     as z32_stem_forward does; defer: the caller's list of postponed running-statistics updates (ops.bn_running_replay)."""
+    up0, bn, up1 = L.up0, L.bn_up, L.up1
     B, nh, H2, W2 = r.shape
     ps = per_sample
     c1, NIN = up0.weight.shape[1], up1.weight.shape[1]
@@ -769,17 +817,18 @@ def z32_tail_forward(up0, bn, up1, r, x, mask, channel_var, per_sample=False, de
     coefd, savedd = _bn_coef(st, bn, 4 * H2 * W2 * (1 if ps else B), ps, B, defer)
     dec, _ = ops.conv3x3(Op(d1, DM_LOAD_AFFINE_RELU, coefd, per_sample=ps), _view_swapped(up1.weight), B, c1, 4 * NIN,
                          2 * H2, 2 * W2, taps=9, pixel_shuffle=True, bias=_w(up1.bias))
-    var = _var(channel_var, NIN, r.device)
+    var = _var(L.channel_var, NIN, r.device)
     slabs = ops.recon_loss(dec, x, mask, var) if x is not None else None
     cx = SimpleNamespace(r=r, d1=d1, coefd=coefd, savedd=savedd, dec=dec, x=x, mask=mask, var=var, loss_slabs=slabs,
                          per_sample=ps, dims=(B, nh, c1, NIN, H2, W2))
     return dec, cx
 
 
-def z32_tail_backward(up0, bn, up1, cx, gscale, gdec_ext, G, want_gr=True, pending=None, zero_fed_biases=True,
+def z32_tail_backward(L, cx, gscale, gdec_ext, G, want_gr=True, pending=None, zero_fed_biases=True,
                       want_param_grads=True):
     """gscale: 1-element device tensor d(total)/d(recon_loss) or None; gdec_ext: upstream gradient w.r.t. decoded or None.
     pending / zero_fed_biases / a per_sample context / want_param_grads: as in z32_stem_backward."""
+    up0, bn, up1 = L.up0, L.bn_up, L.up1
     B, nh, c1, NIN, H2, W2 = cx.dims
     ps = bool(getattr(cx, "per_sample", False))
     nb = B if ps else 0
@@ -810,3 +859,48 @@ def z32_tail_backward(up0, bn, up1, cx, gscale, gdec_ext, G, want_gr=True, pendi
     if want_param_grads:
         reduce()
     return g_r
+
+
+def z32_encoder_forward(L, x, per_sample=False):
+    """x (B,NIN,H,W) -> (z_before (B,nh,H/4,W/4), cx): the stem, then the residual stack (cx.res: its saved contexts)."""
+    h, cx = z32_stem_forward(L, x, per_sample=per_sample)
+    z, cx.res = residual_forward(L.enc_res, h, per_sample)
+    return z, cx
+
+
+def z32_encoder_backward(L, cx, g_z, G, zero_fed_biases=True, pending_extra=(), want_dx=False, want_param_grads=True):
+    """encoder_backward's contract: every parameter gradient G(p) is overwritten, pending_extra rides along in the ONE slab
+    reduction, want_dx returns the gradient w.r.t. the patches, want_param_grads=False is the data gradient alone."""
+    pending = list(pending_extra)
+    g_h, stats = residual_backward(L.enc_res, cx.res, g_z, G, cx.a2, pending=pending, zero_fed_biases=zero_fed_biases,
+                                   want_param_grads=want_param_grads, per_sample=cx.per_sample)
+    dx = z32_stem_backward(L, cx, g_h, G, stats=stats, pending=pending, zero_fed_biases=zero_fed_biases, want_dx=want_dx,
+                           want_param_grads=want_param_grads)
+    if want_param_grads:
+        ops.reduce_slabs_multi(pending)
+    return dx
+
+
+def z32_decoder_forward(L, zq, x=None, mask=None, per_sample=False):
+    """zq (B,nh,H2,W2) -> (decoded, cx): the residual stack (cx.res: its saved contexts), then the tail (+ loss slabs when x is
+    given).  per_sample: the running statistics of all five BatchNorms advance in one launch right behind the tail."""
+    defer = [] if per_sample else None
+    r, saved = residual_forward(L.dec_res, zq, per_sample, defer)
+    dec, cx = z32_tail_forward(L, r, x, mask, per_sample=per_sample, defer=defer)
+    cx.res = saved
+    if per_sample:
+        ops.bn_running_replay(defer)
+    return dec, cx
+
+
+def z32_decoder_backward(L, cx, gscale, gdec_ext, G, want_gz=True, pending=None, zero_fed_biases=True, want_param_grads=True):
+    """decoder_backward's contract (gscale / gdec_ext / pending); zero_fed_biases, a per_sample context and want_param_grads as
+    in z32_stem_backward.  Returns the gradient w.r.t. zq (the stack's backward forms it either way; want_gz=False: None)."""
+    pending, reduce = _pending(pending)
+    g_r = z32_tail_backward(L, cx, gscale, gdec_ext, G, pending=pending, zero_fed_biases=zero_fed_biases,
+                            want_param_grads=want_param_grads)
+    g_zq, _ = residual_backward(L.dec_res, cx.res, g_r, G, None, pending=pending, zero_fed_biases=zero_fed_biases,
+                                want_param_grads=want_param_grads, per_sample=cx.per_sample)
+    if want_param_grads:
+        reduce()
+    return g_zq if want_gz else None

@@ -16,32 +16,24 @@ from . import engine as E
 from .train_utils import zscore_patch
 
 
-def _patch_encoder(model):
-    """(encode, codebook) for `model`: encode(x) -> (z_before, join) runs the HIP encoder on a device batch with PER-SAMPLE
-    BatchNorm statistics; join (or None) is the pending running-statistics replay the caller joins after its next launches."""
-    from .vq_vae import VQ_VAE, VQ_VAE_z32
-    if isinstance(model, VQ_VAE):
-        layers = E.Layers(model)
-        e1 = None                           # composite first-layer weights: once per call (the weights do not change here)
+def _patch_encoder(model, L, **route):
+    """encode(x) -> (z_before, cx, join) for `model` and its engine.layers_of (None: a foreign module): the HIP encoder on a
+    device batch with PER-SAMPLE BatchNorm statistics; join (or None) is the pending running-statistics replay the caller joins
+    after its next launches.  route: encoder_forward's latents_only=True (cx holds nothing to differentiate through) or
+    replay_as_latents=True (it does)."""
+    if L is None:                           # any other module: the reference's batch-of-one loop as it is
+        return lambda x: (torch.cat([model.enc(x[j:j + 1]) for j in range(x.shape[0])], 0), None, None)
+    if L.latent_after_vq:                   # VQ_VAE_z32: no route to choose, and its residual stack flushes the replay itself
+        return lambda x: E.z32_encoder_forward(L, x, per_sample=True) + (None,)
+    e1 = None                               # composite first-layer weights: once per call (the weights do not change here)
 
-        def encode(x):
-            nonlocal e1
-            if e1 is None:
-                e1 = E.e1_operands(layers)
-            z, cx = E.encoder_forward(layers, x, per_sample=True, e1=e1, join=False, latents_only=True)
-            return z, cx.join
-        return encode, layers.codebook.weight
-    if isinstance(model, VQ_VAE_z32):
-        enc = model.enc                     # children 0/1/3/4: conv, BatchNorm, conv, BatchNorm; 5: ResidualBlock
-
-        def encode(x):
-            h, _ = E.z32_stem_forward(enc[0], enc[1], enc[3], enc[4], x, per_sample=True)
-            return E.residual_forward(enc[5]._handles(), h, True)[0], None
-        return encode, model.vq.w.weight
-
-    def encode(x):                          # any other module: the reference's batch-of-one loop as it is
-        return torch.cat([model.enc(x[j:j + 1]) for j in range(x.shape[0])], 0), None
-    return encode, model.vq.w.weight
+    def encode(x):
+        nonlocal e1
+        if e1 is None:
+            e1 = E.e1_operands(L)
+        z, cx = E.encoder_forward(L, x, per_sample=True, e1=e1, join=False, **route)
+        return z, cx, cx.join
+    return encode
 
 
 def _pipelined(inputs, in_dtypes, step, device, batch_size):
@@ -135,7 +127,7 @@ def encode_patches(model, patches, device="cuda:0", batch_size=1024, zscore_on_d
     patches = torch.as_tensor(patches)
     if patches.dim() != 4:
         raise AssertionError("dataset tensor dimension can only be 4, not {}".format(patches.dim()))
-    encode, codebook = _patch_encoder(model)
+    encode, codebook = _patch_encoder(model, E.layers_of(model), latents_only=True), model.vq.w.weight
     device = torch.device(device)
     if patches.shape[0] == 0:
         return np.zeros((0, 0), np.float32), np.zeros((0, 0), np.float32)
@@ -143,7 +135,7 @@ def encode_patches(model, patches, device="cuda:0", batch_size=1024, zscore_on_d
     def step(x):
         if zscore_on_device:
             x = ops.zscore_patch(x)
-        z_b, join = encode(x)
+        z_b, _, join = encode(x)
         z_a, _, _ = E.vq_forward(codebook, z_b, float(model.commitment_cost), want_scalars=False)
         if join is not None:
             join()                                              # the running-statistics replay ran beside the quantiser
@@ -169,7 +161,6 @@ def score_patches(model, patches, masks=None, device="cuda:0", batch_size=1024, 
     (return_code_counts) and decoded (N, C, H, W) (return_decoded).  Every value of a patch is the same to the bit whatever
     batch_size, its position and its neighbours."""
     from . import ops
-    from .vq_vae import VQ_VAE, VQ_VAE_z32
     patches = torch.as_tensor(patches)
     if patches.dim() != 4:
         raise AssertionError("dataset tensor dimension can only be 4, not {}".format(patches.dim()))
@@ -179,9 +170,7 @@ def score_patches(model, patches, masks=None, device="cuda:0", batch_size=1024, 
         if masks.dim() != 4 or masks.shape[0] != N or masks.shape[1] not in (1, C) or tuple(masks.shape[2:]) != (H, W):
             raise ValueError("score_patches: masks must be (N, 1 or C, H, W) for patches (N, C, H, W); got {} for {}".format(
                 tuple(masks.shape), tuple(patches.shape)))
-    if not isinstance(model, (VQ_VAE, VQ_VAE_z32)):
-        raise TypeError("score_patches: {} is not built on the HIP path (VQ_VAE, VQ_VAE_z16, VQ_VAE_z32)".format(
-            type(model).__name__))
+    L = E.layers_of(model, "score_patches")
     if N == 0:
         out = {k: np.zeros((0, C) if k == "recon_loss_per_channel" else ((0, 0) if k.startswith("z_") else (0,)), np.float32)
                for k in SCORE_KEYS}
@@ -190,33 +179,24 @@ def score_patches(model, patches, masks=None, device="cuda:0", batch_size=1024, 
         if return_decoded:
             out["decoded"] = np.zeros((0, C, H, W), np.float32)
         return out
-    encode, codebook = _patch_encoder(model)
+    encode, codebook = _patch_encoder(model, L, latents_only=True), L.codebook.weight
     device = torch.device(device)
     cc = float(model.commitment_cost)
-    z32 = isinstance(model, VQ_VAE_z32)
-    if z32:
-        dec = model.dec                     # children 0: ResidualBlock; 1/2/4: ConvTranspose, BatchNorm, ConvTranspose
-        w_recon = w_commit = 1.0            # vae.py:457
-    else:
-        layers = E.Layers(model)
-        w_recon, w_commit = float(model.weight_recon), float(model.weight_commitment)
+    w_recon, w_commit = L.loss_weights
 
     def step(x, m=None):
         if zscore_on_device:
             x = ops.zscore_patch(x)
         n = x.shape[0]
-        z_b, join = encode(x)
+        z_b, _, join = encode(x)
         z_a, idx, _ = E.vq_forward(codebook, z_b, cc, want_scalars=False)
         # (a model in the EMA codebook mode reports that mode's commitment, cc * mse, and the total built on it)
         vqs, counts = ops.vq_patch_scalars(z_b, idx, codebook.detach(), cc, want_counts=return_code_counts, ema=model.vq.ema)
-        if z32:
-            defer = []
-            r, _ = E.residual_forward(dec[0]._handles(), z_a, True, defer)
-            decoded, _ = E.z32_tail_forward(dec[1], dec[2], dec[4], r, None, None, model.channel_var, per_sample=True, defer=defer)
-            ops.bn_running_replay(defer)
+        if L.latent_after_vq:    # VQ_VAE_z32: a decoder with BatchNorm, per sample; the default one scores in its fused tail
+            decoded, _ = E.z32_decoder_forward(L, z_a, per_sample=True)
             sums = ops.recon_loss_per_sample(decoded, x, m, model.channel_var.detach().reshape(-1))
         else:
-            decoded, sums = E.decoder_score(layers, z_a, x, m, want_decoded=return_decoded)
+            decoded, sums = E.decoder_score(L, z_a, x, m, want_decoded=return_decoded)
         out = ops.score_finalize(sums, vqs, w_recon, w_commit, C * H * W)
         if join is not None:
             join()
@@ -255,13 +235,6 @@ def _pow2_chunks(n):
     return out
 
 
-def _latent_shape(model, H, W):
-    """(D, h, w) of z_before for patches of H x W."""
-    from .vq_vae import VQ_VAE_z32
-    f = 4 if isinstance(model, VQ_VAE_z32) else 8
-    return int(model.num_hiddens), H // f, W // f
-
-
 def patch_gradients(model, patches, masks=None, of="total_loss", device="cuda:0", batch_size=1024, zscore_on_device=False):
     """The gradient of every patch's own loss with respect to its pixels, in batched passes: patch i's array is what the
     reference's batch-of-one call leaves in x.grad for x = patches[i:i+1].requires_grad_() after
@@ -275,7 +248,7 @@ def patch_gradients(model, patches, masks=None, of="total_loss", device="cuda:0"
     Returns float32 (N, C, H, W) in input order.  No parameter and no .grad of the model is touched; every patch's gradient is
     the same to the bit whatever batch_size, its position and its neighbours."""
     from . import ops
-    from .vq_vae import VQ_VAE, VQ_VAE_z32, _GradBag
+    from .vq_vae import _GradBag
     patches = torch.as_tensor(patches)
     if patches.dim() != 4:
         raise AssertionError("dataset tensor dimension can only be 4, not {}".format(patches.dim()))
@@ -285,10 +258,8 @@ def patch_gradients(model, patches, masks=None, of="total_loss", device="cuda:0"
         if masks.dim() != 4 or masks.shape[0] != N or masks.shape[1] not in (1, C) or tuple(masks.shape[2:]) != (H, W):
             raise ValueError("patch_gradients: masks must be (N, 1 or C, H, W) for patches (N, C, H, W); got {} for {}".format(
                 tuple(masks.shape), tuple(patches.shape)))
-    if not isinstance(model, (VQ_VAE, VQ_VAE_z32)):
-        raise TypeError("patch_gradients: {} is not built on the HIP path (VQ_VAE, VQ_VAE_z16, VQ_VAE_z32)".format(
-            type(model).__name__))
-    D, h, w = _latent_shape(model, H, W)
+    L = E.layers_of(model, "patch_gradients")
+    D, h, w = int(model.num_hiddens), H // L.latent_stride, W // L.latent_stride        # of z_before
     cot = None
     if isinstance(of, str):
         if of not in GRADIENT_KEYS:
@@ -302,14 +273,9 @@ def patch_gradients(model, patches, masks=None, of="total_loss", device="cuda:0"
         return np.zeros((0, C, H, W), np.float32)
     device = torch.device(device)
     cc = float(model.commitment_cost)
-    z32 = isinstance(model, VQ_VAE_z32)
-    codebook = model.vq.w.weight
-    if z32:
-        enc, dec = model.enc, model.dec
-        w_recon = w_commit = 1.0            # vae.py:457
-    else:
-        layers = E.Layers(model)
-        w_recon, w_commit = float(model.weight_recon), float(model.weight_commitment)
+    z32 = L.latent_after_vq                 # VQ_VAE_z32
+    codebook = L.codebook.weight
+    w_recon, w_commit = L.loss_weights
     if cot is None and of == "recon_loss":
         w_recon, w_commit = 1.0, 0.0
     elif cot is None and of == "commitment_loss":
@@ -318,7 +284,7 @@ def patch_gradients(model, patches, masks=None, of="total_loss", device="cuda:0"
     shared_cot = None
     if cot is not None and cot.dim() == 1:
         shared_cot = cot.to(device=device, dtype=torch.float32).reshape(1, D, h, w)
-    e1 = None
+    encode = _patch_encoder(model, L, replay_as_latents=True)
     scalars = {}
 
     def scalar(v):
@@ -356,55 +322,36 @@ def patch_gradients(model, patches, masks=None, of="total_loss", device="cuda:0"
         g_zq, g_dir = torch.empty_like(z_a), torch.empty_like(x)
         for lo, hi in chunks:                                   # (no BatchNorm in this decoder: a run of patches is a batch)
             mm = None if m is None else m[lo:hi]
-            decoded, dcx = E.decoder_forward(layers, z_a[lo:hi], x[lo:hi], mm)
-            g_zq[lo:hi] = E.decoder_backward(layers, dcx, scalar((hi - lo) * w_recon), None, _GradBag())
+            decoded, dcx = E.decoder_forward(L, z_a[lo:hi], x[lo:hi], mm)
+            g_zq[lo:hi] = E.decoder_backward(L, dcx, scalar((hi - lo) * w_recon), None, _GradBag())
             g_dir[lo:hi] = direct(x[lo:hi], decoded, mm)
         return g_zq, g_dir
 
     def decode_z32(z_a, x, m, chunks):
-        defer = []
-        hs = dec[0]._handles()
-        r, saved = E.residual_forward(hs, z_a, True, defer)
-        decoded, tcx = E.z32_tail_forward(dec[1], dec[2], dec[4], r, None, None, model.channel_var, per_sample=True, defer=defer)
-        ops.bn_running_replay(defer)
+        decoded, dcx = E.z32_decoder_forward(L, z_a, per_sample=True)   # (BatchNorm per sample: the whole batch at once)
         g = torch.empty_like(decoded)
-        for lo, hi in chunks:
-            g[lo:hi], _ = ops.recon_loss_backward(decoded[lo:hi], x[lo:hi], None if m is None else m[lo:hi], tcx.var,
+        for lo, hi in chunks:                                   # only the loss gradient runs per power-of-two run
+            g[lo:hi], _ = ops.recon_loss_backward(decoded[lo:hi], x[lo:hi], None if m is None else m[lo:hi], dcx.var,
                                                   scalar((hi - lo) * w_recon))
-        g_r = E.z32_tail_backward(dec[1], dec[2], dec[4], tcx, None, g, None, want_param_grads=False)
-        g_zq, _ = E.residual_backward(hs, saved, g_r, None, None, want_param_grads=False, per_sample=True)
-        return g_zq, direct(x, decoded, m)
+        return E.z32_decoder_backward(L, dcx, None, g, None, want_param_grads=False), direct(x, decoded, m)
 
     def step(x, *rest):
-        nonlocal e1
         rest = list(rest)
         m = rest.pop(0) if masks is not None else None
         wt = rest.pop(0) if (cot is not None and shared_cot is None) else None
         if zscore_on_device:
             x = ops.zscore_patch(x)
         n = x.shape[0]
-        if z32:
-            hh, scx = E.z32_stem_forward(enc[0], enc[1], enc[3], enc[4], x, per_sample=True)
-            hs = enc[5]._handles()
-            z_b, saved = E.residual_forward(hs, hh, True)
-            join = None
-        else:
-            if e1 is None:
-                e1 = E.e1_operands(layers)
-            z_b, cx = E.encoder_forward(layers, x, per_sample=True, e1=e1, join=False, replay_as_latents=True)
-            join = cx.join
+        z_b, cx, join = encode(x)
         g_dir = None
         if cot is not None:
             g_z = (shared_cot.expand(n, D, h, w) if wt is None else wt.reshape(n, D, h, w)).contiguous()
         else:
-            g_z, g_dir = loss_gradient(z_b, x, m, decode_z32 if z32 else decode_default)
+            g_z, g_dir = loss_gradient(z_b, x, m, decode_z32 if z32 else decode_default)     # a decoder with / without BatchNorm
         if join is not None:
             join()                                              # the running-statistics replay ran beside the loss kernels
-        if z32:
-            g_h, st = E.residual_backward(hs, saved, g_z, None, scx.a2, want_param_grads=False, per_sample=True)
-            dx = E.z32_stem_backward(enc[0], enc[1], enc[3], enc[4], scx, g_h, None, stats=st, want_dx=True, want_param_grads=False)
-        else:
-            dx = E.encoder_backward(layers, cx, g_z, None, want_dx=True, want_param_grads=False)
+        # (the family's encoder stage, as in _patch_encoder)
+        dx = (E.z32_encoder_backward if z32 else E.encoder_backward)(L, cx, g_z, None, want_dx=True, want_param_grads=False)
         if g_dir is not None:
             dx += g_dir
         return (dx,)

@@ -56,8 +56,7 @@ class FusedTrainer:
 
     def __init__(self, model, lr=1e-3, betas=(.9, .999), eps=1e-8, process_group=None, use_graph=True,
                  global_time_matching=False, sync_batchnorm=False):
-        from .vq_vae import VQ_VAE, VQ_VAE_z32
-        if not isinstance(model, (VQ_VAE, VQ_VAE_z32)):
+        if E.layers_of(model) is None:
             raise TypeError("FusedTrainer is built for VQ_VAE / VQ_VAE_z16 / VQ_VAE_z32; train other modules with a torch optimizer")
         # (a VQ_VAE_z32 with extra_loss, vae.py:463-469: the caller's torch code runs on z_after in the middle of the step,
         # _train_body; it needs the labels: step(..., labels=...))
@@ -65,7 +64,7 @@ class FusedTrainer:
         if self._extra and not hasattr(model, "alpha"):
             raise AttributeError("FusedTrainer: extra_loss needs model.alpha (vae.py:467; pass alpha= to VQ_VAE_z32)")
         self.model = model
-        self._z32 = isinstance(model, VQ_VAE_z32)
+        self._z32 = model._layers_class.latent_after_vq      # the pairwise term's latent: z_after (VQ_VAE_z32), else z_before
         self.lr, self.betas, self.eps = lr, betas, eps
         self.group = process_group
         self.world = D.world_size(process_group)
@@ -119,7 +118,7 @@ class FusedTrainer:
     def latent_numel(self, sample_shape):
         """Elements of one sample's latent the time-matching term acts on, for samples of shape (C, H, W): z_before (VQ_VAE,
         VQ_VAE_z16: three stride-2 convolutions) or z_after (VQ_VAE_z32: two)."""
-        f = 4 if self._z32 else 8
+        f = self.model._layers_class.latent_stride
         return int(self.model.num_hiddens) * (int(sample_shape[-2]) // f) * (int(sample_shape[-1]) // f)
 
     # ------------------------------------------------------------------------------------------ the parts of a step
@@ -134,18 +133,13 @@ class FusedTrainer:
         m = self.model
         B, NIN, H, W = x.shape
         st = types.SimpleNamespace(cc=float(m.commitment_cost), n=B * NIN * H * W)
-        if self._z32:
-            enc, dec = m.enc, m.dec
-            st.er, st.dr, st.cb, st.w = enc[5]._handles(), dec[0]._handles(), m.vq.w.weight, (1.0, 1.0)
-            h, st.scx = E.z32_stem_forward(enc[0], enc[1], enc[3], enc[4], x)
-            st.z, st.esaved = E.residual_forward(st.er, h)
-            zq, st.idx, st.vqs = E.vq_forward(st.cb, st.z, st.cc, defer_scalars=True)
-            r, st.dsaved = E.residual_forward(st.dr, zq)
-            _, st.cx = E.z32_tail_forward(dec[1], dec[2], dec[4], r, x, mask, m.channel_var)
-            lat = zq
-        else:
-            st.L = L = E.Layers(m)
-            st.cb, st.w = L.codebook.weight, (float(m.weight_recon), float(m.weight_commitment))
+        st.L = L = E.layers_of(m)
+        st.cb, st.w = L.codebook.weight, L.loss_weights
+        if self._z32:           # the latent sits behind the quantiser
+            st.z, st.ecx = E.z32_encoder_forward(L, x)
+            lat, st.idx, st.vqs = E.vq_forward(st.cb, st.z, st.cc, defer_scalars=True)
+            _, st.cx = E.z32_decoder_forward(L, lat, x, mask)
+        else:                   # ... before it; the default-only routes: the last residual join in the quantiser, the deferred tail
             z, st.ecx = E.encoder_forward(L, x, defer_last_join=st.cb.shape[0] if JOIN_IN_VQ else 0)
             if z is None:       # the last residual join runs in the quantiser's load path (dm_vq_forward_join), which writes z
                 z, zq, st.idx, st.vqs = E.vq_forward_joined(st.cb, st.ecx.pending_join, st.cc)
@@ -159,13 +153,9 @@ class FusedTrainer:
     def _backward_to_latent(self, st):
         """The gradient at st.lat (shaped like the latent): the decoder's backward and, for VQ_VAE / VQ_VAE_z16, the
         quantiser's straight-through backward.  The slabs of every weight / bias / codebook gradient collect in st.pending."""
-        m, st.pending = self.model, []
-        if self._z32:
-            dec = m.dec
-            g_r = E.z32_tail_backward(dec[1], dec[2], dec[4], st.cx, self.w_recon, None, self.G, pending=st.pending,
-                                      zero_fed_biases=False)
-            g_zq, _ = E.residual_backward(st.dr, st.dsaved, g_r, self.G, None, pending=st.pending, zero_fed_biases=False)
-            return g_zq
+        st.pending = []
+        if self._z32:           # the latent sits behind the quantiser: its backward runs in _backward_from_latent
+            return E.z32_decoder_backward(st.L, st.cx, self.w_recon, None, self.G, pending=st.pending, zero_fed_biases=False)
         g_zq = E.decoder_backward(st.L, st.cx, self.w_recon, None, self.G, pending=st.pending)
         # codebook gradient as slabs, added in the encoder's single slab reduction: nothing to zero, no global atomics
         # (K <= 64: an ordered one-hot product on the matrix cores, bit-reproducible; larger K: LDS adds in arrival order)
@@ -186,16 +176,12 @@ class FusedTrainer:
         """From the gradient at the latent: the rest of the backward (VQ_VAE_z32: the quantiser's straight-through backward,
         then the encoder) and ONE slab reduction for every weight / bias / codebook gradient of the step.  The flat gradient
         buffer starts at zero and nothing ever writes the BatchNorm-fed conv biases' slots (zero_fed_biases=False)."""
-        if not self._z32:
-            E.encoder_backward(st.L, st.ecx, g, self.G, zero_fed_biases=False, pending_extra=st.pending)
-            return
-        enc = self.model.enc
-        dz, cb_seg = self._vq_backward(st, g)
-        st.pending.append(cb_seg)
-        g_h, stats = E.residual_backward(st.er, st.esaved, dz, self.G, st.scx.a2, pending=st.pending, zero_fed_biases=False)
-        E.z32_stem_backward(enc[0], enc[1], enc[3], enc[4], st.scx, g_h, self.G, stats=stats, pending=st.pending,
-                            zero_fed_biases=False)
-        ops.reduce_slabs_multi(st.pending)
+        backward = E.encoder_backward
+        if self._z32:           # the latent sits behind the quantiser: its backward first, its segment behind the decoder's
+            g, cb_seg = self._vq_backward(st, g)
+            st.pending.append(cb_seg)
+            backward = E.z32_encoder_backward
+        backward(st.L, st.ecx, g, self.G, zero_fed_biases=False, pending_extra=st.pending)
 
     def _pairwise(self, st, tm, g=None, zg=None):
         """The pass's scalars (recon, commitment, total, perplexity[, time matching]) with the pairwise term on st.lat (tm: the

@@ -55,19 +55,27 @@ class _GradBag:
 
 
 # =============================================================================== autograd
-class _EncoderFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, layers, per_sample, *params):
-        z, cx = E.encoder_forward(layers, x, per_sample=per_sample)
-        ctx.layers, ctx.cx, ctx.params = layers, cx, params
-        return z
+def _conv_stage_fn(forward, backward):
+    """The autograd Function of a conv stage with parameters, (x, layers, per_sample, *params) -> z, on an engine pair
+    forward(layers, x, per_sample=) -> (z, cx) and backward(layers, cx, g_z, G, want_dx=) -> dx."""
+    class Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, layers, per_sample, *params):
+            z, cx = forward(layers, x, per_sample=per_sample)
+            ctx.layers, ctx.cx, ctx.params = layers, cx, params
+            return z
 
-    @staticmethod
-    def backward(ctx, g_z):
-        G = _GradBag()
-        dx = E.encoder_backward(ctx.layers, ctx.cx, g_z, G, want_dx=ctx.needs_input_grad[0])
-        ctx.cx = None
-        return (dx, None, None) + G.grads_for(ctx.params, ctx.needs_input_grad[3:])
+        @staticmethod
+        def backward(ctx, g_z):
+            G = _GradBag()
+            dx = backward(ctx.layers, ctx.cx, g_z, G, want_dx=ctx.needs_input_grad[0])
+            ctx.cx = None
+            return (dx, None, None) + G.grads_for(ctx.params, ctx.needs_input_grad[3:])
+    return Fn
+
+
+_EncoderFn = _conv_stage_fn(E.encoder_forward, E.encoder_backward)
+_Z32StemFn = _conv_stage_fn(E.z32_stem_forward, E.z32_stem_backward)     # enc[0:5] of VQ_VAE_z32: Conv(4,2,1) BN ReLU Conv BN
 
 
 class _ResidualFn(torch.autograd.Function):
@@ -126,33 +134,40 @@ def _recon_input_grad(cx, channel_var, gscale):
     return g * gscale.reshape(())
 
 
-class _DecoderFn(torch.autograd.Function):
-    """decoded (and, when x is given, the masked reconstruction loss of vq_vae.py:320-322)."""
+def _decoder_stage_fn(forward, backward):
+    """The autograd Function of a decoder stage, (zq, x, mask, layers, *params) -> (decoded, and when x is given the masked
+    reconstruction loss of vq_vae.py:320-322, else None), on an engine pair forward(layers, zq, x, mask) -> (decoded, cx) and
+    backward(layers, cx, gscale, g_dec, G, want the gradient w.r.t. zq) -> g_zq."""
+    class Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, zq, x, mask, layers, *params):
+            dec, cx = forward(layers, zq, x, mask)
+            ctx.layers, ctx.cx, ctx.params = layers, cx, params
+            ctx.set_materialize_grads(False)
+            if x is None:
+                return dec, None
+            B, NIN, H, W = x.shape
+            zeros = torch.zeros(2, device=x.device)
+            recon = ops.loss_finalize(cx.loss_slabs, B * NIN * H * W, zeros, 1.0, 0.0)[0]
+            return dec, recon
 
-    @staticmethod
-    def forward(ctx, zq, x, mask, layers, *params):
-        dec, cx = E.decoder_forward(layers, zq, x, mask)
-        ctx.layers, ctx.cx, ctx.params = layers, cx, params
-        ctx.set_materialize_grads(False)
-        if x is None:
-            return dec, None
-        B, NIN, H, W = x.shape
-        zeros = torch.zeros(2, device=x.device)
-        recon = ops.loss_finalize(cx.loss_slabs, B * NIN * H * W, zeros, 1.0, 0.0)[0]
-        return dec, recon
+        @staticmethod
+        def backward(ctx, g_dec, g_recon):
+            G = _GradBag()
+            gscale = g_recon.reshape(1).contiguous() if g_recon is not None else None
+            if g_dec is not None:
+                g_dec = g_dec.contiguous()
+            if gscale is None and g_dec is None:
+                return (None,) * (4 + len(ctx.params))
+            g_x = _recon_input_grad(ctx.cx, ctx.layers.channel_var, gscale) if ctx.needs_input_grad[1] else None
+            g_zq = backward(ctx.layers, ctx.cx, gscale, g_dec, G, ctx.needs_input_grad[0])
+            ctx.cx = None
+            return (g_zq, g_x, None, None) + G.grads_for(ctx.params, ctx.needs_input_grad[4:])
+    return Fn
 
-    @staticmethod
-    def backward(ctx, g_dec, g_recon):
-        G = _GradBag()
-        gscale = g_recon.reshape(1).contiguous() if g_recon is not None else None
-        if g_dec is not None:
-            g_dec = g_dec.contiguous()
-        if gscale is None and g_dec is None:
-            return (None,) * (4 + len(ctx.params))
-        g_x = _recon_input_grad(ctx.cx, ctx.layers.channel_var, gscale) if ctx.needs_input_grad[1] else None
-        g_zq = E.decoder_backward(ctx.layers, ctx.cx, gscale, g_dec, G, want_gz=ctx.needs_input_grad[0])
-        ctx.cx = None
-        return (g_zq, g_x, None, None) + G.grads_for(ctx.params, ctx.needs_input_grad[4:])
+
+_DecoderFn = _decoder_stage_fn(E.decoder_forward, E.decoder_backward)
+_Z32TailFn = _decoder_stage_fn(E.z32_tail_forward, E.z32_tail_backward)     # dec[1:5] of VQ_VAE_z32: ConvT BN ReLU ConvT
 
 
 # ================================================================================ modules
@@ -381,6 +396,7 @@ class VQ_VAE(nn.Module):
     """Vector-Quantized VAE with a 16 x 16 x num_hiddens latent (reference vq_vae.py:228-342)."""
 
     _z16_loss = False
+    _layers_class = E.Layers         # (engine.layers_of)
 
     def __init__(self,
                  num_inputs=2,
@@ -487,75 +503,28 @@ class VQ_VAE_z16(VQ_VAE):
 
 
 # ================================================================================ VQ_VAE_z32
-class _Z32StemFn(torch.autograd.Function):
-    """enc[0:5] of VQ_VAE_z32: Conv(4,2,1) BN ReLU Conv(4,2,1) BN."""
-
-    @staticmethod
-    def forward(ctx, x, mods, *params):
-        h, cx = E.z32_stem_forward(*mods, x)
-        ctx.mods, ctx.cx, ctx.params = mods, cx, params
-        return h
-
-    @staticmethod
-    def backward(ctx, g_h):
-        G = _GradBag()
-        dx = E.z32_stem_backward(*ctx.mods, ctx.cx, g_h, G, want_dx=ctx.needs_input_grad[0])
-        ctx.cx = None
-        return (dx, None) + G.grads_for(ctx.params, ctx.needs_input_grad[2:])
-
-
-class _Z32TailFn(torch.autograd.Function):
-    """dec[1:5] of VQ_VAE_z32: ConvT BN ReLU ConvT (+ the masked reconstruction loss when x is given)."""
-
-    @staticmethod
-    def forward(ctx, r, x, mask, channel_var, mods, *params):
-        dec, cx = E.z32_tail_forward(*mods, r, x, mask, channel_var)
-        ctx.mods, ctx.cx, ctx.params, ctx.cvar = mods, cx, params, channel_var
-        ctx.set_materialize_grads(False)
-        if x is None:
-            return dec, None
-        B, NIN, H, W = x.shape
-        recon = ops.loss_finalize(cx.loss_slabs, B * NIN * H * W, torch.zeros(2, device=x.device), 1.0, 0.0)[0]
-        return dec, recon
-
-    @staticmethod
-    def backward(ctx, g_dec, g_recon):
-        gscale = g_recon.reshape(1).contiguous() if g_recon is not None else None
-        if g_dec is not None:
-            g_dec = g_dec.contiguous()
-        if gscale is None and g_dec is None:
-            return (None,) * (5 + len(ctx.params))
-        G = _GradBag()
-        g_x = _recon_input_grad(ctx.cx, ctx.cvar, gscale) if ctx.needs_input_grad[1] else None
-        g_r = E.z32_tail_backward(*ctx.mods, ctx.cx, gscale, g_dec, G, want_gr=ctx.needs_input_grad[0])
-        ctx.cx = None
-        return (g_r, g_x, None, None, None) + G.grads_for(ctx.params, ctx.needs_input_grad[5:])
-
-
 class _Z32Encoder(nn.Sequential):
-    """`model.enc` of VQ_VAE_z32 (same child indices as the reference's nn.Sequential)."""
+    """`model.enc` of VQ_VAE_z32 (same child indices as the reference's nn.Sequential): the stem as one autograd node, then
+    the ResidualBlock module."""
 
     def forward(self, x):
         _require_gpu(x, "VQ_VAE_z32.enc")
-        mods = (self[0], self[1], self[3], self[4])
-        params = [p for m in mods for p in (m.weight, m.bias)]
-        h = _Z32StemFn.apply(_prep(x), mods, *params)
-        return self[5](h)
+        L = E.Z32Layers(enc=self)
+        return L.enc_block(_Z32StemFn.apply(_prep(x), L, False, *L.stem_params()))
+
+
+def _z32_decode(L, z, x, mask):
+    """The ResidualBlock module, then the tail as one autograd node -> (decoded, recon_loss or None)."""
+    return _Z32TailFn.apply(L.dec_block(z), x, mask, L, *L.tail_params())
 
 
 class _Z32Decoder(nn.Sequential):
     """`model.dec` of VQ_VAE_z32."""
 
-    def _tail(self, r, x, mask, channel_var):
-        mods = (self[1], self[2], self[4])
-        params = [p for m in mods for p in (m.weight, m.bias)]
-        return _Z32TailFn.apply(r, x, mask, channel_var, mods, *params)
-
     def forward(self, z):
         _require_gpu(z, "VQ_VAE_z32.dec")
         # (no loss here, so the channel variances are not needed: `model.dec` holds no reference to its parent)
-        dec, _ = self._tail(self[0](_prep(z)), None, None, None)
-        return dec
+        return _z32_decode(E.Z32Layers(dec=self), _prep(z), None, None)[0]
 
 
 class VQ_VAE_z32(nn.Module):
@@ -564,6 +533,8 @@ class VQ_VAE_z32(nn.Module):
     weighted-hinge time-matching loss on z_after.  The default widths (num_hiddens 16, num_residual_hiddens 32) run on the
     register-resident kernels, any other width (config_example.yml: 64 / 64 / 512 codes) on the implicit-GEMM kernels of
     csrc/conv_wide.hip."""
+
+    _layers_class = E.Z32Layers      # (engine.layers_of)
 
     def __init__(self, num_inputs=2, num_hiddens=16, num_residual_hiddens=32, num_residual_layers=2, num_embeddings=64,
                  commitment_cost=0.25, channel_var=np.ones(2), weight_matching=0.005, w_a=1.1, w_t=0.1, w_n=-0.5,
@@ -616,7 +587,7 @@ class VQ_VAE_z32(nn.Module):
         z_before = self.enc(x)
         z_after, c_loss, perplexity = self.vq(z_before)
         mask = _prep(batch_mask) if batch_mask is not None else None
-        decoded, recon_loss = self.dec._tail(self.dec[0](z_after), x, mask, self.channel_var)
+        decoded, recon_loss = _z32_decode(E.Z32Layers(self), z_after, x, mask)
         total_loss = recon_loss + c_loss
         if time_matching_mat is not None:
             tml = time_matching_loss(z_after, time_matching_mat, True, self.w_a, self.w_t, self.w_n, self.margin)   # vae.py:441-455

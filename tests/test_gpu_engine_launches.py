@@ -157,27 +157,27 @@ def _z32(form, want_dx=False, want_gr=True, **kw):
     from dynamorph_amd import engine as E, ops
     torch.manual_seed(6)
     m = dynamorph_amd.VQ_VAE_z32(**kw).to(DEV)
-    enc, dec = m.enc, m.dec
+    L = E.Z32Layers(m)
     x = torch.randn(2, 2, 128, 128, device=DEV)
-    er, dr = enc[5]._handles(), dec[0]._handles()
+    er, dr = L.enc_res, L.dec_res
     G = Grads()
     gscale = torch.ones(1, device=DEV)
     shared = form == "shared"
     with Recorder() as calls:
-        h, scx = E.z32_stem_forward(enc[0], enc[1], enc[3], enc[4], x)
+        h, scx = E.z32_stem_forward(L, x)
         z, esaved = E.residual_forward(er, h)
         r, dsaved = E.residual_forward(dr, z)
-        _, cx = E.z32_tail_forward(dec[1], dec[2], dec[4], r, x, None, m.channel_var)
+        _, cx = E.z32_tail_forward(L, r, x, None)
         pending = [] if shared else None
         gext = None if shared else torch.randn_like(x)
-        g_r = E.z32_tail_backward(dec[1], dec[2], dec[4], cx, gscale if want_gr else None, gext, G, want_gr=want_gr,
+        g_r = E.z32_tail_backward(L, cx, gscale if want_gr else None, gext, G, want_gr=want_gr,
                                   pending=pending, zero_fed_biases=not shared)
         if want_gr:
             rp = pending if shared else []
             g_z, _ = E.residual_backward(dr, dsaved, g_r, G, None, pending=rp, zero_fed_biases=not shared)
             g_h, stats = E.residual_backward(er, esaved, g_z, G, scx.a2 if shared else None, pending=rp,
                                              zero_fed_biases=not shared)
-            E.z32_stem_backward(enc[0], enc[1], enc[3], enc[4], scx, g_h, G, stats=stats, pending=pending,
+            E.z32_stem_backward(L, scx, g_h, G, stats=stats, pending=pending,
                                 zero_fed_biases=not shared, want_dx=want_dx)
             ops.reduce_slabs_multi(rp)
     return calls

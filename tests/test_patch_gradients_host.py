@@ -131,7 +131,8 @@ def test_signatures_and_exports():
     assert [sig.parameters[k].default for k in list(sig.parameters)[2:]] == [None, "total_loss", "cuda:0", 1024, False]
     assert list(inspect.signature(patch_vae.patch_gradients_sharded).parameters)[-2:] == ["group", "dst"]
     from dynamorph_amd import engine as E
-    for fn in (E.encoder_backward, E.residual_backward, E.z32_stem_backward, E.z32_tail_backward):
+    for fn in (E.encoder_backward, E.residual_backward, E.z32_stem_backward, E.z32_tail_backward, E.z32_encoder_backward,
+               E.z32_decoder_backward):
         assert inspect.signature(fn).parameters["want_param_grads"].default is True
 
 
