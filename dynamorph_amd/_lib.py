@@ -191,6 +191,9 @@ SIGNATURES = {
     "dm_umap_smooth": (C.c_int, [vp, i64, C.c_int, vp, vp, vp, vp, vp]),
     "dm_umap_membership": (C.c_int, [vp, vp, i64, C.c_int, vp, vp, vp, vp]),
     "dm_umap_epoch": (C.c_int, [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, f32, f32, f32, C.c_uint64, C.c_int, vp]),
+    "dm_umap_transform_prepare": (C.c_int, [vp, vp, i64, C.c_int, i64, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "dm_umap_transform_layout": (C.c_int, [vp, vp, vp, vp, vp, i64, C.c_int, i64, vp, vp, C.c_int, C.c_int, C.c_int, i64, f32, f32,
+                                           f32, C.c_uint64, C.c_int, vp]),
 }
 
 _lib = None

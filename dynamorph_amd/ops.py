@@ -1485,3 +1485,47 @@ def umap_epoch(indptr, cols, eps, eps_neg, nxt, nxt_neg, y_in, y_out, epoch, n_e
                                    float(b), float(gamma), int(seed) & 0xFFFFFFFFFFFFFFFF, int(group), _stream()),
             "dm_umap_epoch")
     return y_out
+
+
+# ----------------------------------------------------------------------------- UMAP transform of new points
+def _umap_query_graph(indices, dists, y_train):
+    if dists.dim() != 2 or tuple(indices.shape) != tuple(dists.shape):
+        raise ValueError("dm_umap_transform: knn_dists must be (R, k) and knn_indices of the same shape")
+    if y_train.dim() != 2 or y_train.shape[1] != 2:
+        raise ValueError(f"dm_umap_transform: y_train must be (M, 2), got {tuple(y_train.shape)}")
+    R, k = dists.shape
+    M = y_train.shape[0]
+    if R < 1 or k < 2 or k > UMAP_MAX_K or k > M:
+        raise ValueError(f"dm_umap_transform: R = {R}, k = {k} outside 2 .. min({UMAP_MAX_K}, M = {M})")
+    return R, k, M
+
+
+@_op
+def umap_transform_prepare(indices, dists, y_train, n_epochs, negative_sample_rate=5):
+    """(sigma (R,), membership (R, k), eps, eps_neg, next, next_neg (R, k), y0 (R, 2)), all fp32, of the (R, k) query graph
+    (indices int32 into the M training rows, fp32 distances, rows sorted) against the fitted embedding y_train (M, 2)
+    (dm_umap_transform_prepare).  The indices must lie in [0, M): the caller has checked them."""
+    R, k, M = _umap_query_graph(indices, dists, y_train)
+    sigma, y0 = _new((R,), dists), _new((R, 2), dists)
+    memb, eps, eps_neg, nxt, nxt_neg = (_new((R, k), dists) for _ in range(5))
+    L.check(L.load().dm_umap_transform_prepare(_ptr(indices, torch.int32), _ptr(dists), R, k, M, _ptr(y_train), int(n_epochs),
+                                               int(negative_sample_rate), _ptr(sigma), _ptr(memb), _ptr(eps), _ptr(eps_neg),
+                                               _ptr(nxt), _ptr(nxt_neg), _ptr(y0), _stream()), "dm_umap_transform_prepare")
+    return sigma, memb, eps, eps_neg, nxt, nxt_neg, y0
+
+
+@_op
+def umap_transform_layout(indices, eps, eps_neg, nxt, nxt_neg, y_train, y, epoch_begin, epoch_end, n_epochs, row_offset, seed,
+                          a, b, gamma, group=0):
+    """Epochs [epoch_begin, epoch_end) of the transform's layout in one launch (dm_umap_transform_layout): y (R, 2) and the
+    schedule state nxt / nxt_neg (R, k) advanced in place.  The indices must lie in [0, M): the caller has checked them."""
+    R, k, M = _umap_query_graph(indices, eps, y_train)
+    if tuple(y.shape) != (R, 2):
+        raise ValueError(f"dm_umap_transform_layout: y must be ({R}, 2)")
+    if not (tuple(eps_neg.shape) == tuple(nxt.shape) == tuple(nxt_neg.shape) == (R, k)):
+        raise ValueError(f"dm_umap_transform_layout: eps / eps_neg / next / next_neg must be ({R}, {k})")
+    L.check(L.load().dm_umap_transform_layout(_ptr(indices, torch.int32), _ptr(eps), _ptr(eps_neg), _ptr(nxt), _ptr(nxt_neg), R, k,
+                                              M, _ptr(y_train), _ptr(y), int(epoch_begin), int(epoch_end), int(n_epochs),
+                                              int(row_offset), float(a), float(b), float(gamma),
+                                              int(seed) & 0xFFFFFFFFFFFFFFFF, int(group), _stream()), "dm_umap_transform_layout")
+    return y

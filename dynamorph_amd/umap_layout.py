@@ -5,7 +5,11 @@ a deterministic layout, as DESIGN.md section 3.5c defines them (McInnes, Healy, 
 dm_umap_smooth, dm_umap_membership and dm_umap_epoch (csrc/umap.hip) are the device kernels; the symmetrisation, the pruning
 and the schedule arrays are sorting and merging of integer keys in torch and run on CPU tensors as well.  The layout keeps
 two position buffers and gives every vertex its row, its position and its entries' schedule state, so a fit is a function of
-its inputs and the seed alone.  Two output dimensions, the Euclidean k-NN graph, a and b given (no fit from min_dist)."""
+its inputs and the seed alone.  Two output dimensions, the Euclidean k-NN graph, a and b given (no fit from min_dist).
+
+A fitted model that kept its training matrix places new rows into the embedding (transform): the
+query graph (knn.knn_query), dm_umap_transform_prepare and ONE launch of dm_umap_transform_layout for all epochs -- the
+training positions are fixed, so a new row reads nothing that another new row writes."""
 import numpy as np
 import torch
 
@@ -67,6 +71,30 @@ def check_graph(knn_indices, knn_dists):
         raise ValueError(f"knn_indices lie outside 0 .. {N - 1}")
     if not np.array_equal(idx[:, 0], np.arange(N)):
         raise ValueError("column 0 of knn_indices must be the row itself (knn_graph(include_self=True))")
+    return np.ascontiguousarray(idx, dtype=np.int64), np.ascontiguousarray(dist, dtype=np.float32)
+
+
+def check_query_graph(knn_indices, knn_dists, M):
+    """The host copies (indices (R, k) int64, distances (R, k) float32) of a query graph against M training rows that the
+    transform kernels accept, or ValueError: R >= 1, 2 <= k <= 256, k <= M, every index in [0, M).  There is no self column.
+    No device call is made on host input."""
+    idx = knn_indices.cpu().numpy() if torch.is_tensor(knn_indices) else np.asarray(knn_indices)
+    dist = knn_dists.cpu().numpy() if torch.is_tensor(knn_dists) else np.asarray(knn_dists)
+    if idx.ndim != 2 or idx.shape != dist.shape:
+        raise ValueError(f"knn_indices {idx.shape} and knn_dists {dist.shape} must be two (R, k) arrays of one shape")
+    if not np.issubdtype(idx.dtype, np.integer):
+        raise ValueError(f"knn_indices must be integers, got {idx.dtype}")
+    R, k = idx.shape
+    if R < 1:
+        raise ValueError("the query graph has no rows")
+    if k < 2 or k > MAX_K:
+        raise ValueError(f"k = {k} is outside 2 .. {MAX_K}")
+    if k > M:
+        raise ValueError(f"k = {k} exceeds the {M} training rows")
+    if M > 0x7fffffff or R > 0x7fffffff:
+        raise ValueError(f"M = {M} or R = {R} does not fit 31 bits")
+    if idx.min() < 0 or idx.max() >= M:
+        raise ValueError(f"knn_indices lie outside 0 .. {M - 1}")
     return np.ascontiguousarray(idx, dtype=np.int64), np.ascontiguousarray(dist, dtype=np.float32)
 
 
@@ -170,9 +198,14 @@ def fuzzy_graph(knn_indices, knn_dists, device=None):
     return indptr, cols, w, rho, sigma
 
 
+DEFAULT_TRANSFORM_CHUNK_ROWS = 16384
+
+
 class UMAPEmbedding:
     """fit_transform(X) / fit_graph(knn_indices, knn_dists, init) leave embedding_ (N, 2) float32 numpy; graph() is the fuzzy
-    set as a scipy CSR matrix.  a, b: the curve parameters as given (the reference's 1.58, 0.9)."""
+    set as a scipy CSR matrix.  a, b: the curve parameters as given (the reference's 1.58, 0.9).  A model fitted by
+    fit_transform, or by fit_graph(..., X=X), also keeps its training matrix and places new rows into the embedding with
+    transform(Q); it pickles with its state on the host."""
 
     def __init__(self, n_neighbors=15, a=1.58, b=0.9, n_epochs=None, negative_sample_rate=5, gamma=1.0, init="pca", seed=0,
                  n_components=2, device=None):
@@ -195,6 +228,8 @@ class UMAPEmbedding:
         self.negative_sample_rate, self.gamma, self.init, self.seed = int(negative_sample_rate), float(gamma), init, int(seed)
         self.device = device
         self.group = 0              # lanes per vertex of dm_umap_epoch (0: chosen by the library; no effect on the result)
+        self.transform_group = 0    # the same for dm_umap_transform_layout
+        self._X = None              # the training matrix (M, F) fp32: the resident device tensor of the fit, or host numpy
 
     def fit_transform(self, X):
         """The exact k-NN graph of X at n_neighbors (knn.knn_graph), then fit_graph; returns embedding_."""
@@ -208,13 +243,18 @@ class UMAPEmbedding:
         idx, dist = _knn.knn_graph(x, self.n_neighbors, include_self=True)
         if isinstance(init, str):
             init = pca_coordinates(x)
-        return self.fit_graph(idx, dist, init).embedding_
+        self.fit_graph(idx, dist, init)
+        self._X = x
+        return self.embedding_
 
-    def fit_graph(self, knn_indices, knn_dists, init=None):
+    def fit_graph(self, knn_indices, knn_dists, init=None, X=None):
         """Fit from a k-NN graph (column 0 the row itself); init: an (N, 2) array of coordinates before rescaling (the PCA
-        scores of pca_coordinates(X) for init="pca").  Returns self."""
+        scores of pca_coordinates(X) for init="pca").  X: the (N, F) matrix the graph was computed from, kept (a device tensor
+        as it is) so that transform can place new rows; without it the model has an embedding only.  Returns self."""
         idx, dist = check_graph(knn_indices, knn_dists)
         N = idx.shape[0]
+        if X is not None and (len(X.shape) != 2 or X.shape[0] != N):
+            raise ValueError(f"X has shape {tuple(X.shape)}, the graph has {N} rows")
         init = self.init if init is None else init
         if isinstance(init, str):
             _check_init(init, N)
@@ -238,7 +278,103 @@ class UMAPEmbedding:
                 y, other = other, y
             self.embedding_ = y.cpu().numpy()
         self.n_epochs_ = n_epochs
+        self._X = X
         return self
+
+    # ------------------------------------------------------------------------------------- transform (section 3.5d)
+    def _fitted(self, need_data):
+        if getattr(self, "embedding_", None) is None or getattr(self, "n_epochs_", None) is None:
+            raise ValueError("the model has no embedding: fit it first")
+        if need_data and self._X is None:
+            raise ValueError("the model has no training data: fit it with fit_transform or fit_graph(..., X=X)")
+        return self.embedding_.shape[0]
+
+    def _transform_args(self, n_epochs, seed, row_offset):
+        n_epochs = max(1, self.n_epochs_ // 3) if n_epochs is None else int(n_epochs)
+        if n_epochs < 1:
+            raise ValueError(f"n_epochs = {n_epochs} must be at least 1")
+        if int(row_offset) < 0:
+            raise ValueError(f"row_offset = {row_offset} is negative")
+        return n_epochs, self.seed if seed is None else int(seed), int(row_offset)
+
+    def _place(self, idx, dist, y_train, n_epochs, seed, row_offset):
+        """prepare and one layout launch for a checked host graph: device (y (R, 2), sigma (R,), y0 (R, 2))."""
+        dev = y_train.device
+        i32 = torch.from_numpy(idx.astype(np.int32)).to(dev)
+        d = torch.from_numpy(dist).to(dev)
+        sigma, _, eps, eps_neg, nxt, nxt_neg, y0 = ops.umap_transform_prepare(i32, d, y_train, n_epochs, self.negative_sample_rate)
+        y = y0.clone()
+        ops.umap_transform_layout(i32, eps, eps_neg, nxt, nxt_neg, y_train, y, 0, n_epochs, n_epochs, row_offset, seed, self.a,
+                                  self.b, self.gamma, self.transform_group)
+        return y, sigma, y0
+
+    def transform_graph(self, knn_indices, knn_dists, n_epochs=None, seed=None, row_offset=0):
+        """(R, 2) float32 numpy: the rows of a query graph -- the k = n_neighbors nearest training rows of every query and
+        their distances, sorted, as knn.knn_query returns them -- placed into the fitted embedding.  n_epochs: default
+        max(1, n_epochs_ // 3); seed: default the model's; row_offset: the global number of row 0 (a row's result depends
+        on its number, not on the other rows of the call).  Leaves sigma_t_ (R,) and init_t_ (R, 2)."""
+        M = self._fitted(need_data=False)
+        idx, dist = check_query_graph(knn_indices, knn_dists, M)
+        n_epochs, seed, row_offset = self._transform_args(n_epochs, seed, row_offset)
+        dev = _device(self.device)
+        with torch.no_grad(), torch.cuda.device(dev):
+            y, sigma, y0 = self._place(idx, dist, torch.from_numpy(self.embedding_).to(dev), n_epochs, seed, row_offset)
+            self.sigma_t_, self.init_t_ = sigma.cpu().numpy(), y0.cpu().numpy()
+            return y.cpu().numpy()
+
+    def transform(self, Q, n_epochs=None, seed=None, row_offset=0, chunk_rows=DEFAULT_TRANSFORM_CHUNK_ROWS):
+        """(R, 2) float32 numpy: the rows of Q (R, F) placed into the fitted embedding -- the exact query graph against the
+        training matrix (knn.knn_query), then transform_graph's steps, chunk_rows rows at a time, so that Q may be larger
+        than the device holds.  The result of a row depends on the row, its global number row_offset + i, the seed and the
+        model alone: not on chunk_rows and not on the other rows."""
+        M = self._fitted(need_data=True)
+        F = self._X.shape[1]
+        shape = tuple(Q.shape) if hasattr(Q, "shape") else np.shape(Q)
+        if len(shape) != 2 or shape[1] != F:
+            raise ValueError(f"Q has shape {shape}, expected (n, {F})")
+        if shape[0] < 1:
+            raise ValueError("Q has no rows")
+        if self.n_neighbors > M:
+            raise ValueError(f"n_neighbors = {self.n_neighbors} exceeds the {M} training rows")
+        if self._X.shape[0] != M:
+            raise ValueError(f"the training matrix has {self._X.shape[0]} rows, the embedding {M}")
+        n_epochs, seed, row_offset = self._transform_args(n_epochs, seed, row_offset)
+        cr = max(1, int(chunk_rows))
+        if not torch.is_tensor(Q):
+            Q = np.asarray(Q)
+        x = self._X = _knn._resident(self._X, self.device)
+        with torch.no_grad(), torch.cuda.device(x.device):
+            shift = _knn.column_shift(x)
+            y_train = torch.from_numpy(self.embedding_).to(x.device)
+            ys, sigmas, inits = [], [], []
+            for lo in range(0, shape[0], cr):
+                idx, dist = _knn.knn_query(x, Q[lo:lo + cr], self.n_neighbors, shift=shift)
+                idx, dist = check_query_graph(idx, dist, M)
+                y, sigma, y0 = self._place(idx, dist, y_train, n_epochs, seed, row_offset + lo)
+                ys.append(y.cpu().numpy())
+                sigmas.append(sigma.cpu().numpy())
+                inits.append(y0.cpu().numpy())
+        self.sigma_t_, self.init_t_ = np.concatenate(sigmas), np.concatenate(inits)
+        return np.concatenate(ys)
+
+    # ------------------------------------------------------------------------------------------------------ pickling
+    def __getstate__(self):
+        """Host state only: the training matrix as fp32 numpy, the embedding, the parameters and the fitted graph."""
+        state = dict(self.__dict__)
+        X = state.get("_X")
+        if torch.is_tensor(X):
+            state["_X"] = X.detach().cpu().numpy().astype(np.float32, copy=False)
+        elif X is not None:
+            state["_X"] = np.ascontiguousarray(X, dtype=np.float32)
+        if torch.is_tensor(state.get("init")):
+            state["init"] = state["init"].detach().cpu().numpy()
+        state["device"] = None if state.get("device") is None else str(state["device"])
+        return state
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        self.__dict__.setdefault("_X", None)
+        self.__dict__.setdefault("transform_group", 0)
 
     def graph(self):
         """The fuzzy simplicial set W (N, N) as scipy.sparse.csr_matrix (float32)."""

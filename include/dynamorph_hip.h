@@ -837,6 +837,28 @@ int dm_umap_epoch(const int64_t *indptr, const int32_t *cols, int64_t N, int64_t
                   float *next, float *next_neg, const float *y_in, float *y_out, int epoch, int n_epochs, float a, float b,
                   float gamma, uint64_t seed, int group, void *stream);
 
+/* ===== UMAP transform of new points into a fitted embedding ==== */
+/* indices / dists: the R x k query graph dm_knn returns for queries Q against the M training rows (no self column, rows
+ * sorted), R >= 1, 2 <= k <= DM_UMAP_MAX_K, k <= M < 2^31, every index in [0, M): the caller checks.  y_train: the fitted
+ * embedding, M x 2 fp32.  Per row, with rho = 0 and over all k columns: sigma (the search of dm_umap_smooth, floored at
+ * 1e-3 * the row's own mean, fp32); membership a = 1 where d <= 0 or sigma == 0, else expf(-(d / sigma)); m = max_j a;
+ * entries with a == 0 or a < m / n_epochs are pruned: +inf in eps, eps_neg, next and next_neg; the others eps = m / a,
+ * eps_neg = eps / negative_sample_rate (1 .. 1000), next = eps, next_neg = eps_neg (fp32 IEEE division); y0 (R x 2) =
+ * sum_j a_j y_train[idx_j] / sum_j a_j over all k entries in float64, rounded once (y_train[idx_0] if every a is 0). */
+int dm_umap_transform_prepare(const int32_t *indices, const float *dists, int64_t R, int k, int64_t M, const float *y_train,
+                              int n_epochs, int negative_sample_rate, float *sigma, float *membership, float *eps,
+                              float *eps_neg, float *next, float *next_neg, float *y0, void *stream);
+/* Epochs [epoch_begin, epoch_end) of n_epochs for every query, in ONE launch: y (R x 2) and the schedule state next /
+ * next_neg (R x k) are read at the start, kept on chip and written back once at the end, so [0, s) followed by [s, n) is
+ * [0, n) bit for bit.  alpha = 0.25 (1 - epoch / n_epochs) in fp32; a firing entry attracts once toward
+ * y_train[indices[i][j]] and repels from y_train[R(seed, epoch, (row_offset + i) k + j, p) mod M]; only y moves.  A query's
+ * result depends on its row, row_offset + i, seed and the model alone.  group: lanes per query, 8 or 64, or 0 = the
+ * library's choice (8); the result does not depend on it.  0 <= epoch_begin <= epoch_end <= n_epochs, row_offset >= 0. */
+int dm_umap_transform_layout(const int32_t *indices, const float *eps, const float *eps_neg, float *next, float *next_neg,
+                             int64_t R, int k, int64_t M, const float *y_train, float *y, int epoch_begin, int epoch_end,
+                             int n_epochs, int64_t row_offset, float a, float b, float gamma, uint64_t seed, int group,
+                             void *stream);
+
 #ifdef __cplusplus
 }
 #endif

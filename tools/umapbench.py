@@ -8,6 +8,12 @@ timed beside it: a baseline, not an oracle.  Prints one JSON line per record.
 
     timeout -k 10 900 python tools/umapbench.py --rows 20000 100000 --ks 15 200 --out profiles/umap_f4096_umapbench.jsonl
 
+--transform: the transform of new rows instead -- per (N, k) a model fitted on N rows, then R queries
+of the same distribution: the query graph, the prepare stage, the layout in ONE launch for each lanes-per-query form, the same
+layout launched epoch by epoch through the range arguments, and the whole UMAPEmbedding.transform by the host clock.
+
+    timeout -k 10 900 python tools/umapbench.py --transform --rows 100000 --queries 20000 --ks 15 200 --out profiles/umap_transform_f4096_umapbench.jsonl
+
 What bounds the epoch kernel is not separable by events: take counters from a run of their own
 (`rocprofv3 --pmc ... -- python tools/umapbench.py --rows 100000 --ks 15 --epochs-only`).
 """
@@ -66,6 +72,75 @@ def layout(indptr, cols, eps, eps_neg, y0, n_epochs, group, seed=0):
     return y, [ev[n].elapsed_time(ev[n + 1]) / 1e3 for n in range(n_epochs)]
 
 
+def data(N, a, dev, seed):
+    g = torch.Generator(device=dev).manual_seed(seed)
+    if a.intrinsic_dim > 0:
+        D = a.intrinsic_dim
+        basis = torch.randn((D, a.features), device=dev, generator=torch.Generator(device=dev).manual_seed(12345))
+        return (torch.randn((N, D), device=dev, generator=g) @ basis).div_(D ** 0.5).add_(30.0)
+    return torch.randn((N, a.features), device=dev, generator=g).add_(30.0)              # knnbench's data
+
+
+def transform_layout(i32, eps, eps_neg, nxt0, neg0, y_train, y0, cuts, n_epochs, group):
+    """The layout from fresh state through the ranges `cuts`: (positions, seconds by device events)."""
+    nxt, neg, y = nxt0.clone(), neg0.clone(), y0.clone()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for lo, hi in zip(cuts[:-1], cuts[1:]):
+        ops.umap_transform_layout(i32, eps, eps_neg, nxt, neg, y_train, y, lo, hi, n_epochs, 0, 0, 1.58, 0.9, 1.0, group)
+    b.record()
+    torch.cuda.synchronize()
+    return y, a.elapsed_time(b) / 1e3
+
+
+def transform_bench(a, dev):
+    for N in a.rows:
+        X, Q = data(N, a, dev, 0), data(a.queries, a, dev, 1)
+        R = a.queries
+        idx_all, dist_all = K.knn_graph(X, max(a.ks), include_self=True)
+        pcs = U.pca_coordinates(X)
+        for k in a.ks:
+            model = U.UMAPEmbedding(n_neighbors=k)
+            t0 = time.perf_counter()
+            model.fit_graph(np.ascontiguousarray(idx_all[:, :k]), np.ascontiguousarray(dist_all[:, :k]), pcs, X=X)
+            t_fit = time.perf_counter() - t0
+            n_t = max(1, model.n_epochs_ // 3)
+            K.knn_query(X, Q, k)                                                          # warm
+            t0 = time.perf_counter()
+            qi, qd = K.knn_query(X, Q, k)
+            t_query = time.perf_counter() - t0
+            i32, d = torch.from_numpy(qi.astype(np.int32)).to(dev), torch.from_numpy(qd).to(dev)
+            y_train = torch.from_numpy(model.embedding_).to(dev)
+            (sigma, mem, eps, eps_neg, nxt, neg, y0), t_prep = timed(lambda: ops.umap_transform_prepare(i32, d, y_train, n_t, 5))
+            live = torch.isfinite(eps)
+            rec = {"record": "transform", "N": N, "R": R, "k": k, "intrinsic_dim": a.intrinsic_dim, "n_epochs_t": n_t,
+                   "entries": R * k, "entries_sampled": int(live.sum().item()),
+                   "fired_per_epoch": float((1.0 / eps.double()).sum().item()), "s_fit_graph_wall": t_fit,
+                   "s_query_graph_wall": t_query, "s_prepare": t_prep}
+            ref = None
+            for group in (0, 8, 64):
+                ts = []
+                for _ in range(4):                                                        # the first is the warm-up
+                    y, t = transform_layout(i32, eps, eps_neg, nxt, neg, y_train, y0, (0, n_t), n_t, group)
+                    ts.append(t)
+                rec[f"s_layout_one_launch_group{group}"] = statistics.median(ts[1:])
+                ref = y if ref is None else ref
+                rec[f"same_bits_group{group}"] = bool(torch.equal(ref.view(torch.int32), y.view(torch.int32)))
+            ts = [transform_layout(i32, eps, eps_neg, nxt, neg, y_train, y0, tuple(range(n_t + 1)), n_t, 0) for _ in range(4)]
+            rec["s_layout_epoch_by_epoch"] = statistics.median(t for _, t in ts[1:])
+            rec["same_bits_epoch_by_epoch"] = bool(torch.equal(ref.view(torch.int32), ts[-1][0].view(torch.int32)))
+            model.transform(Q)                                                            # warm
+            t0 = time.perf_counter()
+            out = model.transform(Q)
+            rec["s_transform_wall"] = time.perf_counter() - t0
+            rec["queries_per_s"] = R / rec["s_transform_wall"]
+            rec["same_bits_transform"] = bool(np.array_equal(out.view(np.uint32), ref.cpu().numpy().view(np.uint32)))
+            rec["finite"] = bool(np.isfinite(out).all())
+            emit(rec, a.out)
+        del X, Q
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, nargs="+", default=[20000, 100000])
@@ -75,11 +150,15 @@ def main():
                     help="D > 0: data of D intrinsic dimensions, 30 + randn(N, D) @ randn(D, F) / sqrt(D), which has far shorter "
                          "hub rows than isotropic noise in F dimensions")
     ap.add_argument("--epochs-only", action="store_true", help="the graph and one layout per shape, nothing else (for counters)")
+    ap.add_argument("--transform", action="store_true", help="measure the transform of --queries new rows into a model of N rows")
+    ap.add_argument("--queries", type=int, default=20000)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("umapbench needs a GPU")
     dev = torch.device("cuda:0")
+    if a.transform:
+        return transform_bench(a, dev)
     try:
         import umap as umap_learn
     except ImportError:
