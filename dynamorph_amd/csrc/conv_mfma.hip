@@ -184,7 +184,8 @@ __device__ __forceinline__ void zero_unowned_slabs(const Epilogue &ep, int NCH, 
 // ============================================================================ kernel A
 // BB: per-position bias from ep.bias_border[3][3][NOUT] (first / interior / last output row x column) instead of
 // ep.bias -- the enc.0 bias seen through enc.1's zero padding, so the first conv needs no ones channel (K = 32, not 48).
-template <int CIN, int NT, int TH, int TW, int SIDE, int WPS, bool BB>
+// DESC: the tile walk runs from the end of the tensor (tile.h: tile_id); tidx stays the ordinal, live while < ntiles.
+template <int CIN, int NT, int TH, int TW, int SIDE, int WPS, bool BB, bool DESC>
 __global__ __launch_bounds__(DM_BLOCK, WPS)
 void conv4x4s2_kernel(Operand in, WeightView wv, float *__restrict__ out, Epilogue ep, int Cphys, int NOUT, int H,
                       int W, int ntiles, int nslabs, int per_tile)
@@ -205,7 +206,7 @@ void conv4x4s2_kernel(Operand in, WeightView wv, float *__restrict__ out, Epilog
     stage.init(H, W);
     int tidx = blockIdx.x, b = 0, oy0 = 0, ox0 = 0;
     if (tidx < ntiles) {
-        int t = tidx;
+        int t = tile_id<DESC>(tidx, ntiles);
         ox0 = (t % tiles_x) * TW; t /= tiles_x;
         oy0 = (t % tiles_y) * TH; b = t / tiles_y;
         stage.issue(in, b, Cphys, H, W, 2 * oy0 - 1, 2 * ox0 - 4);
@@ -249,7 +250,7 @@ void conv4x4s2_kernel(Operand in, WeightView wv, float *__restrict__ out, Epilog
         const int cb = b, cy0 = oy0, cx0 = ox0;            // the tile now in LDS
         const int next = tidx + gridDim.x;
         {                                                  // (no next tile: empty descriptor, every load returns 0)
-            int t = next < ntiles ? next : tidx;
+            int t = tile_id<DESC>(next < ntiles ? next : tidx, ntiles);
             ox0 = (t % tiles_x) * TW; t /= tiles_x;
             oy0 = (t % tiles_y) * TH; b = t / tiles_y;
         }
@@ -312,7 +313,7 @@ void conv4x4s2_kernel(Operand in, WeightView wv, float *__restrict__ out, Epilog
                 }
         }
         if (per_tile && ep.stats) {                         // per-sample BatchNorm statistics: one slab per TILE
-            stats_reduce<NT, false>(s1, s2, s_stat, ep, NOUT, tidx);
+            stats_reduce<NT, false>(s1, s2, s_stat, ep, NOUT, tile_id<DESC>(tidx, ntiles));
 #pragma unroll
             for (int t = 0; t < NT; ++t) { s1[t] = 0.0; s2[t] = 0.0; }
         }
@@ -852,7 +853,8 @@ struct FusedBwdGeom {
 // the side accumulator shifted by one M row, a register rename inside a lane plus one cross-lane value per M tile
 // (ds_bpermute); columns -1 and W are the zero padding.  16 matrix instructions per M tile and phase row instead of 24, a
 // third of the A-operand LDS reads, 32 weight registers instead of 48.
-template <int CD, int CX, int TH, int TW, bool ZF>
+// DESC: the tile walk runs from the end of the tensors (tile.h: tile_id): coords() maps the ordinal, so the three roles agree.
+template <int CD, int CX, int TH, int TW, bool ZF, bool DESC>
 __global__ __launch_bounds__(768, 1)
 void bwd_s2_roles3_kernel(Operand dy, Operand tin, WeightView wv, float *__restrict__ dx, Epilogue ep,
                          float *__restrict__ wslabs, int H, int W, int ntiles, int dbg)
@@ -878,7 +880,8 @@ void bwd_s2_roles3_kernel(Operand dy, Operand tin, WeightView wv, float *__restr
     const int rw = wave & (RW - 1);
     const int OH = 2 * H, OW = 2 * W;
     const int tiles_x = W / TW, tiles_y = H / TH;
-    auto coords = [&](int t, int &tb, int &ty0, int &tx0) {
+    auto coords = [&](int kth, int &tb, int &ty0, int &tx0) {
+        int t = tile_id<DESC>(kth, ntiles);
         tx0 = (t % tiles_x) * TW; t /= tiles_x;
         ty0 = (t % tiles_y) * TH; tb = t / tiles_y;
     };
@@ -1167,6 +1170,12 @@ int conv4_tw(int CIN, int Wo)
     return Wo < cap ? Wo : cap;
 }
 
+// Direction of the tile walk (tile.h: tile_id), one per kernel and the same for all its instantiations.  The directions alternate
+// along the training step so that every large consumer starts where its producer stopped: pair (up) -> kernel A (down) -> enc.7
+// forward (up) ... enc.7 backward (up) -> kernel D (down) -> wgrad (up).
+constexpr bool CONV4_DESC = true;       // conv4x4s2_kernel (enc.4 forward)
+constexpr bool FUSED_BWD_DESC = true;   // bwd_s2_roles3_kernel (kernel D, enc.4 backward)
+
 template <int CIN, int TW>
 void launch_conv4(const ConvArgs &a)
 {
@@ -1181,12 +1190,12 @@ void launch_conv4(const ConvArgs &a)
                                dim3(conv_grid(a.ntiles, WPS, a.per_tile)), dim3(DM_BLOCK), 0, a.stream, a.in, a.wv, \
                                a.out, a.ep, a.Cphys, a.H, a.W, a.ntiles, a.nslabs, a.per_tile);                   \
         else if (SIDE_ == SIDE_NONE && CIN <= 5 && a.ep.bias_border)                                              \
-            hipLaunchKernelGGL((conv4x4s2_kernel<CIN, 1, TH, TW, SIDE_NONE, WPS, true>),                          \
+            hipLaunchKernelGGL((conv4x4s2_kernel<CIN, 1, TH, TW, SIDE_NONE, WPS, true, CONV4_DESC>),              \
                                dim3(conv_grid(a.ntiles, WPS, a.per_tile)), dim3(DM_BLOCK), 0, a.stream, a.in, a.wv, \
                                a.out, a.ep, a.Cphys, a.NOUT, a.H, a.W, a.ntiles, a.nslabs,                        \
                                a.per_tile);                                                                       \
         else                                                                                                      \
-            hipLaunchKernelGGL((conv4x4s2_kernel<CIN, 1, TH, TW, SIDE_, WPS, false>),                             \
+            hipLaunchKernelGGL((conv4x4s2_kernel<CIN, 1, TH, TW, SIDE_, WPS, false, CONV4_DESC>),                 \
                                dim3(conv_grid(a.ntiles, WPS, a.per_tile)), dim3(DM_BLOCK), 0, a.stream, a.in, a.wv, \
                                a.out, a.ep, a.Cphys, a.NOUT, a.H, a.W, a.ntiles, a.nslabs,                        \
                                a.per_tile);                                                                       \
@@ -1519,16 +1528,16 @@ extern "C" int dm_conv_bwd_s2_fused(const dm_operand *dy, const dm_operand *tin,
     if (dm_check_operand(&ep->mask, "dm_conv_bwd_s2_fused(mask)")) return -1;
     using G = FusedBwdGeom<16, 8, 8, 32>;
     using G64 = FusedBwdGeom<16, 8, 4, 64>;
+    constexpr auto kd32 = bwd_s2_roles3_kernel<16, 8, 8, 32, false, FUSED_BWD_DESC>;
+    constexpr auto kd32z = bwd_s2_roles3_kernel<16, 8, 8, 32, true, FUSED_BWD_DESC>;
+    constexpr auto kd64z = bwd_s2_roles3_kernel<16, 8, 4, 64, true, FUSED_BWD_DESC>;
     static DmPerDeviceOnce attr_set;
     if (attr_set.need()) {
-        hipError_t e = hipFuncSetAttribute((const void *)bwd_s2_roles3_kernel<16, 8, 8, 32, false>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
+        hipError_t e = hipFuncSetAttribute((const void *)kd32, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
         if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void *)bwd_s2_roles3_kernel<16, 8, 8, 32, true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
+            e = hipFuncSetAttribute((const void *)kd32z, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
         if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void *)bwd_s2_roles3_kernel<16, 8, 4, 64, true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)G64::LDS_BYTES);
+            e = hipFuncSetAttribute((const void *)kd64z, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G64::LDS_BYTES);
         if (e != hipSuccess) { dm_set_error("dm_conv_bwd_s2_fused: cannot reserve %zu bytes of LDS: %s", G::LDS_BYTES, hipGetErrorString(e)); return (int)e; }
         attr_set.mark();
     }
@@ -1538,13 +1547,13 @@ extern "C" int dm_conv_bwd_s2_fused(const dm_operand *dy, const dm_operand *tin,
     // grids (enc.4 of 256-pixel patches) take tiles of 4 rows x 64 columns, which span the row too (the same number of tiles,
     // hence of slabs, as 8 x 32)
     if (W == 64 && H % 4 == 0)
-        hipLaunchKernelGGL((bwd_s2_roles3_kernel<16, 8, 4, 64, true>), dim3(grid), dim3(768), G64::LDS_BYTES, (hipStream_t)stream,
+        hipLaunchKernelGGL(kd64z, dim3(grid), dim3(768), G64::LDS_BYTES, (hipStream_t)stream,
                            to_dev(dy), to_dev(tin), to_dev(w), dx, to_dev(ep), w_slabs, H, W, B * (H / 4), 0);
     else if (W == 32)
-        hipLaunchKernelGGL((bwd_s2_roles3_kernel<16, 8, 8, 32, true>), dim3(grid), dim3(768), G::LDS_BYTES, (hipStream_t)stream,
+        hipLaunchKernelGGL(kd32z, dim3(grid), dim3(768), G::LDS_BYTES, (hipStream_t)stream,
                            to_dev(dy), to_dev(tin), to_dev(w), dx, to_dev(ep), w_slabs, H, W, ntiles, 0);
     else
-        hipLaunchKernelGGL((bwd_s2_roles3_kernel<16, 8, 8, 32, false>), dim3(grid), dim3(768), G::LDS_BYTES, (hipStream_t)stream,
+        hipLaunchKernelGGL(kd32, dim3(grid), dim3(768), G::LDS_BYTES, (hipStream_t)stream,
                            to_dev(dy), to_dev(tin), to_dev(w), dx, to_dev(ep), w_slabs, H, W, ntiles, 0);
     return dm_launch_status("dm_conv_bwd_s2_fused");
 }

@@ -57,6 +57,16 @@ __device__ __forceinline__ void stage_coef(float *__restrict__ s_coef, const Ope
     coef_put(s_coef, op, coef_fetch(op, b, C), C);
 }
 
+// ---- the order in which a persistent workgroup walks its tiles ---------------------------------------------------------------
+// A workgroup's k-th tile has the ordinal kth = blockIdx.x + k * gridDim.x and is live while kth < ntiles; tile_id maps the ordinal
+// to the tile it decodes into (sample, row band, column band).  Ascending is the ordinal itself.  Descending walks the tensor from
+// its end: a kernel launched straight after the producer of its operand then asks FIRST for the lines written LAST, which are the
+// ones still in the 256 MiB Infinity Cache -- and leaves the start of its own output there for an ascending
+// consumer behind it.  Everything indexed per tile (statistics slabs, per-sample coefficients) takes the mapped id, everything
+// per workgroup blockIdx.x; the map is integer arithmetic ahead of the tile's requests.
+template <bool DESC>
+__device__ __forceinline__ int tile_id(int kth, int ntiles) { return DESC ? ntiles - 1 - kth : kth; }
+
 typedef unsigned short dm_u16x2 __attribute__((ext_vector_type(2)));
 
 // ReLU that keeps EVERY NaN, as torch.relu does: (v < 0) ? 0 : v -- the ordered compare is false for a NaN of either
