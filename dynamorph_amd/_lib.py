@@ -186,6 +186,9 @@ SIGNATURES = {
     "dm_pca_gram_workspace_bytes": (i64, [i64, C.c_int]),
     "dm_pca_gram": (C.c_int, [vp, i64, C.c_int, i64, vp, vp, C.c_int, vp, i64, vp]),
     "dm_pca_transform": (C.c_int, [vp, i64, C.c_int, i64, vp, vp, C.c_int, vp, vp]),
+    "dm_pca_rowgram_workspace_bytes": (i64, [i64, C.c_int]),
+    "dm_pca_rowgram": (C.c_int, [vp, i64, C.c_int, i64, vp, vp, C.c_int, vp, i64, vp]),
+    "dm_pca_components": (C.c_int, [vp, i64, C.c_int, i64, vp, vp, C.c_int, vp, vp]),
     "dm_knn_workspace_bytes": (i64, [i64, i64, C.c_int, C.c_int, C.c_int]),
     "dm_knn": (C.c_int, [vp, i64, C.c_int, i64, vp, i64, i64, i64, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, i64, vp]),
     "dm_umap_smooth": (C.c_int, [vp, i64, C.c_int, vp, vp, vp, vp, vp]),

@@ -11,6 +11,12 @@
 //              DM_PCA_GRAM_SLAB_ROWS rows, slabs added in fp64 registers in row order, row splits reduced in order from an
 //              fp64 workspace and mirrored into the full F x F matrix (no atomics anywhere: repeated launches are bit-equal).
 //   transform  Y = (X - s) V^T for V (k x F), k <= DM_PCA_MAX_COMPONENTS, 64-row tiles on v_mfma_f32_16x16x4_f32.
+// Wider latents (VQ_VAE_z32: 65536 features), N <= DM_PCA_WIDE_MAX_SAMPLES rows, F <= DM_PCA_WIDE_MAX_FEATURES:
+//   rowgram    K = (X - s)(X - s)^T (N x N), knn_gram_kernel's loop on upper-triangular tile pairs of the rows; fp32 within
+//              a slab of DM_PCA_ROWGRAM_SLAB_FEATURES features, slabs in fp64 registers in feature order, the work split over
+//              feature ranges that are reduced in order from an fp64 workspace (or, one range, stored directly and mirrored).
+//   components V = W (X - s) (k x F float64) for W (k x N): the transform turned round, fp32 within slabs of
+//              DM_PCA_COMPONENTS_SLAB_ROWS rows, fp64 across them.
 #include "dm_common.h"
 
 namespace {
@@ -343,7 +349,382 @@ void launch_transform(bool v4, unsigned gx, hipStream_t s, const float *X, long 
     else hipLaunchKernelGGL((transform_kernel<KT, false>), grid, dim3(256), 0, s, X, N, F, ld, shift, V, k, Y);
 }
 
+// ------------------------------------------------------------------------------- row Gram matrix (sample space)
+// K = (X - s)(X - s)^T for latents wider than DM_PCA_MAX_FEATURES: the N x N side of the matrix the covariance route squares.
+constexpr int RG_CH = 16;                           // features per LDS stage (8 k-steps of the 32x32x2 instruction)
+constexpr int RG_SLAB = DM_PCA_ROWGRAM_SLAB_FEATURES;
+static_assert(RG_SLAB % RG_CH == 0, "a slab is a whole number of LDS stages");
+constexpr long long RG_DIRECT_PAIRS = 4 * G_SLOTS;  // from here on the tile pairs fill the part: no feature split
+
+struct RowgramPlan { int T; long long pairs; long long nslabs; int S; long long slabs_per; };
+
+// The feature split depends on (N, F) only.  Few tile pairs (N = 2000: 136 for 256 CUs): S is the split whose last wave of
+// workgroups is fullest (ties: the smaller S), capped by the slabs there are and by a 2 GiB workspace.  RG_DIRECT_PAIRS tile
+// pairs or more: S = 1.  S = 1 needs no workspace: the kernel stores its tile into K and rowgram_mirror_kernel completes K.
+RowgramPlan rowgram_plan(long long N, long long F)
+{
+    RowgramPlan p;
+    p.T = (int)((N + GT - 1) / GT);
+    p.pairs = (long long)p.T * (p.T + 1) / 2;
+    p.nslabs = (F + RG_SLAB - 1) / RG_SLAB;
+    const long long tile_bytes = (long long)GT * GT * 8;
+    int best = 1;
+    double best_eff = 0.0;
+    for (int s = 1; p.pairs < RG_DIRECT_PAIRS && s <= 64 && s <= p.nslabs; ++s) {
+        if (s > 1 && (long long)s * p.pairs * tile_bytes > (2LL << 30)) break;
+        const long long blocks = (long long)s * p.pairs;
+        const double eff = (double)blocks / (double)(((blocks + G_SLOTS - 1) / G_SLOTS) * G_SLOTS);
+        if (eff > best_eff + 1e-9) { best_eff = eff; best = s; }
+    }
+    p.slabs_per = (p.nslabs + best - 1) / best;
+    p.S = (int)((p.nslabs + p.slabs_per - 1) / p.slabs_per);
+    return p;
+}
+
+// Features f .. f + 3 of a row without a branch, for loads that must not be waited for where they are issued: addresses
+// past F are clamped into the row and the caller discards those elements.  V4: the 16-byte form, F % 4 == 0 and F >= 4.
+template <bool V4>
+__device__ __forceinline__ f32x4 row_load4_clamped(const float *__restrict__ row, int f, int F)
+{
+    if (V4) return *(const f32x4 *)(row + (f < F ? f : F - 4));
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = row[f + e < F ? f + e : F - 1];
+    return v;
+}
+
+// Workgroup (tile pair ti <= tj of the rows, feature range y): knn_gram_kernel's loop with both operands taken from X.
+// 4 waves, wave w owns the 64 x 64 quarter (w >> 1, w & 1) as 2 x 2 accumulators of the 32x32x2 instruction.  A thread stages
+// features 4 (tid >> 6) .. + 3 of rows (tid & 63) and (tid & 63) + 64 of both tiles and stores them transposed
+// ([feature][row]).  Two stages of loads are in flight during a stage's products: a fetch only loads -- the shift is
+// subtracted when the registers go to LDS -- and it is unconditional and free of branches (past the range it repeats the
+// last stage; SHIFT is a template parameter, and the 16-byte form V4 is launched on a multiple of four features, the host
+// sends the one to three left over through the scalar form).  Rows past N repeat row N - 1 (their products are never
+// stored); features past the range go to LDS as zeros.
+// ws != NULL: the tile goes to ws[y][pair] (rowgram_reduce_kernel adds the ranges).  ws == NULL (one range): the entries
+// with row <= column go straight into K, (+)=.
+template <bool V4, bool SHIFT>
+__global__ __launch_bounds__(256) void rowgram_kernel(const float *__restrict__ X, int N, int F, long long ld,
+                                                      const float *__restrict__ shift, int T, long long slabs_per,
+                                                      double *__restrict__ ws, double *__restrict__ K, int accumulate)
+{
+    __shared__ __attribute__((aligned(16))) float lds[2][2][RG_CH * GLW];
+    int ti, tj;
+    pair_of(blockIdx.x, T, ti, tj);
+    const int I = ti * GT, J = tj * GT;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int wm = w >> 1, wn = w & 1;
+    const int sr = tid & 63, sf = 4 * (tid >> 6);
+
+    const long long fb = (long long)blockIdx.y * slabs_per * RG_SLAB;
+    const int f_begin = (int)fb;
+    const int f_end = (int)(fb + slabs_per * RG_SLAB < F ? fb + slabs_per * RG_SLAB : F);
+    const int nstages = (f_end - f_begin + RG_CH - 1) / RG_CH;
+
+    const float *arow[2], *brow[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const int ra_ = I + sr + 64 * q, rb_ = J + sr + 64 * q;
+        arow[q] = X + (long long)(ra_ < N ? ra_ : N - 1) * ld;
+        brow[q] = X + (long long)(rb_ < N ? rb_ : N - 1) * ld;
+    }
+
+    f32x4 ra[2][2], rb[2][2], rs[2];
+    auto fetch = [&](int stage, int slot) {
+        const int f = f_begin + (stage < nstages ? stage : nstages - 1) * RG_CH + sf;
+        rs[slot] = SHIFT ? row_load4_clamped<false>(shift, f, F) : (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            ra[slot][q] = row_load4_clamped<V4>(arow[q], f, F);
+            rb[slot][q] = row_load4_clamped<V4>(brow[q], f, F);
+        }
+    };
+    auto stash = [&](int stage, int slot, int buf) {
+        const int f = f_begin + stage * RG_CH + sf;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const f32x4 va = ra[slot][q] - rs[slot], vb = rb[slot][q] - rs[slot];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {       // features past the range: zeros
+                lds[buf][0][(sf + e) * GLW + sr + 64 * q] = f + e < f_end ? va[e] : 0.f;
+                lds[buf][1][(sf + e) * GLW + sr + 64 * q] = f + e < f_end ? vb[e] : 0.f;
+            }
+        }
+    };
+
+    typedef float f32x16 __attribute__((ext_vector_type(16)));
+    f32x16 acc[2][2];
+    double dacc[2][2][16];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            acc[i][j] = (f32x16){};
+#pragma unroll
+            for (int e = 0; e < 16; ++e) dacc[i][j][e] = 0.0;
+        }
+
+    fetch(0, 0);
+    fetch(1, 1);
+    stash(0, 0, 0);
+    __syncthreads();
+    constexpr int STAGES_PER_SLAB = RG_SLAB / RG_CH;
+    for (int st0 = 0; st0 < nstages; st0 += 2) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {           // stage st lives in register slot u and LDS buffer u
+            const int st = st0 + u;
+            if (st >= nstages) break;
+            fetch(st + 2, u);                   // (slot u went to LDS one stage ago)
+            __builtin_amdgcn_sched_barrier(0);  // the loads are issued here, not after the products
+            const float *A = lds[u][0], *B = lds[u][1];
+            const int koff = (lane >> 5) * GLW + (lane & 31);
+#pragma unroll
+            for (int kk = 0; kk < RG_CH / 2; ++kk) {
+                const int o = 2 * kk * GLW + koff;
+                const float a0 = A[o + wm * 64], a1 = A[o + wm * 64 + 32];
+                const float b0 = B[o + wn * 64], b1 = B[o + wn * 64 + 32];
+                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+            }
+            stash(st + 1, u ^ 1, u ^ 1);        // (unconditional like the fetch: past the end it stores zeros nobody reads)
+            __syncthreads();
+            if ((st + 1) % STAGES_PER_SLAB == 0 || st + 1 == nstages) {     // slab done: fold it into fp64, feature order
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+#pragma unroll
+                        for (int e = 0; e < 16; ++e) dacc[i][j][e] += (double)acc[i][j][e];
+                        acc[i][j] = (f32x16){};
+                    }
+            }
+        }
+    }
+    // C/D map of the 32x32 instructions: column lane & 31, row (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
+    double *tile = ws ? ws + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * (GT * GT) : nullptr;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int row = wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
+                const int col = wn * 64 + j * 32 + (lane & 31);
+                if (tile) {
+                    tile[row * GT + col] = dacc[i][j][e];
+                } else if (I + row <= J + col && J + col < N) {
+                    double *k = K + (long long)(I + row) * N + (J + col);
+                    *k = accumulate ? *k + dacc[i][j][e] : dacc[i][j][e];
+                }
+            }
+}
+
+// K[i][j] (+)= sum over the feature ranges, in order, of the entry (min, max) of the pair's tile.
+__global__ __launch_bounds__(256) void rowgram_reduce_kernel(const double *__restrict__ ws, int S, long long pairs, int T, int N,
+                                                             double *__restrict__ K, int accumulate)
+{
+    const int j = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int i = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (i >= N || j >= N) return;
+    const int a = i < j ? i : j, b = i < j ? j : i;
+    const int ta = a / GT, tb = b / GT;
+    const long long p = (long long)ta * T - (long long)ta * (ta - 1) / 2 + (tb - ta);
+    const long long off = p * (GT * GT) + (a % GT) * GT + (b % GT);
+    double v = 0.0;
+    for (int s = 0; s < S; ++s) v += ws[(long long)s * pairs * (GT * GT) + off];
+    double *k = K + (long long)i * N + j;
+    *k = accumulate ? *k + v : v;
+}
+
+// One range: the entries below the diagonal are copies of the ones the kernel stored above it.
+__global__ __launch_bounds__(256) void rowgram_mirror_kernel(int N, double *__restrict__ K)
+{
+    const int j = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int i = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (i >= N || j >= i) return;
+    K[(long long)i * N + j] = K[(long long)j * N + i];
+}
+
+// ------------------------------------------------------------------------------------------- components (sample space)
+constexpr int CP_FT = 64;               // features per workgroup (16 per wave)
+constexpr int CP_RC = 64;               // rows of X per LDS stage (16 k-steps of the 16x16x4 instruction)
+constexpr int CP_XLW = CP_FT + 16;      // X stage [row][feature]: lane (feature l & 15, k l >> 4) -> bank 16 (l >> 4) + (l & 15)
+constexpr int CP_WLW = CP_RC + 4;       // W stage [component][row]: lane (comp. l & 15, k l >> 4) -> bank 4 (l & 15) + (l >> 4)
+constexpr int CP_SLAB = DM_PCA_COMPONENTS_SLAB_ROWS;
+static_assert(CP_SLAB % CP_RC == 0, "a slab is a whole number of LDS stages");
+
+// transform_kernel turned round: V = W (X - s), the rows of X are the inner dimension.  Workgroup (feature tile, component
+// tile of KT): stages of 64 rows of X and of W in LDS, each wave 16 features x KT components as KT / 16 accumulators of
+// v_mfma_f32_16x16x4_f32 (A[i][k] = W[j][n], B[k][j] = X[n][f] - s[f]); the next stage is loaded into registers before the
+// products.  fp32 within a slab of CP_SLAB rows, the slabs added in float64 in row order and stored as they are.
+template <int KT, bool V4>
+__global__ __launch_bounds__(256) void components_kernel(const float *__restrict__ X, int N, int F, long long ld,
+                                                         const float *__restrict__ shift, const float *__restrict__ W, int k,
+                                                         double *__restrict__ V)
+{
+    __shared__ __attribute__((aligned(16))) float xs[CP_RC * CP_XLW];
+    __shared__ __attribute__((aligned(16))) float wl[KT * CP_WLW];
+    constexpr int XQ = CP_RC * CP_FT / 4 / 256;         // float4 per thread: X stage
+    constexpr int WQ = KT * CP_RC / 256;                // floats per thread: W stage
+    const int f0 = blockIdx.x * CP_FT, j0 = blockIdx.y * KT;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int c4 = (tid & 15) * 4, rr = tid >> 4;       // 16 threads per 64-feature row segment
+    const f32x4 sh = shift4(shift, f0 + c4, F);
+
+    f32x4 rx[XQ];
+    float rw[WQ];
+    auto fetch = [&](int n0) {
+#pragma unroll
+        for (int q = 0; q < XQ; ++q) rx[q] = load_centred4<V4>(X, n0 + rr + 16 * q, f0 + c4, N, F, ld, sh);
+#pragma unroll
+        for (int q = 0; q < WQ; ++q) {                      // components past k, rows past N: zeros
+            const int j = j0 + w + 4 * q, n = n0 + lane;
+            rw[q] = j < k && n < N ? W[(long long)j * N + n] : 0.f;
+        }
+    };
+    auto stash = [&]() {
+#pragma unroll
+        for (int q = 0; q < XQ; ++q) *(f32x4 *)&xs[(rr + 16 * q) * CP_XLW + c4] = rx[q];
+#pragma unroll
+        for (int q = 0; q < WQ; ++q) wl[(w + 4 * q) * CP_WLW + lane] = rw[q];
+    };
+
+    f32x4 acc[KT / 16];
+    double dacc[KT / 16][4];
+#pragma unroll
+    for (int t = 0; t < KT / 16; ++t) {
+        acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) dacc[t][e] = 0.0;
+    }
+    fetch(0);
+    for (int n0 = 0; n0 < N; n0 += CP_RC) {
+        stash();
+        __syncthreads();
+        if (n0 + CP_RC < N) fetch(n0 + CP_RC);
+        const int ao = (lane & 15) * CP_WLW + (lane >> 4);
+        const int bo = (lane >> 4) * CP_XLW + w * 16 + (lane & 15);
+#pragma unroll
+        for (int kk = 0; kk < CP_RC / 4; ++kk) {
+            const float b = xs[bo + 4 * kk * CP_XLW];
+#pragma unroll
+            for (int t = 0; t < KT / 16; ++t)
+                acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wl[ao + t * 16 * CP_WLW + 4 * kk], b, acc[t], 0, 0, 0);
+        }
+        __syncthreads();
+        if ((n0 + CP_RC) % CP_SLAB == 0 || n0 + CP_RC >= N) {           // slab done: fold it into fp64, row order
+#pragma unroll
+            for (int t = 0; t < KT / 16; ++t) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) dacc[t][e] += (double)acc[t][e];
+                acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            }
+        }
+    }
+    // C/D map of the 16x16 instructions: column (feature) lane & 15, row (component) 4 (lane >> 4) + e
+    const int f = f0 + w * 16 + (lane & 15);
+    if (f >= F) return;
+#pragma unroll
+    for (int t = 0; t < KT / 16; ++t)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int j = j0 + t * 16 + 4 * (lane >> 4) + e;
+            if (j < k) V[(long long)j * F + f] = dacc[t][e];
+        }
+}
+
+template <int KT>
+void launch_components(bool v4, hipStream_t s, const float *X, int N, int F, long long ld, const float *shift, const float *W,
+                       int k, double *V)
+{
+    const dim3 grid((F + CP_FT - 1) / CP_FT, (k + KT - 1) / KT);
+    if (v4) hipLaunchKernelGGL((components_kernel<KT, true>), grid, dim3(256), 0, s, X, N, F, ld, shift, W, k, V);
+    else hipLaunchKernelGGL((components_kernel<KT, false>), grid, dim3(256), 0, s, X, N, F, ld, shift, W, k, V);
+}
+
+int check_wide_x(const char *who, const float *X, long long N, int F, long long ld)
+{
+    DM_REQUIRE(X, "%s: X is NULL", who);
+    DM_REQUIRE(N >= 1 && N <= DM_PCA_WIDE_MAX_SAMPLES, "%s: N = %lld rows, supported 1 .. %d", who, N, DM_PCA_WIDE_MAX_SAMPLES);
+    DM_REQUIRE(F >= 1 && F <= DM_PCA_WIDE_MAX_FEATURES, "%s: F = %d features, supported 1 .. %d", who, F,
+               DM_PCA_WIDE_MAX_FEATURES);
+    DM_REQUIRE(ld >= F, "%s: leading dimension %lld < F = %d", who, ld, F);
+    return 0;
+}
+
+// One launch of the row Gram kernel and of what completes K behind it, on features [0, F) of X.
+template <bool V4>
+void launch_rowgram(hipStream_t s, const float *X, int N, int F, long long ld, const float *shift, double *K, int accumulate,
+                    double *workspace)
+{
+    const RowgramPlan p = rowgram_plan(N, F);
+    double *ws = p.S > 1 ? workspace : nullptr;
+    const dim3 grid((unsigned)p.pairs, p.S), red((unsigned)((N + 63) / 64), (unsigned)((N + 3) / 4));
+    if (shift)
+        hipLaunchKernelGGL((rowgram_kernel<V4, true>), grid, dim3(256), 0, s, X, N, F, ld, shift, p.T, p.slabs_per, ws, K,
+                           accumulate);
+    else
+        hipLaunchKernelGGL((rowgram_kernel<V4, false>), grid, dim3(256), 0, s, X, N, F, ld, shift, p.T, p.slabs_per, ws, K,
+                           accumulate);
+    if (ws)
+        hipLaunchKernelGGL(rowgram_reduce_kernel, red, dim3(256), 0, s, (const double *)ws, p.S, p.pairs, p.T, N, K, accumulate);
+    else
+        hipLaunchKernelGGL(rowgram_mirror_kernel, red, dim3(256), 0, s, N, K);
+}
+
+int64_t rowgram_ws_bytes(long long N, int F)
+{
+    const RowgramPlan p = rowgram_plan(N, F);
+    return p.S > 1 ? (int64_t)p.S * p.pairs * GT * GT * (int64_t)sizeof(double) : 0;
+}
+
 }  // namespace
+
+// (the 16-byte form runs on F & ~3 features, the scalar form on all F or on the F & 3 left over: the larger need)
+extern "C" int64_t dm_pca_rowgram_workspace_bytes(int64_t N, int F)
+{
+    if (N < 1 || N > DM_PCA_WIDE_MAX_SAMPLES || F < 1 || F > DM_PCA_WIDE_MAX_FEATURES) return -1;
+    const int64_t a = rowgram_ws_bytes(N, F), b = F >= 4 ? rowgram_ws_bytes(N, F & ~3) : 0;
+    return a > b ? a : b;
+}
+
+extern "C" int dm_pca_rowgram(const float *X, int64_t N, int F, int64_t ld, const float *shift, double *K, int accumulate,
+                              void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (check_wide_x("dm_pca_rowgram", X, N, F, ld)) return -1;
+    DM_REQUIRE(K, "dm_pca_rowgram: K is NULL");
+    const int64_t need = dm_pca_rowgram_workspace_bytes(N, F);
+    DM_REQUIRE(need == 0 || workspace, "dm_pca_rowgram: workspace is NULL");
+    DM_REQUIRE(workspace_bytes >= need, "dm_pca_rowgram: workspace of %lld bytes, need %lld", (long long)workspace_bytes,
+               (long long)need);
+    hipStream_t s = (hipStream_t)stream;
+    double *ws = (double *)workspace;
+    int acc = accumulate ? 1 : 0;
+    const int Fv = vec4_ok(X, ld) ? F & ~3 : 0;         // the features the 16-byte form takes
+    if (Fv) {
+        launch_rowgram<true>(s, X, (int)N, Fv, ld, shift, K, acc, ws);
+        acc = 1;
+    }
+    if (F > Fv) launch_rowgram<false>(s, X + Fv, (int)N, F - Fv, ld, shift ? shift + Fv : nullptr, K, acc, ws);
+    return dm_launch_status("dm_pca_rowgram");
+}
+
+extern "C" int dm_pca_components(const float *X, int64_t N, int F, int64_t ld, const float *shift, const float *W, int k,
+                                 double *V, void *stream)
+{
+    if (check_wide_x("dm_pca_components", X, N, F, ld)) return -1;
+    DM_REQUIRE(W && V, "dm_pca_components: W / V is NULL");
+    DM_REQUIRE(k >= 1 && k <= DM_PCA_MAX_COMPONENTS, "dm_pca_components: k = %d components, supported 1 .. %d", k,
+               DM_PCA_MAX_COMPONENTS);
+    hipStream_t s = (hipStream_t)stream;
+    const bool v4 = vec4_ok(X, ld);
+    if (k <= 16) launch_components<16>(v4, s, X, (int)N, F, ld, shift, W, k, V);
+    else if (k <= 32) launch_components<32>(v4, s, X, (int)N, F, ld, shift, W, k, V);
+    else launch_components<64>(v4, s, X, (int)N, F, ld, shift, W, k, V);
+    return dm_launch_status("dm_pca_components");
+}
 
 extern "C" int64_t dm_pca_colsum_workspace_bytes(int64_t N, int F)
 {

@@ -1,5 +1,5 @@
 """PCA stage of the pipeline: mirror of run_dim_reduction.py (fit_PCA lines 14-50, process_PCA 52-92, the PCA branch of
-dim_reduction 177-281) on dynamorph_amd.pca.PCA; and its UMAP stage: fit_umap (143-207) and umap_transform (94-127) on
+dim_reduction 177-281) on dynamorph_amd.pca.PCA / WidePCA; and its UMAP stage: fit_umap (143-207) and umap_transform (94-127) on
 dynamorph_amd.umap_layout.UMAPEmbedding.
 
 File names are the ones process_VAE writes: <prefix>_latent_space<suffix>.pkl in, <prefix>_latent_space<suffix>_PCAed.pkl
@@ -12,7 +12,7 @@ import pickle
 import numpy as np
 
 from . import knn as _knn
-from .pca import PCA
+from .pca import MAX_FEATURES, PCA, WidePCA
 
 
 def _sklearn_available():
@@ -25,11 +25,13 @@ def _sklearn_available():
 
 def fit_PCA(train_data, weights_dir, labels=None, conditions=None, n_components=0.5, **kw):
     """Fit PCA(n_components) to the pooled latents, write <weights_dir>/pca_model.pkl (protocol 4) and return the fitted
-    device PCA.  The pickle holds the fitted sklearn PCA when scikit-learn is importable (what the reference's
+    device PCA (WidePCA, the sample-space route, when the latents have more than MAX_FEATURES columns: the VQ_VAE_z32
+    latents).  The pickle holds the fitted sklearn PCA when scikit-learn is importable (what the reference's
     process_PCA unpickles), else this package's PCA with its state on the host.  PCA.png is drawn when matplotlib imports."""
     os.makedirs(weights_dir, exist_ok=True)
     model_path = os.path.join(weights_dir, 'pca_model.pkl')
-    pca = PCA(n_components, **kw)
+    wide = np.ndim(train_data) == 2 and np.shape(train_data)[1] > MAX_FEATURES
+    pca = (WidePCA if wide else PCA)(n_components, **kw)
     pcas = pca.fit_transform(train_data)
     with open(model_path, 'wb') as f:
         pickle.dump(pca.to_sklearn() if _sklearn_available() else pca, f, protocol=4)
@@ -70,7 +72,9 @@ def load_model(weights_dir, device=None):
             obj = pickle.load(f)
     except Exception as ex:
         raise ValueError("Error in loading pre-saved PCA weights") from ex
-    return obj if isinstance(obj, PCA) else PCA.from_sklearn(obj, device=device)
+    if isinstance(obj, PCA):
+        return obj
+    return (WidePCA if int(obj.n_features_in_) > MAX_FEATURES else PCA).from_sklearn(obj, device=device)
 
 
 def process_PCA(input_dir, output_dir, weights_dir, prefix, suffix='_after', pca=None):

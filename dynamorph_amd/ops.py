@@ -1374,6 +1374,48 @@ def pca_transform(X, V, shift=None, out=None):
     return out
 
 
+@_op
+def pca_rowgram(X, shift=None, K=None, accumulate=False, workspace=None):
+    """K (N, N) float64 (+)= (X - shift)(X - shift)^T (dm_pca_rowgram); shift (F,) fp32 or None."""
+    lib = L.load()
+    p, N, F, ld = _rows(X)
+    nbytes = lib.dm_pca_rowgram_workspace_bytes(N, F)
+    if nbytes < 0:
+        raise ValueError(f"dm_pca_rowgram: bad shape ({N}, {F})")
+    if shift is not None and shift.numel() != F:
+        raise ValueError(f"dm_pca_rowgram: shift has {shift.numel()} entries, F = {F}")
+    if K is None:
+        if accumulate:
+            raise ValueError("dm_pca_rowgram: accumulate needs K")
+        K = _new((N, N), X, torch.float64)
+    elif tuple(K.shape) != (N, N) or not K.is_contiguous():
+        raise ValueError(f"dm_pca_rowgram: K has shape {tuple(K.shape)}, need a contiguous ({N}, {N})")
+    if workspace is None or workspace.numel() * 8 < nbytes:
+        workspace = _pca_workspace(nbytes, X)
+    L.check(lib.dm_pca_rowgram(p, N, F, ld, _ptr(shift), _ptr(K, torch.float64), 1 if accumulate else 0,
+                               _ptr(workspace, torch.float64), workspace.numel() * 8, _stream()), "dm_pca_rowgram")
+    return K
+
+
+@_op
+def pca_components(X, W, shift=None, out=None):
+    """V (k, F) float64 = W (X - shift) (dm_pca_components); W (k, N) fp32."""
+    lib = L.load()
+    p, N, F, ld = _rows(X)
+    if W.dim() != 2 or W.shape[1] != N:
+        raise ValueError(f"dm_pca_components: W has shape {tuple(W.shape)}, need (k, {N})")
+    if shift is not None and shift.numel() != F:
+        raise ValueError(f"dm_pca_components: shift has {shift.numel()} entries, F = {F}")
+    k = W.shape[0]
+    if out is None:
+        out = _new((k, F), X, torch.float64)
+    elif tuple(out.shape) != (k, F) or not out.is_contiguous():
+        raise ValueError(f"dm_pca_components: out has shape {tuple(out.shape)}, need a contiguous ({k}, {F})")
+    L.check(lib.dm_pca_components(p, N, F, ld, _ptr(shift), _ptr(W), k, _ptr(out, torch.float64), _stream()),
+            "dm_pca_components")
+    return out
+
+
 # ----------------------------------------------------------------------------- exact k-NN graph of the latents
 KNN_MAX_K = 256                # DM_KNN_MAX_K
 KNN_MAX_SLACK = 256            # DM_KNN_MAX_SLACK

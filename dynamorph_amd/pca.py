@@ -7,6 +7,10 @@ device: fp64 column sums (dm_pca_colsum), then the centred Gram matrix (X - s)^T
 chunks merged with the pairwise (Chan) update, so the data cross PCIe once.  Finalisation -- eigendecomposition, component
 count, signs -- is plain float64 torch and runs on a CPU tensor as well.  Every fitted attribute follows scikit-learn's names
 and conventions, so PCA(0.5) here chooses the components and signs the reference's call chooses.
+
+Latents wider than MAX_FEATURES (VQ_VAE_z32: 65536 features) take the sample-space route of WidePCA: the N x N matrix
+K = (X - s)(X - s)^T (dm_pca_rowgram) has the covariance's non-zero spectrum, and its eigenvectors U give the components as
+Lambda^(-1/2) U^T (X - s) (dm_pca_components).  finalize_samples / orient_components are its float64 finalisation.
 """
 import numpy as np
 import torch
@@ -15,6 +19,8 @@ from . import ops
 
 MAX_FEATURES = 16384           # DM_PCA_MAX_FEATURES
 MAX_COMPONENTS = 512           # DM_PCA_MAX_COMPONENTS (one transform launch; more are done in blocks of this many)
+WIDE_MAX_SAMPLES = 24576       # DM_PCA_WIDE_MAX_SAMPLES
+WIDE_MAX_FEATURES = 1 << 20    # DM_PCA_WIDE_MAX_FEATURES
 _ATTRS = ("mean_", "components_", "explained_variance_", "explained_variance_ratio_", "singular_values_",
           "noise_variance_", "n_components_", "n_samples_", "n_features_in_")
 
@@ -108,6 +114,73 @@ def finalize(C, mean, N, n_components=0.5):
     }
 
 
+def _check_wide_shape(N, F):
+    if N < 2:
+        raise ValueError(f"PCA needs at least 2 samples, got {N}")
+    if F < 1:
+        raise ValueError("PCA needs at least 1 feature")
+    if F > WIDE_MAX_FEATURES:
+        raise ValueError(f"PCA on the GPU supports up to {WIDE_MAX_FEATURES} features, got {F}")
+    if N > WIDE_MAX_SAMPLES:
+        raise ValueError(f"PCA of {N} samples of {F} features: more than {MAX_FEATURES} features need the sample-space route, "
+                         f"which holds all rows and their {N} x {N} float64 Gram matrix on the device and supports up to "
+                         f"{WIDE_MAX_SAMPLES} samples")
+
+
+def finalize_samples(K, N, F, n_components=0.5):
+    """The sample-space finalisation: from the float64 matrix K = (X - s)(X - s)^T (N x N, any device, s any shift) to the
+    fitted attributes that do not need X (a dict as finalize returns, without mean_ and components_) and "W": the
+    (n_components_, N) float64 tensor (U_k / sqrt(lambda_k))^T on K's device, whose product with X - s is the components.
+
+    K is double-centred in float64 -- K - row means - column means + grand mean = (X - mean)(X - mean)^T whatever s was --
+    in place.  eigh in float64 on K's device; eigenvalues clipped at 0; the top min(N, F) are the spectrum of the full SVD
+    _fit_full's 'full' solver computes.  A requested component whose eigenvalue is at most N 2^-52 lambda_max is not
+    defined (centred data have rank <= N - 1): ValueError."""
+    _check_wide_shape(N, F)
+    _check_n_components(n_components)
+    if tuple(K.shape) != (N, N) or K.dtype != torch.float64:
+        raise ValueError(f"K has shape {tuple(K.shape)} and dtype {K.dtype}, need a float64 ({N}, {N})")
+    rm = K.mean(dim=1)
+    cm = K.mean(dim=0)
+    gm = rm.mean()
+    K -= rm[:, None]
+    K -= cm[None, :]
+    K += gm
+    evals, evecs = torch.linalg.eigh(K)
+    m = min(N, F)
+    evals = torch.flip(evals, (0,))[:m].clamp_min(0.0)
+    lam = evals.cpu().numpy()
+    ev = lam / (N - 1)
+    ratio = ev / ev.sum() if ev.sum() > 0 else np.zeros_like(ev)
+    k = select_n_components(n_components, ratio, N, F)
+    rank = int((lam > N * 2.0 ** -52 * lam[0]).sum())
+    if k > rank:
+        raise ValueError(f"n_components={n_components!r} asks for {k} components of {N} samples, but at most {rank} "
+                         f"components are defined (the others have zero variance: centred data have rank <= n_samples - 1)")
+    W = (torch.flip(evecs, (1,))[:, :k] / evals[:k].sqrt()).T.contiguous()
+    return {
+        "W": W,
+        "explained_variance_": ev[:k].copy(),
+        "explained_variance_ratio_": ratio[:k].copy(),
+        "singular_values_": np.sqrt(ev[:k] * (N - 1)),
+        "noise_variance_": float(ev[k:].mean()) if k < m else 0.0,
+        "n_components_": int(k),
+        "n_samples_": int(N),
+        "n_features_in_": int(F),
+    }
+
+
+def orient_components(V):
+    """Rows of V (k x F float64 tensor) scaled to unit length and signed by svd_flip(u_based_decision=False), as finalize
+    signs them: the entry of largest magnitude of each component is positive.  In place; returns V."""
+    V /= torch.linalg.vector_norm(V, dim=1, keepdim=True)
+    idx = V.abs().argmax(dim=1)
+    signs = torch.sign(V.gather(1, idx[:, None]))
+    signs[signs == 0] = 1.0
+    V *= signs
+    return V
+
+
 def _host_rows(X):
     """Host data as a 2-D torch tensor (a view when it can be)."""
     if isinstance(X, np.ndarray):
@@ -124,6 +197,8 @@ class PCA:
 
     X: a CUDA tensor (used in place: fp32, unit column stride) or host data (numpy array / CPU tensor, streamed in chunks of
     `chunk_rows` rows through pinned staging).  transform returns a CUDA fp32 tensor."""
+
+    _check_shape = staticmethod(_check_shape)
 
     def __init__(self, n_components=0.5, whiten=False, chunk_rows=65536, device=None, eigh_device="cuda"):
         if whiten:
@@ -231,8 +306,8 @@ class PCA:
             self._dev[key] = (V, torch.as_tensor(s).to(device), corr)
         return self._dev[key]
 
-    def transform(self, X):
-        """(X - mean_) components_^T as a CUDA fp32 tensor (N, n_components_)."""
+    def _device_rows(self, X):
+        """X as the fp32 device matrix (n, n_features_in_) the kernels read."""
         if not hasattr(self, "components_"):
             raise ValueError("this PCA instance is not fitted yet")
         if torch.is_tensor(X) and X.is_cuda:
@@ -243,6 +318,11 @@ class PCA:
             x = x.to(dev, dtype=torch.float32)
         if x.dim() != 2 or x.shape[1] != self.n_features_in_:
             raise ValueError(f"X has shape {tuple(x.shape)}, expected (n, {self.n_features_in_})")
+        return x
+
+    def transform(self, X):
+        """(X - mean_) components_^T as a CUDA fp32 tensor (N, n_components_)."""
+        x = self._device_rows(X)
         V, s, corr = self._operands(x.device)
         with torch.cuda.device(x.device):
             k = V.shape[0]
@@ -286,8 +366,7 @@ class PCA:
         attrs["noise_variance_"] = float(attrs["noise_variance_"])
         for a in ("n_components_", "n_samples_", "n_features_in_"):
             attrs[a] = int(attrs[a])
-        if attrs["n_features_in_"] > MAX_FEATURES:
-            _check_shape(2, attrs["n_features_in_"])
+        cls._check_shape(2, attrs["n_features_in_"])
         self._set(attrs)
         return self
 
@@ -296,3 +375,133 @@ class PCA:
         st["_dev"] = {}
         st["_home"] = None
         return st
+
+
+class WidePCA(PCA):
+    """PCA for latents of more than MAX_FEATURES features (the VQ_VAE_z32 latents: 65536) and up to WIDE_MAX_SAMPLES rows,
+    by the sample-space route: K = (X - s)(X - s)^T (N x N float64, dm_pca_rowgram), double-centred and decomposed in
+    float64, components Lambda^(-1/2) U^T (X - s) (dm_pca_components).  Same constructor, attributes, methods and pickle
+    as PCA.  All row pairs are needed, so host data are uploaded (in chunks of rows through pinned staging) into one
+    resident fp32 matrix instead of being streamed."""
+
+    _check_shape = staticmethod(_check_wide_shape)
+    STAGE_BYTES = 1 << 28               # pinned staging: two buffers of at most this many bytes
+
+    # ------------------------------------------------------------------------------------------------------ fitting
+    def _resident(self, X):
+        """X as one fp32 matrix on the device: a CUDA tensor as it lies (fp32, unit column stride), host data uploaded."""
+        if torch.is_tensor(X) and X.is_cuda:
+            if X.dim() != 2:
+                raise ValueError(f"PCA expects a 2-D (samples, features) array, got shape {tuple(X.shape)}")
+            _check_wide_shape(*X.shape)
+            self._check_memory(X.device, X.shape[0], X.shape[1], resident=True)
+            return X if X.dtype == torch.float32 else X.float()
+        X = _host_rows(X)
+        N, F = X.shape
+        _check_wide_shape(N, F)
+        dev = self._device_of(X)
+        self._check_memory(dev, N, F, resident=False)
+        with torch.no_grad(), torch.cuda.device(dev):
+            x = torch.empty((N, F), dtype=torch.float32, device=dev)
+            if X.dtype == torch.float32 and X.is_contiguous() and X.is_pinned():
+                x.copy_(X, non_blocking=True)
+                torch.cuda.current_stream().synchronize()
+                return x
+            cr = max(1, min(self.chunk_rows, N, self.STAGE_BYTES // (4 * F)))
+            stage = [torch.empty((cr, F), dtype=torch.float32, pin_memory=True) for _ in range(2)]
+            ev_in = [torch.cuda.Event() for _ in range(2)]       # chunk has left staging k
+            for it, lo in enumerate(range(0, N, cr)):
+                k = it & 1
+                m = min(cr, N - lo)
+                ev_in[k].synchronize()
+                stage[k][:m].copy_(X[lo:lo + m])
+                x[lo:lo + m].copy_(stage[k][:m], non_blocking=True)
+                ev_in[k].record()
+            torch.cuda.current_stream().synchronize()
+        return x
+
+    @staticmethod
+    def _check_memory(dev, N, F, resident):
+        """X (unless it is on the device already), K, the row Gram's workspace and eigh's eigenvectors and workspace
+        (taken as 3 N^2 float64) against the free memory of the device."""
+        need_x = 0 if resident else 4 * N * F
+        need_k = 8 * N * N
+        need_ws = max(int(ops.L.load().dm_pca_rowgram_workspace_bytes(N, F)), 0)
+        need_eigh = 3 * 8 * N * N
+        free, _ = torch.cuda.mem_get_info(dev)
+        need = need_x + need_k + max(need_ws, need_eigh)
+        if need > free:
+            raise ValueError(f"PCA of {N} samples of {F} features needs {need / 2**30:.1f} GiB on the device (X "
+                             f"{need_x / 2**30:.1f}, K {need_k / 2**30:.1f}, row-Gram workspace {need_ws / 2**30:.1f}, eigh "
+                             f"{need_eigh / 2**30:.1f} GiB), {free / 2**30:.1f} GiB are free")
+
+    @staticmethod
+    def _blocks(F):
+        return [(lo, min(lo + MAX_FEATURES, F)) for lo in range(0, F, MAX_FEATURES)]
+
+    def gram(self, x):
+        """(mean (F,) float64, s = fp32(mean), K (N, N) float64 = (x - s)(x - s)^T) of a resident fp32 matrix."""
+        N, F = x.shape
+        mean = torch.cat([ops.pca_colsum(x[:, lo:hi]) for lo, hi in self._blocks(F)]) / N
+        s = mean.float()
+        return mean, s, ops.pca_rowgram(x, s)
+
+    def _fit_resident(self, x):
+        N, F = x.shape
+        with torch.no_grad(), torch.cuda.device(x.device):
+            mean, s, K = self.gram(x)
+            attrs = finalize_samples(K.cpu() if self.eigh_device == "cpu" else K, N, F, self.n_components)
+            del K
+            W = attrs.pop("W").to(device=x.device, dtype=torch.float32)
+            k = W.shape[0]
+            V = torch.empty((k, F), dtype=torch.float64, device=x.device)
+            for j in range(0, k, MAX_COMPONENTS):
+                ops.pca_components(x, W[j:j + MAX_COMPONENTS].contiguous(), s, out=V[j:j + MAX_COMPONENTS])
+            attrs["components_"] = orient_components(V).cpu().numpy()
+            attrs["mean_"] = mean.cpu().numpy()
+        self._set(attrs, x.device)
+
+    def fit(self, X, chunk_rows=None):
+        if chunk_rows:
+            self.chunk_rows = int(chunk_rows)
+        self._fit_resident(self._resident(X))
+        return self
+
+    def fit_transform(self, X, chunk_rows=None):
+        if chunk_rows:
+            self.chunk_rows = int(chunk_rows)
+        x = self._resident(X)                       # uploaded once for the fit and the transform
+        self._fit_resident(x)
+        return self.transform(x)
+
+    def moments(self, X, chunk_rows=None):
+        raise ValueError("WidePCA forms the N x N row Gram matrix (gram), not the F x F moments")
+
+    # ---------------------------------------------------------------------------------------------------- applying
+    def _operands(self, device):
+        """Per column block of at most MAX_FEATURES features: (lo, hi, V block (k, hi - lo) contiguous fp32, shift block);
+        and the float64 projection of mean - fp32(mean), removed afterwards."""
+        key = str(device)
+        if key not in self._dev:
+            comps = np.asarray(self.components_)
+            mean = np.asarray(self.mean_, dtype=np.float64)
+            s = mean.astype(np.float32)
+            corr = (mean - s.astype(np.float64)) @ comps.astype(np.float64, copy=False).T
+            blocks = [(lo, hi, torch.as_tensor(np.ascontiguousarray(comps[:, lo:hi], dtype=np.float32)).to(device),
+                       torch.as_tensor(s[lo:hi]).to(device)) for lo, hi in self._blocks(comps.shape[1])]
+            self._dev[key] = (blocks, torch.as_tensor(corr).to(device) if np.any(corr != 0) else None)
+        return self._dev[key]
+
+    def transform(self, X):
+        """(X - mean_) components_^T as a CUDA fp32 tensor (N, n_components_): dm_pca_transform per column block, the blocks
+        added in float64 in order and rounded to fp32 once."""
+        x = self._device_rows(X)
+        blocks, corr = self._operands(x.device)
+        with torch.no_grad(), torch.cuda.device(x.device):
+            Y = torch.zeros((x.shape[0], self.n_components_), dtype=torch.float64, device=x.device)
+            for lo, hi, V, s in blocks:
+                for j in range(0, V.shape[0], MAX_COMPONENTS):
+                    Y[:, j:j + MAX_COMPONENTS] += ops.pca_transform(x[:, lo:hi], V[j:j + MAX_COMPONENTS], s)
+            if corr is not None:
+                Y -= corr
+            return Y.float()

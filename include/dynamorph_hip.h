@@ -789,6 +789,29 @@ int dm_pca_gram(const float *X, int64_t N, int F, int64_t ld, const float *shift
  * of run_dim_reduction.py:85 (X @ components_.T - mean_ @ components_.T).  shift NULL = no centring. */
 int dm_pca_transform(const float *X, int64_t N, int F, int64_t ld, const float *shift, const float *V, int k, float *Y,
                      void *stream);
+/* The sample-space ("wide") route, for latents of more than DM_PCA_MAX_FEATURES features (VQ_VAE_z32: 64 x 32 x 32 = 65536):
+ * K = (X - s)(X - s)^T (N x N) has the non-zero spectrum of the F x F covariance, and its eigenvectors U give the components
+ * as Lambda^(-1/2) U^T (X - s).  X as above with 1 <= N <= DM_PCA_WIDE_MAX_SAMPLES (K is 4.8 GB there and X at 65536 features
+ * 6.4 GB; the float64 eigh of K on the device, which follows, works at 24576 and fails in its workspace query at 32768) and
+ * 1 <= F <= DM_PCA_WIDE_MAX_FEATURES.  Every summation order is fixed by (N, F). */
+#define DM_PCA_WIDE_MAX_SAMPLES 24576
+#define DM_PCA_WIDE_MAX_FEATURES (1 << 20)
+#define DM_PCA_ROWGRAM_SLAB_FEATURES 256   /* features accumulated in fp32 before a row-Gram partial is added in float64 */
+#define DM_PCA_COMPONENTS_SLAB_ROWS 256    /* rows accumulated in fp32 before a components partial is added in float64 */
+/* HOST: bytes of device workspace dm_pca_rowgram needs (0 when the plan has one feature range; -1 for a bad shape). */
+int64_t dm_pca_rowgram_workspace_bytes(int64_t N, int F);
+/* K (N x N float64, full and symmetric) = (X - shift)(X - shift)^T, or K += that when accumulate != 0 (a caller can go
+ * through column blocks of one X): the sample-space counterpart of dm_pca_gram for PCA._fit_full on N < F data
+ * (run_dim_reduction.py:32-35).  shift: F floats, NULL = no centring.  fp32 products within slabs of
+ * DM_PCA_ROWGRAM_SLAB_FEATURES features, slabs and feature ranges added in float64 in a fixed order, no atomics: repeated
+ * calls are bit-identical.  workspace may be NULL when dm_pca_rowgram_workspace_bytes is 0. */
+int dm_pca_rowgram(const float *X, int64_t N, int F, int64_t ld, const float *shift, double *K, int accumulate,
+                   void *workspace, int64_t workspace_bytes, void *stream);
+/* V (k x F float64, row-major) = W (X - shift), W: k x N fp32 row-major, 1 <= k <= DM_PCA_MAX_COMPONENTS: the components
+ * Lambda^(-1/2) U^T (X - s) of the sample-space route.  fp32 products within slabs of DM_PCA_COMPONENTS_SLAB_ROWS rows, slabs
+ * added in float64 in row order and stored unrounded; X crosses HBM once per 64 components.  shift NULL = no centring. */
+int dm_pca_components(const float *X, int64_t N, int F, int64_t ld, const float *shift, const float *W, int k, double *V,
+                      void *stream);
 
 /* ===== exact k-nearest-neighbour graph of the latents (the graph umap.UMAP takes as precomputed_knn) ==== */
 /* X: M x F fp32 row-major, leading dimension ldx >= F, 1 <= F <= DM_KNN_MAX_FEATURES: the point set.  Queries: Q (R x F,
