@@ -808,6 +808,320 @@ void convT_phase_kernel(Operand in, WeightView wv, float *__restrict__ out, Epil
     }
 }
 
+// ============================================================================ kernel E
+// ConvTranspose2d(4,2,1) forward (bias, ReLU, no side input) as shifted products: no matrix column holds a zero weight.
+// Input column X feeds both x phases of output position X (kx = 1 | 2: the CENTRE product) and the facing phase of its two
+// neighbours (px = 1 of X - 1 with kx = 0, px = 0 of X + 1 with kx = 3: the SIDE product); rows likewise with ky.  Both
+// products take the position's own channels as the A operand -- no halo column is staged -- and
+//     out[.][X][px] = centre[X] + side[X + (px ? 1 : -1)]
+// The side product moves one M row: a register rename inside the lane, one ds_bpermute per M tile for the row that crosses
+// the lane groups (kernel A2's recipe, here in both directions by the lane's px).  A tile spans the image row, so the value
+// that would come from column -1 or W is the zero padding itself, never a product.
+//   COUT = 4 (dec.2): n = (co, py, px) fills the N tile.  The row direction needs no shift at all: accumulator S_k holds output
+//            row 2k in its py = 0 lanes and row 2k - 1 in its py = 1 lanes, both made of input rows k (ky = 1 | 0) and k - 1
+//            (ky = 3 | 2), and the matrix pipe adds the two.  2 products x 2 rows x CIN/4 = CIN MFMAs per 16 positions where
+//            kernel B issues 2.25 CIN.  A tile takes S_y0 .. S_(y0+TH-1) -- its first output row is the tile above's last --
+//            and the image's last tile also S_H (input row H - 1 alone, py = 1 lanes), on a wave that changes with the sample.
+//   COUT = 8 (dec.0): one N tile per phase row py (n = (px, co)) as in kernel C, whose A rows are Y and Y + (py ? 1 : -1):
+//            2 CIN MFMAs per 16 positions (kernel C: 3 CIN).
+// side_send: the request for the row that crosses the lane groups -- px = 0 takes the side value of column X - 1 (the lane group
+// below sends its last row), px = 1 that of X + 1; side_join, as late as the caller can place it: centre + shifted side.
+template <int CG>
+__device__ __forceinline__ void side_send(const f32x4 (&V)[CG], bool px, int nb_addr, float (&xs)[CG])
+{
+#pragma unroll
+    for (int i = 0; i < CG; ++i) {
+        // (opaque, no instruction: hipcc otherwise turns the select of two elements into ONE element at a per-lane index,
+        //  which it serves from scratch)
+        float first = V[i].x;
+        asm("" : "+v"(first));
+        xs[i] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(nb_addr, __builtin_bit_cast(int, px ? first : V[i].w)));
+    }
+}
+template <int CG>
+__device__ __forceinline__ void side_join(const f32x4 (&U)[CG], const f32x4 (&V)[CG], const float (&xs)[CG], bool px, bool wrap,
+                                          f32x4 (&o)[CG])
+{
+#pragma unroll
+    for (int i = 0; i < CG; ++i) {
+        // wrap: the row comes from the neighbouring M tile, or is the padding column
+        float far = px ? (i + 1 < CG ? xs[i + 1 < CG ? i + 1 : i] : 0.f) : (i > 0 ? xs[i > 0 ? i - 1 : i] : 0.f);
+        const f32x4 v = V[i];
+        float vx = v.x, vy = v.y;                          // (opaque, as in side_send)
+        asm("" : "+v"(vx), "+v"(vy), "+v"(far));
+        const float e = wrap ? far : xs[i];
+        o[i] = U[i] + (px ? (f32x4){v.y, v.z, v.w, e} : (f32x4){e, vx, vy, v.z});
+    }
+}
+
+template <int CIN, int TH, int TW, int WPS>
+__global__ __launch_bounds__(DM_BLOCK, WPS)
+void convT_shift4_kernel(Operand in, WeightView wv, float *__restrict__ out, Epilogue ep, int Cphys, int H, int W, int ntiles)
+{
+    constexpr int COUT = 4, IH = TH + 1, RS = TW, COLS4 = RS / 4;
+    constexpr int PSRAW = IH * RS;
+    constexpr int PS = PSRAW + ((16 - (PSRAW % 32)) + 32) % 32;      // PS == 16 (mod 32)
+    constexpr int CG = TW / 16, C4 = CIN / 4, RPW = TH / 4;          // S rows per wave
+    static_assert(CIN % 4 == 0 && TH % 4 == 0 && TW % 16 == 0, "shape");
+    __shared__ __attribute__((aligned(16))) float tile[CIN * PS];   // rows y0 - 1 .. y0 + TH - 1, the image's columns
+    __shared__ __attribute__((aligned(16))) float s_coef[DM_COEF_MAX_C * 4];
+
+    const int tiles_y = H / TH;                            // (TW == W)
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), m = lane & 15, kq = lane >> 4;
+    const int OH = 2 * H, OW = 2 * W;
+    const int co = m >> 2;
+    const bool py = (m >> 1) & 1, px = m & 1;
+
+    TileStage<CIN, IH, COLS4, RS, PS, false> stage;
+    stage.init(H, W);
+    int tidx = blockIdx.x, b = 0, y0 = 0;
+    if (tidx < ntiles) {
+        y0 = (tidx % tiles_y) * TH; b = tidx / tiles_y;
+        stage.issue(in, b, Cphys, H, W, y0 - 1, 0);
+        stage_coef(s_coef, in, b, Cphys);
+    }
+
+    // B[k = kq][n = m] of K step (c4, a): channel 4 c4 + kq of input row k (a = 0) or k - 1 (a = 1)
+    float wU[C4][2], wV[C4][2];
+#pragma unroll
+    for (int c4 = 0; c4 < C4; ++c4)
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const int ky = a ? (py ? 2 : 3) : (py ? 0 : 1);
+            const long long base = wv.off + co * wv.sn + (4 * c4 + kq) * wv.sc + ky * wv.sky;
+            wU[c4][a] = wv.w[base + (px ? 2 : 1) * wv.skx];
+            wV[c4][a] = wv.w[base + (px ? 0 : 3) * wv.skx];
+        }
+    const float bias = ep.bias ? ep.bias[co] : 0.f;
+    const float *ap = tile + kq * PS + m + RPW * wave * RS;          // A[m][k = kq] of the wave's first LDS row
+    const int nb_addr = ((px ? lane + 16 : lane - 16) & 63) * 4;
+    const bool wrap = px ? kq == 3 : kq == 0;
+    EpiCtx<SIDE_NONE> cx;
+    const long long sample_elems = (long long)COUT * OH * OW;
+    // byte offset of the lane's channel plane, output row 2k - py of S_0, its 4 output columns of a 16-position group
+    const int chan_off = ((co * OH - (py ? 1 : 0)) * OW + 8 * kq + 4 * (px ? 1 : 0)) * 4;
+
+    // one S row: column shift, bias, ReLU, the two x phases interleaved with the partner lane, one 16-byte store per M tile
+    auto emit = [&](const f32x4 (&U)[CG], const f32x4 (&V)[CG], int k, bool valid) __attribute__((always_inline)) {
+        f32x4 o[CG];
+        float xs[CG];
+        side_send<CG>(V, px, nb_addr, xs);
+        side_join<CG>(U, V, xs, px, wrap, o);
+#pragma unroll
+        for (int i = 0; i < CG; ++i) {
+            const f32x4 v = bias_relu(o[i], ep, bias);
+            const f32x4 pv = lane_xor1(v);
+            const f32x4 q = px ? (f32x4){pv.z, v.z, pv.w, v.w} : (f32x4){v.x, pv.x, v.y, pv.y};
+            __builtin_amdgcn_raw_buffer_store_b128(q, cx.out_r, valid ? chan_off + (2 * k * OW + 32 * i) * 4 : DM_VOFF_NONE, 0, 0);
+        }
+    };
+
+    while (tidx < ntiles) {
+        __syncthreads();
+        stage.commit(tile, s_coef, Cphys, H, W, y0 - 1, 0, in.mode);
+        __syncthreads();
+        const int cb = b, cy0 = y0;
+        const int next = tidx + gridDim.x;
+        {                                              // (no next tile: empty descriptor, every load returns 0)
+            const int t = next < ntiles ? next : tidx;
+            y0 = (t % tiles_y) * TH; b = t / tiles_y;
+        }
+        const auto scx = stage.begin(in, next < ntiles, b, Cphys, H, W, y0 - 1, 0);
+        const bool recoef = next < ntiles && coef_changes(in, cb, b);       // (uniform) the next tile is another sample's
+        f32x4 cfn = {1.f, 0.f, 0.f, 0.f};
+        if (recoef) cfn = coef_fetch(in, b, Cphys);
+        cx.rebase(ep, out, sample_elems, cb);
+#pragma unroll
+        for (int e = 0; e < decltype(stage)::N; ++e) stage.issue_one(e, scx);
+        {
+            float av[RPW + 1][CG][C4];                     // LDS rows RPW wave .. RPW wave + RPW: S row j reads rows j + 1 and j
+#pragma unroll
+            for (int r = 0; r <= RPW; ++r)
+#pragma unroll
+                for (int i = 0; i < CG; ++i)
+#pragma unroll
+                    for (int c4 = 0; c4 < C4; ++c4) av[r][i][c4] = ap[r * RS + 16 * i + 4 * c4 * PS];
+            // JB S rows per batch of products: all of the wave's while their accumulators fit the three-wave register budget
+            constexpr int JB = CG <= 2 ? RPW : 1;
+#pragma unroll
+            for (int j0 = 0; j0 < RPW; j0 += JB) {
+                f32x4 U[JB][CG], V[JB][CG];
+#pragma unroll
+                for (int j = 0; j < JB; ++j)
+#pragma unroll
+                    for (int i = 0; i < CG; ++i) { U[j][i] = (f32x4){0.f, 0.f, 0.f, 0.f}; V[j][i] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int c4 = 0; c4 < C4; ++c4)
+#pragma unroll
+                    for (int a = 0; a < 2; ++a)
+#pragma unroll
+                        for (int j = 0; j < JB; ++j)
+#pragma unroll
+                            for (int i = 0; i < CG; ++i) {
+                                const float x = av[j0 + j + 1 - a][i][c4];
+                                U[j][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(x, wU[c4][a], U[j][i], 0, 0, 0);
+                                V[j][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(x, wV[c4][a], V[j][i], 0, 0, 0);
+                            }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int j = 0; j < JB; ++j) {
+                    const int k = cy0 + RPW * wave + j0 + j;
+                    emit(U[j], V[j], k, !(py && k == 0));
+                }
+            }
+        }
+        if (cy0 + TH == H && wave == (cb & 3)) {           // (uniform) S_H: input row H - 1 alone, output row 2H - 1
+            f32x4 U[CG], V[CG];
+#pragma unroll
+            for (int i = 0; i < CG; ++i) { U[i] = (f32x4){0.f, 0.f, 0.f, 0.f}; V[i] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+            float av[CG][C4];
+#pragma unroll
+            for (int i = 0; i < CG; ++i)
+#pragma unroll
+                for (int c4 = 0; c4 < C4; ++c4) av[i][c4] = tile[kq * PS + m + TH * RS + 16 * i + 4 * c4 * PS];
+#pragma unroll
+            for (int c4 = 0; c4 < C4; ++c4)
+#pragma unroll
+                for (int i = 0; i < CG; ++i) {
+                    U[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i][c4], wU[c4][1], U[i], 0, 0, 0);
+                    V[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i][c4], wV[c4][1], V[i], 0, 0, 0);
+                }
+            emit(U, V, H, py);
+        }
+        if (recoef) coef_put(s_coef, in, cfn, Cphys);   // visible after the barrier at the loop top
+        tidx = next;
+    }
+}
+
+template <int CIN, int TH, int TW, int WPS>
+__global__ __launch_bounds__(DM_BLOCK, WPS)
+void convT_shift8_kernel(Operand in, WeightView wv, float *__restrict__ out, Epilogue ep, int Cphys, int H, int W, int ntiles)
+{
+    constexpr int COUT = 8, IH = TH + 2, RS = TW, COLS4 = RS / 4;
+    constexpr int PSRAW = IH * RS;
+    constexpr int PS = PSRAW + ((16 - (PSRAW % 32)) + 32) % 32;      // PS == 16 (mod 32)
+    constexpr int CG = TW / 16, C4 = CIN / 4, RPW = TH / 4;          // input rows per wave
+    static_assert(CIN % 4 == 0 && TH % 4 == 0 && TW % 16 == 0, "shape");
+    __shared__ __attribute__((aligned(16))) float tile[CIN * PS];   // rows y0 - 1 .. y0 + TH, the image's columns
+    __shared__ __attribute__((aligned(16))) float s_coef[DM_COEF_MAX_C * 4];
+
+    const int tiles_y = H / TH;                            // (TW == W)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = lane & 15, kq = lane >> 4;
+    const int OH = 2 * H, OW = 2 * W;
+    const int co = m & 7;
+    const bool px = m >> 3;
+
+    TileStage<CIN, IH, COLS4, RS, PS, false> stage;
+    stage.init(H, W);
+    int tidx = blockIdx.x, b = 0, y0 = 0;
+    if (tidx < ntiles) {
+        y0 = (tidx % tiles_y) * TH; b = tidx / tiles_y;
+        stage.issue(in, b, Cphys, H, W, y0 - 1, 0);
+        stage_coef(s_coef, in, b, Cphys);
+    }
+
+    // B[k = kq][n = m] of N tile py, K step (c4, a): channel 4 c4 + kq of input row Y (a = 0) or Y + (py ? 1 : -1) (a = 1)
+    float wU[2][C4][2], wV[2][C4][2];
+#pragma unroll
+    for (int py = 0; py < 2; ++py)
+#pragma unroll
+        for (int c4 = 0; c4 < C4; ++c4)
+#pragma unroll
+            for (int a = 0; a < 2; ++a) {
+                const int ky = a ? (py ? 0 : 3) : (py ? 2 : 1);
+                const long long base = wv.off + co * wv.sn + (4 * c4 + kq) * wv.sc + ky * wv.sky;
+                wU[py][c4][a] = wv.w[base + (px ? 2 : 1) * wv.skx];
+                wV[py][c4][a] = wv.w[base + (px ? 0 : 3) * wv.skx];
+            }
+    const float bias = ep.bias ? ep.bias[co] : 0.f;
+    const float *ap = tile + kq * PS + m + RPW * wave * RS;          // A[m][k = kq] of the wave's first LDS row
+    const int nb_addr = ((px ? lane + 16 : lane - 16) & 63) * 4;
+    const bool wrap = px ? kq == 3 : kq == 0;
+    EpiCtx<SIDE_NONE> cx;
+    const long long sample_elems = (long long)COUT * OH * OW;
+    // byte offset of the lane's channel plane + its 4 output columns of a 16-position group
+    const int chan_off = (co * OH * OW + 8 * kq + 4 * (px ? 1 : 0)) * 4;
+
+    while (tidx < ntiles) {
+        __syncthreads();
+        stage.commit(tile, s_coef, Cphys, H, W, y0 - 1, 0, in.mode);
+        __syncthreads();
+        const int cb = b, cy0 = y0;
+        const int next = tidx + gridDim.x;
+        {                                              // (no next tile: empty descriptor, every load returns 0)
+            const int t = next < ntiles ? next : tidx;
+            y0 = (t % tiles_y) * TH; b = t / tiles_y;
+        }
+        const auto scx = stage.begin(in, next < ntiles, b, Cphys, H, W, y0 - 1, 0);
+        const bool recoef = next < ntiles && coef_changes(in, cb, b);       // (uniform) the next tile is another sample's
+        f32x4 cfn = {1.f, 0.f, 0.f, 0.f};
+        if (recoef) cfn = coef_fetch(in, b, Cphys);
+        cx.rebase(ep, out, sample_elems, cb);
+        float av[RPW + 2][CG][C4];                         // LDS rows RPW wave .. RPW wave + RPW + 1: input row j reads j .. j + 2
+#pragma unroll
+        for (int r = 0; r < RPW + 2; ++r)
+#pragma unroll
+            for (int i = 0; i < CG; ++i)
+#pragma unroll
+                for (int c4 = 0; c4 < C4; ++c4) av[r][i][c4] = ap[r * RS + 16 * i + 4 * c4 * PS];
+        constexpr int NE = decltype(stage)::N;
+        // row j's cross-lane requests leave before the products of row j + 1 and are joined behind them
+        f32x4 U[2][2][CG], V[2][2][CG];                    // [row parity][py][M tile]
+#pragma unroll
+        for (int j = 0; j <= RPW; ++j) {
+            float xs[2][CG];
+            if (j > 0) {
+#pragma unroll
+                for (int py = 0; py < 2; ++py) side_send<CG>(V[(j - 1) & 1][py], px, nb_addr, xs[py]);
+            }
+            if (j < RPW) {
+#pragma unroll
+                for (int e = 0; e < NE; ++e)
+                    if (e >= j * NE / RPW && e < (j + 1) * NE / RPW) stage.issue_one(e, scx);
+#pragma unroll
+                for (int py = 0; py < 2; ++py)
+#pragma unroll
+                    for (int i = 0; i < CG; ++i) {
+                        U[j & 1][py][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                        V[j & 1][py][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                    }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int c4 = 0; c4 < C4; ++c4)
+#pragma unroll
+                    for (int a = 0; a < 2; ++a)
+#pragma unroll
+                        for (int py = 0; py < 2; ++py)
+#pragma unroll
+                            for (int i = 0; i < CG; ++i) {
+                                const float x = av[j + 1 + (a ? (py ? 1 : -1) : 0)][i][c4];
+                                U[j & 1][py][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(x, wU[py][c4][a], U[j & 1][py][i], 0, 0, 0);
+                                V[j & 1][py][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(x, wV[py][c4][a], V[j & 1][py][i], 0, 0, 0);
+                            }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (j > 0) {
+#pragma unroll
+                for (int py = 0; py < 2; ++py) {
+                    f32x4 o[CG];
+                    side_join<CG>(U[(j - 1) & 1][py], V[(j - 1) & 1][py], xs[py], px, wrap, o);
+#pragma unroll
+                    for (int i = 0; i < CG; ++i) {
+                        const f32x4 v = bias_relu(o[i], ep, bias);
+                        const f32x4 pv = lane_xor8(v);     // partner lane holds the other x phase of the same channel
+                        const f32x4 q = px ? (f32x4){pv.z, v.z, pv.w, v.w} : (f32x4){v.x, pv.x, v.y, pv.y};
+                        __builtin_amdgcn_raw_buffer_store_b128(
+                            q, cx.out_r, chan_off + ((2 * (cy0 + RPW * wave + j - 1) + py) * OW + 32 * i) * 4, 0, 0);
+                    }
+                }
+            }
+        }
+        if (recoef) coef_put(s_coef, in, cfn, Cphys);   // visible after the barrier at the loop top
+        tidx = next;
+    }
+}
+
 // ============================================================================ kernel D
 // Backward of a Conv2d(CX -> CD, 4, stride 2, padding 1) in ONE pass over its operands: the data gradient (the
 // phase-decomposed transposed convolution of kernel C) AND the weight gradient (wgrad_mfma.hip) from one staging of
@@ -1265,6 +1579,19 @@ void launch_convT_phase(const ConvArgs &a)
 #undef DM_LP
 }
 
+// kernel E at the occupancy of the instantiations it replaces: three waves per SIMD for 4 output channels, two for 8
+template <int CIN, int COUT, int TW>
+void launch_convT_shift(const ConvArgs &a)
+{
+    constexpr int TH = conv3_th(TW, CIN), WPS = COUT == 4 ? 3 : 2;
+    if constexpr (COUT == 4)
+        hipLaunchKernelGGL((convT_shift4_kernel<CIN, TH, TW, WPS>), dim3(conv_grid(a.ntiles, WPS, 0)), dim3(DM_BLOCK), 0, a.stream,
+                           a.in, a.wv, a.out, a.ep, a.Cphys, a.H, a.W, a.ntiles);
+    else
+        hipLaunchKernelGGL((convT_shift8_kernel<CIN, TH, TW, WPS>), dim3(conv_grid(a.ntiles, WPS, 0)), dim3(DM_BLOCK), 0, a.stream,
+                           a.in, a.wv, a.out, a.ep, a.Cphys, a.H, a.W, a.ntiles);
+}
+
 }  // namespace
 
 // =============================================================================== C ABI
@@ -1414,6 +1741,11 @@ extern "C" int dm_conv4x4s2(const dm_operand *in, const dm_weight_view *w, float
     X(16, 4, 2, 2, 9, true, 16) X(16, 4, 2, 2, 9, true, 32)                                \
     X(8, 1, 1, 1, 9, true, 32) X(8, 1, 1, 1, 9, true, 64)                                  \
     X(4, 1, 1, 1, 9, true, 64)
+// Kernel E, one row per launch_convT_shift<CIN, COUT, TW>: the forward ConvTranspose2d of dec.2 and dec.0 on grids where a tile
+// spans the image row (W == TW: C3's 32 / 16 columns, C5's 64 / 32), without side input, second operand or statistics.
+// Everything else those shapes are called with (data gradients, per-sample statistics, wider grids) stays on the rows below.
+#define DM_CONVT_SHIFT_ROWS(X) X(8, 4, 32) X(16, 8, 16) X(8, 4, 64) X(16, 8, 32)
+#define DM_CS_IS(C, CO, T) (shift_ops && CIN == C && NOUT == 4 * CO && TW == T && a.W == T)
 #define DM_CP_IS(CO, T) (pix && CIN == 16 && NOUT == 4 * CO && TW == T && !per_tile)
 #define DM_C3_IS(C, NTOT, TP, PX, T) (CIN == C && (NOUT + 15) / 16 == NTOT && taps == TP && pix == PX && TW == T)
 
@@ -1431,6 +1763,10 @@ static bool conv3_has_kernel(int CIN, int NOUT, int taps, bool pix, int per_tile
 static void conv3_launch_resident(const ConvArgs &a, int taps, bool pix, int TW)
 {
     const int CIN = a.CIN, NOUT = a.NOUT, per_tile = a.per_tile;
+    const bool shift_ops = pix && !per_tile && side_mode(a.ep) == SIDE_NONE && !a.ep.stats && a.in.mode != DM_LOAD_AFFINE2;
+#define DM_CS(C, CO, T) if (DM_CS_IS(C, CO, T)) return launch_convT_shift<C, CO, T>(a);
+    DM_CONVT_SHIFT_ROWS(DM_CS)
+#undef DM_CS
 #define DM_CP(CO, T) if (DM_CP_IS(CO, T)) return launch_convT_phase<16, CO, T>(a);
 #define DM_C3(C, NTOT, NT_, NP_, TP, PX, T) if (DM_C3_IS(C, NTOT, TP, PX, T)) return launch_conv3<C, NT_, NP_, TP, PX, T>(a);
     DM_CONVT_PHASE_ROWS(DM_CP)
@@ -1438,6 +1774,7 @@ static void conv3_launch_resident(const ConvArgs &a, int taps, bool pix, int TW)
 #undef DM_CP
 #undef DM_C3
 }
+#undef DM_CS_IS
 #undef DM_CP_IS
 #undef DM_C3_IS
 
