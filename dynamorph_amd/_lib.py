@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(_HERE, "libdynamorph_hip.so")
 
 DM_LOAD_IDENT, DM_LOAD_RELU, DM_LOAD_AFFINE, DM_LOAD_AFFINE_RELU, DM_LOAD_AFFINE2 = range(5)
 DM_VQ_AUTO, DM_VQ_EXACT, DM_VQ_MFMA, DM_VQ_BF16 = range(4)
+DM_VQ_KERNEL_EXACT, DM_VQ_KERNEL_ANY, DM_VQ_KERNEL_MFMA, DM_VQ_KERNEL_CELLS = range(4)      # dm_vq_forward_plan's `kind`
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -75,6 +76,7 @@ SIGNATURES = {
     "dm_vq_forward_variant": (C.c_int, [vp, vp, vp, vp, vp, vp] + [C.c_int] * 5 + [vp, C.c_size_t, C.c_int, vp]),
     "dm_vq_forward_repeat": (C.c_int, [vp, vp, vp, vp, vp, vp] + [C.c_int] * 5 + [vp, C.c_size_t, C.c_int, C.c_int, vp]),
     "dm_vq_forward_join_supported": (C.c_int, [C.c_int] * 4),
+    "dm_vq_forward_plan": (C.c_int, [C.c_int] * 5 + [i64, C.c_int, vp, vp, vp]),
     "dm_vq_forward_join": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp] + [C.c_int] * 5 + [vp, C.c_size_t, vp]),
     "dm_vq_decode": (C.c_int, [vp, vp, vp] + [C.c_int] * 5 + [vp]),
     "dm_vq_finalize": (C.c_int, [vp, C.c_int, vp, C.c_int, i64, C.c_int, f32, vp, vp]),
@@ -218,7 +220,8 @@ call_device = _CallDevice()
 # entry points that only compute on the host (grid sizes, scratch sizes, capability queries): they touch no device, so
 # they are bound without the device guard and do NOT consume the device recorded for the launch being assembled
 HOST_ONLY_SUFFIXES = ("_num_blocks", "_num_slabs", "_scratch_floats", "_workspace_bytes", "_workspace_floats", "_supported", "_state_ints")
-HOST_ONLY = ("dm_last_error", "dm_version", "dm_backward_precision", "dm_augment_codes", "dm_reorder_with_trajectories")
+HOST_ONLY = ("dm_last_error", "dm_version", "dm_backward_precision", "dm_augment_codes", "dm_reorder_with_trajectories",
+             "dm_vq_forward_plan")
 
 
 def is_host_only(name):

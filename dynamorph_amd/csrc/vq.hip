@@ -1869,7 +1869,7 @@ extern "C" size_t dm_vq_workspace_bytes(int K, int D)
     return (size_t)vq2_layout(K, D).total * sizeof(float);
 }
 
-constexpr int VQ_PP = 2;      // positions per lane in the exact kernel (1 for embedding_dim 64: registers)
+constexpr int VQ_PP = 2;      // positions per lane in the exact kernel below embedding_dim 64 (vq_exact_pp)
 
 extern "C" int dm_vq_num_blocks(int64_t positions)
 {
@@ -1935,6 +1935,40 @@ VqRoute vq_route(int variant, int D, int K, int HW, uintptr_t al /* every tensor
     return r;
 }
 
+// positions per lane in the exact kernel (1 from embedding_dim 64 on: registers)
+constexpr int vq_exact_pp(int D) { return D >= 64 ? 1 : VQ_PP; }
+
+// The main kernel's workgroup count on route `r`: what the launches below launch and what dm_vq_forward_plan answers.
+// nslabs: the squared-error slabs of the call (dm_vq_num_blocks), which bound vq_forward_any_kernel's grid.
+long long vq_route_grid(const VqRoute &r, int D, long long P, int nslabs)
+{
+    switch (r.kind) {
+    case VQ_ROUTE_MFMA: {
+        int wgs = 1;
+#define DM_V2W(DD, SINGLE_, MINW_, WGS_) if (D == DD && r.single == SINGLE_) wgs = WGS_;
+        DM_VQ2_ROWS(DM_V2W)
+#undef DM_V2W
+        const long long groups = ((P >> 6) + 3) / 4;             // four chunks of 64 positions per workgroup and iteration
+        long long g = groups < 256 * wgs ? groups : 256 * wgs;
+        if (r.inl && g > VQ2_SLAB_ROWS) g = VQ2_SLAB_ROWS;       // one counter row per workgroup
+        return g;
+    }
+    case VQ_ROUTE_CELLS: {
+        const long long g = ((P >> 7) + 3) / 4;                  // a pass of 128 positions per wave
+        return g > 512 ? 512 : g;                                // two workgroups per CU, persistent over the passes
+    }
+    case VQ_ROUTE_ANY: {
+        long long g = (P + 63) / 64;
+        if (g > nslabs) g = nslabs;                              // one squared-error slab per workgroup (the rest were zeroed)
+        return g > 4096 ? 4096 : g;
+    }
+    default: {
+        const int per_wg = VQ_BLOCK * vq_exact_pp(D);
+        return (P + per_wg - 1) / per_wg;
+    }
+    }
+}
+
 struct VqArgs {
     const float *z, *cb, *jh, *jcoef;      // jh, jcoef, jz: the join's block input and coefficients, the latents it writes (else NULL)
     float *out, *jz, *ws;
@@ -1955,9 +1989,7 @@ void vq2_launch_row(const VqRoute &r, const VqArgs &a)
     if constexpr (!BF && D % 16 == 0) { if (r.bf) return vq2_launch_row<D, SINGLE, MINW, WGS, true, INL, JOIN>(r, a); }
     if constexpr (!INL && SINGLE && D % 16 == 0) { if (r.inl) return vq2_launch_row<D, SINGLE, MINW, WGS, BF, true, JOIN>(r, a); }
     if constexpr (INL && !JOIN && D == 16) { if (r.join) return vq2_launch_row<D, SINGLE, MINW, WGS, BF, true, true>(r, a); }
-    const long long groups = ((a.P >> 6) + 3) / 4;               // four chunks of 64 positions per workgroup and iteration
-    long long g = groups < 256 * WGS ? groups : 256 * WGS;
-    if (INL && g > VQ2_SLAB_ROWS) g = VQ2_SLAB_ROWS;             // one counter row per workgroup
+    const long long g = vq_route_grid(r, D, a.P, a.nslabs);
     hipLaunchKernelGGL((vq_forward_mfma_kernel<D, SINGLE, MINW, BF, INL, JOIN>), dim3((unsigned)g), dim3(256), 0, a.s, a.z, a.cb,
                        a.ws + (BF ? a.L.cbB : a.L.cbA), a.ws + a.L.nrm, a.ws + a.L.cbH, a.idx, a.out, a.slabs, a.hrep, a.L.R,
                        (int *)a.ws, a.K, a.HW, a.P, a.nslabs, a.jh, a.jcoef, a.jz);
@@ -1972,9 +2004,7 @@ void vq2_launch(const VqRoute &r, const VqArgs &a)
 
 void vq_cells_launch(const VqRoute &r, const VqArgs &a)
 {
-    const long long passes = a.P >> 7;
-    long long g = (passes + 3) / 4;
-    if (g > 512) g = 512;                                        // two workgroups per CU, persistent over the passes
+    const long long passes = a.P >> 7, g = vq_route_grid(r, a.D, a.P, a.nslabs);
     // half a pass in units of 64 cycles (s_sleep): a pass streams K / 32 chunks of 12 (16) matrix instructions of 32
     // cycles, started 90 % of the way in; only where both slots of the CUs are taken and every wave has more than one pass
     const long long chunk_cycles = (long long)(r.prod == 4 ? 16 : 12) * 32;
@@ -1984,26 +2014,25 @@ void vq_cells_launch(const VqRoute &r, const VqArgs &a)
                        a.ws + a.L.nrmP, a.ws + a.L.nrm, a.idx, a.out, a.slabs, a.hrep, a.L.R, (int *)a.ws, a.K, a.HW, a.P, stagger);
 }
 
-void vq_any_launch(const VqArgs &a)
+void vq_any_launch(const VqRoute &r, const VqArgs &a)
 {
-    long long g = (a.P + 63) / 64;
-    if (g > a.nslabs) g = a.nslabs;                              // one squared-error slab per workgroup (the rest were zeroed)
-    if (g > 4096) g = 4096;
+    const long long g = vq_route_grid(r, a.D, a.P, a.nslabs);
     hipLaunchKernelGGL(vq_forward_any_kernel, dim3((unsigned)g), dim3(64), (size_t)a.D * 64 * sizeof(float), a.s, a.z, a.cb, a.idx,
                        a.out, a.slabs, a.hrep, a.L.R, a.K, a.D, a.HW, a.P);
 }
 
-void vq_exact_launch(const VqArgs &a)
+void vq_exact_launch(const VqRoute &r, const VqArgs &a)
 {
-#define DM_VQ_FWD(DD, PP_)                                                                                             \
-    hipLaunchKernelGGL((vq_forward_kernel<DD, PP_>), dim3((unsigned)((a.P + VQ_BLOCK * PP_ - 1) / (VQ_BLOCK * PP_))),   \
-                       dim3(VQ_BLOCK), 0, a.s, a.z, a.cb, a.ws + a.L.cbT, a.idx, a.out, a.slabs, a.hrep, a.L.R, a.K, a.HW, a.P)
+    const long long g = vq_route_grid(r, a.D, a.P, a.nslabs);
+#define DM_VQ_FWD(DD)                                                                                                  \
+    hipLaunchKernelGGL((vq_forward_kernel<DD, vq_exact_pp(DD)>), dim3((unsigned)g), dim3(VQ_BLOCK), 0, a.s, a.z, a.cb,  \
+                       a.ws + a.L.cbT, a.idx, a.out, a.slabs, a.hrep, a.L.R, a.K, a.HW, a.P)
     switch (a.D) {
-    case 8: DM_VQ_FWD(8, VQ_PP); break;
-    case 16: DM_VQ_FWD(16, VQ_PP); break;
-    case 32: DM_VQ_FWD(32, VQ_PP); break;
-    case 64: DM_VQ_FWD(64, 1); break;
-    default: DM_VQ_FWD(128, 1); break;        // VectorQuantizer's own default embedding_dim (vq_vae.py:35)
+    case 8: DM_VQ_FWD(8); break;
+    case 16: DM_VQ_FWD(16); break;
+    case 32: DM_VQ_FWD(32); break;
+    case 64: DM_VQ_FWD(64); break;
+    default: DM_VQ_FWD(128); break;           // VectorQuantizer's own default embedding_dim (vq_vae.py:35)
     }
 #undef DM_VQ_FWD
 }
@@ -2060,8 +2089,8 @@ int vq_forward_launch(const float *z, const float *codebook, int64_t *idx, float
         switch (r.kind) {
         case VQ_ROUTE_CELLS: vq_cells_launch(r, a); break;
         case VQ_ROUTE_MFMA: vq2_launch(r, a); break;
-        case VQ_ROUTE_ANY: vq_any_launch(a); break;
-        default: vq_exact_launch(a); break;
+        case VQ_ROUTE_ANY: vq_any_launch(r, a); break;
+        default: vq_exact_launch(r, a); break;
         }
     }
     if (hist) hipLaunchKernelGGL(vq_hist_reduce_kernel, dim3((K + 63) / 64), dim3(1024), 0, a.s, a.hrep, (int *)ws, K, (int *)hist);
@@ -2097,6 +2126,35 @@ extern "C" int dm_vq_forward(const float *z, const float *codebook, int64_t *idx
 extern "C" int dm_vq_forward_join_supported(int D, int K, int H, int W)
 {
     return (H > 0 && W > 0 && vq_join_built(D, K, H * W)) ? 1 : 0;
+}
+
+// The route and the main kernel's grid of a dm_vq_forward_variant (join != 0: dm_vq_forward_join) call of this shape on
+// 16-byte aligned tensors: vq_route and vq_route_grid, which the launch reads too.  Host only.
+extern "C" int dm_vq_forward_plan(int variant, int D, int K, int H, int W, int64_t positions, int join, int *kind, int *grid,
+                                  int *positions_per_round)
+{
+    static_assert(VQ_ROUTE_EXACT == DM_VQ_KERNEL_EXACT && VQ_ROUTE_ANY == DM_VQ_KERNEL_ANY && VQ_ROUTE_MFMA == DM_VQ_KERNEL_MFMA &&
+                  VQ_ROUTE_CELLS == DM_VQ_KERNEL_CELLS, "the header's names of the routes");
+    DM_REQUIRE(kind && grid && positions_per_round, "dm_vq_forward_plan: NULL pointer");
+    DM_REQUIRE(H > 0 && W > 0 && K > 0, "dm_vq_forward_plan: bad shape K=%d H=%d W=%d", K, H, W);
+    DM_REQUIRE(positions > 0 && positions % ((int64_t)H * W) == 0 && positions / ((int64_t)H * W) <= INT32_MAX,
+               "dm_vq_forward_plan: %lld positions are no batch of %d x %d latents", (long long)positions, H, W);
+    DM_REQUIRE(vq_dim_supported(D), "dm_vq_forward_plan: embedding_dim %d outside 1 .. 512", D);
+    DM_REQUIRE(variant >= DM_VQ_AUTO && variant <= DM_VQ_BF16, "dm_vq_forward_plan: bad variant %d", variant);
+    DM_REQUIRE(variant != DM_VQ_BF16 || D % 16 == 0, "dm_vq_forward_plan: the bf16-split filter needs embedding_dim 16, 32 or 64");
+    DM_REQUIRE(!join || variant == DM_VQ_AUTO, "dm_vq_forward_plan: the join runs as DM_VQ_AUTO");
+    const VqRoute r = vq_route(variant, D, K, H * W, 0, join != 0);
+    DM_REQUIRE((variant != DM_VQ_MFMA && variant != DM_VQ_BF16) || r.mfma_ok,
+               "dm_vq_forward_plan: the MFMA variant needs embedding_dim 8/16/32/64 and H*W %% 64 == 0");
+    DM_REQUIRE(!join || r.join, "dm_vq_forward_plan: the join is built for the one-launch form (<= 64 codes, embedding_dim 16, H*W %% 64 == 0)");
+    const long long g = vq_route_grid(r, D, positions, dm_vq_num_blocks(positions));
+    *kind = r.kind;
+    *grid = (int)g;
+    // positions a round of the kernel's loop covers: a workgroup takes 4 chunks of 64 (vq_forward_mfma_kernel) resp. 4 passes
+    // of 128 (vq_cells_kernel), vq_forward_any_kernel's one wave 64 positions per round; the exact kernel has no loop
+    const int per_wg = r.kind == VQ_ROUTE_MFMA ? 256 : r.kind == VQ_ROUTE_CELLS ? 512 : r.kind == VQ_ROUTE_ANY ? 64 : 0;
+    *positions_per_round = per_wg * (int)g;
+    return 0;
 }
 
 extern "C" int dm_vq_forward_join(const float *rb, const float *h_in, const float *coef, float *z_out, const float *codebook,

@@ -140,12 +140,14 @@ def self_launch(script, argv, n, timeout=None, env=None, stdout=None, stderr=Non
     child_env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # dmabuf IPC: what this pool's driver supports (RCCL needs it)
     child_env["DM_SELF_LAUNCHED"] = "1"
     # the ranks share ONE stdout pipe and flush every line themselves; unbuffered, Python writes a line and its newline
-    # as two system calls, and another rank's line can land between them -- the JSON line then no longer stands alone
+    # as two system calls, and another rank's line can land between them -- the JSON line then no longer stands alone.
+    # torchrun starts a Python script as `python -u`, so the interpreter is named here (--no-python) without that flag
     child_env.pop("PYTHONUNBUFFERED", None)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         child_env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
-           "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.abspath(script)] + list(argv)
+           "--master-addr", "127.0.0.1", "--master-port", str(free_port()), "--no-python", sys.executable,
+           os.path.abspath(script)] + list(argv)
     print("launch:", " ".join(cmd), file=stderr, flush=True)
     proc = subprocess.Popen(cmd, env=child_env, stdout=subprocess.PIPE, text=True, bufsize=1, start_new_session=True)
     lines = queue.Queue()

@@ -128,6 +128,18 @@ int dm_vq_forward_variant(const float *z, const float *codebook, int64_t *idx, f
                           double *sse_slabs, int32_t *hist, int B, int D, int K, int H, int W,
                           void *workspace, size_t workspace_bytes, int variant, void *stream);
 
+/* Which kernel a dm_vq_forward_variant call of this shape runs, and how it walks the batch (host only; the tensors are taken
+ * as 16-byte aligned; join != 0: dm_vq_forward_join, which runs as DM_VQ_AUTO).  `positions` = B*H*W.
+ *   kind                 DM_VQ_KERNEL_EXACT (one launch-wide pass, no loop), _ANY (the run-time-width kernel), _MFMA (the
+ *                        streamed matrix filter) or _CELLS (the cell kernel: 64 < K <= 4096 at embedding_dim 16);
+ *   grid                 workgroups of that kernel -- computed by the function the launch itself sizes its grid with;
+ *   positions_per_round  positions the grid covers in one round of the kernel's loop (MFMA 256 per workgroup, CELLS 512,
+ *                        ANY 64); a workgroup walks ceil(positions / positions_per_round) rounds.  0: the kernel has no loop.
+ * Negative return (and nothing written) for a shape or variant dm_vq_forward_variant / dm_vq_forward_join refuses. */
+enum { DM_VQ_KERNEL_EXACT = 0, DM_VQ_KERNEL_ANY = 1, DM_VQ_KERNEL_MFMA = 2, DM_VQ_KERNEL_CELLS = 3 };
+int dm_vq_forward_plan(int variant, int D, int K, int H, int W, int64_t positions, int join, int *kind, int *grid,
+                       int *positions_per_round);
+
 /* dm_vq_forward with the encoder's LAST RESIDUAL JOIN in its load path (ResidualBlock.forward, vq_vae.py:222-224, followed
  * by VectorQuantizer.forward, vq_vae.py:52-84): the latents are formed on the way in,
  *     z = fma(coef[d][0], rb, coef[d][2]) + h_in        (dm_apply's arithmetic: BatchNorm of the block's last conv + skip)

@@ -49,8 +49,9 @@ def main():
     if rank == 0:
         rec = {"n_gpus": world, "sum": t.item(), "max_rank": slowest, "self_launched": os.environ.get("DM_SELF_LAUNCHED")}
         if world > 2:
+            # (an unbuffered rank -- `python -u` -- writes a line and its newline as two system calls into the shared pipe)
             rec.update(collective={"world": world, "backend": torch.distributed.get_backend(), "rank_ms_per_step": rank_ms},
-                       shard_weights=weights)
+                       shard_weights=weights, stdout_write_through=sys.stdout.write_through)
         print(json.dumps(rec), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

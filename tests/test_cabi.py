@@ -81,6 +81,26 @@ def test_version_and_host_only_queries(lib):
     assert lib.dm_conv1x1_bwd_fused_num_blocks(3, 16, 32, 32, 32) == 12
     assert lib.dm_vq_forward_join_supported(16, 64, 16, 16) == 1 and lib.dm_vq_forward_join_supported(16, 4096, 32, 32) == 0
     assert lib.dm_vq_forward_join_supported(8, 64, 16, 16) == 0 and lib.dm_vq_forward_join_supported(16, 64, 10, 10) == 0
+    # dm_vq_forward_plan: (kind, workgroups, positions per round of the grid) -- the function the launch sizes its grid with
+    from dynamorph_amd import _lib
+
+    def plan(variant, D, K, H, W, B, join=0):
+        kind, grid, ppr = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int(-1)
+        assert lib.dm_vq_forward_plan(variant, D, K, H, W, B * H * W, join, ctypes.byref(kind), ctypes.byref(grid), ctypes.byref(ppr)) == 0
+        return kind.value, grid.value, ppr.value
+    EXACT, ANY, MFMA, CELLS = _lib.DM_VQ_KERNEL_EXACT, _lib.DM_VQ_KERNEL_ANY, _lib.DM_VQ_KERNEL_MFMA, _lib.DM_VQ_KERNEL_CELLS
+    assert plan(_lib.DM_VQ_AUTO, 16, 64, 16, 16, 2048) == (MFMA, 768, 768 * 256)          # the headline shape: 3 workgroups per CU
+    assert plan(_lib.DM_VQ_AUTO, 16, 64, 16, 16, 2048, join=1) == (MFMA, 768, 768 * 256)
+    assert plan(_lib.DM_VQ_AUTO, 16, 64, 16, 16, 3) == (MFMA, 3, 768)
+    assert plan(_lib.DM_VQ_MFMA, 8, 100, 8, 8, 3) == (MFMA, 1, 256)                        # 3 chunks of 64: one workgroup
+    assert plan(_lib.DM_VQ_BF16, 32, 300, 8, 24, 4000) == (MFMA, 512, 512 * 256)
+    assert plan(_lib.DM_VQ_AUTO, 64, 64, 8, 24, 819) == (MFMA, 256, 65536) and plan(_lib.DM_VQ_AUTO, 64, 512, 32, 32, 300) == (MFMA, 512, 131072)
+    assert plan(_lib.DM_VQ_AUTO, 16, 4096, 32, 32, 256) == (CELLS, 512, 512 * 512)         # 2048 passes of 128 on 2048 waves
+    assert plan(_lib.DM_VQ_AUTO, 16, 777, 16, 16, 40) == (CELLS, 20, 20 * 512) and plan(_lib.DM_VQ_AUTO, 16, 777, 8, 24, 40) == (MFMA, 30, 30 * 256)
+    assert plan(_lib.DM_VQ_MFMA, 16, 777, 16, 16, 40) == (MFMA, 40, 40 * 256)              # the f32 filter: the streamed kernel
+    assert plan(_lib.DM_VQ_EXACT, 16, 64, 16, 16, 2048) == (EXACT, 1024, 0) and plan(_lib.DM_VQ_EXACT, 64, 64, 16, 16, 8) == (EXACT, 8, 0)
+    assert plan(_lib.DM_VQ_AUTO, 128, 128, 8, 8, 2) == (EXACT, 1, 0) and plan(_lib.DM_VQ_AUTO, 16, 63, 8, 12, 2) == (EXACT, 1, 0)
+    assert plan(_lib.DM_VQ_AUTO, 24, 64, 16, 16, 3) == (ANY, 3, 192) and plan(_lib.DM_VQ_AUTO, 12, 40, 8, 8, 70000) == (ANY, 4096, 4096 * 64)
     assert lib.dm_conv4x4s2_num_blocks(2048, 3, 8, 128, 128, 1) == 2048 * 8   # one slab per tile (per-sample stats)
     assert lib.dm_conv4x4s2_num_blocks(2048, 3, 8, 128, 128, 0) == 768        # persistent grid
     assert lib.dm_conv4x4s2_num_blocks(1, 3, 8, 100, 100, 0) == 1             # not tileable by the MFMA path: generic kernel, one slab per sample
@@ -131,6 +151,20 @@ def test_argument_errors_are_reported_before_any_launch(lib):
     assert lib.dm_csr_block(None, None, None, 0, None, 1, None, 1, None, None) == -1
     assert lib.dm_vq_forward_join(None, None, None, None, None, None, None, None, None, 1, 16, 64, 16, 16, None, 0, None) == -1
     assert lib.dm_augment_codes(None, 0, 1, None, None) == -1
+    # dm_vq_forward_plan refuses what the launch refuses, and writes nothing
+    k, g, r = ctypes.c_int(-7), ctypes.c_int(-7), ctypes.c_int(-7)
+    out = (ctypes.byref(k), ctypes.byref(g), ctypes.byref(r))
+    assert lib.dm_vq_forward_plan(_lib.DM_VQ_AUTO, 16, 64, 16, 16, 256, 0, None, None, None) == -1 and b"NULL" in lib.dm_last_error()
+    assert lib.dm_vq_forward_plan(_lib.DM_VQ_MFMA, 16, 4, 8, 12, 96, 0, *out) == -1 and b"MFMA variant" in lib.dm_last_error()
+    assert lib.dm_vq_forward_plan(_lib.DM_VQ_MFMA, 128, 4, 8, 8, 64, 0, *out) == -1
+    assert lib.dm_vq_forward_plan(_lib.DM_VQ_BF16, 8, 4, 8, 8, 64, 0, *out) == -1 and b"bf16-split" in lib.dm_last_error()
+    assert lib.dm_vq_forward_plan(4, 16, 64, 16, 16, 256, 0, *out) == -1 and b"bad variant" in lib.dm_last_error()
+    assert lib.dm_vq_forward_plan(_lib.DM_VQ_AUTO, 513, 64, 16, 16, 256, 0, *out) == -1 and lib.dm_vq_forward_plan(_lib.DM_VQ_AUTO, 16, 0, 16, 16, 256, 0, *out) == -1
+    assert lib.dm_vq_forward_plan(_lib.DM_VQ_AUTO, 16, 64, 16, 16, 255, 0, *out) == -1 and b"no batch" in lib.dm_last_error()
+    assert lib.dm_vq_forward_plan(_lib.DM_VQ_AUTO, 16, 64, 16, 16, 0, 0, *out) == -1
+    assert lib.dm_vq_forward_plan(_lib.DM_VQ_AUTO, 16, 4096, 16, 16, 256, 1, *out) == -1 and b"join" in lib.dm_last_error()
+    assert lib.dm_vq_forward_plan(_lib.DM_VQ_AUTO, 32, 64, 16, 16, 256, 1, *out) == -1 and lib.dm_vq_forward_plan(_lib.DM_VQ_MFMA, 16, 64, 16, 16, 256, 1, *out) == -1
+    assert (k.value, g.value, r.value) == (-7, -7, -7)
     import numpy as np
     raw = np.array([3, 3, 1, 2, 0, 3, 7, 7], dtype=np.uint32)        # words & 3: 3 3 1 2 | 0 3 | 3 3
     fl, ro = np.zeros(2, np.int32), np.zeros(2, np.int32)

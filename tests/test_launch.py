@@ -51,6 +51,9 @@ def test_eight_ranks_like_the_8_gpu_node_of_config_c4():
     assert rec["collective"]["rank_ms_per_step"] == [1.0 + k for k in range(8)]
     w = rec["shard_weights"]
     assert w == [2 * 8 / 13] * 5 + [1 * 8 / 13] * 3 and abs(sum(w) - 8.0) < 1e-12
+    # the ranks share one stdout pipe: each must write a flushed line as ONE system call (not `python -u`, under which
+    # another rank's line can land between the JSON line and its newline, and the parent then forwards no JSON line)
+    assert rec["stdout_write_through"] is False
 
 
 def _alive(pid):
