@@ -193,6 +193,11 @@ SIGNATURES = {
     "dm_pca_components": (C.c_int, [vp, i64, C.c_int, i64, vp, vp, C.c_int, vp, vp]),
     "dm_knn_workspace_bytes": (i64, [i64, i64, C.c_int, C.c_int, C.c_int]),
     "dm_knn": (C.c_int, [vp, i64, C.c_int, i64, vp, i64, i64, i64, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, i64, vp]),
+    "dm_knn_wide_workspace_bytes": (i64, [i64, i64, C.c_int, C.c_int, C.c_int]),
+    "dm_knn_wide": (C.c_int, [vp, i64, C.c_int, i64, vp, i64, i64, C.c_int, C.c_int, vp, vp, vp, vp, vp, i64, vp]),
+    "dm_knn_wide_self_workspace_bytes": (i64, [i64, C.c_int, C.c_int, C.c_int]),
+    "dm_knn_wide_self": (C.c_int, [vp, i64, C.c_int, i64, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, i64,
+                                   vp]),
     "dm_umap_smooth": (C.c_int, [vp, i64, C.c_int, vp, vp, vp, vp, vp]),
     "dm_umap_membership": (C.c_int, [vp, vp, i64, C.c_int, vp, vp, vp, vp]),
     "dm_umap_epoch": (C.c_int, [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, f32, f32, f32, C.c_uint64, C.c_int, vp]),

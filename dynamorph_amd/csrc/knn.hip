@@ -17,6 +17,9 @@
 //             the lowest column, the order of the result) and the same refine without a certificate.  The host does not
 //             know how many rows are listed: the launches are always made and leave at once when the list is shorter (no
 //             read-back, capture-free).
+// Latents of more than DM_KNN_MAX_FEATURES features: dm_knn_wide is the foreign form with the wide
+// feature cap; dm_knn_wide_self computes the whole graph of at most DM_PCA_WIDE_MAX_SAMPLES rows from their row Gram matrix
+// (dm_pca_rowgram) -- a streaming panel kernel instead of the Gram product, and a refine that evaluates a pair once.
 // No atomics on floating-point data and no dependence on the launch shape in any value: results are a function of the inputs.
 #include "dm_common.h"
 #include <math.h>
@@ -383,38 +386,25 @@ __global__ __launch_bounds__(256) void knn_select_kernel(const float *__restrict
 // ------------------------------------------------------------------------------------------ refine and certificate
 __device__ __forceinline__ bool pair_less(float da, int ia, float db, int ib) { return da < db || (da == db && ia < ib); }
 
-// One workgroup per row: exact-form distances of its K candidates (a wave per pair), bitonic sort by (distance, column) in
-// LDS, the first kk written behind the optional self column.  certify: the row goes onto the list unless
-//     d[kk - 1]^2 (1 + 2^-20) < (rej - cbound (|q|^2 + max |x|^2) - tiny) (1 - 2^-21):
-// the right side is a lower bound of the float64 sum of every row left out, and a sum above d^2 (1 + 2^-20) has a root above
-// d (1 + 2^-22), more than one fp32 step past d: its rounded distance is strictly larger.
-template <bool V4>
-__global__ __launch_bounds__(256) void knn_refine_kernel(const float *__restrict__ Q, long long ldq, const float *__restrict__ X,
-                                                         long long ldx, int F, const int *__restrict__ cand, int ldc, int K,
-                                                         int kk, int include_self, int self_r0, const double *__restrict__ rej,
-                                                         const double *__restrict__ nq, const double *__restrict__ nxmax,
-                                                         double cbound, int certify, int *__restrict__ idx_out,
-                                                         float *__restrict__ dist_out, int *__restrict__ fail_list,
-                                                         int *__restrict__ n_fail, RowList rl)
+// The LDS sorts work on a power of two >= K entries (at least 2), padded with (+inf, INT_MAX).
+__device__ __forceinline__ int knn_sort_size(int K)
 {
-    __shared__ float s_d[KN_CAND];
-    __shared__ int s_i[KN_CAND];
-    const int slot = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int row = row_of_slot(rl, slot);
-    if (row < 0) return;
     int P = 2;
     while (P < K) P <<= 1;
-    const float *__restrict__ q = Q + (long long)row * ldq;
-    for (int c = w; c < P; c += 4) {
-        float d = INFINITY;
-        int j = 0x7fffffff;
-        if (c < K) {
-            j = cand[(long long)slot * ldc + c];
-            d = knn_dist_of(knn_exact_d2<V4>(q, X + (long long)j * ldx, F, lane));
-        }
-        if (lane == 0) { s_d[c] = d; s_i[c] = j; }
-    }
-    __syncthreads();
+    return P;
+}
+
+// The tail of a refine, by the whole workgroup of 256 threads once s_d / s_i hold the row's P (distance, column) pairs and a
+// barrier has passed: bitonic sort by (distance, column) in LDS, the first kk written behind the optional self column, and
+// (certify) the row listed unless the certificate stated at knn_refine_kernel holds.  (distance, column) is a total order
+// -- a row names no column twice -- so the result does not depend on the order the pairs arrived in.
+__device__ __forceinline__ void knn_sort_write_certify(float *s_d, int *s_i, int P, int kk, int include_self, int self_r0, int row,
+                                                       const double *__restrict__ rej_slot, const double *__restrict__ nq,
+                                                       const double *__restrict__ nxmax, double cbound, int certify,
+                                                       int *__restrict__ idx_out, float *__restrict__ dist_out,
+                                                       int *__restrict__ fail_list, int *__restrict__ n_fail)
+{
+    const int tid = threadIdx.x;
     for (int size = 2; size <= P; size <<= 1)
         for (int stride = size >> 1; stride > 0; stride >>= 1) {
             const int pos = 2 * tid - (tid & (stride - 1));
@@ -440,9 +430,44 @@ __global__ __launch_bounds__(256) void knn_refine_kernel(const float *__restrict
     if (certify && tid == 0) {
         const double a = cbound * (nq[row] + *nxmax) + 1e-30;
         const double dk = (double)s_d[kk - 1];
-        const bool ok = dk * dk * (1.0 + 0x1p-20) < (rej[slot] - a) * (1.0 - 0x1p-21);
+        const bool ok = dk * dk * (1.0 + 0x1p-20) < (*rej_slot - a) * (1.0 - 0x1p-21);
         if (!ok) fail_list[atomicAdd(n_fail, 1)] = row;
     }
+}
+
+// One workgroup per row: exact-form distances of its K candidates (a wave per pair), bitonic sort by (distance, column) in
+// LDS, the first kk written behind the optional self column.  certify: the row goes onto the list unless
+//     d[kk - 1]^2 (1 + 2^-20) < (rej - cbound (|q|^2 + max |x|^2) - tiny) (1 - 2^-21):
+// the right side is a lower bound of the float64 sum of every row left out, and a sum above d^2 (1 + 2^-20) has a root above
+// d (1 + 2^-22), more than one fp32 step past d: its rounded distance is strictly larger.
+template <bool V4>
+__global__ __launch_bounds__(256) void knn_refine_kernel(const float *__restrict__ Q, long long ldq, const float *__restrict__ X,
+                                                         long long ldx, int F, const int *__restrict__ cand, int ldc, int K,
+                                                         int kk, int include_self, int self_r0, const double *__restrict__ rej,
+                                                         const double *__restrict__ nq, const double *__restrict__ nxmax,
+                                                         double cbound, int certify, int *__restrict__ idx_out,
+                                                         float *__restrict__ dist_out, int *__restrict__ fail_list,
+                                                         int *__restrict__ n_fail, RowList rl)
+{
+    __shared__ float s_d[KN_CAND];
+    __shared__ int s_i[KN_CAND];
+    const int slot = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int row = row_of_slot(rl, slot);
+    if (row < 0) return;
+    const int P = knn_sort_size(K);
+    const float *__restrict__ q = Q + (long long)row * ldq;
+    for (int c = w; c < P; c += 4) {
+        float d = INFINITY;
+        int j = 0x7fffffff;
+        if (c < K) {
+            j = cand[(long long)slot * ldc + c];
+            d = knn_dist_of(knn_exact_d2<V4>(q, X + (long long)j * ldx, F, lane));
+        }
+        if (lane == 0) { s_d[c] = d; s_i[c] = j; }
+    }
+    __syncthreads();
+    knn_sort_write_certify(s_d, s_i, P, kk, include_self, self_r0, row, rej + slot, nq, nxmax, cbound, certify, idx_out,
+                           dist_out, fail_list, n_fail);
 }
 
 // include_self with k = 1: the graph is the self column alone.
@@ -452,6 +477,121 @@ __global__ __launch_bounds__(256) void knn_self_only_kernel(int R, int self_r0, 
     const int r = blockIdx.x * 256 + threadIdx.x;
     if (r == 0) *counter = 0;
     if (r < R) { idx_out[r] = self_r0 + r; dist_out[r] = 0.f; }
+}
+
+// ---------------------------------------------------------------- the wide self form: panel from a row Gram matrix
+// g[i][j] = fp32(n_i + n_j - 2 K[i][j]) for K = (X - s)(X - s)^T as dm_pca_rowgram wrote it (float64, N x N, full), the
+// diagonal +inf.  A stream: a thread takes four consecutive columns of one row, 32 bytes of K in and 16 bytes of the panel
+// out.  V2 (N even, K on 16 bytes): every row of K starts on 16 bytes and is read in 16-byte steps.
+template <bool V2>
+__global__ __launch_bounds__(256) void knn_wide_panel_kernel(const double *__restrict__ K, int N, const double *__restrict__ nx,
+                                                             float *__restrict__ panel, long long ldp)
+{
+    typedef double f64x2 __attribute__((ext_vector_type(2)));
+    const int i = blockIdx.y;
+    const int j = 4 * (int)(blockIdx.x * 256 + threadIdx.x);
+    if (j >= N) return;
+    const double *__restrict__ krow = K + (long long)i * N;
+    float *__restrict__ prow = panel + (long long)i * ldp;
+    const double ni = nx[i];
+    if (V2 && j + 3 < N) {
+        const f64x2 ka = *(const f64x2 *)(krow + j), kb = *(const f64x2 *)(krow + j + 2);
+        const f64x2 na = *(const f64x2 *)(nx + j), nb = *(const f64x2 *)(nx + j + 2);
+        f32x4 g;
+        g.x = (float)(ni + na.x - 2.0 * ka.x);
+        g.y = (float)(ni + na.y - 2.0 * ka.y);
+        g.z = (float)(ni + nb.x - 2.0 * kb.x);
+        g.w = (float)(ni + nb.y - 2.0 * kb.y);
+        if (i == j) g.x = INFINITY;
+        if (i == j + 1) g.y = INFINITY;
+        if (i == j + 2) g.z = INFINITY;
+        if (i == j + 3) g.w = INFINITY;
+        *(f32x4 *)(prow + j) = g;
+    } else {
+        for (int e = 0; e < 4 && j + e < N; ++e)
+            prow[j + e] = i == j + e ? INFINITY : (float)(ni + nx[j + e] - 2.0 * krow[j + e]);
+    }
+}
+
+// ------------------------------------------------------------------------------- the wide self form: pair-once refine
+// The exact-form distance is symmetric to the bit (fl(a - b) = -fl(b - a), equal squares, the same order of sums), so a
+// pair that is on both rows' candidate lists is evaluated once.  Three launches replace knn_refine_kernel:
+//   sort      every row's K candidates ascending by column (bitonic in LDS), so that a row can be searched;
+//   evaluate  workgroup = row i, wave = candidate j: i is looked up in row j's list; a mutual pair belongs to the smaller row
+//             and the other skips it; the owner's lane 0 writes the distance into row i's slot and, when mutual, into row j's
+//             slot at the position found.  Every slot is written exactly once;
+//   certify   knn_refine_kernel's tail on those distances.
+// One workgroup per row; block 0 also clears the pair counter.
+__global__ __launch_bounds__(256) void knn_cand_sort_kernel(int *__restrict__ cand, int K, int *__restrict__ n_pairs)
+{
+    __shared__ int s[KN_CAND];
+    const int tid = threadIdx.x;
+    const int P = knn_sort_size(K);
+    int *__restrict__ row = cand + (long long)blockIdx.x * K;
+    if (blockIdx.x == 0 && tid == 0 && n_pairs) *n_pairs = 0;
+    for (int c = tid; c < P; c += 256) s[c] = c < K ? row[c] : 0x7fffffff;
+    __syncthreads();
+    for (int size = 2; size <= P; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            const int pos = 2 * tid - (tid & (stride - 1));
+            if (pos + stride < P) {
+                const bool up = (pos & size) == 0;
+                const int a = s[pos], b = s[pos + stride];
+                if ((b < a) == up) { s[pos] = b; s[pos + stride] = a; }
+            }
+            __syncthreads();
+        }
+    for (int c = tid; c < K; c += 256) row[c] = s[c];
+}
+
+template <bool V4>
+__global__ __launch_bounds__(256) void knn_pair_eval_kernel(const float *__restrict__ X, long long ldx, int F,
+                                                            const int *__restrict__ cand, int K, float *__restrict__ dsts,
+                                                            int *__restrict__ n_pairs)
+{
+    const int i = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const float *__restrict__ q = X + (long long)i * ldx;
+    const int *__restrict__ mine = cand + (long long)i * K;
+    int done = 0;
+    for (int c = w; c < K; c += 4) {
+        const int j = mine[c];
+        const int *__restrict__ theirs = cand + (long long)j * K;
+        int lo = 0, hi = K;                     // the first position of row j's list that holds i or more
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (theirs[mid] < i) lo = mid + 1;
+            else hi = mid;
+        }
+        const bool mutual = lo < K && theirs[lo] == i;
+        if (mutual && j < i) continue;          // row j owns the pair
+        const float d = knn_dist_of(knn_exact_d2<V4>(q, X + (long long)j * ldx, F, lane));
+        if (lane == 0) {
+            dsts[(long long)i * K + c] = d;
+            if (mutual) dsts[(long long)j * K + lo] = d;
+        }
+        ++done;
+    }
+    if (n_pairs && lane == 0 && done) atomicAdd(n_pairs, done);
+}
+
+__global__ __launch_bounds__(256) void knn_sort_certify_kernel(const int *__restrict__ cand, const float *__restrict__ dsts, int K,
+                                                               int kk, int include_self, const double *__restrict__ rej,
+                                                               const double *__restrict__ nx, const double *__restrict__ nxmax,
+                                                               double cbound, int *__restrict__ idx_out,
+                                                               float *__restrict__ dist_out, int *__restrict__ fail_list,
+                                                               int *__restrict__ n_fail)
+{
+    __shared__ float s_d[KN_CAND];
+    __shared__ int s_i[KN_CAND];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const int P = knn_sort_size(K);
+    for (int c = tid; c < P; c += 256) {
+        s_d[c] = c < K ? dsts[(long long)row * K + c] : INFINITY;
+        s_i[c] = c < K ? cand[(long long)row * K + c] : 0x7fffffff;
+    }
+    __syncthreads();
+    knn_sort_write_certify(s_d, s_i, P, kk, include_self, 0, row, rej + row, nx, nxmax, cbound, 1, idx_out, dist_out, fail_list,
+                           n_fail);
 }
 
 // ------------------------------------------------------------------------------------------------------- host
@@ -471,16 +611,18 @@ size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 struct KnnPlan {
     int kk, K, fb_rows, rounds;
     long long ldp, ldd;
-    size_t o_panel, o_nx, o_nq, o_max, o_zero, o_cand, o_rej, o_list, o_fb, total;
+    size_t o_panel, o_nx, o_nq, o_max, o_zero, o_cand, o_rej, o_list, o_fb, o_dst, total;
 };
 
-// 0, or the reason the shape is refused.
-const char *knn_plan(long long R, long long M, int F, int k, int slack, int self_form, int include_self, KnnPlan *p)
+// 0, or the reason the shape is refused.  wide: the feature cap of the dm_knn_wide entries.
+const char *knn_plan(long long R, long long M, int F, int k, int slack, int self_form, int include_self, bool wide, KnnPlan *p)
 {
     if (R < 1 || M < 1) return "R and M must be >= 1";
     if (R > 0x7fffffffLL || M > 0x7fffffffLL) return "R and M must fit 31 bits";
     if (((R + KN_T - 1) / KN_T) * ((M + KN_T - 1) / KN_T) > 0x7fffffffLL) return "more than 2^31 tiles in one panel: split R";
-    if (F < 1 || F > DM_KNN_MAX_FEATURES) return "F outside 1 .. DM_KNN_MAX_FEATURES";
+    if (!wide && (F < 1 || F > DM_KNN_MAX_FEATURES)) return "F outside 1 .. DM_KNN_MAX_FEATURES";
+    if (wide && (F < 1 || F > DM_KNN_WIDE_MAX_FEATURES)) return "F outside 1 .. DM_KNN_WIDE_MAX_FEATURES";
+    if (wide && M > DM_PCA_WIDE_MAX_SAMPLES) return "more than DM_PCA_WIDE_MAX_SAMPLES rows of X";
     if (k < 1 || k > DM_KNN_MAX_K) return "k outside 1 .. DM_KNN_MAX_K";
     if (slack < 0 || slack > DM_KNN_MAX_SLACK) return "slack outside 0 .. DM_KNN_MAX_SLACK";
     if (include_self && !self_form) return "include_self needs the self form";
@@ -503,8 +645,31 @@ const char *knn_plan(long long R, long long M, int F, int k, int slack, int self
     p->o_rej = o;   o += align256((size_t)R * sizeof(double));
     p->o_list = o;  o += align256((size_t)R * sizeof(int));
     p->o_fb = o;    o += align256((size_t)p->fb_rows * p->ldd * sizeof(float));
+    p->o_dst = o;   o += wide && self_form ? align256((size_t)R * ldc * sizeof(float)) : 0;     // (pair-once distances)
     p->total = o;
     return nullptr;
+}
+
+// The fallback rounds: the listed rows, fb_rows at a time, from exact-form distances to all M columns.
+template <bool V4>
+void knn_fallback_rounds(const KnnPlan &p, const float *X, int M, int F, long long ldx, const float *Q, long long ldq,
+                         int self_r0, int include_self, int *idx, float *dist, int *n_fallback, char *ws, hipStream_t s)
+{
+    double *nmax = (double *)(ws + p.o_max), *rej = (double *)(ws + p.o_rej);
+    const double *nq = self_r0 >= 0 ? (const double *)(ws + p.o_nx) + self_r0 : (const double *)(ws + p.o_nq);
+    int *cand = (int *)(ws + p.o_cand), *list = (int *)(ws + p.o_list);
+    float *fb = (float *)(ws + p.o_fb);
+    const unsigned gx = (unsigned)(M / 4 + 1 < 64 ? M / 4 + 1 : 64);      // (a round without listed rows costs a launch, not a grid)
+    for (int b = 0; b < p.rounds; ++b) {
+        const RowList rl = {list, n_fallback, b * p.fb_rows};
+        hipLaunchKernelGGL(knn_exact_panel_kernel<V4>, dim3(gx, p.fb_rows), dim3(256), 0, s, Q, ldq, X, M, ldx, F, self_r0, fb,
+                           p.ldd, rl);
+        hipLaunchKernelGGL(knn_select_kernel, dim3(p.fb_rows), dim3(256), 0, s, (const float *)fb, p.ldd, M, p.kk,
+                           cand, p.K, rej, rl);
+        hipLaunchKernelGGL(knn_refine_kernel<V4>, dim3(p.fb_rows), dim3(256), 0, s, Q, ldq, X, ldx, F, (const int *)cand, p.K,
+                           p.kk, p.kk, include_self, self_r0, (const double *)rej, nq, (const double *)nmax,
+                           0.0, 0, idx, dist, list, n_fallback, rl);
+    }
 }
 
 template <bool V4>
@@ -516,8 +681,7 @@ void knn_launch(const KnnPlan &p, const float *X, int M, int F, long long ldx, c
     double *nx = (double *)(ws + p.o_nx), *nq = (double *)(ws + p.o_nq), *nmax = (double *)(ws + p.o_max);
     int *cand = (int *)(ws + p.o_cand), *list = (int *)(ws + p.o_list);
     double *rej = (double *)(ws + p.o_rej);
-    float *fb = (float *)(ws + p.o_fb);
-    const float *gram_shift = shift ? shift : (const float *)(ws + p.o_zero);   // (zeros: dm_knn cleared them)
+    const float *gram_shift = shift ? shift : (const float *)(ws + p.o_zero);   // (zeros: the caller cleared them)
     const RowList all = {nullptr, nullptr, 0};
 
     hipLaunchKernelGGL(knn_norms_kernel<V4>, dim3((M + 3) / 4), dim3(256), 0, s, X, (long long)M, F, ldx, shift, nx);
@@ -532,64 +696,82 @@ void knn_launch(const KnnPlan &p, const float *X, int M, int F, long long ldx, c
     hipLaunchKernelGGL(knn_refine_kernel<V4>, dim3(R), dim3(256), 0, s, Q, ldq, X, ldx, F, (const int *)cand, p.K, p.K, p.kk,
                        include_self, self_r0, (const double *)rej, (const double *)nq, (const double *)nmax, filter_bound(), 1,
                        idx, dist, list, n_fallback, all);
-    const unsigned gx = (unsigned)(M / 4 + 1 < 64 ? M / 4 + 1 : 64);      // (a round without listed rows costs a launch, not a grid)
-    for (int b = 0; b < p.rounds; ++b) {
-        const RowList rl = {list, n_fallback, b * p.fb_rows};
-        hipLaunchKernelGGL(knn_exact_panel_kernel<V4>, dim3(gx, p.fb_rows), dim3(256), 0, s, Q, ldq, X, M, ldx, F, self_r0, fb,
-                           p.ldd, rl);
-        hipLaunchKernelGGL(knn_select_kernel, dim3(p.fb_rows), dim3(256), 0, s, (const float *)fb, p.ldd, M, p.kk,
-                           cand, p.K, rej, rl);
-        hipLaunchKernelGGL(knn_refine_kernel<V4>, dim3(p.fb_rows), dim3(256), 0, s, Q, ldq, X, ldx, F, (const int *)cand, p.K,
-                           p.kk, p.kk, include_self, self_r0, (const double *)rej, (const double *)nq, (const double *)nmax,
-                           0.0, 0, idx, dist, list, n_fallback, rl);
+    knn_fallback_rounds<V4>(p, X, M, F, ldx, Q, ldq, self_r0, include_self, idx, dist, n_fallback, ws, s);
+}
+
+// The wide self form: the panel comes from the row Gram matrix, each candidate pair is evaluated
+// once (pair_once) or by knn_refine_kernel on the same lists; the norms, the selection, the certificate and the fallback are
+// dm_knn's.  The filter's operands are dm_pca_rowgram's: the same fl(x - s), the same slab of features.
+static_assert(KN_SLAB == DM_PCA_ROWGRAM_SLAB_FEATURES, "the certificate's slab is the row Gram's");
+
+template <bool V4>
+void knn_wide_self_launch(const KnnPlan &p, const float *X, int N, int F, long long ldx, const float *shift, const double *K,
+                          int include_self, int pair_once, int *idx, float *dist, int *n_fallback, int *n_pairs, char *ws,
+                          hipStream_t s)
+{
+    float *panel = (float *)(ws + p.o_panel), *dsts = (float *)(ws + p.o_dst);
+    double *nx = (double *)(ws + p.o_nx), *nmax = (double *)(ws + p.o_max), *rej = (double *)(ws + p.o_rej);
+    int *cand = (int *)(ws + p.o_cand), *list = (int *)(ws + p.o_list);
+    const RowList all = {nullptr, nullptr, 0};
+
+    hipLaunchKernelGGL(knn_norms_kernel<V4>, dim3((N + 3) / 4), dim3(256), 0, s, X, (long long)N, F, ldx, shift, nx);
+    hipLaunchKernelGGL(knn_max_kernel, dim3(1), dim3(256), 0, s, (const double *)nx, (long long)N, nmax, n_fallback);
+    const dim3 pg((unsigned)((N + 1023) / 1024), (unsigned)N);
+    if (N % 2 == 0 && ((uintptr_t)K & 15) == 0)
+        hipLaunchKernelGGL(knn_wide_panel_kernel<true>, pg, dim3(256), 0, s, K, N, (const double *)nx, panel, p.ldp);
+    else
+        hipLaunchKernelGGL(knn_wide_panel_kernel<false>, pg, dim3(256), 0, s, K, N, (const double *)nx, panel, p.ldp);
+    hipLaunchKernelGGL(knn_select_kernel, dim3(N), dim3(256), 0, s, (const float *)panel, p.ldp, N, p.K, cand, p.K, rej, all);
+    if (pair_once) {
+        hipLaunchKernelGGL(knn_cand_sort_kernel, dim3(N), dim3(256), 0, s, cand, p.K, n_pairs);
+        hipLaunchKernelGGL(knn_pair_eval_kernel<V4>, dim3(N), dim3(256), 0, s, X, ldx, F, (const int *)cand, p.K, dsts, n_pairs);
+        hipLaunchKernelGGL(knn_sort_certify_kernel, dim3(N), dim3(256), 0, s, (const int *)cand, (const float *)dsts, p.K, p.kk,
+                           include_self, (const double *)rej, (const double *)nx, (const double *)nmax, filter_bound(), idx,
+                           dist, list, n_fallback);
+    } else {
+        hipLaunchKernelGGL(knn_refine_kernel<V4>, dim3(N), dim3(256), 0, s, X, ldx, X, ldx, F, (const int *)cand, p.K, p.K, p.kk,
+                           include_self, 0, (const double *)rej, (const double *)nx, (const double *)nmax, filter_bound(), 1,
+                           idx, dist, list, n_fallback, all);
     }
+    knn_fallback_rounds<V4>(p, X, N, F, ldx, X, ldx, 0, include_self, idx, dist, n_fallback, ws, s);
 }
 
-}  // namespace
-
-extern "C" int64_t dm_knn_workspace_bytes(int64_t R, int64_t M, int F, int k, int slack)
+// dm_knn and dm_knn_wide (foreign form): one body, the feature cap and the name in the error texts differ.
+int knn_call(const char *who, bool wide, const float *X, int64_t M, int F, int64_t ldx, const float *Q, int64_t R, int64_t ldq,
+             int64_t self_r0, int k, int slack, int include_self, const float *shift, int32_t *indices, float *distances,
+             int32_t *n_fallback, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    KnnPlan p;
-    // the larger of the two forms: the foreign form keeps K = k + slack up to M
-    if (knn_plan(R, M, F, k, slack, 0, 0, &p)) return -1;
-    return (int64_t)p.total;
-}
-
-extern "C" int dm_knn(const float *X, int64_t M, int F, int64_t ldx, const float *Q, int64_t R, int64_t ldq, int64_t self_r0,
-                      int k, int slack, int include_self, const float *shift, int32_t *indices, float *distances,
-                      int32_t *n_fallback, void *workspace, int64_t workspace_bytes, void *stream)
-{
-    DM_REQUIRE(X, "dm_knn: X is NULL");
-    DM_REQUIRE(indices && distances && n_fallback, "dm_knn: indices / distances / n_fallback is NULL");
-    DM_REQUIRE(workspace, "dm_knn: workspace is NULL");
+    DM_REQUIRE(X, "%s: X is NULL", who);
+    DM_REQUIRE(indices && distances && n_fallback, "%s: indices / distances / n_fallback is NULL", who);
+    DM_REQUIRE(workspace, "%s: workspace is NULL", who);
     const int self_form = Q == nullptr;
     KnnPlan p;
-    const char *why = knn_plan(R, M, F, k, slack, self_form, include_self, &p);
-    DM_REQUIRE(!why, "dm_knn: R = %lld, M = %lld, F = %d, k = %d, slack = %d, %s form: %s", (long long)R, (long long)M, F, k,
+    const char *why = knn_plan(R, M, F, k, slack, self_form, include_self, wide, &p);
+    DM_REQUIRE(!why, "%s: R = %lld, M = %lld, F = %d, k = %d, slack = %d, %s form: %s", who, (long long)R, (long long)M, F, k,
                slack, self_form ? "self" : "foreign", why ? why : "");
-    DM_REQUIRE(ldx >= F, "dm_knn: leading dimension of X %lld < F = %d", (long long)ldx, F);
+    DM_REQUIRE(ldx >= F, "%s: leading dimension of X %lld < F = %d", who, (long long)ldx, F);
     if (self_form) {
-        DM_REQUIRE(self_r0 >= 0 && self_r0 + R <= M, "dm_knn: rows %lld .. %lld of the self form lie outside X (M = %lld)",
+        DM_REQUIRE(self_r0 >= 0 && self_r0 + R <= M, "%s: rows %lld .. %lld of the self form lie outside X (M = %lld)", who,
                    (long long)self_r0, (long long)(self_r0 + R - 1), (long long)M);
         Q = X + self_r0 * ldx;
         ldq = ldx;
     } else {
-        DM_REQUIRE(ldq >= F, "dm_knn: leading dimension of Q %lld < F = %d", (long long)ldq, F);
+        DM_REQUIRE(ldq >= F, "%s: leading dimension of Q %lld < F = %d", who, (long long)ldq, F);
         self_r0 = -1;
     }
-    DM_REQUIRE(workspace_bytes >= (int64_t)p.total, "dm_knn: workspace of %lld bytes, need %lld", (long long)workspace_bytes,
+    DM_REQUIRE(workspace_bytes >= (int64_t)p.total, "%s: workspace of %lld bytes, need %lld", who, (long long)workspace_bytes,
                (long long)p.total);
-    DM_REQUIRE(((uintptr_t)workspace & 255) == 0, "dm_knn: workspace is not 256-byte aligned");
+    DM_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: workspace is not 256-byte aligned", who);
     hipStream_t s = (hipStream_t)stream;
     if (p.kk == 0) {
         hipLaunchKernelGGL(knn_self_only_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, (int)R, (int)self_r0,
                            indices, distances, n_fallback);
-        return dm_launch_status("dm_knn");
+        return dm_launch_status(who);
     }
     if (!shift) {                           // the Gram kernel's loads are unconditional: no shift = a vector of zeros
         const hipError_t e = hipMemsetAsync((char *)workspace + p.o_zero, 0, (size_t)F * sizeof(float), s);
         if (e != hipSuccess) {
-            dm_set_error("dm_knn: hipMemsetAsync: %s", hipGetErrorString(e));
+            dm_set_error("%s: hipMemsetAsync: %s", who, hipGetErrorString(e));
             return (int)e;
         }
     }
@@ -599,5 +781,85 @@ extern "C" int dm_knn(const float *X, int64_t M, int F, int64_t ldx, const float
     else
         knn_launch<false>(p, X, (int)M, F, ldx, Q, (int)R, ldq, (int)self_r0, include_self ? 1 : 0, shift, indices, distances,
                           n_fallback, (char *)workspace, s);
-    return dm_launch_status("dm_knn");
+    return dm_launch_status(who);
+}
+
+}  // namespace
+
+extern "C" int64_t dm_knn_workspace_bytes(int64_t R, int64_t M, int F, int k, int slack)
+{
+    KnnPlan p;
+    // the larger of the two forms: the foreign form keeps K = k + slack up to M
+    if (knn_plan(R, M, F, k, slack, 0, 0, false, &p)) return -1;
+    return (int64_t)p.total;
+}
+
+extern "C" int dm_knn(const float *X, int64_t M, int F, int64_t ldx, const float *Q, int64_t R, int64_t ldq, int64_t self_r0,
+                      int k, int slack, int include_self, const float *shift, int32_t *indices, float *distances,
+                      int32_t *n_fallback, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    return knn_call("dm_knn", false, X, M, F, ldx, Q, R, ldq, self_r0, k, slack, include_self, shift, indices, distances,
+                    n_fallback, workspace, workspace_bytes, stream);
+}
+
+extern "C" int64_t dm_knn_wide_workspace_bytes(int64_t R, int64_t M, int F, int k, int slack)
+{
+    KnnPlan p;
+    if (knn_plan(R, M, F, k, slack, 0, 0, true, &p)) return -1;
+    return (int64_t)p.total;
+}
+
+extern "C" int dm_knn_wide(const float *X, int64_t M, int F, int64_t ldx, const float *Q, int64_t R, int64_t ldq, int k,
+                           int slack, const float *shift, int32_t *indices, float *distances, int32_t *n_fallback,
+                           void *workspace, int64_t workspace_bytes, void *stream)
+{
+    DM_REQUIRE(Q, "dm_knn_wide: Q is NULL (the self form is dm_knn_wide_self)");
+    return knn_call("dm_knn_wide", true, X, M, F, ldx, Q, R, ldq, -1, k, slack, 0, shift, indices, distances, n_fallback,
+                    workspace, workspace_bytes, stream);
+}
+
+extern "C" int64_t dm_knn_wide_self_workspace_bytes(int64_t N, int F, int k, int slack)
+{
+    KnnPlan p;
+    // the larger of include_self or not: k others, K = k + slack up to N, and the pair-once distances beside the candidates
+    if (knn_plan(N, N, F, k, slack, 0, 0, true, &p)) return -1;
+    return (int64_t)(p.total + align256((size_t)N * (p.K > 0 ? p.K : 1) * sizeof(float)));
+}
+
+extern "C" int dm_knn_wide_self(const float *X, int64_t N, int F, int64_t ldx, const float *shift, const double *K, int k,
+                                int slack, int include_self, int pair_once, int32_t *indices, float *distances,
+                                int32_t *n_fallback, int32_t *n_pairs, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    DM_REQUIRE(X, "dm_knn_wide_self: X is NULL");
+    DM_REQUIRE(K, "dm_knn_wide_self: K is NULL");
+    DM_REQUIRE(indices && distances && n_fallback, "dm_knn_wide_self: indices / distances / n_fallback is NULL");
+    DM_REQUIRE(workspace, "dm_knn_wide_self: workspace is NULL");
+    KnnPlan p;
+    const char *why = knn_plan(N, N, F, k, slack, 1, include_self, true, &p);
+    DM_REQUIRE(!why, "dm_knn_wide_self: N = %lld, F = %d, k = %d, slack = %d: %s", (long long)N, F, k, slack, why ? why : "");
+    DM_REQUIRE(ldx >= F, "dm_knn_wide_self: leading dimension of X %lld < F = %d", (long long)ldx, F);
+    DM_REQUIRE(((uintptr_t)K & 7) == 0, "dm_knn_wide_self: K is not 8-byte aligned");
+    DM_REQUIRE(workspace_bytes >= (int64_t)p.total, "dm_knn_wide_self: workspace of %lld bytes, need %lld",
+               (long long)workspace_bytes, (long long)p.total);
+    DM_REQUIRE(((uintptr_t)workspace & 255) == 0, "dm_knn_wide_self: workspace is not 256-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    if (n_pairs) {                          // (the plain refine and the self-only graph evaluate no pair once)
+        const hipError_t e = hipMemsetAsync(n_pairs, 0, sizeof(int32_t), s);
+        if (e != hipSuccess) {
+            dm_set_error("dm_knn_wide_self: hipMemsetAsync: %s", hipGetErrorString(e));
+            return (int)e;
+        }
+    }
+    if (p.kk == 0) {
+        hipLaunchKernelGGL(knn_self_only_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, (int)N, 0, indices,
+                           distances, n_fallback);
+        return dm_launch_status("dm_knn_wide_self");
+    }
+    if (vec4_ok(X, ldx, F) && ((uintptr_t)shift & 15) == 0)
+        knn_wide_self_launch<true>(p, X, (int)N, F, ldx, shift, K, include_self ? 1 : 0, pair_once, indices, distances,
+                                   n_fallback, n_pairs, (char *)workspace, s);
+    else
+        knn_wide_self_launch<false>(p, X, (int)N, F, ldx, shift, K, include_self ? 1 : 0, pair_once, indices, distances,
+                                    n_fallback, n_pairs, (char *)workspace, s);
+    return dm_launch_status("dm_knn_wide_self");
 }

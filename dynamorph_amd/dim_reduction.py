@@ -130,12 +130,17 @@ def fit_knn(train_data, weights_dir, n_nbrs=(15, 50, 200), **kw):
     """The neighbour graphs fit_umap's three umap.UMAP(n_neighbors=n) fits start from (run_dim_reduction.py:143-207): ONE
     exact graph at max(n_nbrs) with the row itself in column 0, written as <weights_dir>/knn_nbr<n>.pkl (protocol 4,
     [knn_indices int64, knn_dists float32]) for every n -- the first n columns of that graph, which is sorted.  Returns
-    {n: (knn_indices, knn_dists)}.  umap.UMAP(n_neighbors=n, precomputed_knn=tuple(pickle.load(f))) takes a file as it is."""
+    {n: (knn_indices, knn_dists)}.  umap.UMAP(n_neighbors=n, precomputed_knn=tuple(pickle.load(f))) takes a file as it is.
+    More than MAX_FEATURES columns (the VQ_VAE_z32 latents): knn.wide_knn_graph, at most knn.WIDE_MAX_ROWS rows; kw goes to it
+    (gram=(mean, s, K) hands it a row Gram matrix that exists already)."""
     n_nbrs = sorted(set(int(n) for n in n_nbrs))
     if not n_nbrs or n_nbrs[0] < 1:
         raise ValueError(f"n_nbrs={n_nbrs!r}: need at least one neighbour count >= 1")
     os.makedirs(weights_dir, exist_ok=True)
-    indices, dists = _knn.knn_graph(train_data, n_nbrs[-1], include_self=True, **kw)
+    if _knn.is_wide(train_data):
+        indices, dists = _knn.wide_knn_graph(train_data, n_nbrs[-1], include_self=True, **kw)
+    else:
+        indices, dists = _knn.knn_graph(train_data, n_nbrs[-1], include_self=True, **kw)
     out = {}
     for n in n_nbrs:
         out[n] = (np.ascontiguousarray(indices[:, :n]), np.ascontiguousarray(dists[:, :n]))
@@ -160,17 +165,28 @@ def fit_umap_embedding(train_data, weights_dir, labels=None, n_nbrs=(15, 50, 200
     (protocol 4, [embedding (N, 2) float32, labels]).  The name does not start with 'umap': the reference's umap_transform
     lists umap*.pkl there and calls .transform on what it unpickles.  save_models=True also writes the fitted UMAPEmbedding
     itself as <weights_dir>/umap_model_nbr<n>_a<a>_b<b>.pkl (protocol 4) -- a name that umap_transform, here and in the
-    reference, does pick up; every such file carries the training matrix (N F 4 bytes).  kw: UMAPEmbedding's (n_epochs,
-    negative_sample_rate, gamma, init, seed, device).  Returns {(n, a, b): embedding}."""
-    from .umap_layout import UMAPEmbedding, pca_coordinates
+    reference, does pick up; every such file carries the training matrix (N F 4 bytes: 5.2 GB for 20 000 VQ_VAE_z32 latents of
+    65536 features).  kw: UMAPEmbedding's (n_epochs, negative_sample_rate, gamma, init, seed, device).  More than MAX_FEATURES
+    columns: the wide route -- ONE row Gram matrix serves the graph's filter and the PCA initialisation.  Returns
+    {(n, a, b): embedding}."""
+    import torch
+    from .umap_layout import UMAPEmbedding, pca_coordinates, wide_gram
     init = kw.pop("init", "pca")
     device = kw.get("device")
+    if isinstance(init, str) and init != "pca":
+        raise ValueError(f"init={init!r}: 'pca' or an (N, 2) array")
+    wide = _knn.is_wide(train_data)
     x = _knn._resident(train_data, device)
-    graphs = fit_knn(x, weights_dir, n_nbrs=n_nbrs)
-    if isinstance(init, str):
-        if init != "pca":
-            raise ValueError(f"init={init!r}: 'pca' or an (N, 2) array")
-        init = pca_coordinates(x).cpu().numpy()
+    if wide and isinstance(init, str):
+        with torch.no_grad(), torch.cuda.device(x.device):
+            g = wide_gram(x)
+        graphs = fit_knn(x, weights_dir, n_nbrs=n_nbrs, gram=g)
+        init = pca_coordinates(x, gram=g, consume_gram=True).cpu().numpy()      # (the graph is done: K may be used up)
+        del g
+    else:
+        graphs = fit_knn(x, weights_dir, n_nbrs=n_nbrs)
+        if isinstance(init, str):
+            init = pca_coordinates(x).cpu().numpy()
     out = {}
     keep = {"X": x} if save_models else {}          # only a model that is saved holds on to the training matrix
     for n in sorted(graphs):

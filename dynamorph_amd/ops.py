@@ -1476,6 +1476,72 @@ def knn(X, Q=None, k=15, rows=None, shift=None, slack=None, include_self=False, 
     return idx, dist, nfb
 
 
+KNN_WIDE_MAX_FEATURES = 1 << 20    # DM_KNN_WIDE_MAX_FEATURES
+KNN_WIDE_MAX_ROWS = 24576          # DM_PCA_WIDE_MAX_SAMPLES
+
+
+def _knn_out(out, R, k, X, who):
+    if out is None:
+        return _new((R, k), X, torch.int32), _new((R, k), X)
+    idx, dist = out
+    if tuple(idx.shape) != (R, k) or tuple(dist.shape) != (R, k):
+        raise ValueError(f"{who}: out has shapes {tuple(idx.shape)}, {tuple(dist.shape)}, need ({R}, {k}) twice")
+    return idx, dist
+
+
+def _knn_ws(nbytes, workspace, X):
+    if nbytes >= 0 and (workspace is None or workspace.numel() * workspace.element_size() < nbytes):
+        workspace = torch.empty(int(nbytes), device=X.device, dtype=torch.uint8)
+    if workspace is None:       # a bad shape: the entry names it (nothing is launched)
+        workspace = torch.empty(256, device=X.device, dtype=torch.uint8)
+    return workspace
+
+
+@_op
+def knn_wide(X, Q, k=15, shift=None, slack=None, out=None, workspace=None):
+    """knn(X, Q) for 1 .. 2^20 features and at most 24576 rows of X (dm_knn_wide): the same launches, the wide feature cap."""
+    lib = L.load()
+    px, M, F, ldx = _rows(X)
+    pq, R, Fq, ldq = _rows(Q)
+    if Fq != F:
+        raise ValueError(f"dm_knn_wide: Q has {Fq} features, X has {F}")
+    k = int(k)
+    slack = KNN_DEFAULT_SLACK if slack is None else int(slack)
+    if shift is not None and shift.numel() != F:
+        raise ValueError(f"dm_knn_wide: shift has {shift.numel()} entries, F = {F}")
+    idx, dist = _knn_out(out, R, k, X, "dm_knn_wide")
+    nfb = _new((1,), X, torch.int32)
+    workspace = _knn_ws(lib.dm_knn_wide_workspace_bytes(R, M, F, k, slack), workspace, X)
+    L.check(lib.dm_knn_wide(px, M, F, ldx, pq, R, ldq, k, slack, _ptr(shift), _ptr(idx, torch.int32), _ptr(dist),
+                            _ptr(nfb, torch.int32), _ptr(workspace, workspace.dtype),
+                            workspace.numel() * workspace.element_size(), _stream()), "dm_knn_wide")
+    return idx, dist, nfb
+
+
+@_op
+def knn_wide_self(X, K, k=15, shift=None, slack=None, include_self=False, pair_once=True, out=None, workspace=None):
+    """The whole k-NN graph of X (N <= 24576 rows, 1 .. 2^20 features) from its row Gram matrix K = pca_rowgram(X, shift)
+    (dm_knn_wide_self; the SAME shift, or None for both): (indices (N, k) int32, distances (N, k) fp32, n_fallback_rows (1,)
+    int32, n_pairs (1,) int32 -- the exact pair evaluations of the pair-once refine -- on the device)."""
+    lib = L.load()
+    px, N, F, ldx = _rows(X)
+    if K.dtype != torch.float64 or tuple(K.shape) != (N, N) or not K.is_contiguous():
+        raise ValueError(f"dm_knn_wide_self: K has shape {tuple(K.shape)} and dtype {K.dtype}, need a contiguous float64 "
+                         f"({N}, {N})")
+    k = int(k)
+    slack = KNN_DEFAULT_SLACK if slack is None else int(slack)
+    if shift is not None and shift.numel() != F:
+        raise ValueError(f"dm_knn_wide_self: shift has {shift.numel()} entries, F = {F}")
+    idx, dist = _knn_out(out, N, k, X, "dm_knn_wide_self")
+    nfb, npairs = _new((1,), X, torch.int32), _new((1,), X, torch.int32)
+    workspace = _knn_ws(lib.dm_knn_wide_self_workspace_bytes(N, F, k, slack), workspace, X)
+    L.check(lib.dm_knn_wide_self(px, N, F, ldx, _ptr(shift), _ptr(K, torch.float64), k, slack, 1 if include_self else 0,
+                                 1 if pair_once else 0, _ptr(idx, torch.int32), _ptr(dist), _ptr(nfb, torch.int32),
+                                 _ptr(npairs, torch.int32), _ptr(workspace, workspace.dtype),
+                                 workspace.numel() * workspace.element_size(), _stream()), "dm_knn_wide_self")
+    return idx, dist, nfb, npairs
+
+
 # ----------------------------------------------------------------------------- UMAP behind the k-NN graph (DESIGN.md 3.5c)
 UMAP_MAX_K = 256               # DM_UMAP_MAX_K
 

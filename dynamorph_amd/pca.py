@@ -181,6 +181,12 @@ def orient_components(V):
     return V
 
 
+def column_mean(x):
+    """float64 column mean (F,) of a resident fp32 matrix of any width: dm_pca_colsum per block of MAX_FEATURES columns."""
+    N, F = x.shape
+    return torch.cat([ops.pca_colsum(x[:, lo:min(lo + MAX_FEATURES, F)]) for lo in range(0, F, MAX_FEATURES)]) / N
+
+
 def _host_rows(X):
     """Host data as a 2-D torch tensor (a view when it can be)."""
     if isinstance(X, np.ndarray):
@@ -441,37 +447,53 @@ class WidePCA(PCA):
 
     def gram(self, x):
         """(mean (F,) float64, s = fp32(mean), K (N, N) float64 = (x - s)(x - s)^T) of a resident fp32 matrix."""
-        N, F = x.shape
-        mean = torch.cat([ops.pca_colsum(x[:, lo:hi]) for lo, hi in self._blocks(F)]) / N
+        mean = column_mean(x)
         s = mean.float()
         return mean, s, ops.pca_rowgram(x, s)
 
-    def _fit_resident(self, x):
+    def _fit_resident(self, x, gram=None, consume_gram=False):
+        """Fit from the resident matrix; gram=(mean, s, K) as self.gram(x) returned it is used instead of computing it (the
+        k-NN graph of wide latents needs the same matrix: knn.wide_knn_graph).  The finalisation centres K in place: a
+        given K is copied first unless consume_gram, one that was computed here is simply used up."""
         N, F = x.shape
         with torch.no_grad(), torch.cuda.device(x.device):
-            mean, s, K = self.gram(x)
-            attrs = finalize_samples(K.cpu() if self.eigh_device == "cpu" else K, N, F, self.n_components)
-            del K
-            W = attrs.pop("W").to(device=x.device, dtype=torch.float32)
-            k = W.shape[0]
-            V = torch.empty((k, F), dtype=torch.float64, device=x.device)
-            for j in range(0, k, MAX_COMPONENTS):
-                ops.pca_components(x, W[j:j + MAX_COMPONENTS].contiguous(), s, out=V[j:j + MAX_COMPONENTS])
-            attrs["components_"] = orient_components(V).cpu().numpy()
-            attrs["mean_"] = mean.cpu().numpy()
+            if gram is None:
+                mean, s, K = self.gram(x)
+            else:
+                mean, s, K = gram
+                if tuple(K.shape) != (N, N) or mean.numel() != F or s.numel() != F:
+                    raise ValueError(f"gram=(mean, s, K) has shapes {tuple(mean.shape)}, {tuple(s.shape)}, {tuple(K.shape)}; "
+                                     f"X is ({N}, {F})")
+                if not consume_gram:
+                    K = K.clone()
+            self._fit_gram(x, mean, s, K)
+
+    def _fit_gram(self, x, mean, s, K):
+        """The fit behind the row Gram matrix: K = (x - s)(x - s)^T is centred in place and decomposed (the caller holds the
+        device and no_grad)."""
+        N, F = x.shape
+        attrs = finalize_samples(K.cpu() if self.eigh_device == "cpu" else K, N, F, self.n_components)
+        W = attrs.pop("W").to(device=x.device, dtype=torch.float32)
+        k = W.shape[0]
+        V = torch.empty((k, F), dtype=torch.float64, device=x.device)
+        for j in range(0, k, MAX_COMPONENTS):
+            ops.pca_components(x, W[j:j + MAX_COMPONENTS].contiguous(), s, out=V[j:j + MAX_COMPONENTS])
+        attrs["components_"] = orient_components(V).cpu().numpy()
+        attrs["mean_"] = mean.cpu().numpy()
         self._set(attrs, x.device)
 
-    def fit(self, X, chunk_rows=None):
+    def fit(self, X, chunk_rows=None, gram=None, consume_gram=False):
+        """gram=(mean, s, K) of self.gram(x) for the resident matrix x = X: the fit equals the plain one bit for bit."""
         if chunk_rows:
             self.chunk_rows = int(chunk_rows)
-        self._fit_resident(self._resident(X))
+        self._fit_resident(self._resident(X), gram, consume_gram)
         return self
 
-    def fit_transform(self, X, chunk_rows=None):
+    def fit_transform(self, X, chunk_rows=None, gram=None, consume_gram=False):
         if chunk_rows:
             self.chunk_rows = int(chunk_rows)
         x = self._resident(X)                       # uploaded once for the fit and the transform
-        self._fit_resident(x)
+        self._fit_resident(x, gram, consume_gram)
         return self.transform(x)
 
     def moments(self, X, chunk_rows=None):

@@ -9,7 +9,11 @@ its inputs and the seed alone.  Two output dimensions, the Euclidean k-NN graph,
 
 A fitted model that kept its training matrix places new rows into the embedding (transform): the
 query graph (knn.knn_query), dm_umap_transform_prepare and ONE launch of dm_umap_transform_layout for all epochs -- the
-training positions are fixed, so a new row reads nothing that another new row writes."""
+training positions are fixed, so a new row reads nothing that another new row writes.
+
+Latents of more than knn.MAX_FEATURES columns (VQ_VAE_z32: 65536) take the wide route, chosen from
+the column count alone: knn.wide_knn_graph / knn.wide_knn_query and WidePCA(n_components=2), the fit computing ONE row Gram
+matrix for both the graph and the PCA initialisation.  Such a model keeps (and pickles) its N x F x 4-byte training matrix."""
 import numpy as np
 import torch
 
@@ -173,8 +177,22 @@ def init_layout(y, seed):
     return (t * 10.0 + u * 1e-4).contiguous()
 
 
-def pca_coordinates(X, device=None):
-    """The first two principal-component scores of X from this package's PCA(n_components=2): init="pca" before rescaling."""
+def wide_gram(x):
+    """(mean, s, K) of a resident wide matrix, as WidePCA.gram forms it: what wide_knn_graph and WidePCA both start from.  The
+    free memory of the device is checked first, as for a WidePCA fit (K, and eigh's 3 N^2 float64, which exceed the graph's
+    fp32 panel)."""
+    from .pca import WidePCA
+    WidePCA._check_memory(x.device, x.shape[0], x.shape[1], resident=True)
+    return WidePCA().gram(x)
+
+
+def pca_coordinates(X, device=None, gram=None, consume_gram=False):
+    """The first two principal-component scores of X from this package's PCA(n_components=2): init="pca" before rescaling.
+    More than knn.MAX_FEATURES columns: WidePCA(n_components=2), from gram=(mean, s, K) = wide_gram(x) when it is given (K is
+    left unchanged unless consume_gram)."""
+    if _knn.is_wide(X):
+        from .pca import WidePCA
+        return WidePCA(n_components=2, device=device).fit_transform(X, gram=gram, consume_gram=consume_gram)
     from .pca import PCA
     return PCA(n_components=2, device=device).fit_transform(X)
 
@@ -232,17 +250,30 @@ class UMAPEmbedding:
         self._X = None              # the training matrix (M, F) fp32: the resident device tensor of the fit, or host numpy
 
     def fit_transform(self, X):
-        """The exact k-NN graph of X at n_neighbors (knn.knn_graph), then fit_graph; returns embedding_."""
+        """The exact k-NN graph of X at n_neighbors (knn.knn_graph; knn.wide_knn_graph above knn.MAX_FEATURES columns), then
+        fit_graph; returns embedding_."""
         N = X.shape[0]
         if self.n_neighbors > N:
             raise ValueError(f"n_neighbors = {self.n_neighbors} exceeds the {N} rows of X")
         init = self.init
         if not isinstance(init, str):
             init = _check_init(init, N)
+        wide = _knn.is_wide(X)
+        if wide:
+            _knn._check_wide(N, X.shape[1], self.n_neighbors, N)
         x = _knn._resident(X, self.device)
-        idx, dist = _knn.knn_graph(x, self.n_neighbors, include_self=True)
-        if isinstance(init, str):
-            init = pca_coordinates(x)
+        if not wide:
+            idx, dist = _knn.knn_graph(x, self.n_neighbors, include_self=True)
+            if isinstance(init, str):
+                init = pca_coordinates(x)
+        elif isinstance(init, str):                 # one row Gram matrix: the graph's filter first, then the PCA uses it up
+            with torch.no_grad(), torch.cuda.device(x.device):
+                g = wide_gram(x)
+            idx, dist = _knn.wide_knn_graph(x, self.n_neighbors, include_self=True, gram=g)
+            init = pca_coordinates(x, gram=g, consume_gram=True)
+            del g
+        else:
+            idx, dist = _knn.wide_knn_graph(x, self.n_neighbors, include_self=True)
         self.fit_graph(idx, dist, init)
         self._X = x
         return self.embedding_
@@ -343,12 +374,16 @@ class UMAPEmbedding:
         if not torch.is_tensor(Q):
             Q = np.asarray(Q)
         x = self._X = _knn._resident(self._X, self.device)
+        wide = F > _knn.MAX_FEATURES
         with torch.no_grad(), torch.cuda.device(x.device):
-            shift = _knn.column_shift(x)
+            shift = _knn.wide_column_shift(x) if wide else _knn.column_shift(x)
             y_train = torch.from_numpy(self.embedding_).to(x.device)
             ys, sigmas, inits = [], [], []
             for lo in range(0, shape[0], cr):
-                idx, dist = _knn.knn_query(x, Q[lo:lo + cr], self.n_neighbors, shift=shift)
+                if wide:
+                    idx, dist = _knn.wide_knn_query(x, Q[lo:lo + cr], self.n_neighbors, shift=shift)
+                else:
+                    idx, dist = _knn.knn_query(x, Q[lo:lo + cr], self.n_neighbors, shift=shift)
                 idx, dist = check_query_graph(idx, dist, M)
                 y, sigma, y0 = self._place(idx, dist, y_train, n_epochs, seed, row_offset + lo)
                 ys.append(y.cpu().numpy())
@@ -359,7 +394,8 @@ class UMAPEmbedding:
 
     # ------------------------------------------------------------------------------------------------------ pickling
     def __getstate__(self):
-        """Host state only: the training matrix as fp32 numpy, the embedding, the parameters and the fitted graph."""
+        """Host state only: the training matrix as fp32 numpy (N x F x 4 bytes: 5.2 GB for 20 000 rows of 65536 features), the
+        embedding, the parameters and the fitted graph."""
         state = dict(self.__dict__)
         X = state.get("_X")
         if torch.is_tensor(X):

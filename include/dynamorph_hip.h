@@ -847,6 +847,26 @@ int dm_knn(const float *X, int64_t M, int F, int64_t ldx, const float *Q, int64_
            int slack, int include_self, const float *shift, int32_t *indices, float *distances, int32_t *n_fallback,
            void *workspace, int64_t workspace_bytes, void *stream);
 
+/* The same graph for latents of more than DM_KNN_MAX_FEATURES features (VQ_VAE_z32: 65536), 1 <= F <= DM_KNN_WIDE_MAX_FEATURES,
+ * against at most DM_PCA_WIDE_MAX_SAMPLES rows of X.  Same semantics, the same exact-form distance bits and
+ * the same certificate as dm_knn; negative return + dm_last_error() text before any launch; asynchronous, no read-back. */
+#define DM_KNN_WIDE_MAX_FEATURES (1 << 20)
+/* FOREIGN form: queries Q (R x F, any R >= 1, not NULL) against X (M x F, M <= DM_PCA_WIDE_MAX_SAMPLES): dm_knn's launches. */
+int64_t dm_knn_wide_workspace_bytes(int64_t R, int64_t M, int F, int k, int slack);
+int dm_knn_wide(const float *X, int64_t M, int F, int64_t ldx, const float *Q, int64_t R, int64_t ldq, int k, int slack,
+                const float *shift, int32_t *indices, float *distances, int32_t *n_fallback, void *workspace,
+                int64_t workspace_bytes, void *stream);
+/* SELF form: the whole graph of X (N x F, N <= DM_PCA_WIDE_MAX_SAMPLES) in one call.  K: the N x N float64 matrix
+ * dm_pca_rowgram(X, shift) wrote for the SAME shift (NULL = none); the filter panel is fp32(n_i + n_j - 2 K_ij) with the
+ * norms computed here.  include_self and k = 1 as in dm_knn.  pair_once != 0: a candidate pair on both rows' lists is
+ * evaluated once (the distance is symmetric to the bit); 0: dm_knn's refine kernel on the same lists -- the same results.
+ * *n_pairs (device int, may be NULL; cleared by the call): exact pair evaluations made before the fallback by the
+ * pair-once kernels (0 otherwise). */
+int64_t dm_knn_wide_self_workspace_bytes(int64_t N, int F, int k, int slack);
+int dm_knn_wide_self(const float *X, int64_t N, int F, int64_t ldx, const float *shift, const double *K, int k, int slack,
+                     int include_self, int pair_once, int32_t *indices, float *distances, int32_t *n_fallback,
+                     int32_t *n_pairs, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ===== UMAP behind the exact k-NN graph: smooth distances, membership strengths, one layout epoch ==== */
 /* dists / indices: the N x k graph dm_knn returns with include_self (column 0 the row itself at 0.0, rows sorted),
  * 2 <= k <= DM_UMAP_MAX_K, k <= N < 2^31.  Negative return + dm_last_error() text for NULL or bad arguments before any

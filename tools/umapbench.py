@@ -14,6 +14,12 @@ layout launched epoch by epoch through the range arguments, and the whole UMAPEm
 
     timeout -k 10 900 python tools/umapbench.py --transform --rows 100000 --queries 20000 --ks 15 200 --out profiles/umap_transform_f4096_umapbench.jsonl
 
+--wide: one fit of latents wider than 16384 features (default F = 65536, N = 8192, n = 200): the whole
+UMAPEmbedding.fit_transform by the host clock with the ONE row Gram matrix it shares between the graph and the PCA
+initialisation, the same steps with the matrix computed twice, and the Gram matrix's own time.
+
+    timeout -k 10 900 python tools/umapbench.py --wide --out profiles/knn_wide_umapbench.jsonl
+
 What bounds the epoch kernel is not separable by events: take counters from a run of their own
 (`rocprofv3 --pmc ... -- python tools/umapbench.py --rows 100000 --ks 15 --epochs-only`).
 """
@@ -141,11 +147,46 @@ def transform_bench(a, dev):
         torch.cuda.empty_cache()
 
 
+def wide_bench(a, dev):
+    """One fit at width: shared Gram against the Gram computed twice."""
+    from dynamorph_amd.pca import WidePCA
+    F = a.features
+    for N in a.rows:
+        g = torch.Generator(device=dev).manual_seed(0)
+        A, B = torch.randn((N, 8), device=dev, generator=g), torch.randn((8, F), device=dev, generator=g)
+        X = torch.randn((N, F), device=dev, generator=g).mul_(0.05).addmm_(A, B).add_(30.0)   # knnbench --wide's planted rows
+        for k in a.ks:
+            _, t_gram = timed(lambda: WidePCA().gram(X))
+            model = U.UMAPEmbedding(n_neighbors=k)
+            model.fit_transform(X)                                                        # warm
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            emb = model.fit_transform(X)
+            t_shared = time.perf_counter() - t0
+
+            def twice():
+                idx, dist = K.wide_knn_graph(X, k, include_self=True)
+                return U.UMAPEmbedding(n_neighbors=k).fit_graph(idx, dist, U.pca_coordinates(X)).embedding_
+            twice()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            emb2 = twice()
+            t_twice = time.perf_counter() - t0
+            emit({"record": "wide_fit", "N": N, "F": F, "k": k, "n_epochs": model.n_epochs_, "s_fit_shared_gram_wall": t_shared,
+                  "s_fit_gram_twice_wall": t_twice, "s_rowgram": t_gram, "gram_share_shared": t_gram / t_shared,
+                  "gram_share_twice": 2 * t_gram / t_twice,
+                  "same_bits": bool(np.array_equal(emb.view(np.uint32), emb2.view(np.uint32))),
+                  "finite": bool(np.isfinite(emb).all())}, a.out)
+        del X
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rows", type=int, nargs="+", default=[20000, 100000])
-    ap.add_argument("--features", type=int, default=4096)
-    ap.add_argument("--ks", type=int, nargs="+", default=[15, 200])
+    ap.add_argument("--rows", type=int, nargs="+", default=None)
+    ap.add_argument("--features", type=int, default=None)
+    ap.add_argument("--wide", action="store_true", help="one fit of latents wider than 16384 features (F = 65536, N = 8192, n = 200)")
+    ap.add_argument("--ks", type=int, nargs="+", default=None)
     ap.add_argument("--intrinsic-dim", type=int, default=0,
                     help="D > 0: data of D intrinsic dimensions, 30 + randn(N, D) @ randn(D, F) / sqrt(D), which has far shorter "
                          "hub rows than isotropic noise in F dimensions")
@@ -157,6 +198,11 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("umapbench needs a GPU")
     dev = torch.device("cuda:0")
+    a.rows = a.rows or ([8192] if a.wide else [20000, 100000])
+    a.features = a.features or (65536 if a.wide else 4096)
+    a.ks = a.ks or ([200] if a.wide else [15, 200])
+    if a.wide:
+        return wide_bench(a, dev)
     if a.transform:
         return transform_bench(a, dev)
     try:
