@@ -14,6 +14,13 @@ DM_LOAD_IDENT, DM_LOAD_RELU, DM_LOAD_AFFINE, DM_LOAD_AFFINE_RELU, DM_LOAD_AFFINE
 DM_VQ_AUTO, DM_VQ_EXACT, DM_VQ_MFMA, DM_VQ_BF16 = range(4)
 DM_VQ_KERNEL_EXACT, DM_VQ_KERNEL_ANY, DM_VQ_KERNEL_MFMA, DM_VQ_KERNEL_CELLS = range(4)      # dm_vq_forward_plan's `kind`
 
+# dm_launch_plan's `kernel` and `dealing` (include/dynamorph_hip.h)
+DM_KERNEL_RESIDENT, DM_KERNEL_PATCH, DM_KERNEL_WIDE_TILED, DM_KERNEL_GENERIC, DM_KERNEL_CONV1X1_BWD_TILED = range(5)
+(DM_KERNEL_CONV1X1_STREAM, DM_KERNEL_CONV_S2_THIN_STREAM, DM_KERNEL_CONVT_THIN_STREAM, DM_KERNEL_CONV_S2_WIDE_STREAM,
+ DM_KERNEL_CONVT_WIDE_STREAM, DM_KERNEL_CONV3X3_WIDE_STREAM, DM_KERNEL_CONV1X1_BWD_WIDE_STREAM, DM_KERNEL_WGRAD1X1_STREAM,
+ DM_KERNEL_WGRAD_S2_THIN_STREAM, DM_KERNEL_WGRAD_WIDE1) = range(16, 26)
+DM_DEAL_NONE, DM_DEAL_RANGE_STRIDED, DM_DEAL_RANGE, DM_DEAL_GRID_STRIDED = range(4)
+
 vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 
@@ -29,6 +36,11 @@ class WeightView(C.Structure):
 class Epilogue(C.Structure):
     _fields_ = [("bias", vp), ("bias_border", vp), ("relu", i32), ("stats_per_tile", i32), ("mask", Operand),
                 ("resid", vp), ("stat_q", vp), ("stats", vp)]
+
+
+class LaunchPlan(C.Structure):
+    _fields_ = [("kernel", i32), ("workgroups", i32), ("waves", i32), ("walkers", i32), ("dealing", i32), ("ring", i32),
+                ("units", i64)]
 
 
 class Scatter(C.Structure):
@@ -64,7 +76,7 @@ class LatentTailBwdArgs(C.Structure):
                [(k, i32) for k in ("B", "C", "CR", "H", "W", "nres")] + [("res", LatentTailBwdRes * 4)]
 
 
-OP, WV, EP = C.POINTER(Operand), C.POINTER(WeightView), C.POINTER(Epilogue)
+OP, WV, EP, PLAN = C.POINTER(Operand), C.POINTER(WeightView), C.POINTER(Epilogue), C.POINTER(LaunchPlan)
 
 # name -> (restype, argtypes); every symbol include/dynamorph_hip.h declares
 SIGNATURES = {
@@ -95,6 +107,10 @@ SIGNATURES = {
     "dm_conv3x3": (C.c_int, [OP, WV, vp, EP] + [C.c_int] * 7 + [vp]),
     "dm_conv3x3_num_blocks": (C.c_int, [C.c_int] * 8),
     "dm_conv3x3_scratch_floats": (i64, [C.c_int] * 7),
+    "dm_conv4x4s2_plan": (C.c_int, [OP, WV, EP] + [C.c_int] * 5 + [PLAN]),
+    "dm_conv3x3_plan": (C.c_int, [OP, WV, EP] + [C.c_int] * 7 + [PLAN]),
+    "dm_wgrad_plan": (C.c_int, [OP, OP] + [C.c_int] * 6 + [PLAN]),
+    "dm_conv1x1_bwd_fused_plan": (C.c_int, [OP] + [C.c_int] * 5 + [PLAN]),
     "dm_backward_precision": (C.c_int, [C.c_int]),
     "dm_conv_bwd_s2_fused_supported": (C.c_int, [C.c_int] * 4),
     "dm_conv_bwd_s2_fused_num_blocks": (C.c_int, [C.c_int] * 5),
@@ -224,7 +240,8 @@ call_device = _CallDevice()
 
 # entry points that only compute on the host (grid sizes, scratch sizes, capability queries): they touch no device, so
 # they are bound without the device guard and do NOT consume the device recorded for the launch being assembled
-HOST_ONLY_SUFFIXES = ("_num_blocks", "_num_slabs", "_scratch_floats", "_workspace_bytes", "_workspace_floats", "_supported", "_state_ints")
+HOST_ONLY_SUFFIXES = ("_num_blocks", "_num_slabs", "_scratch_floats", "_workspace_bytes", "_workspace_floats", "_supported", "_state_ints",
+                      "_plan")
 HOST_ONLY = ("dm_last_error", "dm_version", "dm_backward_precision", "dm_augment_codes", "dm_reorder_with_trajectories",
              "dm_vq_forward_plan")
 

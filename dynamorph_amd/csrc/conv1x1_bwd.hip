@@ -15,10 +15,12 @@
 //     weight gradient  dW[co][ci] += sum_p da[co][p] * relu(t[ci][p])                                  (M = co, K = positions)
 // plus the (sum dx, sum dx*x) slabs BatchNorm's backward of the layer below needs.  201 MB moved once.
 #include "dm_common.h"
+#include "wide_host.h"
 
 // 64 -> 64 channels (the wide residual blocks): wide_stream.hip
 bool dm_stream_conv1x1_bwd_shape(int CD, int CX, int H, int W);
 int dm_stream_conv1x1_bwd_slabs(int B, int H, int W);
+dm_launch_plan dm_stream_conv1x1_bwd_plan(int B, int H, int W);      // the grid dm_stream_conv1x1_bwd launches
 int dm_stream_conv1x1_bwd(const Operand &dy, const float *x, const float *xcoef, const float *w, float *dx, double *stats,
                           float *wslabs, int B, int H, int W, hipStream_t st);
 
@@ -205,6 +207,18 @@ extern "C" int dm_conv1x1_bwd_fused_num_blocks(int B, int CD, int CX, int H, int
     if (B <= 0 || !conv1x1_bwd_shape(CD, CX, H, W)) return -1;
     const long long ntiles = (long long)B * (H * W / C1_TP);
     return (int)(ntiles < C1_MAX_GRID ? ntiles : C1_MAX_GRID);
+}
+
+extern "C" int dm_conv1x1_bwd_fused_plan(const dm_operand *dy, int B, int CD, int CX, int H, int W, dm_launch_plan *plan)
+{
+    DM_REQUIRE(dy && dy->p0 && plan, "dm_conv1x1_bwd_fused_plan: NULL pointer");
+    DM_REQUIRE(B > 0 && (conv1x1_bwd_shape(CD, CX, H, W) || dm_stream_conv1x1_bwd_shape(CD, CX, H, W)),
+               "dm_conv1x1_bwd_fused_plan: shape %d -> %d channels on %dx%d not built", CX, CD, H, W);
+    Operand d;
+    if (dm_bwd_dy_operand(dy, "dm_conv1x1_bwd_fused_plan", &d)) return -1;
+    DM_REQUIRE((long long)B * CX * H * W < (1LL << 31), "dm_conv1x1_bwd_fused_plan: tensor too large");
+    *plan = dm_stream_conv1x1_bwd_shape(CD, CX, H, W) ? dm_stream_conv1x1_bwd_plan(B, H, W) : family_plan(DM_KERNEL_CONV1X1_BWD_TILED);
+    return 0;
 }
 
 extern "C" int dm_conv1x1_bwd_fused(const dm_operand *dy, const float *x, const float *xcoef, const float *w, float *dx,

@@ -359,13 +359,20 @@ void conv4x4s2_patch_forward_kernel(Operand in, WeightView wv, const float *__re
 
 }  // namespace
 
-// Called by dm_conv4x4s2 (conv_mfma.hip) for the shape this kernel is built for; returns false when it does not apply.
-bool dm_conv4x4s2_patch_forward(const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B, int Cphys, int CIN,
-                                int NOUT, int H, int W, int per_tile, int nslabs, hipStream_t stream, int *rc)
+// The shape and operands this kernel is built for (host arithmetic only: dm_conv4x4s2 and dm_conv4x4s2_plan both ask).
+bool dm_conv4x4s2_patch_takes(const Operand &in, const Epilogue &ep, int B, int Cphys, int CIN, int NOUT, int H, int W, int per_tile,
+                              int nslabs)
 {
     if (CIN != 16 || Cphys != 16 || NOUT != 16 || H != 32 || W != 32) return false;
     if (in.mode == DM_LOAD_AFFINE2 || in.ones || ep.mask.p0 || ep.resid || ep.stat_q || ep.bias_border) return false;
     if (per_tile && (!ep.stats || nslabs % B != 0)) return false;
+    return true;
+}
+
+// Called by dm_conv4x4s2 (conv_mfma.hip) where dm_conv4x4s2_patch_takes holds; returns false when the device refuses its LDS.
+bool dm_conv4x4s2_patch_forward(const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B, int Cphys, int CIN,
+                                int NOUT, int H, int W, int per_tile, int nslabs, hipStream_t stream, int *rc)
+{
     static DmPerDeviceOnce attr_done;
     if (dm_reserve_lds(attr_done, {{(const void *)conv4x4s2_patch_forward_kernel, F2_LDS_BYTES}}, nullptr)) return false;
     const int grid = B < 256 ? B : 256;

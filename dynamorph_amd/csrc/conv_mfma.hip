@@ -33,6 +33,7 @@
 #include "dm_common.h"
 #include "tile.h"
 #include "mfma_util.h"
+#include "wide_host.h"
 
 // fallbacks for shapes / channel families without an MFMA instantiation (conv_generic.hip)
 int dm_generic_conv_slabs(int B, int per_tile);
@@ -44,7 +45,12 @@ int dm_wide_conv_slabs(int form, int B, int H, int W, int per_tile);
 long long dm_wide_conv_scratch_floats(int form, int CIN, int NOUT, int taps);
 int dm_wide_conv(int form, const Operand &in, const WeightView &wv, float *scratch, float *out, const Epilogue &ep, int B,
                  int Cphys, int CIN, int NOUT, int H, int W, int taps, int nslabs, int per_tile, hipStream_t st);
+// which kernel dm_wide_conv launches for the call and with what grid (what dm_wide_conv itself reads)
+dm_launch_plan dm_wide_conv_plan(int form, const Operand &in, bool has_scratch, const Epilogue &ep, int B, int Cphys, int CIN,
+                                 int NOUT, int H, int W, int taps, int nslabs, int per_tile);
 
+bool dm_conv4x4s2_patch_takes(const Operand &in, const Epilogue &ep, int B, int Cphys, int CIN, int NOUT, int H, int W, int per_tile,
+                              int nslabs);
 bool dm_conv4x4s2_patch_forward(const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B, int Cphys, int CIN,
                                 int NOUT, int H, int W, int per_tile, int nslabs, hipStream_t stream, int *rc);
 
@@ -1699,6 +1705,38 @@ extern "C" int64_t dm_conv4x4s2_scratch_floats(int CIN, int NOUT, int H, int W, 
     return r.kind == ROUTE_RESIDENT && !fallback ? 0 : r.wide_floats;
 }
 
+// The family a call runs on once the shape's route is known: the operands may send a ROUTE_RESIDENT shape to the implicit GEMM,
+// and without scratch for its packed weights that one gives way to the generic kernel.  Read by the launches and the plans.
+static int conv_family(const ConvRoute &r, bool resident_takes, const dm_weight_view *w)
+{
+    if (r.kind == ROUTE_RESIDENT && resident_takes) return DM_KERNEL_RESIDENT;
+    return (r.wide_ok && w->scratch && w->scratch_floats >= r.wide_floats) ? DM_KERNEL_WIDE_TILED : DM_KERNEL_GENERIC;
+}
+
+// the checks of a launch that a plan repeats (`out` apart): a plan is refused where the launch is
+static int conv_plan_checks(const char *who, const dm_operand *in, const dm_weight_view *w, const dm_epilogue *ep, int B, int CIN,
+                            int NOUT, int H, int W, dm_launch_plan *plan)
+{
+    DM_REQUIRE(plan, "%s: NULL plan", who);
+    float out_present;
+    return conv_common_checks(who, in, w, &out_present, ep, B, CIN, NOUT, H, W);
+}
+
+extern "C" int dm_conv4x4s2_plan(const dm_operand *in, const dm_weight_view *w, const dm_epilogue *ep, int B, int CIN, int NOUT,
+                                 int H, int W, dm_launch_plan *plan)
+{
+    if (conv_plan_checks("dm_conv4x4s2_plan", in, w, ep, B, CIN, NOUT, H, W, plan)) return -1;
+    DM_REQUIRE(H % 2 == 0 && W % 2 == 0, "dm_conv4x4s2_plan: H and W must be even (got %dx%d)", H, W);
+    const int per_tile = ep ? ep->stats_per_tile : 0, Cphys = CIN - (in->ones_channel ? 1 : 0);
+    const ConvRoute r = conv4_route(B, CIN, NOUT, H, W, per_tile);
+    const Operand i = to_dev(in);
+    const Epilogue e = to_dev(ep);
+    if (dm_conv4x4s2_patch_takes(i, e, B, Cphys, CIN, NOUT, H, W, per_tile, r.nslabs)) { *plan = family_plan(DM_KERNEL_PATCH); return 0; }
+    const int fam = conv_family(r, conv4_resident_takes(in, ep, CIN, W), w);
+    *plan = fam == DM_KERNEL_WIDE_TILED ? dm_wide_conv_plan(0, i, true, e, B, Cphys, CIN, NOUT, H, W, 16, r.nslabs, per_tile) : family_plan(fam);
+    return 0;
+}
+
 extern "C" int dm_conv4x4s2(const dm_operand *in, const dm_weight_view *w, float *out, const dm_epilogue *ep,
                             int B, int CIN, int NOUT, int H, int W, void *stream)
 {
@@ -1710,12 +1748,14 @@ extern "C" int dm_conv4x4s2(const dm_operand *in, const dm_weight_view *w, float
                per_tile, r.ntiles, r.nslabs, (hipStream_t)stream};
     {   // enc.7's shape: the whole-patch kernel (conv4x4s2_patch.hip)
         int rc = 0;
-        if (dm_conv4x4s2_patch_forward(a.in, a.wv, out, a.ep, B, a.Cphys, CIN, NOUT, H, W, per_tile, r.nslabs, a.stream, &rc))
+        if (dm_conv4x4s2_patch_takes(a.in, a.ep, B, a.Cphys, CIN, NOUT, H, W, per_tile, r.nslabs) &&
+            dm_conv4x4s2_patch_forward(a.in, a.wv, out, a.ep, B, a.Cphys, CIN, NOUT, H, W, per_tile, r.nslabs, a.stream, &rc))
             return rc;
     }
-    if (r.kind == ROUTE_RESIDENT && conv4_resident_takes(in, ep, CIN, W))
+    const int fam = conv_family(r, conv4_resident_takes(in, ep, CIN, W), w);
+    if (fam == DM_KERNEL_RESIDENT)
         conv4_launch_resident(a, r.TW);
-    else if (r.wide_ok && w->scratch && w->scratch_floats >= r.wide_floats)
+    else if (fam == DM_KERNEL_WIDE_TILED)
         dm_wide_conv(0, a.in, a.wv, w->scratch, out, a.ep, B, a.Cphys, CIN, NOUT, H, W, 16, r.nslabs, per_tile, a.stream);
     else
         dm_generic_conv(0, a.in, a.wv, out, a.ep, B, a.Cphys, CIN, NOUT, H, W, 16, r.nslabs, per_tile, a.stream);
@@ -1798,6 +1838,23 @@ extern "C" int64_t dm_conv3x3_scratch_floats(int CIN, int NOUT, int H, int W, in
     return r.kind == ROUTE_RESIDENT || (taps != 9 && taps != 1) ? 0 : r.wide_floats;
 }
 
+extern "C" int dm_conv3x3_plan(const dm_operand *in, const dm_weight_view *w, const dm_epilogue *ep, int B, int CIN, int NOUT,
+                               int H, int W, int taps, int pixel_shuffle, dm_launch_plan *plan)
+{
+    if (conv_plan_checks("dm_conv3x3_plan", in, w, ep, B, CIN, NOUT, H, W, plan)) return -1;
+    DM_REQUIRE(taps == 9 || taps == 1, "dm_conv3x3_plan: taps must be 9 or 1");
+    DM_REQUIRE(!pixel_shuffle || (taps == 9 && NOUT % 4 == 0), "dm_conv3x3_plan: pixel_shuffle needs taps=9, NOUT%%4==0");
+    DM_REQUIRE(!in->ones_channel, "dm_conv3x3_plan: ones_channel not supported");
+    DM_REQUIRE(!(ep && ep->bias_border), "dm_conv3x3_plan: bias_border not supported (dm_conv4x4s2 only)");
+    const bool pix = pixel_shuffle != 0;
+    const int form = pix ? 2 : 1, per_tile = ep ? ep->stats_per_tile : 0;
+    const ConvRoute r = conv3_route(B, CIN, NOUT, H, W, taps, pix, per_tile);
+    const int fam = conv_family(r, true, w);
+    *plan = fam == DM_KERNEL_WIDE_TILED ? dm_wide_conv_plan(form, to_dev(in), true, to_dev(ep), B, CIN, CIN, NOUT, H, W, taps, r.nslabs, per_tile)
+                                        : family_plan(fam);
+    return 0;
+}
+
 extern "C" int dm_conv3x3(const dm_operand *in, const dm_weight_view *w, float *out, const dm_epilogue *ep,
                           int B, int CIN, int NOUT, int H, int W, int taps, int pixel_shuffle, void *stream)
 {
@@ -1811,9 +1868,10 @@ extern "C" int dm_conv3x3(const dm_operand *in, const dm_weight_view *w, float *
     const ConvRoute r = conv3_route(B, CIN, NOUT, H, W, taps, pix, per_tile);
     ConvArgs a{to_dev(in), to_dev(w), out, to_dev(ep), B, CIN, CIN, NOUT, H, W, per_tile, r.ntiles, r.nslabs,
                (hipStream_t)stream};
-    if (r.kind == ROUTE_RESIDENT)
+    const int fam = conv_family(r, true, w);
+    if (fam == DM_KERNEL_RESIDENT)
         conv3_launch_resident(a, taps, pix, r.TW);
-    else if (r.wide_ok && w->scratch && w->scratch_floats >= r.wide_floats)
+    else if (fam == DM_KERNEL_WIDE_TILED)
         dm_wide_conv(form, a.in, a.wv, w->scratch, out, a.ep, B, CIN, CIN, NOUT, H, W, taps, r.nslabs, per_tile, a.stream);
     else
         dm_generic_conv(form, a.in, a.wv, out, a.ep, B, CIN, CIN, NOUT, H, W, taps, r.nslabs, per_tile, a.stream);

@@ -821,23 +821,31 @@ __global__ __launch_bounds__(512, 1) void wgrad_wide1_kernel(Operand S, Operand 
 
 }  // namespace
 
-bool dm_stream_conv1x1(const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B, int Cphys, int CIN,
-                       int NOUT, int H, int W, int nslabs, int per_tile, hipStream_t st);
-
-bool dm_stream_conv_s2_thin(const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B, int Cphys, int CIN,
-                            int NOUT, int H, int W, int nslabs, int per_tile, hipStream_t st);
-
-bool dm_stream_convT_thin(const Operand &in, const WeightView &wv, float *scratch, float *out, const Epilogue &ep, int B, int Cphys,
-                          int CIN, int NOUT, int H, int W, int per_tile, hipStream_t st);
-
-bool dm_stream_conv_s2_wide(const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B, int Cphys, int CIN,
-                            int NOUT, int H, int W, int nslabs, int per_tile, hipStream_t st);
-
-bool dm_stream_convT_wide(const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B, int Cphys, int CIN,
-                          int NOUT, int H, int W, int nslabs, int per_tile, hipStream_t st);
-
-bool dm_stream_conv3x3_wide(const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B, int Cphys, int CIN,
-                            int NOUT, int H, int W, int nslabs, int per_tile, hipStream_t st);
+// streaming forms of the memory-bound layers (wide_stream.hip): X_plan = does it take the call, and with what grid; X = launch it
+bool dm_stream_conv1x1_plan(const Operand &in, const Epilogue &ep, int B, int Cphys, int CIN, int NOUT, int H, int W, int nslabs,
+                            int per_tile, dm_launch_plan *p);
+void dm_stream_conv1x1(const dm_launch_plan &p, const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B,
+                       int CIN, int NOUT, int H, int W, int nslabs, hipStream_t st);
+bool dm_stream_conv_s2_thin_plan(const Operand &in, const Epilogue &ep, int B, int Cphys, int CIN, int NOUT, int H, int W,
+                                 int nslabs, int per_tile, dm_launch_plan *p);
+void dm_stream_conv_s2_thin(const dm_launch_plan &p, const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B,
+                            int CIN, int NOUT, int H, int nslabs, hipStream_t st);
+bool dm_stream_convT_thin_plan(const Operand &in, bool has_scratch, const Epilogue &ep, int B, int Cphys, int CIN, int NOUT, int H,
+                               int W, int per_tile, dm_launch_plan *p);
+void dm_stream_convT_thin(const dm_launch_plan &p, const Operand &in, const WeightView &wv, float *scratch, float *out,
+                          const Epilogue &ep, int B, int CIN, int NOUT, int H, hipStream_t st);
+bool dm_stream_conv_s2_wide_plan(const Operand &in, const Epilogue &ep, int B, int Cphys, int CIN, int NOUT, int H, int W,
+                                 int nslabs, int per_tile, dm_launch_plan *p);
+bool dm_stream_conv_s2_wide(const dm_launch_plan &p, const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B,
+                            int nslabs, hipStream_t st);
+bool dm_stream_convT_wide_plan(const Operand &in, const Epilogue &ep, int B, int Cphys, int CIN, int NOUT, int H, int W,
+                               int nslabs, int per_tile, dm_launch_plan *p);
+bool dm_stream_convT_wide(const dm_launch_plan &p, const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B,
+                          int nslabs, hipStream_t st);
+bool dm_stream_conv3x3_wide_plan(const Operand &in, const Epilogue &ep, int B, int Cphys, int CIN, int NOUT, int H, int W,
+                                 int nslabs, int per_tile, dm_launch_plan *p);
+bool dm_stream_conv3x3_wide(const dm_launch_plan &p, const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B,
+                            int nslabs, hipStream_t st);
 
 // ---- entry points used by the dispatchers in conv_mfma.hip / wgrad_mfma.hip (not part of the public header) ----------
 // base grid (output pixels for the strided / plain forms, input pixels for the transposed form) must tile by 8 x 16
@@ -900,17 +908,37 @@ long long dm_wide_conv_scratch_floats(int form, int CIN, int NOUT, int taps)
     return r;
 }
 
+// The streaming kernel that takes a dm_wide_conv call, if one does (the order is the order they are tried in), else the tiled
+// kernel: the launch below and the host-only queries of conv_mfma.hip both read this.
+dm_launch_plan dm_wide_conv_plan(int form, const Operand &in, bool has_scratch, const Epilogue &ep, int B, int Cphys, int CIN,
+                                 int NOUT, int H, int W, int taps, int nslabs, int per_tile)
+{
+    dm_launch_plan p;
+    if (form == W_PIX && CIN * 32 <= dm_wide_conv_scratch_floats(form, CIN, NOUT, taps) &&
+        dm_stream_convT_thin_plan(in, has_scratch, ep, B, Cphys, CIN, NOUT, H, W, per_tile, &p))
+        return p;
+    if (form == W_S1 && taps == 9 && dm_stream_conv3x3_wide_plan(in, ep, B, Cphys, CIN, NOUT, H, W, nslabs, per_tile, &p)) return p;
+    if (form == W_PIX && dm_stream_convT_wide_plan(in, ep, B, Cphys, CIN, NOUT, H, W, nslabs, per_tile, &p)) return p;
+    if (form == W_S2 && dm_stream_conv_s2_wide_plan(in, ep, B, Cphys, CIN, NOUT, H, W, nslabs, per_tile, &p)) return p;
+    if (form == W_S2 && dm_stream_conv_s2_thin_plan(in, ep, B, Cphys, CIN, NOUT, H, W, nslabs, per_tile, &p)) return p;
+    if (form == W_S1 && taps == 1 && dm_stream_conv1x1_plan(in, ep, B, Cphys, CIN, NOUT, H, W, nslabs, per_tile, &p)) return p;
+    return family_plan(DM_KERNEL_WIDE_TILED);
+}
+
 int dm_wide_conv(int form, const Operand &in, const WeightView &wv, float *scratch, float *out, const Epilogue &ep, int B,
                  int Cphys, int CIN, int NOUT, int H, int W, int taps, int nslabs, int per_tile, hipStream_t st)
 {
-    if (form == W_PIX && CIN * 32 <= dm_wide_conv_scratch_floats(form, CIN, NOUT, taps) &&
-        dm_stream_convT_thin(in, wv, scratch, out, ep, B, Cphys, CIN, NOUT, H, W, per_tile, st))
-        return 0;
-    if (form == W_S1 && taps == 9 && dm_stream_conv3x3_wide(in, wv, out, ep, B, Cphys, CIN, NOUT, H, W, nslabs, per_tile, st)) return 0;
-    if (form == W_PIX && dm_stream_convT_wide(in, wv, out, ep, B, Cphys, CIN, NOUT, H, W, nslabs, per_tile, st)) return 0;
-    if (form == W_S2 && dm_stream_conv_s2_wide(in, wv, out, ep, B, Cphys, CIN, NOUT, H, W, nslabs, per_tile, st)) return 0;
-    if (form == W_S2 && dm_stream_conv_s2_thin(in, wv, out, ep, B, Cphys, CIN, NOUT, H, W, nslabs, per_tile, st)) return 0;
-    if (form == W_S1 && taps == 1 && dm_stream_conv1x1(in, wv, out, ep, B, Cphys, CIN, NOUT, H, W, nslabs, per_tile, st)) return 0;
+    const dm_launch_plan p = dm_wide_conv_plan(form, in, scratch != nullptr, ep, B, Cphys, CIN, NOUT, H, W, taps, nslabs, per_tile);
+    switch (p.kernel) {
+    case DM_KERNEL_CONVT_THIN_STREAM: dm_stream_convT_thin(p, in, wv, scratch, out, ep, B, CIN, NOUT, H, st); return 0;
+    case DM_KERNEL_CONV_S2_THIN_STREAM: dm_stream_conv_s2_thin(p, in, wv, out, ep, B, CIN, NOUT, H, nslabs, st); return 0;
+    case DM_KERNEL_CONV1X1_STREAM: dm_stream_conv1x1(p, in, wv, out, ep, B, CIN, NOUT, H, W, nslabs, st); return 0;
+    // the three weights-in-LDS kernels: false = the device refused the dynamic LDS, the tiled kernel runs
+    case DM_KERNEL_CONV3X3_WIDE_STREAM: if (dm_stream_conv3x3_wide(p, in, wv, out, ep, B, nslabs, st)) return 0; break;
+    case DM_KERNEL_CONVT_WIDE_STREAM: if (dm_stream_convT_wide(p, in, wv, out, ep, B, nslabs, st)) return 0; break;
+    case DM_KERNEL_CONV_S2_WIDE_STREAM: if (dm_stream_conv_s2_wide(p, in, wv, out, ep, B, nslabs, st)) return 0; break;
+    default: break;
+    }
     const int gx = persistent_grid(per_tile ? B : wide_conv_tiles(form, B, H, W), 1, WIDE_MAX_BLOCKS, ep.stats && !per_tile, nslabs);
     const int np = wide_npw(form, NOUT);
     const int nn = form == W_PIX ? NOUT / 4 : NOUT;
@@ -938,13 +966,16 @@ int dm_wide_conv(int form, const Operand &in, const WeightView &wv, float *scrat
 // streaming forms of the memory-bound layers (wide_stream.hip)
 bool dm_stream_wgrad1x1_shape(int B, int CS, int CT, int Hs, int Ws);
 int dm_stream_wgrad1x1_slabs(int B, int Hs, int Ws);
-bool dm_stream_wgrad1x1(const Operand &S, const Operand &T, float *slabs, int B, int CS, int CT, int Hs, int Ws, int nslabs,
-                        hipStream_t st);
+bool dm_stream_wgrad1x1_plan(const Operand &S, const Operand &T, int B, int CS, int CT, int Hs, int Ws, int nslabs, dm_launch_plan *p);
+void dm_stream_wgrad1x1(const dm_launch_plan &p, const Operand &S, const Operand &T, float *slabs, int B, int CS, int CT, int Hs,
+                        int Ws, int nslabs, hipStream_t st);
 
 bool dm_stream_wgrad_s2_thin_shape(int B, int CS, int CT, int Hs, int Ws);
 int dm_stream_wgrad_s2_thin_slabs(int B, int Hs, int Ws);
-bool dm_stream_wgrad_s2_thin(const Operand &S, const Operand &T, float *slabs, int B, int CS, int CT, int Hs, int Ws, int nslabs,
-                             hipStream_t st);
+bool dm_stream_wgrad_s2_thin_plan(const Operand &S, const Operand &T, int B, int CS, int CT, int Hs, int Ws, int nslabs,
+                                  dm_launch_plan *p);
+void dm_stream_wgrad_s2_thin(const dm_launch_plan &p, const Operand &S, const Operand &T, float *slabs, int B, int CS, int CT,
+                             int Hs, int Ws, int nslabs, hipStream_t st);
 
 // T as an AFFINE2 operand (two tensors): only where the one-pass kernel prefetches both
 bool dm_wide_wgrad_t_affine2_ok(int CS, int CT, int Hs, int Ws, int k);
@@ -993,13 +1024,29 @@ int dm_wide_wgrad_slabs(int B, int CS, int CT, int Hs, int Ws, int k)
     return (int)(units < cap ? units : cap);
 }
 
+// The kernel that takes a dm_wide_wgrad call: a streaming one, the one-pass kernel (a workgroup walks 8 x 16 tiles of the S
+// grid, grid-strided) or the tiled one.  Read by the launch below and by dm_wgrad_plan.
+dm_launch_plan dm_wide_wgrad_plan(const Operand &S, const Operand &T, int B, int CS, int CT, int CTphys, int Hs, int Ws, int k,
+                                  int nslabs)
+{
+    dm_launch_plan p;
+    if (k == 1 && dm_stream_wgrad1x1_plan(S, T, B, CS, CT, Hs, Ws, nslabs, &p)) return p;
+    if (k == 4 && CT == CTphys && dm_stream_wgrad_s2_thin_plan(S, T, B, CS, CT, Hs, Ws, nslabs, &p)) return p;
+    if (wide_wgrad1_shape(CS, CT, k) && wide_wgrad1_takes(S, T, CT, CTphys, k)) {
+        const long long units = wide_wgrad_units(B, Hs, Ws);
+        return persistent_plan(DM_KERNEL_WGRAD_WIDE1, persistent_grid(units, 1, 256, true, nslabs), 8, 1, DM_DEAL_GRID_STRIDED, units);
+    }
+    return family_plan(DM_KERNEL_WIDE_TILED);
+}
+
 int dm_wide_wgrad(const Operand &S, const Operand &T, float *slabs, int B, int CS, int CT, int CTphys, int Hs, int Ws,
                   int k, int nslabs, hipStream_t st)
 {
-    if (k == 1 && dm_stream_wgrad1x1(S, T, slabs, B, CS, CT, Hs, Ws, nslabs, st)) return 0;
-    if (k == 4 && CT == CTphys && dm_stream_wgrad_s2_thin(S, T, slabs, B, CS, CT, Hs, Ws, nslabs, st)) return 0;
-    if (wide_wgrad1_shape(CS, CT, k) && wide_wgrad1_takes(S, T, CT, CTphys, k)) {
-        const int g1 = persistent_grid(wide_wgrad_units(B, Hs, Ws), 1, 256, true, nslabs);
+    const dm_launch_plan p = dm_wide_wgrad_plan(S, T, B, CS, CT, CTphys, Hs, Ws, k, nslabs);
+    if (p.kernel == DM_KERNEL_WGRAD1X1_STREAM) { dm_stream_wgrad1x1(p, S, T, slabs, B, CS, CT, Hs, Ws, nslabs, st); return 0; }
+    if (p.kernel == DM_KERNEL_WGRAD_S2_THIN_STREAM) { dm_stream_wgrad_s2_thin(p, S, T, slabs, B, CS, CT, Hs, Ws, nslabs, st); return 0; }
+    if (p.kernel == DM_KERNEL_WGRAD_WIDE1) {
+        const int g1 = p.workgroups;
         const bool two = S.mode == DM_LOAD_AFFINE2;
         if (T.mode == DM_LOAD_AFFINE2) {       // the decoder's first transposed convolution: T = BatchNorm backward of its output gradient
             hipLaunchKernelGGL((wgrad_wide1_kernel<4, 32, false, true>), dim3(g1), dim3(512), 0, st, S, T, slabs, B, Hs, Ws, nslabs);

@@ -18,6 +18,7 @@
 #include "dm_common.h"
 #include "tile.h"
 #include "mfma_util.h"
+#include "wide_host.h"
 
 // fallback for shapes / channel families without an MFMA instantiation (conv_generic.hip)
 int dm_generic_wgrad(const Operand &S, const Operand &T, float *slabs, int B, int CS, int CT, int CTphys, int Hs, int Ws,
@@ -26,6 +27,8 @@ int dm_generic_wgrad(const Operand &S, const Operand &T, float *slabs, int B, in
 bool dm_wide_wgrad_ok(int Hs, int Ws);
 bool dm_wide_wgrad_t_affine2_ok(int CS, int CT, int Hs, int Ws, int k);
 int dm_wide_wgrad_slabs(int B, int CS, int CT, int Hs, int Ws, int k);
+dm_launch_plan dm_wide_wgrad_plan(const Operand &S, const Operand &T, int B, int CS, int CT, int CTphys, int Hs, int Ws, int k,
+                                  int nslabs);
 int dm_wide_wgrad(const Operand &S, const Operand &T, float *slabs, int B, int CS, int CT, int CTphys, int Hs, int Ws,
                   int k, int nslabs, hipStream_t st);
 
@@ -562,22 +565,43 @@ extern "C" int dm_wgrad_num_blocks(int B, int CS, int CT, int Hs, int Ws, int k)
     return wgrad_route(B, CS, CT, Hs, Ws, k).nslabs;
 }
 
+// what dm_wgrad and dm_wgrad_plan check alike before the route is read
+static int wgrad_checks(const char *who, const dm_operand *S, const dm_operand *T, int B, int CS, int CT, int Hs, int Ws, int k,
+                        WgradRoute *route)
+{
+    if (dm_check_operand(S, who) || dm_check_operand(T, who)) return -1;
+    DM_REQUIRE((long long)B * (CS > 4 * CT ? CS : 4 * CT) * Hs * Ws < (1LL << 31), "%s: tensor too large for 32-bit offsets", who);
+    DM_REQUIRE(k == 4 || k == 3 || k == 1, "%s: kernel size %d not built", who, k);
+    DM_REQUIRE(!S->ones_channel, "%s: S cannot carry a ones channel", who);
+    DM_REQUIRE(B > 0, "%s: bad shape", who);
+    const WgradRoute r = wgrad_route(B, CS, CT, Hs, Ws, k);
+    DM_REQUIRE(T->mode != DM_LOAD_AFFINE2 || (r.kind != ROUTE_RESIDENT && dm_wide_wgrad_t_affine2_ok(CS, CT, Hs, Ws, k) &&
+                                              S->mode != DM_LOAD_AFFINE2 && !T->ones_channel),
+               "%s: T operand cannot be AFFINE2 for this shape (dm_wgrad_t_affine2_supported)", who);
+    DM_REQUIRE(CT - (T->ones_channel ? 1 : 0) > 0, "%s: no physical T channel", who);
+    *route = r;
+    return 0;
+}
+
+extern "C" int dm_wgrad_plan(const dm_operand *S, const dm_operand *T, int B, int CS, int CT, int Hs, int Ws, int k,
+                             dm_launch_plan *plan)
+{
+    WgradRoute r;
+    DM_REQUIRE(plan, "dm_wgrad_plan: NULL plan");
+    if (wgrad_checks("dm_wgrad_plan", S, T, B, CS, CT, Hs, Ws, k, &r)) return -1;
+    if (r.kind == ROUTE_WIDE) *plan = dm_wide_wgrad_plan(to_dev(S), to_dev(T), B, CS, CT, CT - (T->ones_channel ? 1 : 0), Hs, Ws, k, r.nslabs);
+    else *plan = family_plan(r.kind == ROUTE_RESIDENT ? DM_KERNEL_RESIDENT : DM_KERNEL_GENERIC);
+    return 0;
+}
+
 extern "C" int dm_wgrad(const dm_operand *S, const dm_operand *T, float *slabs, float *dst,
                         int B, int CS, int CT, int Hs, int Ws, int k, void *stream)
 {
-    if (dm_check_operand(S, "dm_wgrad(S)") || dm_check_operand(T, "dm_wgrad(T)")) return -1;
+    WgradRoute r;
     DM_REQUIRE(slabs, "dm_wgrad: NULL slabs");
-    DM_REQUIRE((long long)B * (CS > 4 * CT ? CS : 4 * CT) * Hs * Ws < (1LL << 31), "dm_wgrad: tensor too large for 32-bit offsets");
-    DM_REQUIRE(k == 4 || k == 3 || k == 1, "dm_wgrad: kernel size %d not built", k);
-    DM_REQUIRE(!S->ones_channel, "dm_wgrad: S cannot carry a ones channel");
-    DM_REQUIRE(B > 0, "dm_wgrad: bad shape");
-    const WgradRoute r = wgrad_route(B, CS, CT, Hs, Ws, k);
+    if (wgrad_checks("dm_wgrad", S, T, B, CS, CT, Hs, Ws, k, &r)) return -1;
     const int grid = r.nslabs;          // = slabs: every workgroup writes one
-    DM_REQUIRE(T->mode != DM_LOAD_AFFINE2 || (r.kind != ROUTE_RESIDENT && dm_wide_wgrad_t_affine2_ok(CS, CT, Hs, Ws, k) &&
-                                              S->mode != DM_LOAD_AFFINE2 && !T->ones_channel),
-               "dm_wgrad: T operand cannot be AFFINE2 for this shape (dm_wgrad_t_affine2_supported)");
     const int CTphys = CT - (T->ones_channel ? 1 : 0);
-    DM_REQUIRE(CTphys > 0, "dm_wgrad: no physical T channel");
     hipStream_t st = (hipStream_t)stream;
     const Operand s = to_dev(S), t = to_dev(T);
     const int E = CS * CT * k * k;

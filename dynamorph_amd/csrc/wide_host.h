@@ -27,6 +27,19 @@ static inline int persistent_grid(long long units, int per_wg, int cap, bool sla
     return grid < 1 ? 1 : grid;
 }
 
+// What a dispatcher decided for a persistent kernel (dm_launch_plan, include/dynamorph_hip.h): filled by the *_plan function of
+// a launcher, which is where "does it take the call, and with what grid" lives; the launcher launches p.workgroups and the
+// host-only queries (dm_conv4x4s2_plan ...) hand the same struct out.
+static inline dm_launch_plan persistent_plan(int kernel, int workgroups, int waves, int walkers, int dealing, long long units, int ring = 0)
+{
+    dm_launch_plan p{};
+    p.kernel = kernel; p.workgroups = workgroups; p.waves = waves; p.walkers = walkers; p.dealing = dealing; p.ring = ring;
+    p.units = units;
+    return p;
+}
+// a kernel family that is not a persistent stream: only the kernel value is set
+static inline dm_launch_plan family_plan(int kernel) { return persistent_plan(kernel, 0, 0, 0, DM_DEAL_NONE, 0); }
+
 // Dynamic LDS beyond 64 KB has to be granted per kernel (per launch: the attribute belongs to the current device's copy of it).
 static inline bool reserve_dynamic_lds(std::initializer_list<const void *> kernels, int bytes)
 {

@@ -19,6 +19,9 @@
 
 namespace {
 
+// stages of 32 pixels the two streaming weight gradients keep in flight per walker (also what their plans report as `ring`)
+constexpr int WGRAD1X1_RING = 2, WGRAD_S2_THIN_RING = 1;
+
 __device__ __forceinline__ f32x4 sx_max(f32x4 v, float lo)
 {
     return (f32x4){__builtin_elementwise_maximum(v.x, lo), __builtin_elementwise_maximum(v.y, lo),
@@ -58,7 +61,7 @@ template <int MT, int NT, bool S2>
 __global__ __launch_bounds__(256, 3) void wgrad1x1_stream_kernel(Operand S, Operand T, float *__restrict__ slabs,
                                                                  int B, int CS, int CT, int HW, int nslabs)
 {
-    constexpr int D = 2;                                         // groups of 32 pixels in flight per wave
+    constexpr int D = WGRAD1X1_RING;                             // groups of 32 pixels in flight per wave
     constexpr int NG = 4 / MT, NTW = NT / NG;
     static_assert(MT * NG == 4 && NTW * NG == NT, "four waves share MT x NT tiles");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, p = lane & 15, kq = lane >> 4;
@@ -1388,8 +1391,11 @@ int stream_switch()
 }  // namespace
 
 // ---- entry points used by conv_wide.hip's dispatchers (not part of the public header) ----------------------------------
-// shapes the 1x1 streaming weight gradient is built for (operands are checked at the launch: dm_stream_wgrad1x1 returns
-// false and the caller falls back to the tiled kernel, which accepts any slab count)
+// Every launcher comes as a pair: dm_stream_X_plan says whether the streaming kernel takes the call and with what grid (host
+// arithmetic only: the dispatchers' launches and the host-only dm_*_plan queries both ask it), dm_stream_X launches that plan.
+
+// shapes the 1x1 streaming weight gradient is built for (operands are checked by dm_stream_wgrad1x1_plan: where it returns
+// false the caller falls back to the tiled kernel, which accepts any slab count)
 bool dm_stream_wgrad1x1_shape(int B, int CS, int CT, int Hs, int Ws)
 {
     if (!(stream_switch() & 1)) return false;
@@ -1403,13 +1409,21 @@ int dm_stream_wgrad1x1_slabs(int B, int Hs, int Ws)
     return (int)(groups < 768 ? groups : 768);                 // three workgroups per CU, one contiguous range each
 }
 
-bool dm_stream_wgrad1x1(const Operand &S, const Operand &T, float *slabs, int B, int CS, int CT, int Hs, int Ws, int nslabs,
-                        hipStream_t st)
+bool dm_stream_wgrad1x1_plan(const Operand &S, const Operand &T, int B, int CS, int CT, int Hs, int Ws, int nslabs, dm_launch_plan *p)
 {
     if (!dm_stream_wgrad1x1_shape(B, CS, CT, Hs, Ws) || T.ones || S.ones || T.mode == DM_LOAD_AFFINE2) return false;
     if (per_sample_coef(S) || per_sample_coef(T)) return false;
     int grid = dm_stream_wgrad1x1_slabs(B, Hs, Ws);
     if (grid > nslabs) grid = nslabs;
+    // the four waves of a workgroup share every group of 32 pixels: the workgroup is the walker
+    *p = persistent_plan(DM_KERNEL_WGRAD1X1_STREAM, grid, 4, 1, DM_DEAL_RANGE, (long long)B * ((Hs * Ws) >> 5), WGRAD1X1_RING);
+    return true;
+}
+
+void dm_stream_wgrad1x1(const dm_launch_plan &p, const Operand &S, const Operand &T, float *slabs, int B, int CS, int CT, int Hs,
+                        int Ws, int nslabs, hipStream_t st)
+{
+    const int grid = p.workgroups;
     const int HW = Hs * Ws;
     const bool two = S.mode == DM_LOAD_AFFINE2;
 #define DM_SW(MT_, NT_)                                                                                                  \
@@ -1419,18 +1433,26 @@ bool dm_stream_wgrad1x1(const Operand &S, const Operand &T, float *slabs, int B,
     }
     DM_SW(4, 4) DM_SW(4, 2) DM_SW(2, 4) DM_SW(2, 2)
 #undef DM_SW
-    return true;
 }
 
 // 1x1 convolution, 64 -> 64 / 32 -> 32 ... channels (multiples of 16 up to 64 on both sides), shared coefficients, statistics
-// per workgroup.  Returns false when the call is not one the streaming kernel takes (the caller runs the tiled kernel).
-bool dm_stream_conv1x1(const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B, int Cphys, int CIN,
-                       int NOUT, int H, int W, int nslabs, int per_tile, hipStream_t st)
+// per workgroup.  The plan returns false when the call is not one the streaming kernel takes (the caller runs the tiled kernel).
+bool dm_stream_conv1x1_plan(const Operand &in, const Epilogue &ep, int B, int Cphys, int CIN, int NOUT, int H, int W, int nslabs,
+                            int per_tile, dm_launch_plan *p)
 {
     if (!(stream_switch() & 2) || !stream_operand_ok(in, ep, Cphys, CIN, per_tile) || !stream_mask_ok(ep)) return false;
     const long long HW = (long long)H * W;
     if (!((CIN == 64 || CIN == 32) && (NOUT == 64 || NOUT == 32)) || HW % 64 || (long long)B * 64 * HW * 4 >= (1LL << 32)) return false;
-    const int grid = persistent_grid((long long)B * HW / 64, 4, 512, ep.stats, nslabs);
+    const long long units = (long long)B * HW / 64;
+    *p = persistent_plan(DM_KERNEL_CONV1X1_STREAM, persistent_grid(units, 4, 512, ep.stats, nslabs), 4, 4, DM_DEAL_RANGE_STRIDED, units);
+    return true;
+}
+
+void dm_stream_conv1x1(const dm_launch_plan &p, const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B,
+                       int CIN, int NOUT, int H, int W, int nslabs, hipStream_t st)
+{
+    const long long HW = (long long)H * W;
+    const int grid = p.workgroups;
     const bool two = in.mode == DM_LOAD_AFFINE2;
 #define DM_SC(K4_, MT_)                                                                                                      \
     if (CIN == 16 * K4_ && NOUT == 16 * MT_) {                                                                                \
@@ -1439,7 +1461,6 @@ bool dm_stream_conv1x1(const Operand &in, const WeightView &wv, float *out, cons
     }
     DM_SC(4, 4) DM_SC(4, 2) DM_SC(2, 4) DM_SC(2, 2)
 #undef DM_SC
-    return true;
 }
 
 // weight gradient of a 4x4 / stride 2 layer with 16 / 32 / 64 S channels and 1-4 T channels
@@ -1456,66 +1477,102 @@ int dm_stream_wgrad_s2_thin_slabs(int B, int Hs, int Ws)
     return (int)(stages / 4 < 768 ? (stages + 3) / 4 : 768);
 }
 
-bool dm_stream_wgrad_s2_thin(const Operand &S, const Operand &T, float *slabs, int B, int CS, int CT, int Hs, int Ws, int nslabs,
-                             hipStream_t st)
+bool dm_stream_wgrad_s2_thin_plan(const Operand &S, const Operand &T, int B, int CS, int CT, int Hs, int Ws, int nslabs,
+                                  dm_launch_plan *p)
 {
     if (!dm_stream_wgrad_s2_thin_shape(B, CS, CT, Hs, Ws) || T.ones || S.ones || T.mode == DM_LOAD_AFFINE2) return false;
     if (per_sample_coef(S) || per_sample_coef(T)) return false;
     int grid = dm_stream_wgrad_s2_thin_slabs(B, Hs, Ws);
     if (grid > nslabs) grid = nslabs;
-    const bool two = S.mode == DM_LOAD_AFFINE2;
-#define DM_ST(MT_, NT_)                                                                                                      \
-    if (CS == 16 * MT_ && CT == NT_) {                                                                                        \
-        if (two) hipLaunchKernelGGL((wgrad_s2_thin_stream_kernel<MT_, NT_, true, 1>), dim3(grid), dim3(256), 0, st, S, T, slabs, B, CS, Hs, Ws, nslabs); \
-        else hipLaunchKernelGGL((wgrad_s2_thin_stream_kernel<MT_, NT_, false, 1>), dim3(grid), dim3(256), 0, st, S, T, slabs, B, CS, Hs, Ws, nslabs); \
-    }
-    DM_ST(1, 1) DM_ST(1, 2) DM_ST(1, 3) DM_ST(1, 4) DM_ST(2, 1) DM_ST(2, 2) DM_ST(2, 3) DM_ST(2, 4) DM_ST(4, 1)
-#undef DM_ST
+    *p = persistent_plan(DM_KERNEL_WGRAD_S2_THIN_STREAM, grid, 4, 4, DM_DEAL_RANGE, (long long)B * Hs * (Ws >> 5), WGRAD_S2_THIN_RING);
     return true;
 }
 
+void dm_stream_wgrad_s2_thin(const dm_launch_plan &p, const Operand &S, const Operand &T, float *slabs, int B, int CS, int CT,
+                             int Hs, int Ws, int nslabs, hipStream_t st)
+{
+    const int grid = p.workgroups;
+    const bool two = S.mode == DM_LOAD_AFFINE2;
+#define DM_ST(MT_, NT_)                                                                                                      \
+    if (CS == 16 * MT_ && CT == NT_) {                                                                                        \
+        if (two) hipLaunchKernelGGL((wgrad_s2_thin_stream_kernel<MT_, NT_, true, WGRAD_S2_THIN_RING>), dim3(grid), dim3(256), 0, st, S, T, slabs, B, CS, Hs, Ws, nslabs); \
+        else hipLaunchKernelGGL((wgrad_s2_thin_stream_kernel<MT_, NT_, false, WGRAD_S2_THIN_RING>), dim3(grid), dim3(256), 0, st, S, T, slabs, B, CS, Hs, Ws, nslabs); \
+    }
+    DM_ST(1, 1) DM_ST(1, 2) DM_ST(1, 3) DM_ST(1, 4) DM_ST(2, 1) DM_ST(2, 2) DM_ST(2, 3) DM_ST(2, 4) DM_ST(4, 1)
+#undef DM_ST
+}
+
 // 4x4 / stride 2 convolution, 1-4 input channels -> 16 / 32 / 64 output channels, 128-column input
-bool dm_stream_conv_s2_thin(const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B, int Cphys, int CIN,
-                            int NOUT, int H, int W, int nslabs, int per_tile, hipStream_t st)
+bool dm_stream_conv_s2_thin_plan(const Operand &in, const Epilogue &ep, int B, int Cphys, int CIN, int NOUT, int H, int W,
+                                 int nslabs, int per_tile, dm_launch_plan *p)
 {
     if (!(stream_switch() & 8) || !stream_operand_ok(in, ep, Cphys, CIN, per_tile) || !stream_mask_ok(ep) || in.mode == DM_LOAD_AFFINE2) return false;
     if (CIN < 1 || CIN > 4 || !(NOUT == 16 || NOUT == 32 || (NOUT == 64 && CIN <= 2)) || W != 128 || H % 2) return false;
     if ((long long)B * NOUT * (H / 2) * (W / 2) * 4 >= (1LL << 32) || (long long)B * CIN * H * W * 4 >= (1LL << 31)) return false;
-    const int grid = persistent_grid((long long)B * (H / 2), 4, 768, ep.stats, nslabs);
+    const long long units = (long long)B * (H / 2);
+    *p = persistent_plan(DM_KERNEL_CONV_S2_THIN_STREAM, persistent_grid(units, 4, 768, ep.stats, nslabs), 4, 4, DM_DEAL_RANGE_STRIDED, units);
+    return true;
+}
+
+void dm_stream_conv_s2_thin(const dm_launch_plan &p, const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B,
+                            int CIN, int NOUT, int H, int nslabs, hipStream_t st)
+{
+    const int grid = p.workgroups;
 #define DM_CT(C_, MT_)                                                                                                       \
     if (CIN == C_ && NOUT == 16 * MT_)                                                                                        \
         hipLaunchKernelGGL((conv_s2_thin_stream_kernel<C_, MT_>), dim3(grid), dim3(256), 0, st, in, wv, out, ep, B, H, nslabs);
     DM_CT(1, 1) DM_CT(2, 1) DM_CT(3, 1) DM_CT(4, 1) DM_CT(1, 2) DM_CT(2, 2) DM_CT(3, 2) DM_CT(4, 2) DM_CT(1, 4) DM_CT(2, 4)
 #undef DM_CT
-    return true;
 }
 
 // ConvTranspose2d(4, 2, 1) from up to 64 channels on a 64-column grid to 1 or 2 channels, no gate / residual / statistics
-bool dm_stream_convT_thin(const Operand &in, const WeightView &wv, float *scratch, float *out, const Epilogue &ep, int B, int Cphys,
-                          int CIN, int NOUT, int H, int W, int per_tile, hipStream_t st)
+bool dm_stream_convT_thin_plan(const Operand &in, bool has_scratch, const Epilogue &ep, int B, int Cphys, int CIN, int NOUT, int H,
+                               int W, int per_tile, dm_launch_plan *p)
 {
     if (!(stream_switch() & 16) || !stream_operand_ok(in, ep, Cphys, CIN, per_tile) || in.mode == DM_LOAD_AFFINE2) return false;
-    if (!(NOUT == 4 || NOUT == 8) || W != 64 || H % 4 || CIN < 1 || CIN > 64 || !scratch) return false;
+    if (!(NOUT == 4 || NOUT == 8) || W != 64 || H % 4 || CIN < 1 || CIN > 64 || !has_scratch) return false;
     if (ep.mask.p0 || ep.resid || ep.stats || (long long)B * CIN * H * W * 4 >= (1LL << 31)) return false;
+    const long long units = (long long)B * (H / 4);
+    *p = persistent_plan(DM_KERNEL_CONVT_THIN_STREAM, persistent_grid(units, 4, 1024, false, 0), 4, 4, DM_DEAL_GRID_STRIDED, units);
+    return true;
+}
+
+void dm_stream_convT_thin(const dm_launch_plan &p, const Operand &in, const WeightView &wv, float *scratch, float *out,
+                          const Epilogue &ep, int B, int CIN, int NOUT, int H, hipStream_t st)
+{
     hipLaunchKernelGGL(convT_thin_pack_kernel, dim3((CIN * 32 + 255) / 256), dim3(256), 0, st, wv, scratch, CIN, NOUT / 4);
-    const int grid = persistent_grid((long long)B * (H / 4), 4, 1024, false, 0);
+    const int grid = p.workgroups;
     if (NOUT == 8) hipLaunchKernelGGL((convT_thin_stream_kernel<2>), dim3(grid), dim3(256), 0, st, in, (const float *)scratch, out, ep, B, CIN, H);
     else hipLaunchKernelGGL((convT_thin_stream_kernel<1>), dim3(grid), dim3(256), 0, st, in, (const float *)scratch, out, ep, B, CIN, H);
-    return true;
+}
+
+// The three weights-in-LDS kernels: 16 units of 2 rows x 32 pixels per sample, eight waves, one workgroup per CU.  Their
+// launchers return false where the device refuses the dynamic LDS (the caller then runs the tiled kernel).
+static dm_launch_plan lds_stream_plan(int kernel, const Epilogue &ep, int B, int nslabs)
+{
+    const long long units = (long long)B * 16;
+    return persistent_plan(kernel, persistent_grid(units, 8, 256, ep.stats, nslabs), 8, 8, DM_DEAL_RANGE_STRIDED, units);
 }
 
 // 4x4 / stride 2 convolution 32 -> 64 channels on a 64 x 64 input (the wide encoder's second convolution, the data gradient
 // of the decoder's first transposed convolution)
-bool dm_stream_conv_s2_wide(const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B, int Cphys, int CIN,
-                            int NOUT, int H, int W, int nslabs, int per_tile, hipStream_t st)
+bool dm_stream_conv_s2_wide_plan(const Operand &in, const Epilogue &ep, int B, int Cphys, int CIN, int NOUT, int H, int W,
+                                 int nslabs, int per_tile, dm_launch_plan *p)
 {
     if (!(stream_switch() & 32) || !stream_operand_ok(in, ep, Cphys, CIN, per_tile) || !stream_mask_ok(ep)) return false;
     if (CIN != 32 || NOUT != 64 || H != 64 || W != 64 || (long long)B * 64 * 32 * 32 * 4 >= (1LL << 31)) return false;
+    *p = lds_stream_plan(DM_KERNEL_CONV_S2_WIDE_STREAM, ep, B, nslabs);
+    return true;
+}
+
+bool dm_stream_conv_s2_wide(const dm_launch_plan &p, const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B,
+                            int nslabs, hipStream_t st)
+{
     const int lds = 128 * 1024;
     if (!reserve_dynamic_lds({(const void *)conv_s2_wide_stream_kernel<true>, (const void *)conv_s2_wide_stream_kernel<false>,
                               (const void *)conv_s2_wide_stream_kernel<true, true>}, lds))
         return false;
-    const int grid = persistent_grid((long long)B * 16, 8, 256, ep.stats, nslabs);
+    const int grid = p.workgroups;
     if (in.mode == DM_LOAD_AFFINE2)
         hipLaunchKernelGGL((conv_s2_wide_stream_kernel<true, true>), dim3(grid), dim3(512), lds, st, in, wv, out, ep, B, nslabs);
     else if (in.mode >= DM_LOAD_AFFINE || in.mode == DM_LOAD_RELU)
@@ -1527,15 +1584,22 @@ bool dm_stream_conv_s2_wide(const Operand &in, const WeightView &wv, float *out,
 
 // ConvTranspose2d(64 -> 32, 4, 2, 1) on a 32 x 32 input (the wide decoder's first transposed convolution, the data gradient of
 // the encoder's second convolution)
-bool dm_stream_convT_wide(const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B, int Cphys, int CIN,
-                          int NOUT, int H, int W, int nslabs, int per_tile, hipStream_t st)
+bool dm_stream_convT_wide_plan(const Operand &in, const Epilogue &ep, int B, int Cphys, int CIN, int NOUT, int H, int W,
+                               int nslabs, int per_tile, dm_launch_plan *p)
 {
     if (!(stream_switch() & 64) || !stream_operand_ok(in, ep, Cphys, CIN, per_tile) || !stream_mask_ok(ep)) return false;
     if (CIN != 64 || NOUT != 128 || H != 32 || W != 32 || (long long)B * 64 * 32 * 32 * 4 >= (1LL << 31)) return false;
+    *p = lds_stream_plan(DM_KERNEL_CONVT_WIDE_STREAM, ep, B, nslabs);
+    return true;
+}
+
+bool dm_stream_convT_wide(const dm_launch_plan &p, const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B,
+                          int nslabs, hipStream_t st)
+{
     const int lds = 128 * 1024;
     if (!reserve_dynamic_lds({(const void *)convT_wide_stream_kernel<true>, (const void *)convT_wide_stream_kernel<false>}, lds))
         return false;
-    const int grid = persistent_grid((long long)B * 16, 8, 256, ep.stats, nslabs);
+    const int grid = p.workgroups;
     if (in.mode == DM_LOAD_AFFINE2)
         hipLaunchKernelGGL((convT_wide_stream_kernel<true>), dim3(grid), dim3(512), lds, st, in, wv, out, ep, B, nslabs);
     else
@@ -1544,16 +1608,23 @@ bool dm_stream_convT_wide(const Operand &in, const WeightView &wv, float *out, c
 }
 
 // 3x3 convolution 64 -> 64 channels on a 32 x 32 grid (the wide residual blocks; forward and data-gradient form)
-bool dm_stream_conv3x3_wide(const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B, int Cphys, int CIN,
-                            int NOUT, int H, int W, int nslabs, int per_tile, hipStream_t st)
+bool dm_stream_conv3x3_wide_plan(const Operand &in, const Epilogue &ep, int B, int Cphys, int CIN, int NOUT, int H, int W,
+                                 int nslabs, int per_tile, dm_launch_plan *p)
 {
     const int bit = ep.mask.p0 ? 256 : 128;
     if (!(stream_switch() & bit) || !stream_operand_ok(in, ep, Cphys, CIN, per_tile) || !stream_mask_ok(ep)) return false;
     if (CIN != 64 || NOUT != 64 || H != 32 || W != 32 || (long long)B * 64 * 32 * 32 * 4 >= (1LL << 31)) return false;
+    *p = lds_stream_plan(DM_KERNEL_CONV3X3_WIDE_STREAM, ep, B, nslabs);
+    return true;
+}
+
+bool dm_stream_conv3x3_wide(const dm_launch_plan &p, const Operand &in, const WeightView &wv, float *out, const Epilogue &ep, int B,
+                            int nslabs, hipStream_t st)
+{
     const int lds = 9 * 64 * 64 * 4;
     if (!reserve_dynamic_lds({(const void *)conv3x3_wide_stream_kernel<true>, (const void *)conv3x3_wide_stream_kernel<false>}, lds))
         return false;
-    const int grid = persistent_grid((long long)B * 16, 8, 256, ep.stats, nslabs);
+    const int grid = p.workgroups;
     if (in.mode == DM_LOAD_AFFINE2)
         hipLaunchKernelGGL((conv3x3_wide_stream_kernel<true>), dim3(grid), dim3(512), lds, st, in, wv, out, ep, B, nslabs);
     else
@@ -1567,20 +1638,27 @@ bool dm_stream_conv1x1_bwd_shape(int CD, int CX, int H, int W)
     return (stream_switch() & 512) && CD == 64 && CX == 64 && H > 0 && W > 0 && ((long long)H * W) % 64 == 0;
 }
 
-int dm_stream_conv1x1_bwd_slabs(int B, int H, int W)
+dm_launch_plan dm_stream_conv1x1_bwd_plan(int B, int H, int W)
 {
     const long long units = (long long)B * H * W / 64;
     const long long wg = units / 4 < 512 ? (units + 3) / 4 : 512;
-    return (int)(wg * 4);
+    return persistent_plan(DM_KERNEL_CONV1X1_BWD_WIDE_STREAM, (int)wg, 4, 4, DM_DEAL_RANGE, units);
+}
+
+int dm_stream_conv1x1_bwd_slabs(int B, int H, int W)
+{
+    const dm_launch_plan p = dm_stream_conv1x1_bwd_plan(B, H, W);
+    return p.workgroups * p.walkers;
 }
 
 int dm_stream_conv1x1_bwd(const Operand &dy, const float *x, const float *xcoef, const float *w, float *dx, double *stats,
                           float *wslabs, int B, int H, int W, hipStream_t st)
 {
-    const int nslabs = dm_stream_conv1x1_bwd_slabs(B, H, W);
+    const dm_launch_plan p = dm_stream_conv1x1_bwd_plan(B, H, W);
+    const int nslabs = p.workgroups * p.walkers;
     if (dy.mode == DM_LOAD_AFFINE2)
-        hipLaunchKernelGGL((conv1x1_bwd_wide_stream_kernel<true>), dim3(nslabs / 4), dim3(256), 0, st, dy, x, xcoef, w, dx, stats, wslabs, B, H * W, nslabs);
+        hipLaunchKernelGGL((conv1x1_bwd_wide_stream_kernel<true>), dim3(p.workgroups), dim3(256), 0, st, dy, x, xcoef, w, dx, stats, wslabs, B, H * W, nslabs);
     else
-        hipLaunchKernelGGL((conv1x1_bwd_wide_stream_kernel<false>), dim3(nslabs / 4), dim3(256), 0, st, dy, x, xcoef, w, dx, stats, wslabs, B, H * W, nslabs);
+        hipLaunchKernelGGL((conv1x1_bwd_wide_stream_kernel<false>), dim3(p.workgroups), dim3(256), 0, st, dy, x, xcoef, w, dx, stats, wslabs, B, H * W, nslabs);
     return 0;
 }

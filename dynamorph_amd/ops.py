@@ -4,6 +4,7 @@ device pointers and the current HIP stream, and allocate outputs with PyTorch.
 Nothing here computes on the host and nothing falls back to ATen: a tensor that is not a
 contiguous fp32 device tensor is an error.
 """
+import collections
 import ctypes as C
 import functools
 
@@ -329,9 +330,7 @@ def conv4x4s2(inp, wv, B, CIN, NOUT, H, W, ep=None, out=None, want_stats=False, 
         stats = _new((nb, NOUT, 2), like, torch.float64)
     e = epilogue(stats=stats, **epkw)
     o = inp.struct()
-    # the operand / epilogue forms dm_conv4x4s2 keeps off its register-resident kernels (conv_mfma.hip, conv4_resident_takes)
-    fallback = inp.mode == L.DM_LOAD_AFFINE2 or (epkw.get("bias_border") is not None and
-                                                  any(epkw.get(k) is not None for k in ("mask", "resid", "stat_q")))
+    fallback = _conv4_fallback(inp.mode, epkw)
     wv.with_scratch(lib.dm_conv4x4s2_scratch_floats(CIN, NOUT, H, W, 1 if fallback else 0))
     L.check(lib.dm_conv4x4s2(C.byref(o), wv.ref(), _ptr(out), C.byref(e), B, CIN, NOUT, H, W, _stream()),
             "dm_conv4x4s2")
@@ -380,6 +379,92 @@ def wgrad(S, T, dst, B, CS, CT, Hs, Ws, k, pending=None):
 def wgrad_t_affine2_supported(CS, CT, Hs, Ws, k):
     """True where dm_wgrad takes T as an AFFINE2 operand (a BatchNorm backward folded into the load of the output gradient)."""
     return bool(L.load().dm_wgrad_t_affine2_supported(CS, CT, Hs, Ws, k))
+
+
+# ------------------------------------------------------------------ launch plans (host only)
+Plan = collections.namedtuple("Plan", "kernel workgroups waves walkers dealing ring units")
+_SOME = 64          # stands for a non-NULL device pointer in a plan query: the library reads which pointers are set, never what they point to
+
+
+def _given(v):
+    return v is not None and v is not False
+
+
+def _plan_op(x, per_sample=False, ones=False):
+    """dm_operand of a plan query from an Op (its tensors are not touched) or from a bare DM_LOAD_* mode; None: no operand."""
+    if x is None:
+        return _null_operand()
+    if isinstance(x, Op):
+        return L.Operand(_SOME, _SOME if x.p1 is not None else None, _SOME if x.coef is not None else None, x.bstride,
+                         x.mode, 1 if x.ones else 0)
+    mode = int(x)
+    return L.Operand(_SOME, _SOME if mode == L.DM_LOAD_AFFINE2 else None, _SOME if mode >= L.DM_LOAD_AFFINE else None,
+                     4 if per_sample else 0, mode, 1 if ones else 0)
+
+
+def _plan_ep(mask=None, resid=None, stat_q=None, stats=None, per_tile=False, bias=None, bias_border=None, relu=False):
+    """dm_epilogue of a plan query: every argument but `mask` (an Op or a mode) counts as present when it is not None / False;
+    stat_q "gate" (or the mask Op's own tensor) = the gate tensor doubles as the statistics' second factor."""
+    some = lambda v: _SOME if _given(v) else None
+    gate = mask is not None and (stat_q == "gate" if isinstance(stat_q, str) else (isinstance(mask, Op) and stat_q is mask.p0))
+    m = _plan_op(mask)
+    return L.Epilogue(some(bias), some(bias_border), 1 if relu else 0, 1 if per_tile else 0, m, some(resid),
+                      m.p0 if gate else (_SOME + 64 if _given(stat_q) else None), some(stats))
+
+
+def _plan_wv(nfloats, scratch):
+    return L.WeightView(_SOME, 0, 1, 1, 1, 1, _SOME if (scratch and nfloats > 0) else None, nfloats if scratch else 0)
+
+
+def _plan_result(rc, plan, who):
+    L.check(rc, who)
+    return Plan(*(getattr(plan, k) for k in Plan._fields))
+
+
+def _conv4_fallback(mode, epkw):
+    """The operand / epilogue forms dm_conv4x4s2 keeps off its register-resident kernels (conv_mfma.hip, conv4_resident_takes)."""
+    return mode == L.DM_LOAD_AFFINE2 or (_given(epkw.get("bias_border")) and
+                                         any(_given(epkw.get(k)) for k in ("mask", "resid", "stat_q")))
+
+
+def conv4x4s2_plan(inp, B, CIN, NOUT, H, W, per_sample=False, ones=False, scratch=True, **epkw):
+    """Which kernel conv4x4s2 launches for this call and how it deals its units (include/dynamorph_hip.h, dm_launch_plan).
+    inp: the Op of the call or a bare DM_LOAD_* mode (then per_sample / ones describe it); epkw as conv4x4s2 takes them, with
+    True standing for any tensor and stat_q="gate" for the mask's own tensor; scratch: the weight view carries the scratch
+    conv4x4s2 attaches.  Touches no device."""
+    lib = L.load()
+    o, e = _plan_op(inp, per_sample, ones), _plan_ep(**epkw)
+    w = _plan_wv(lib.dm_conv4x4s2_scratch_floats(CIN, NOUT, H, W, 1 if _conv4_fallback(o.mode, epkw) else 0), scratch)
+    plan = L.LaunchPlan()
+    return _plan_result(lib.dm_conv4x4s2_plan(C.byref(o), C.byref(w), C.byref(e), B, CIN, NOUT, H, W, C.byref(plan)), plan,
+                        "dm_conv4x4s2_plan")
+
+
+def conv3x3_plan(inp, B, CIN, NOUT, H, W, taps=9, pixel_shuffle=False, per_sample=False, scratch=True, **epkw):
+    """conv4x4s2_plan for a conv3x3 call (taps 9 or 1, or the transposed form)."""
+    lib = L.load()
+    o, e = _plan_op(inp, per_sample), _plan_ep(**epkw)
+    w = _plan_wv(lib.dm_conv3x3_scratch_floats(CIN, NOUT, H, W, taps, 1 if pixel_shuffle else 0, 1 if epkw.get("per_tile") else 0),
+                 scratch)
+    plan = L.LaunchPlan()
+    return _plan_result(lib.dm_conv3x3_plan(C.byref(o), C.byref(w), C.byref(e), B, CIN, NOUT, H, W, taps,
+                                            1 if pixel_shuffle else 0, C.byref(plan)), plan, "dm_conv3x3_plan")
+
+
+def wgrad_plan(S, T, B, CS, CT, Hs, Ws, k, per_sample=False, t_ones=False):
+    """Which kernel wgrad launches (S, T: Ops or bare modes; per_sample: both carry per-sample coefficients; t_ones: T has the
+    ones channel) and how it deals its units."""
+    s, t = _plan_op(S, per_sample), _plan_op(T, per_sample, t_ones)
+    plan = L.LaunchPlan()
+    return _plan_result(L.load().dm_wgrad_plan(C.byref(s), C.byref(t), B, CS, CT, Hs, Ws, k, C.byref(plan)), plan, "dm_wgrad_plan")
+
+
+def conv1x1_bwd_fused_plan(dy, B, CD, CX, H, W):
+    """Which kernel conv1x1_bwd_fused launches (dy: Op or bare mode) and how it deals its units."""
+    d = _plan_op(dy)
+    plan = L.LaunchPlan()
+    return _plan_result(L.load().dm_conv1x1_bwd_fused_plan(C.byref(d), B, CD, CX, H, W, C.byref(plan)), plan,
+                        "dm_conv1x1_bwd_fused_plan")
 
 
 def backward_precision(mode=None):

@@ -313,6 +313,58 @@ int dm_conv1x1_bwd_fused_num_blocks(int B, int CD, int CX, int H, int W);
 int dm_conv1x1_bwd_fused(const dm_operand *dy, const float *x, const float *xcoef, const float *w, float *dx,
                          double *stats, float *wslabs, int B, int CD, int CX, int H, int W, void *stream);
 
+/* ---- launch plans (host only: no device memory is read or written, no launch, no device call) -------------------------
+ * Which kernel a dm_conv4x4s2 / dm_conv3x3 / dm_wgrad / dm_conv1x1_bwd_fused call launches and, for the persistent streaming
+ * kernels (csrc/wide_stream.hip) and the one-pass wide weight gradient (wgrad_wide1_kernel), how its units are dealt to the
+ * walkers.  The functions read the same decision code as the launches (the launch asks it first and then launches what it
+ * says), so the answer cannot drift from what runs.  The operand structs are read as the launch reads them: modes, ones_channel,
+ * coef_bstride, which pointers are NULL, stat_q == mask.p0, scratch / scratch_floats -- no pointer is dereferenced, so any
+ * non-NULL value stands for "present".  One case is not foreseen: the three weights-in-LDS kernels ask the device for their
+ * dynamic LDS at the launch, and a device that refuses runs the tiled kernel instead.
+ *   kernel      DM_KERNEL_*: one value per streaming kernel and one for wgrad_wide1; the other families share coarse values
+ *   workgroups  the grid (x) of that kernel; waves: waves per workgroup
+ *   walkers     independent unit walks per workgroup: `waves` where every wave owns units of its own, 1 where the whole
+ *               workgroup walks together (wgrad1x1_stream, wgrad_wide1).  Walker j of workgroup g is walker g * walkers + j
+ *               of workgroups * walkers.
+ *   units       work items of the launch (64-pixel units, output rows, 4-row units, 2-row x 32-pixel units, 32-pixel stages,
+ *               8 x 16 tiles: see the kernel)
+ *   dealing     DM_DEAL_RANGE_STRIDED: workgroup g owns units [units g / workgroups, units (g + 1) / workgroups) and its
+ *                                      walker j takes the first + j, + walkers, ...;
+ *               DM_DEAL_RANGE:         walker v of V = workgroups * walkers owns [units v / V, units (v + 1) / V);
+ *               DM_DEAL_GRID_STRIDED:  walker v takes v, v + V, ...
+ *   ring        stages of operand loads a walker keeps in flight in its register ring (the two streaming weight gradients;
+ *               else 0)
+ * For the kernels that are not persistent streams workgroups .. ring are 0.  Negative return (plan untouched) for a call the
+ * launch refuses by shape. */
+enum {
+    DM_KERNEL_RESIDENT = 0,             /* a register-resident kernel of conv_mfma.hip / wgrad_mfma.hip */
+    DM_KERNEL_PATCH = 1,                /* the whole-patch 4x4/s2 forward (conv4x4s2_patch.hip) */
+    DM_KERNEL_WIDE_TILED = 2,           /* conv_wide_kernel / wgrad_wide_kernel (conv_wide.hip) */
+    DM_KERNEL_GENERIC = 3,              /* conv_generic.hip */
+    DM_KERNEL_CONV1X1_BWD_TILED = 4,    /* conv1x1_bwd_kernel (32 -> 16 channels) */
+    DM_KERNEL_CONV1X1_STREAM = 16,
+    DM_KERNEL_CONV_S2_THIN_STREAM = 17,
+    DM_KERNEL_CONVT_THIN_STREAM = 18,
+    DM_KERNEL_CONV_S2_WIDE_STREAM = 19,
+    DM_KERNEL_CONVT_WIDE_STREAM = 20,
+    DM_KERNEL_CONV3X3_WIDE_STREAM = 21,
+    DM_KERNEL_CONV1X1_BWD_WIDE_STREAM = 22,
+    DM_KERNEL_WGRAD1X1_STREAM = 23,
+    DM_KERNEL_WGRAD_S2_THIN_STREAM = 24,
+    DM_KERNEL_WGRAD_WIDE1 = 25
+};
+enum { DM_DEAL_NONE = 0, DM_DEAL_RANGE_STRIDED = 1, DM_DEAL_RANGE = 2, DM_DEAL_GRID_STRIDED = 3 };
+typedef struct dm_launch_plan {
+    int32_t kernel, workgroups, waves, walkers, dealing, ring;
+    int64_t units;
+} dm_launch_plan;
+int dm_conv4x4s2_plan(const dm_operand *in, const dm_weight_view *w, const dm_epilogue *ep, int B, int CIN, int NOUT, int H,
+                      int W, dm_launch_plan *plan);
+int dm_conv3x3_plan(const dm_operand *in, const dm_weight_view *w, const dm_epilogue *ep, int B, int CIN, int NOUT, int H,
+                    int W, int taps, int pixel_shuffle, dm_launch_plan *plan);
+int dm_wgrad_plan(const dm_operand *S, const dm_operand *T, int B, int CS, int CT, int Hs, int Ws, int k, dm_launch_plan *plan);
+int dm_conv1x1_bwd_fused_plan(const dm_operand *dy, int B, int CD, int CX, int H, int W, dm_launch_plan *plan);
+
 /* Backward of a 3x3 convolution (padding 1) on a 16 x 16 latent grid whose output feeds a train-mode BatchNorm (enc.10 and
  * the first convolution of a ResidualBlock layer, vq_vae.py:287, 205): aten::convolution_backward for input AND weight from
  * ONE staging of a whole patch,

@@ -41,6 +41,12 @@ def test_struct_layouts_match_the_header():
     assert ctypes.sizeof(_lib.WeightView) == 64          # 6 words + scratch pointer + scratch size
     assert ctypes.sizeof(_lib.Epilogue) == 24 + 40 + 24   # bias, bias_border, relu, stats_per_tile | mask | 3 pointers
     assert _lib.Epilogue.mask.offset == 24 and _lib.Epilogue.stats.offset == 80
+    assert ctypes.sizeof(_lib.LaunchPlan) == 32 and _lib.LaunchPlan.units.offset == 24          # 6 int32 + int64
+    text = open(HEADER).read()
+    for name in re.findall(r"\b(DM_KERNEL_[A-Z0-9_]+|DM_DEAL_[A-Z_]+)\b(?= = \d+| = \d+,|,| })", text):
+        m = re.search(r"\b%s = (\d+)" % name, text)
+        assert m and getattr(_lib, name) == int(m.group(1)), name
+    assert len(re.findall(r"\bDM_KERNEL_[A-Z0-9_]+ = \d+", text)) == 15 and len(re.findall(r"\bDM_DEAL_[A-Z_]+ = \d+", text)) == 4
 
 
 def test_version_and_host_only_queries(lib):
@@ -101,6 +107,53 @@ def test_version_and_host_only_queries(lib):
     assert plan(_lib.DM_VQ_EXACT, 16, 64, 16, 16, 2048) == (EXACT, 1024, 0) and plan(_lib.DM_VQ_EXACT, 64, 64, 16, 16, 8) == (EXACT, 8, 0)
     assert plan(_lib.DM_VQ_AUTO, 128, 128, 8, 8, 2) == (EXACT, 1, 0) and plan(_lib.DM_VQ_AUTO, 16, 63, 8, 12, 2) == (EXACT, 1, 0)
     assert plan(_lib.DM_VQ_AUTO, 24, 64, 16, 16, 3) == (ANY, 3, 192) and plan(_lib.DM_VQ_AUTO, 12, 40, 8, 8, 70000) == (ANY, 4096, 4096 * 64)
+    # dm_*_plan: the kernel a call launches and how a persistent one deals its units, from the structs as the launch reads them
+    # (pointers stand for "present": nothing is dereferenced)
+    some = 64
+    ident = _lib.Operand(some, None, None, 0, _lib.DM_LOAD_IDENT, 0)
+    two = _lib.Operand(some, some, some, 0, _lib.DM_LOAD_AFFINE2, 0)
+    wv = _lib.WeightView(some, 0, 1, 1, 1, 1, some, 1 << 40)
+    ep = _lib.Epilogue(None, None, 0, 0, _lib.Operand(None, None, None, 0, 0, 0), None, None, some)
+
+    def fields(p):
+        return (p.kernel, p.workgroups, p.waves, p.walkers, p.dealing, p.ring, p.units)
+    p = _lib.LaunchPlan()
+    assert lib.dm_conv3x3_plan(ctypes.byref(ident), ctypes.byref(wv), ctypes.byref(ep), 768, 64, 64, 32, 32, 9, 0, ctypes.byref(p)) == 0
+    assert fields(p) == (_lib.DM_KERNEL_CONV3X3_WIDE_STREAM, 256, 8, 8, _lib.DM_DEAL_RANGE_STRIDED, 0, 768 * 16)      # z32ex: 6 units per wave
+    assert lib.dm_conv3x3_plan(ctypes.byref(ident), ctypes.byref(wv), None, 768, 64, 64, 32, 32, 1, 0, ctypes.byref(p)) == 0
+    assert fields(p) == (_lib.DM_KERNEL_CONV1X1_STREAM, 512, 4, 4, _lib.DM_DEAL_RANGE_STRIDED, 0, 768 * 16)
+    assert lib.dm_conv3x3_plan(ctypes.byref(ident), ctypes.byref(wv), None, 768, 32, 8, 64, 64, 9, 1, ctypes.byref(p)) == 0
+    assert fields(p) == (_lib.DM_KERNEL_CONVT_THIN_STREAM, 1024, 4, 4, _lib.DM_DEAL_GRID_STRIDED, 0, 768 * 16)
+    assert lib.dm_conv3x3_plan(ctypes.byref(ident), ctypes.byref(wv), None, 768, 16, 16, 16, 16, 9, 0, ctypes.byref(p)) == 0
+    assert fields(p) == (_lib.DM_KERNEL_RESIDENT, 0, 0, 0, _lib.DM_DEAL_NONE, 0, 0)
+    assert lib.dm_conv4x4s2_plan(ctypes.byref(ident), ctypes.byref(wv), ctypes.byref(ep), 768, 2, 32, 128, 128, ctypes.byref(p)) == 0
+    assert fields(p) == (_lib.DM_KERNEL_CONV_S2_THIN_STREAM, 768, 4, 4, _lib.DM_DEAL_RANGE_STRIDED, 0, 768 * 64)
+    assert lib.dm_conv4x4s2_plan(ctypes.byref(two), ctypes.byref(wv), ctypes.byref(ep), 768, 32, 64, 64, 64, ctypes.byref(p)) == 0
+    assert fields(p) == (_lib.DM_KERNEL_CONV_S2_WIDE_STREAM, 256, 8, 8, _lib.DM_DEAL_RANGE_STRIDED, 0, 768 * 16)
+    assert lib.dm_conv4x4s2_plan(ctypes.byref(ident), ctypes.byref(wv), ctypes.byref(ep), 768, 3, 8, 100, 100, ctypes.byref(p)) == 0
+    assert p.kernel == _lib.DM_KERNEL_GENERIC
+    assert lib.dm_wgrad_plan(ctypes.byref(two), ctypes.byref(ident), 768, 64, 64, 32, 32, 1, ctypes.byref(p)) == 0
+    assert fields(p) == (_lib.DM_KERNEL_WGRAD1X1_STREAM, 768, 4, 1, _lib.DM_DEAL_RANGE, 2, 768 * 32)
+    assert lib.dm_wgrad_plan(ctypes.byref(two), ctypes.byref(ident), 768, 32, 2, 64, 64, 4, ctypes.byref(p)) == 0
+    assert fields(p) == (_lib.DM_KERNEL_WGRAD_S2_THIN_STREAM, 768, 4, 4, _lib.DM_DEAL_RANGE, 1, 768 * 128)
+    assert lib.dm_wgrad_plan(ctypes.byref(ident), ctypes.byref(two), 768, 64, 32, 32, 32, 4, ctypes.byref(p)) == 0
+    assert fields(p) == (_lib.DM_KERNEL_WGRAD_WIDE1, 256, 8, 1, _lib.DM_DEAL_GRID_STRIDED, 0, 768 * 8)
+    assert lib.dm_wgrad_plan(ctypes.byref(ident), ctypes.byref(ident), 768, 64, 48, 32, 32, 3, ctypes.byref(p)) == 0
+    assert p.kernel == _lib.DM_KERNEL_WIDE_TILED
+    assert lib.dm_conv1x1_bwd_fused_plan(ctypes.byref(two), 768, 64, 64, 32, 32, ctypes.byref(p)) == 0
+    assert fields(p) == (_lib.DM_KERNEL_CONV1X1_BWD_WIDE_STREAM, 512, 4, 4, _lib.DM_DEAL_RANGE, 0, 768 * 16)
+    assert lib.dm_conv1x1_bwd_fused_plan(ctypes.byref(two), 768, 16, 32, 16, 16, ctypes.byref(p)) == 0
+    assert p.kernel == _lib.DM_KERNEL_CONV1X1_BWD_TILED
+    # a refused plan writes nothing
+    assert lib.dm_conv1x1_bwd_fused_plan(ctypes.byref(two), 768, 48, 48, 16, 16, ctypes.byref(p)) == -1 and b"not built" in lib.dm_last_error()
+    assert p.kernel == _lib.DM_KERNEL_CONV1X1_BWD_TILED
+    assert lib.dm_conv3x3_plan(ctypes.byref(ident), ctypes.byref(wv), None, 768, 64, 64, 32, 32, 4, 0, ctypes.byref(p)) == -1 and b"taps" in lib.dm_last_error()
+    assert lib.dm_conv3x3_plan(ctypes.byref(ident), ctypes.byref(wv), None, 768, 64, 64, 32, 32, 9, 0, None) == -1 and b"NULL plan" in lib.dm_last_error()
+    assert lib.dm_conv4x4s2_plan(ctypes.byref(ident), ctypes.byref(wv), None, 768, 2, 32, 127, 128, ctypes.byref(p)) == -1 and b"even" in lib.dm_last_error()
+    assert lib.dm_wgrad_plan(ctypes.byref(ident), ctypes.byref(two), 768, 64, 64, 32, 32, 3, ctypes.byref(p)) == -1 and b"AFFINE2" in lib.dm_last_error()
+    assert lib.dm_wgrad_plan(ctypes.byref(ident), ctypes.byref(ident), 768, 64, 64, 32, 32, 2, ctypes.byref(p)) == -1
+    assert lib.dm_wgrad_plan(ctypes.byref(ident), ctypes.byref(ident), 768, 64, 64, 32, 32, 3, None) == -1 and b"NULL plan" in lib.dm_last_error()
+    assert all(_lib.is_host_only(n) for n in ("dm_conv4x4s2_plan", "dm_conv3x3_plan", "dm_wgrad_plan", "dm_conv1x1_bwd_fused_plan"))
     assert lib.dm_conv4x4s2_num_blocks(2048, 3, 8, 128, 128, 1) == 2048 * 8   # one slab per tile (per-sample stats)
     assert lib.dm_conv4x4s2_num_blocks(2048, 3, 8, 128, 128, 0) == 768        # persistent grid
     assert lib.dm_conv4x4s2_num_blocks(1, 3, 8, 100, 100, 0) == 1             # not tileable by the MFMA path: generic kernel, one slab per sample

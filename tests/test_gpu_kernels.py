@@ -4,6 +4,7 @@ fp32 accumulation-order tolerance (stated per test) for everything else."""
 import ctypes
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -11,6 +12,9 @@ import torch
 import torch.nn.functional as F
 
 from conftest import ROOT
+
+sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+import stream_walk as SW  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -1882,8 +1886,10 @@ def test_stream_wgrad_1x1(ops, B, cs, ct, hs, ws, smode, tmode):
     w = torch.zeros(cs, ct, 1, 1, requires_grad=True)
     F.conv2d(load_ref(t.double(), tmode, tcoef.double()), w.double(), None).backward(load_ref(dy.double(), smode, coef.double(), a.double()))
     dst = torch.empty(cs, ct, 1, 1, device=DEV)
-    ops.wgrad(ops.Op(dy.to(DEV), smode, coef.to(DEV) if smode >= 2 else None, p1=a.to(DEV) if smode == 4 else None),
-              ops.Op(t.to(DEV), tmode, tcoef.to(DEV) if tmode >= 2 else None), dst, B, cs, ct, hs, ws, 1)
+    S = ops.Op(dy.to(DEV), smode, coef.to(DEV) if smode >= 2 else None, p1=a.to(DEV) if smode == 4 else None)
+    T = ops.Op(t.to(DEV), tmode, tcoef.to(DEV) if tmode >= 2 else None)
+    assert ops.wgrad_plan(S, T, B, cs, ct, hs, ws, 1).kernel == SW.KERNELS["wgrad1x1_stream"]
+    ops.wgrad(S, T, dst, B, cs, ct, hs, ws, 1)
     close(dst, w.grad.float(), 5e-5, 5e-5 * max(w.grad.abs().max().item(), 1e-6), "stream wgrad 1x1")
 
 
@@ -1927,6 +1933,7 @@ def test_stream_conv_1x1(ops, B, cin, nout, h, w, mode, transposed, epi):
     elif epi == "all":
         kw.update(stat_q=q.to(DEV))
         sq = q
+    assert ops.conv3x3_plan(inp, B, cin, nout, h, w, taps=1, stats=epi != "none", **kw).kernel == SW.KERNELS["conv1x1_stream"]
     out, st = ops.conv3x3(inp, wv, B, cin, nout, h, w, taps=1, want_stats=epi != "none", **kw)
     close(out, ref.float(), 5e-5, 5e-5, "stream conv 1x1")
     if st is not None:
@@ -1948,19 +1955,21 @@ def test_stream_wgrad_4x4s2_few_t_channels(ops, B, cs, ct, hs, ws, smode, tmode)
     F.conv2d(load_ref(t.double(), tmode, tcoef.double()), w, None, stride=2, padding=1).backward(
         load_ref(dy.double(), smode, coef.double(), a.double()))
     dst = torch.empty(cs, ct, 4, 4, device=DEV)
-    ops.wgrad(ops.Op(dy.to(DEV), smode, coef.to(DEV) if smode >= 2 else None, p1=a.to(DEV) if smode == 4 else None),
-              ops.Op(t.to(DEV), tmode, tcoef.to(DEV) if tmode >= 2 else None), dst, B, cs, ct, hs, ws, 4)
+    S = ops.Op(dy.to(DEV), smode, coef.to(DEV) if smode >= 2 else None, p1=a.to(DEV) if smode == 4 else None)
+    T = ops.Op(t.to(DEV), tmode, tcoef.to(DEV) if tmode >= 2 else None)
+    assert ops.wgrad_plan(S, T, B, cs, ct, hs, ws, 4).kernel == SW.KERNELS["wgrad_s2_thin_stream"]
+    ops.wgrad(S, T, dst, B, cs, ct, hs, ws, 4)
     close(dst, w.grad.float(), 5e-5, 5e-5 * max(w.grad.abs().max().item(), 1e-6), "stream wgrad 4x4/s2")
 
 
-@pytest.mark.parametrize("B,cin,nout,h,w,mode,epi", [(3, 2, 32, 128, 128, 0, "bias"), (2, 2, 32, 128, 128, 0, "gate+q"),
-                                                     (2, 1, 16, 16, 128, 3, "all"), (2, 4, 32, 8, 128, 1, "gate"),
-                                                     (1, 3, 16, 4, 128, 3, "all"), (20, 2, 64, 32, 128, 0, "bias"),
-                                                     (2, 2, 32, 6, 128, 2, "none")])
+@pytest.mark.parametrize("B,cin,nout,h,w,mode,epi", list(SW.OLD_S2_THIN))
 def test_stream_conv_4x4s2_few_input_channels(ops, B, cin, nout, h, w, mode, epi):
-    """wide_stream.hip: the wide encoder's first convolution (image -> 32 channels) and the data gradient of the decoder's last
-    transposed convolution: K = (channel, ky, kx), input rows read by unaligned loads, zero padding applied AFTER the operand
-    transform, rows outside the image skipped; bias / ReLU / gate / residual / statistics."""
+    """4x4 / stride 2 from 1-4 input channels on 128 columns: the wide encoder's first convolution (image -> 32 channels) and
+    the data gradient of the decoder's last transposed convolution; bias / ReLU / gate / residual / statistics.  The cases and
+    the kernel each runs are tests/helpers/stream_walk.py's OLD_S2_THIN (asserted from the launch plan): wide_stream.hip's
+    conv_s2_thin_stream_kernel (K = (channel, ky, kx), zero padding applied AFTER the operand transform, output rows 0 and
+    OH - 1) only where the output grid tiles by 8 x 16, i.e. H % 16 == 0 -- at H = 4, 6, 8 the generic kernel runs, and
+    1 -> 16 channels at H = 16 is a register-resident kernel's; the H = 16 cases beside them reach the streaming kernel."""
     x = rnd(B, cin, h, w, seed=1)
     coef = torch.stack([rnd(cin, seed=3).abs() + 0.5, torch.zeros(cin), rnd(cin, seed=5) * 0.3 + 0.2, torch.zeros(cin)], 1)
     xin = load_ref(x.double(), mode, coef.double())
@@ -1987,18 +1996,23 @@ def test_stream_conv_4x4s2_few_input_channels(ops, B, cin, nout, h, w, mode, epi
     elif epi == "gate+q":
         kw.update(stat_q=kw["mask"].p0)
         sq = gate
-    out, st = ops.conv4x4s2(ops.Op(x.to(DEV), mode, coef.to(DEV) if mode >= 2 else None), ops.weight_view(wt.to(DEV), cin * 16, 16, 4, 1),
+    inp = ops.Op(x.to(DEV), mode, coef.to(DEV) if mode >= 2 else None)
+    kernel = SW.OLD_S2_THIN[(B, cin, nout, h, w, mode, epi)]
+    assert ops.conv4x4s2_plan(inp, B, cin, nout, h, w, stats=epi != "none", **kw).kernel == SW.KERNELS[kernel]
+    out, st = ops.conv4x4s2(inp, ops.weight_view(wt.to(DEV), cin * 16, 16, 4, 1),
                             B, cin, nout, h, w, want_stats=epi != "none", **kw)
     close(out, ref.float(), 5e-5, 5e-5, "stream conv 4x4/s2")
     if st is not None:
         close_stats(st.sum(0), ref.float(), sq)
 
 
-@pytest.mark.parametrize("B,ci,co,h,mode,relu", [(3, 32, 2, 64, 3, False), (2, 32, 1, 8, 0, True), (5, 64, 2, 16, 1, False),
-                                                 (1, 8, 2, 4, 2, False), (2, 17, 2, 12, 3, True), (70, 32, 2, 64, 3, False)])
+@pytest.mark.parametrize("B,ci,co,h,mode,relu", list(SW.OLD_CONVT_THIN))
 def test_stream_conv_transpose_to_few_channels(ops, B, ci, co, h, mode, relu):
-    """wide_stream.hip: ConvTranspose2d(C -> 1 / 2, 4, 2, 1) on a 64-column grid -- the wide decoder's last layer -- on the vector
-    units: weights as scalar-register pairs, one lane = 4 pixels, neighbours by DPP, padding rows zeroed AFTER the transform."""
+    """ConvTranspose2d(C -> 1 / 2, 4, 2, 1) on a 64-column grid -- the wide decoder's last layer.  The cases and the kernel each
+    runs are tests/helpers/stream_walk.py's OLD_CONVT_THIN (asserted from the launch plan): wide_stream.hip's
+    convT_thin_stream_kernel (vector units: weights as scalar-register pairs, one lane = 4 pixels, neighbours by DPP, padding rows
+    zeroed AFTER the transform) where H % 8 == 0; at H = 4 and 12 the generic kernel runs, and the H = 8 / 16 cases beside those
+    two reach the streaming kernel (12 input channels, not 8: 8 -> 2 on a tileable grid is a register-resident kernel's)."""
     w = 64
     x = rnd(B, ci, h, w, seed=1)
     coef = torch.stack([rnd(ci, seed=3).abs() + 0.5, torch.zeros(ci), rnd(ci, seed=5) * 0.3 + 0.2, torch.zeros(ci)], 1)
@@ -2007,7 +2021,10 @@ def test_stream_conv_transpose_to_few_channels(ops, B, ci, co, h, mode, relu):
     ref = F.conv_transpose2d(load_ref(x.double(), mode, coef.double()), wt.double(), bias.double(), stride=2, padding=1)
     if relu:
         ref = F.relu(ref)
-    out, _ = ops.conv3x3(ops.Op(x.to(DEV), mode, coef.to(DEV) if mode >= 2 else None), ops.weight_view(wt.to(DEV), 16, co * 16, 4, 1),
+    inp = ops.Op(x.to(DEV), mode, coef.to(DEV) if mode >= 2 else None)
+    kernel = SW.OLD_CONVT_THIN[(B, ci, co, h, mode, relu)]
+    assert ops.conv3x3_plan(inp, B, ci, 4 * co, h, w, taps=9, pixel_shuffle=True, bias=True, relu=relu).kernel == SW.KERNELS[kernel]
+    out, _ = ops.conv3x3(inp, ops.weight_view(wt.to(DEV), 16, co * 16, 4, 1),
                          B, ci, 4 * co, h, w, taps=9, pixel_shuffle=True, bias=bias.to(DEV), relu=relu)
     close(out, ref.float(), 5e-5, 5e-5, "stream conv transpose")
 
@@ -2069,8 +2086,9 @@ def test_stream_conv_4x4s2_32_to_64_weights_in_lds(ops, B, mode, epi):
     elif epi == "gate+q":
         kw.update(stat_q=kw["mask"].p0)
         sq = gate
-    out, st = ops.conv4x4s2(ops.Op(x.to(DEV), mode, coef.to(DEV) if mode >= 2 else None, p1=x1.to(DEV) if mode == 4 else None),
-                            ops.weight_view(wt.to(DEV), cin * 16, 16, 4, 1),
+    inp = ops.Op(x.to(DEV), mode, coef.to(DEV) if mode >= 2 else None, p1=x1.to(DEV) if mode == 4 else None)
+    assert ops.conv4x4s2_plan(inp, B, cin, nout, h, w, stats=epi != "none", **kw).kernel == SW.KERNELS["conv_s2_wide_stream"]
+    out, st = ops.conv4x4s2(inp, ops.weight_view(wt.to(DEV), cin * 16, 16, 4, 1),
                             B, cin, nout, h, w, want_stats=epi != "none", **kw)
     close(out, ref.float(), 5e-5, 5e-5, "stream conv 4x4/s2 32 -> 64")
     if st is not None:
@@ -2109,6 +2127,8 @@ def test_stream_conv_transpose_64_to_32_weights_in_lds(ops, B, mode, epi):
         kw.update(stat_q=kw["mask"].p0)
         sq = gate
     inp = ops.Op(x.to(DEV), mode, coef.to(DEV) if mode >= 2 else None, p1=x1.to(DEV) if mode == 4 else None)
+    assert ops.conv3x3_plan(inp, B, ci, 4 * co, h, w, taps=9, pixel_shuffle=True, stats=epi != "none",
+                            **kw).kernel == SW.KERNELS["convT_wide_stream"]
     out, st = ops.conv3x3(inp, ops.weight_view(wt.to(DEV), 16, co * 16, 4, 1), B, ci, 4 * co, h, w, taps=9, pixel_shuffle=True,
                           want_stats=epi != "none", **kw)
     close(out, ref.float(), 5e-5, 5e-5, "stream conv transpose 64 -> 32")
@@ -2142,6 +2162,7 @@ def test_stream_conv_3x3_64_channels_weights_in_lds(ops, B, mode, dgrad, epi):
         kw.update(mask=ops.Op(gate.to(DEV)), resid=resid.to(DEV), stat_q=q.to(DEV))
         ref = ref * (gate > 0) + resid
         sq = q
+    assert ops.conv3x3_plan(inp, B, c, c, h, h, taps=9, stats=epi != "none", **kw).kernel == SW.KERNELS["conv3x3_wide_stream"]
     out, st = ops.conv3x3(inp, wv, B, c, c, h, h, taps=9, want_stats=epi != "none", **kw)
     close(out, ref.float(), 5e-5, 5e-5, "stream conv 3x3")
     if st is not None:
@@ -2168,6 +2189,7 @@ def test_stream_conv1x1_backward_fused_64_channels(ops, B, H, W, two):
     assert ops.conv1x1_bwd_fused_supported(C, C, H, W)
     dst = torch.empty(C, C, 1, 1, device=DEV)
     op = ops.Op(dy.to(DEV), 4, coef.to(DEV), p1=y.to(DEV)) if two else ops.Op(dy.to(DEV))
+    assert ops.conv1x1_bwd_fused_plan(op, B, C, C, H, W).kernel == SW.KERNELS["conv1x1_bwd_wide_stream"]
     dx, st = ops.conv1x1_bwd_fused(op, x.to(DEV), xcoef.to(DEV), w.to(DEV), dst, B, C, C, H, W)
     close(dx, dx_ref.float(), 5e-5, 5e-5, "fused 1x1 backward: dx")
     close(dst, wd.grad.float(), 5e-5, 5e-5 * float(wd.grad.abs().max()), "fused 1x1 backward: dW")
@@ -2187,6 +2209,7 @@ def test_wide_wgrad_one_pass_with_an_affine2_t_operand(ops, B, tmode):
     F.conv2d(load_ref(t.double(), tmode, tcoef.double(), t1.double()), w, None, stride=2, padding=1).backward(s_.double())
     dst = torch.empty(cs, ct, 4, 4, device=DEV)
     top = ops.Op(t.to(DEV), tmode, tcoef.to(DEV) if tmode >= 2 else None, p1=t1.to(DEV) if tmode == 4 else None)
+    assert ops.wgrad_plan(ops.Op(s_.to(DEV)), top, B, cs, ct, hs, hs, 4).kernel == SW.KERNELS["wgrad_wide1"]
     ops.wgrad(ops.Op(s_.to(DEV)), top, dst, B, cs, ct, hs, hs, 4)
     close(dst, w.grad.float(), 5e-5, 5e-5 * float(w.grad.abs().max()), "one-pass wgrad, AFFINE2 T")
     if tmode == 4:
