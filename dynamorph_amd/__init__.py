@@ -6,9 +6,12 @@ computed by hand-written gfx950 HIP kernels behind the C ABI in include/dynamorp
 of the inference path:
     score_patches, score_patches_sharded, score_VAE                     (dynamorph_amd.patch_vae)
     patch_gradients, patch_gradients_sharded                            (dynamorph_amd.patch_vae)
+and the clustering of the latents behind them (sklearn.cluster.KMeans of the reference's clustering scripts):
+    KMeans                                                              (dynamorph_amd.kmeans)
 """
 from .vq_vae import VQ_VAE, VQ_VAE_z16, VQ_VAE_z32, VectorQuantizer, ResidualBlock  # noqa: F401
 from .patch_vae import score_patches, score_patches_sharded, score_VAE, patch_gradients, patch_gradients_sharded  # noqa: F401
+from .kmeans import KMeans  # noqa: F401
 
 __all__ = ["VQ_VAE", "VQ_VAE_z16", "VQ_VAE_z32", "VectorQuantizer", "ResidualBlock",
-           "score_patches", "score_patches_sharded", "score_VAE", "patch_gradients", "patch_gradients_sharded"]
+           "score_patches", "score_patches_sharded", "score_VAE", "patch_gradients", "patch_gradients_sharded", "KMeans"]

@@ -214,7 +214,11 @@ SIGNATURES = {
     "dm_knn_wide_self_workspace_bytes": (i64, [i64, C.c_int, C.c_int, C.c_int]),
     "dm_knn_wide_self": (C.c_int, [vp, i64, C.c_int, i64, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, i64,
                                    vp]),
-    "dm_umap_smooth": (C.c_int, [vp, i64, C.c_int, vp, vp, vp, vp, vp]),
+    "dm_kmeans_workspace_bytes": (i64, [i64, C.c_int, C.c_int]),
+    "dm_kmeans_assign": (C.c_int, [vp, i64, C.c_int, i64, vp, C.c_int, vp, vp, vp, vp, vp, i64, vp]),
+    "dm_kmeans_sums": (C.c_int, [vp, i64, C.c_int, i64, vp, C.c_int, vp, vp, vp, i64, vp]),
+    "dm_kmeans_row_d2": (C.c_int, [vp, i64, C.c_int, i64, vp, C.c_int, vp, vp, vp]),
+    "dm_umap_smooth": (C.c_int,[vp, i64, C.c_int, vp, vp, vp, vp, vp]),
     "dm_umap_membership": (C.c_int, [vp, vp, i64, C.c_int, vp, vp, vp, vp]),
     "dm_umap_epoch": (C.c_int, [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, f32, f32, f32, C.c_uint64, C.c_int, vp]),
     "dm_umap_transform_prepare": (C.c_int, [vp, vp, i64, C.c_int, i64, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -1,6 +1,7 @@
 """PCA stage of the pipeline: mirror of run_dim_reduction.py (fit_PCA lines 14-50, process_PCA 52-92, the PCA branch of
 dim_reduction 177-281) on dynamorph_amd.pca.PCA / WidePCA; and its UMAP stage: fit_umap (143-207) and umap_transform (94-127) on
-dynamorph_amd.umap_layout.UMAPEmbedding.
+dynamorph_amd.umap_layout.UMAPEmbedding; and the clustering of the reduced latents (HiddenStateExtractor/deprecated/
+morphology_clustering.py:103-141) on dynamorph_amd.kmeans.KMeans.
 
 File names are the ones process_VAE writes: <prefix>_latent_space<suffix>.pkl in, <prefix>_latent_space<suffix>_PCAed.pkl
 out (the reference's '{}_latent_space_{}.pkl'.format(prefix, '_after') names a '..._latent_space__after.pkl' its own pipeline
@@ -252,3 +253,89 @@ def dim_reduction_umap_transform(input_dirs, output_dirs, weights_dir, prefixes)
     prefixes = _prefix_list(prefixes)
     models = load_umap_models(weights_dir)
     return [umap_transform(d, o, weights_dir, p, models=models) for d, o in zip(input_dirs, output_dirs) for p in prefixes]
+
+
+# ------------------------------------------------------------------ k-means of the reduced latents
+def _sklearn_cluster_available():
+    try:
+        import sklearn.cluster  # noqa: F401
+    except ImportError:
+        return False
+    return True
+
+
+def fit_kmeans(train_data, weights_dir, n_clusters=4, **kw):
+    """Fit KMeans(n_clusters) to the (PCA-ed) latents, write <weights_dir>/kmeans_model.pkl (protocol 4) and return the fitted
+    device KMeans.  The pickle holds the fitted sklearn KMeans when scikit-learn is importable, else this package's KMeans, as
+    fit_PCA does.  kw: KMeans's (init, n_init, max_iter, tol, seed, device)."""
+    from .kmeans import KMeans
+    os.makedirs(weights_dir, exist_ok=True)
+    model = KMeans(n_clusters, **kw).fit(train_data)
+    with open(os.path.join(weights_dir, 'kmeans_model.pkl'), 'wb') as f:
+        pickle.dump(model.to_sklearn() if _sklearn_cluster_available() else model, f, protocol=4)
+    return model
+
+
+def load_kmeans_model(weights_dir, device=None):
+    """<weights_dir>/kmeans_model.pkl -- a fitted sklearn KMeans or this package's KMeans -- as a device KMeans."""
+    from .kmeans import KMeans
+    try:
+        with open(os.path.join(weights_dir, 'kmeans_model.pkl'), 'rb') as f:
+            obj = pickle.load(f)
+    except Exception as ex:
+        raise ValueError("Error in loading pre-saved k-means weights") from ex
+    return obj if isinstance(obj, KMeans) else KMeans.from_sklearn(obj, device=device)
+
+
+def process_kmeans(input_dir, output_dir, weights_dir, prefix, suffix='_after_PCAed', model=None):
+    """<input_dir>/<prefix>_latent_space<suffix>.pkl -> <output_dir>/<prefix>_latent_space<suffix>_clusters.pkl (int32 labels,
+    protocol 4), labelled on the GPU by the model in <weights_dir> (or `model`)."""
+    os.makedirs(output_dir, exist_ok=True)
+    if model is None:
+        model = load_kmeans_model(weights_dir)
+    with open(os.path.join(input_dir, '{}_latent_space{}.pkl'.format(prefix, suffix)), 'rb') as f:
+        dats = pickle.load(f)
+    labels = np.asarray(model.predict(np.asarray(dats)), dtype=np.int32)
+    with open(os.path.join(output_dir, '{}_latent_space{}_clusters.pkl'.format(prefix, suffix)), 'wb') as f:
+        pickle.dump(labels, f, protocol=4)
+    return labels
+
+
+def trajectory_windows(vs, trajs, length=5, diffs=False):
+    """generate_short_traj_morphorlogy over list(trajs.values()) (morphology_clustering.py:103-113): every window of `length`
+    consecutive frames of every trajectory, in the reference's order, as one row of length * F descriptors -- or, diffs=True,
+    the (length - 1) * F differences of consecutive frames (Kmean_on_short_traj_diffs).  trajs: {name: frame indices into vs}
+    or a list of index lists; a trajectory shorter than `length` contributes nothing.  Returns (windows float32 (n, .),
+    owners: the position of each window's trajectory in trajs, int64 (n,))."""
+    vs = np.asarray(vs)
+    if vs.ndim != 2:
+        raise ValueError(f"vs has shape {vs.shape}, expected (frames, features)")
+    length = int(length)
+    if length < 1 or (diffs and length < 2):
+        raise ValueError(f"length = {length}: at least 1 frame, 2 for differences")
+    tlist = list(trajs.values()) if isinstance(trajs, dict) else list(trajs)
+    starts, owners = [], []
+    for o, t in enumerate(tlist):
+        t = np.asarray(t, dtype=np.int64)
+        n_sub = len(t) - (length - 1)
+        for i in range(max(n_sub, 0)):
+            starts.append(t[i:i + length])
+            owners.append(o)
+    F = vs.shape[1]
+    if not starts:
+        return np.zeros((0, (length - 1 if diffs else length) * F), np.float32), np.zeros(0, np.int64)
+    w = vs[np.stack(starts, 0)]                                    # (n, length, F)
+    if diffs:
+        w = w[:, 1:] - w[:, :-1]
+    return np.ascontiguousarray(w.reshape(len(starts), -1), dtype=np.float32), np.asarray(owners, np.int64)
+
+
+def kmeans_on_short_trajs(vs, trajs, length=5, n_clusters=4, diffs=False, **kw):
+    """Kmean_on_short_trajs / Kmean_on_short_traj_diffs (morphology_clustering.py:115-141): one KMeans(n_clusters) over the
+    windows of all trajectories, then {trajectory: labels of its windows} (int32; an empty array for a trajectory shorter than
+    `length`, where the reference's np.stack raises).  The labels of the fit ARE the prediction of the fitted centres for
+    the same rows, so nothing is labelled twice."""
+    from .kmeans import KMeans
+    windows, owners = trajectory_windows(vs, trajs, length=length, diffs=diffs)
+    labels = KMeans(n_clusters, **kw).fit(windows).labels_
+    return {t: labels[owners == o].astype(np.int32) for o, t in enumerate(trajs)}

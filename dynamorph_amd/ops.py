@@ -1627,6 +1627,92 @@ def knn_wide_self(X, K, k=15, shift=None, slack=None, include_self=False, pair_o
     return idx, dist, nfb, npairs
 
 
+# ----------------------------------------------------------------------------- exact k-means of the latents
+KMEANS_MAX_CLUSTERS = 1024     # DM_KMEANS_MAX_CLUSTERS
+
+
+def kmeans_workspace(N, F, K, like):
+    """A workspace dm_kmeans_assign and dm_kmeans_sums accept for the shape (uint8, 256-byte aligned by the allocator)."""
+    nbytes = L.load().dm_kmeans_workspace_bytes(N, F, K)
+    if nbytes < 0:
+        raise ValueError(f"dm_kmeans: bad shape N = {N}, F = {F}, K = {K}")
+    return torch.empty(max(int(nbytes), 256), device=like.device, dtype=torch.uint8)
+
+
+def _kmeans_centres(C, F, who):
+    if C.dim() != 2 or C.shape[1] != F:
+        raise ValueError(f"{who}: C has shape {tuple(C.shape)}, need (K, {F})")
+    return C.shape[0]
+
+
+@_op
+def kmeans_assign(X, C, shift=None, labels=None, dist=None, want_dist=True, workspace=None):
+    """Per row of X (N, F) the centre of C (K, F) of smallest (exact-form fp32 distance, index) (dm_kmeans_assign): (labels (N,)
+    int32, distances (N,) fp32 or None, rechecked rows (1,) int32 on the device).  shift (F,) fp32: subtracted in the
+    filter's operand load; the results do not depend on it."""
+    lib = L.load()
+    px, N, F, ldx = _rows(X)
+    K = _kmeans_centres(C, F, "dm_kmeans_assign")
+    if shift is not None and shift.numel() != F:
+        raise ValueError(f"dm_kmeans_assign: shift has {shift.numel()} entries, F = {F}")
+    if labels is None:
+        labels = _new((N,), X, torch.int32)
+    elif tuple(labels.shape) != (N,):
+        raise ValueError(f"dm_kmeans_assign: labels has shape {tuple(labels.shape)}, need ({N},)")
+    if dist is None and want_dist:
+        dist = _new((N,), X)
+    elif dist is not None and tuple(dist.shape) != (N,):
+        raise ValueError(f"dm_kmeans_assign: dist has shape {tuple(dist.shape)}, need ({N},)")
+    n = _new((1,), X, torch.int32)
+    workspace = _knn_ws(lib.dm_kmeans_workspace_bytes(N, F, K), workspace, X)
+    L.check(lib.dm_kmeans_assign(px, N, F, ldx, _ptr(C), K, _ptr(shift), _ptr(labels, torch.int32), _ptr(dist),
+                                 _ptr(n, torch.int32), _ptr(workspace, workspace.dtype),
+                                 workspace.numel() * workspace.element_size(), _stream()), "dm_kmeans_assign")
+    return labels, dist, n
+
+
+@_op
+def kmeans_sums(X, labels, K, sums=None, counts=None, workspace=None):
+    """(sums (K, F) float64, counts (K,) int64) of the rows of X by label, in an order fixed by the shape and the labels
+    (dm_kmeans_sums)."""
+    lib = L.load()
+    px, N, F, ldx = _rows(X)
+    K = int(K)
+    if tuple(labels.shape) != (N,):
+        raise ValueError(f"dm_kmeans_sums: labels has shape {tuple(labels.shape)}, need ({N},)")
+    if sums is None:
+        sums = _new((max(K, 0), F), X, torch.float64)
+    elif tuple(sums.shape) != (K, F):
+        raise ValueError(f"dm_kmeans_sums: sums has shape {tuple(sums.shape)}, need ({K}, {F})")
+    if counts is None:
+        counts = _new((max(K, 0),), X, torch.int64)
+    elif tuple(counts.shape) != (K,):
+        raise ValueError(f"dm_kmeans_sums: counts has shape {tuple(counts.shape)}, need ({K},)")
+    workspace = _knn_ws(lib.dm_kmeans_workspace_bytes(N, F, K), workspace, X)
+    L.check(lib.dm_kmeans_sums(px, N, F, ldx, _ptr(labels, torch.int32), K, _ptr(sums, torch.float64),
+                               _ptr(counts, torch.int64), _ptr(workspace, workspace.dtype),
+                               workspace.numel() * workspace.element_size(), _stream()), "dm_kmeans_sums")
+    return sums, counts
+
+
+@_op
+def kmeans_row_d2(X, C, labels=None, out=None):
+    """d2 (N,) float64: the exact-form squared distance of every row to centre labels[row] of C, or to row 0 of C when labels
+    is None (dm_kmeans_row_d2)."""
+    lib = L.load()
+    px, N, F, ldx = _rows(X)
+    K = _kmeans_centres(C, F, "dm_kmeans_row_d2")
+    if labels is not None and tuple(labels.shape) != (N,):
+        raise ValueError(f"dm_kmeans_row_d2: labels has shape {tuple(labels.shape)}, need ({N},)")
+    if out is None:
+        out = _new((N,), X, torch.float64)
+    elif tuple(out.shape) != (N,):
+        raise ValueError(f"dm_kmeans_row_d2: out has shape {tuple(out.shape)}, need ({N},)")
+    L.check(lib.dm_kmeans_row_d2(px, N, F, ldx, _ptr(C), K, _ptr(labels, torch.int32), _ptr(out, torch.float64), _stream()),
+            "dm_kmeans_row_d2")
+    return out
+
+
 # ----------------------------------------------------------------------------- UMAP behind the k-NN graph (DESIGN.md 3.5c)
 UMAP_MAX_K = 256               # DM_UMAP_MAX_K
 

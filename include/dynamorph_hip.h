@@ -919,6 +919,32 @@ int dm_knn_wide_self(const float *X, int64_t N, int F, int64_t ldx, const float 
                      int include_self, int pair_once, int32_t *indices, float *distances, int32_t *n_fallback,
                      int32_t *n_pairs, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ===== exact Lloyd k-means of the latents (sklearn.cluster.KMeans of the reference's clustering scripts) ==== */
+/* X: N x F fp32 row-major, leading dimension ldx >= F, 1 <= F <= DM_KNN_MAX_FEATURES; C: K x F fp32 contiguous centres,
+ * 1 <= K <= DM_KMEANS_MAX_CLUSTERS (a fit also needs K <= N: KMeans.fit checks it; labelling fewer rows than centres is
+ * fine).  The distance of a row and a centre is dm_knn's exact form; every entry point
+ * returns a negative code + dm_last_error() text for NULL or bad arguments before any launch, is asynchronous on `stream`
+ * and makes no read-back.  One workspace of dm_kmeans_workspace_bytes(N, F, K) serves dm_kmeans_assign and dm_kmeans_sums. */
+#define DM_KMEANS_MAX_CLUSTERS 1024
+/* HOST: bytes of device workspace (256-byte aligned) for the shape; -1 for a bad shape. */
+int64_t dm_kmeans_workspace_bytes(int64_t N, int F, int K);
+/* labels (N int32): per row the centre of smallest (fp32 exact-form distance, index) -- the index dm_knn(C, X, k = 1) returns;
+ * dist (N fp32, may be NULL): that distance, the same bits.  The shifted products (x - s).(c - s) on the f32 matrix
+ * instruction only filter: a row whose best centre the proven error bound cannot certify is redone from exact-form distances
+ * to all K centres inside the call.  *rechecked (device int, cleared by the call) counts those rows.  Results depend on
+ * the inputs only -- not on shift (F floats or NULL), the path a row took or the launch. */
+int dm_kmeans_assign(const float *X, int64_t N, int F, int64_t ldx, const float *C, int K, const float *shift, int32_t *labels,
+                     float *dist, int32_t *rechecked, void *workspace, int64_t workspace_bytes, void *stream);
+/* sums (K x F float64) and counts (K int64) of the rows by label; a label outside 0 .. K - 1 belongs to no cluster, a cluster
+ * without rows gets count 0 and a zero sum.  No floating-point atomics: the order of every addition depends on (N, F, K)
+ * and the labels only, and repeated launches are bit-identical. */
+int dm_kmeans_sums(const float *X, int64_t N, int F, int64_t ldx, const int32_t *labels, int K, double *sums, int64_t *counts,
+                   void *workspace, int64_t workspace_bytes, void *stream);
+/* d2 (N float64): the exact-form squared distance (the float64 sum before the root) of every row to centre labels[row], or to
+ * row 0 of C when labels is NULL; +inf for a label outside 0 .. K - 1. */
+int dm_kmeans_row_d2(const float *X, int64_t N, int F, int64_t ldx, const float *C, int K, const int32_t *labels, double *d2,
+                     void *stream);
+
 /* ===== UMAP behind the exact k-NN graph: smooth distances, membership strengths, one layout epoch ==== */
 /* dists / indices: the N x k graph dm_knn returns with include_self (column 0 the row itself at 0.0, rows sorted),
  * 2 <= k <= DM_UMAP_MAX_K, k <= N < 2^31.  Negative return + dm_last_error() text for NULL or bad arguments before any
