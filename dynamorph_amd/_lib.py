@@ -218,6 +218,9 @@ SIGNATURES = {
     "dm_kmeans_assign": (C.c_int, [vp, i64, C.c_int, i64, vp, C.c_int, vp, vp, vp, vp, vp, i64, vp]),
     "dm_kmeans_sums": (C.c_int, [vp, i64, C.c_int, i64, vp, C.c_int, vp, vp, vp, i64, vp]),
     "dm_kmeans_row_d2": (C.c_int, [vp, i64, C.c_int, i64, vp, C.c_int, vp, vp, vp]),
+    "dm_eig_apply_workspace_bytes": (i64, [i64, i64]),
+    "dm_eig_apply_plan": (C.c_int, [i64, i64, vp, vp, vp, vp]),
+    "dm_eig_apply": (C.c_int, [vp, i64, i64, vp, i64, i64, vp, i64, vp, C.c_size_t, vp]),
     "dm_umap_smooth": (C.c_int,[vp, i64, C.c_int, vp, vp, vp, vp, vp]),
     "dm_umap_membership": (C.c_int, [vp, vp, i64, C.c_int, vp, vp, vp, vp]),
     "dm_umap_epoch": (C.c_int, [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, f32, f32, f32, C.c_uint64, C.c_int, vp]),

@@ -167,27 +167,28 @@ def fit_umap_embedding(train_data, weights_dir, labels=None, n_nbrs=(15, 50, 200
     lists umap*.pkl there and calls .transform on what it unpickles.  save_models=True also writes the fitted UMAPEmbedding
     itself as <weights_dir>/umap_model_nbr<n>_a<a>_b<b>.pkl (protocol 4) -- a name that umap_transform, here and in the
     reference, does pick up; every such file carries the training matrix (N F 4 bytes: 5.2 GB for 20 000 VQ_VAE_z32 latents of
-    65536 features).  kw: UMAPEmbedding's (n_epochs, negative_sample_rate, gamma, init, seed, device).  More than MAX_FEATURES
+    65536 features).  kw: UMAPEmbedding's (n_epochs, negative_sample_rate, gamma, init, init_eigensolver, seed, device).  More than MAX_FEATURES
     columns: the wide route -- ONE row Gram matrix serves the graph's filter and the PCA initialisation.  Returns
     {(n, a, b): embedding}."""
     import torch
     from .umap_layout import UMAPEmbedding, pca_coordinates, wide_gram
     init = kw.pop("init", "pca")
     device = kw.get("device")
+    solver = {"eigensolver": kw["init_eigensolver"]} if kw.get("init_eigensolver", "full") != "full" else {}
     if isinstance(init, str) and init != "pca":
         raise ValueError(f"init={init!r}: 'pca' or an (N, 2) array")
     wide = _knn.is_wide(train_data)
     x = _knn._resident(train_data, device)
     if wide and isinstance(init, str):
         with torch.no_grad(), torch.cuda.device(x.device):
-            g = wide_gram(x)
+            g = wide_gram(x, **solver)
         graphs = fit_knn(x, weights_dir, n_nbrs=n_nbrs, gram=g)
-        init = pca_coordinates(x, gram=g, consume_gram=True).cpu().numpy()      # (the graph is done: K may be used up)
+        init = pca_coordinates(x, gram=g, consume_gram=True, **solver).cpu().numpy()      # (the graph is done: K may be used up)
         del g
     else:
         graphs = fit_knn(x, weights_dir, n_nbrs=n_nbrs)
         if isinstance(init, str):
-            init = pca_coordinates(x).cpu().numpy()
+            init = pca_coordinates(x, **solver).cpu().numpy()
     out = {}
     keep = {"X": x} if save_models else {}          # only a model that is saved holds on to the training matrix
     for n in sorted(graphs):

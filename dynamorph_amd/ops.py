@@ -1713,6 +1713,61 @@ def kmeans_row_d2(X, C, labels=None, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- Y = A Q of the partial eigensolver
+EIG_MAX_BLOCK = 256            # DM_EIG_MAX_BLOCK
+
+
+def _rows64(X, who):
+    """A 2-D float64 device matrix with unit column stride: (pointer, rows, columns, leading dimension)."""
+    if not X.is_cuda:
+        raise ValueError("dynamorph_amd: tensor is not on the GPU (the HIP path has no CPU fallback)")
+    if X.dtype != torch.float64 or X.dim() != 2:
+        raise ValueError(f"{who}: expected a 2-D float64 matrix, got {X.dtype} of shape {tuple(X.shape)}")
+    if X.shape[1] > 1 and X.stride(1) != 1:
+        raise ValueError(f"{who}: the matrix needs unit column stride")
+    if X.shape[0] > 1 and X.stride(0) < X.shape[1]:
+        raise ValueError(f"{who}: the rows of the matrix overlap")
+    _note_device(X.device.index)
+    return X.data_ptr(), X.shape[0], X.shape[1], max(X.stride(0), X.shape[1]) if X.shape[0] > 1 else X.shape[1]
+
+
+def eig_workspace(n, b, like):
+    """A workspace dm_eig_apply accepts for the shape (uint8, 256-byte aligned by the allocator)."""
+    nbytes = L.load().dm_eig_apply_workspace_bytes(n, b)
+    if nbytes < 0:
+        raise ValueError(f"dm_eig_apply: bad shape n = {n}, b = {b}")
+    return torch.empty(int(nbytes), device=like.device, dtype=torch.uint8)
+
+
+def eig_plan(n, b):
+    """(row_tiles, splits, tile_rows, stage) of dm_eig_apply for the shape (dm_eig_apply_plan; host only)."""
+    out = [C.c_int(0) for _ in range(4)]
+    L.check(L.load().dm_eig_apply_plan(n, b, *[C.addressof(o) for o in out]), "dm_eig_apply_plan")
+    return tuple(o.value for o in out)
+
+
+@_op
+def eig_apply(A, Q, out=None, workspace=None):
+    """Y (n, b) float64 = A Q (dm_eig_apply): A (n, n) and Q (n, b) float64 with unit column stride (row views are taken as
+    they lie), b a multiple of 16 in 16 .. 256.  A is not assumed symmetric."""
+    lib = L.load()
+    pa, n, na, lda = _rows64(A, "dm_eig_apply")
+    if na != n:
+        raise ValueError(f"dm_eig_apply: A has shape {tuple(A.shape)}, need a square matrix")
+    pq, nq, b, ldq = _rows64(Q, "dm_eig_apply")
+    if nq != n:
+        raise ValueError(f"dm_eig_apply: Q has shape {tuple(Q.shape)}, A has {n} rows")
+    if out is None:
+        out = _new((n, b), A, torch.float64)
+    py, ny, by, ldy = _rows64(out, "dm_eig_apply")
+    if (ny, by) != (n, b):
+        raise ValueError(f"dm_eig_apply: out has shape {tuple(out.shape)}, need ({n}, {b})")
+    workspace = _knn_ws(lib.dm_eig_apply_workspace_bytes(n, b), workspace, A)
+    L.check(lib.dm_eig_apply(pa, n, lda, pq, b, ldq, py, ldy, _ptr(workspace, workspace.dtype),
+                             workspace.numel() * workspace.element_size(), _stream()), "dm_eig_apply")
+    return out
+
+
 # ----------------------------------------------------------------------------- UMAP behind the k-NN graph (DESIGN.md 3.5c)
 UMAP_MAX_K = 256               # DM_UMAP_MAX_K
 

@@ -81,26 +81,86 @@ def merge_moments(n, mean, C, n_c, mean_c):
     return tot, mean + d * (n_c / tot)
 
 
-def finalize(C, mean, N, n_components=0.5):
+EIGENSOLVERS = ("full", "partial")
+EIG_BLOCK = 32                 # the partial solver's first block; a matrix of order <= 2 EIG_BLOCK takes the full route
+
+
+def _check_eigensolver(eigensolver):
+    if eigensolver not in EIGENSOLVERS:
+        raise ValueError(f"eigensolver={eigensolver!r}: one of {EIGENSOLVERS}")
+
+
+def _leading_pairs(M, n_components, N, F, eigensolver):
+    """The partial route: (theta (k,) descending clipped at 0, V (order, k), trace, info) of the symmetric float64 matrix M
+    from eig.top_eigenpairs -- or None where the full route is taken: eigensolver="full", n_components=None, a matrix of
+    order <= 2 EIG_BLOCK, or a solve that eig.NotApplicable / eig.NotConverged gave up on."""
+    if eigensolver != "partial" or n_components is None or M.shape[0] <= 2 * EIG_BLOCK:
+        return None
+    from . import eig
+    m = min(N, F)
+    if isinstance(n_components, (int, np.integer)):
+        if n_components > m:
+            raise ValueError(f"n_components={n_components} must be between 0 and min(n_samples, n_features)={m}")
+        want = {"k": int(n_components)}
+    else:
+        want = {"fraction": float(n_components)}
+    trace = float(torch.diagonal(M).sum(dtype=torch.float64))
+    try:
+        theta, V, info = eig.top_eigenpairs(M, trace=trace, block=EIG_BLOCK, **want)
+    except (eig.NotApplicable, eig.NotConverged):
+        return None
+    return theta.clamp_min(0.0), V, trace, info
+
+
+def _partial_attrs(theta, trace, N, F):
+    """The attributes the partial route fills from theta (numpy, clipped) and the trace."""
+    k, m = theta.shape[0], min(N, F)
+    ev = theta / (N - 1)
+    return {
+        "explained_variance_": ev.copy(),
+        "explained_variance_ratio_": theta / trace if trace > 0 else np.zeros_like(theta),
+        "singular_values_": np.sqrt(theta),
+        "noise_variance_": max(float(trace - theta.sum()), 0.0) / (N - 1) / (m - k) if k < m else 0.0,
+        "n_components_": int(k),
+        "n_samples_": int(N),
+        "n_features_in_": int(F),
+    }
+
+
+def finalize(C, mean, N, n_components=0.5, eigensolver="full"):
     """From the float64 scatter matrix C = sum (x - mean)(x - mean)^T (F x F, any device) to scikit-learn's fitted attributes
     (a dict of float64 numpy arrays and ints).  eigh in float64 on C's device; eigenvalues clipped at 0; the top min(N, F)
     eigenpairs are kept (the spectrum of the full SVD _fit_full's 'full' solver computes); signs by
-    svd_flip(u_based_decision=False): the entry of largest magnitude of each component is positive."""
+    svd_flip(u_based_decision=False): the entry of largest magnitude of each component is positive.
+
+    eigensolver="partial": only the leading pairs, from eig.top_eigenpairs (_leading_pairs); ratios against the trace and
+    the noise variance from the trace's remainder.  "eigensolver_" names the route taken, "eig_info_" the solver's record."""
     F = C.shape[0]
     _check_shape(N, F)
     _check_n_components(n_components)
-    evals, evecs = torch.linalg.eigh(C.to(torch.float64))
-    m = min(N, F)
-    evals = torch.flip(evals, (0,))[:m].clamp_min(0.0)
-    comps = torch.flip(evecs, (1,))[:, :m].T.contiguous()                 # (m, F): rows are components
+    _check_eigensolver(eigensolver)
+    C = C.to(torch.float64)
+    mean = mean.to(torch.float64).cpu().numpy() if torch.is_tensor(mean) else np.asarray(mean, np.float64)
+    part = _leading_pairs(C, n_components, N, F, eigensolver)
+    if part is not None:
+        theta, V, trace, info = part
+        comps = V.T.contiguous()
+    else:
+        evals, evecs = torch.linalg.eigh(C)
+        m = min(N, F)
+        evals = torch.flip(evals, (0,))[:m].clamp_min(0.0)
+        comps = torch.flip(evecs, (1,))[:, :m].T.contiguous()             # (m, F): rows are components
     idx = comps.abs().argmax(dim=1)
     signs = torch.sign(comps.gather(1, idx[:, None]))
     signs[signs == 0] = 1.0
     comps *= signs
+    if part is not None:
+        attrs = _partial_attrs(theta.cpu().numpy(), trace, N, F)
+        attrs.update(mean_=mean, components_=comps.cpu().numpy(), eigensolver_="partial", eig_info_=info)
+        return attrs
     ev = (evals / (N - 1)).cpu().numpy()
     ratio = ev / ev.sum() if ev.sum() > 0 else np.zeros_like(ev)
     k = select_n_components(n_components, ratio, N, F)
-    mean = mean.to(torch.float64).cpu().numpy() if torch.is_tensor(mean) else np.asarray(mean, np.float64)
     return {
         "mean_": mean,
         "components_": comps[:k].cpu().numpy(),
@@ -111,6 +171,8 @@ def finalize(C, mean, N, n_components=0.5):
         "n_components_": int(k),
         "n_samples_": int(N),
         "n_features_in_": int(F),
+        "eigensolver_": "full",
+        "eig_info_": None,
     }
 
 
@@ -127,7 +189,7 @@ def _check_wide_shape(N, F):
                          f"{WIDE_MAX_SAMPLES} samples")
 
 
-def finalize_samples(K, N, F, n_components=0.5):
+def finalize_samples(K, N, F, n_components=0.5, eigensolver="full"):
     """The sample-space finalisation: from the float64 matrix K = (X - s)(X - s)^T (N x N, any device, s any shift) to the
     fitted attributes that do not need X (a dict as finalize returns, without mean_ and components_) and "W": the
     (n_components_, N) float64 tensor (U_k / sqrt(lambda_k))^T on K's device, whose product with X - s is the components.
@@ -135,9 +197,12 @@ def finalize_samples(K, N, F, n_components=0.5):
     K is double-centred in float64 -- K - row means - column means + grand mean = (X - mean)(X - mean)^T whatever s was --
     in place.  eigh in float64 on K's device; eigenvalues clipped at 0; the top min(N, F) are the spectrum of the full SVD
     _fit_full's 'full' solver computes.  A requested component whose eigenvalue is at most N 2^-52 lambda_max is not
-    defined (centred data have rank <= N - 1): ValueError."""
+    defined (centred data have rank <= N - 1): ValueError.
+
+    eigensolver="partial": the leading pairs only, as in finalize; "eigensolver_" names the route taken."""
     _check_wide_shape(N, F)
     _check_n_components(n_components)
+    _check_eigensolver(eigensolver)
     if tuple(K.shape) != (N, N) or K.dtype != torch.float64:
         raise ValueError(f"K has shape {tuple(K.shape)} and dtype {K.dtype}, need a float64 ({N}, {N})")
     rm = K.mean(dim=1)
@@ -146,6 +211,18 @@ def finalize_samples(K, N, F, n_components=0.5):
     K -= rm[:, None]
     K -= cm[None, :]
     K += gm
+    part = _leading_pairs(K, n_components, N, F, eigensolver)
+    if part is not None:
+        theta, V, trace, info = part
+        lam = theta.cpu().numpy()
+        k = lam.shape[0]
+        rank = int((lam > N * 2.0 ** -52 * lam[0]).sum())
+        if k > rank:
+            raise ValueError(f"n_components={n_components!r} asks for {k} components of {N} samples, but at most {rank} "
+                             f"components are defined (the others have zero variance: centred data have rank <= n_samples - 1)")
+        attrs = _partial_attrs(lam, trace, N, F)
+        attrs.update(W=(V / theta.sqrt()).T.contiguous(), eigensolver_="partial", eig_info_=info)
+        return attrs
     evals, evecs = torch.linalg.eigh(K)
     m = min(N, F)
     evals = torch.flip(evals, (0,))[:m].clamp_min(0.0)
@@ -167,6 +244,8 @@ def finalize_samples(K, N, F, n_components=0.5):
         "n_components_": int(k),
         "n_samples_": int(N),
         "n_features_in_": int(F),
+        "eigensolver_": "full",
+        "eig_info_": None,
     }
 
 
@@ -205,11 +284,18 @@ class PCA:
     `chunk_rows` rows through pinned staging).  transform returns a CUDA fp32 tensor."""
 
     _check_shape = staticmethod(_check_shape)
+    # eigensolver: "full" (eigh of the whole matrix) or "partial" (eig.top_eigenpairs where it applies: _leading_pairs);
+    # eigensolver_ / eig_info_: the route the last fit took and the partial solver's record.  Not part of the pickle.
+    eigensolver = "full"
+    eigensolver_ = None
+    eig_info_ = None
 
-    def __init__(self, n_components=0.5, whiten=False, chunk_rows=65536, device=None, eigh_device="cuda"):
+    def __init__(self, n_components=0.5, whiten=False, chunk_rows=65536, device=None, eigh_device="cuda", eigensolver="full"):
         if whiten:
             raise ValueError("PCA(whiten=True) is not supported")
         _check_n_components(n_components)
+        _check_eigensolver(eigensolver)
+        self.eigensolver = eigensolver
         self.n_components = n_components
         self.whiten = False
         self.chunk_rows = int(chunk_rows)
@@ -287,7 +373,7 @@ class PCA:
         N, mean, C = self.moments(X, chunk_rows)
         if self.eigh_device == "cpu":
             C = C.cpu()
-        self._set(finalize(C, mean, N, self.n_components), self._device_of(X))
+        self._set(finalize(C, mean, N, self.n_components, self.eigensolver), self._device_of(X))
         return self
 
     def fit_transform(self, X, chunk_rows=None):
@@ -297,6 +383,7 @@ class PCA:
     def _set(self, attrs, device=None):
         for a in _ATTRS:
             setattr(self, a, attrs[a])
+        self.eigensolver_, self.eig_info_ = attrs.get("eigensolver_"), attrs.get("eig_info_")
         self._dev = {}
         self._home = device
 
@@ -380,6 +467,8 @@ class PCA:
         st = dict(self.__dict__)
         st["_dev"] = {}
         st["_home"] = None
+        for a in ("eigensolver", "eigensolver_", "eig_info_"):
+            st.pop(a, None)
         return st
 
 
@@ -400,13 +489,13 @@ class WidePCA(PCA):
             if X.dim() != 2:
                 raise ValueError(f"PCA expects a 2-D (samples, features) array, got shape {tuple(X.shape)}")
             _check_wide_shape(*X.shape)
-            self._check_memory(X.device, X.shape[0], X.shape[1], resident=True)
+            self._check_memory(X.device, X.shape[0], X.shape[1], resident=True, eigensolver=self.eigensolver)
             return X if X.dtype == torch.float32 else X.float()
         X = _host_rows(X)
         N, F = X.shape
         _check_wide_shape(N, F)
         dev = self._device_of(X)
-        self._check_memory(dev, N, F, resident=False)
+        self._check_memory(dev, N, F, resident=False, eigensolver=self.eigensolver)
         with torch.no_grad(), torch.cuda.device(dev):
             x = torch.empty((N, F), dtype=torch.float32, device=dev)
             if X.dtype == torch.float32 and X.is_contiguous() and X.is_pinned():
@@ -427,13 +516,18 @@ class WidePCA(PCA):
         return x
 
     @staticmethod
-    def _check_memory(dev, N, F, resident):
+    def _check_memory(dev, N, F, resident, eigensolver="full"):
         """X (unless it is on the device already), K, the row Gram's workspace and eigh's eigenvectors and workspace
-        (taken as 3 N^2 float64) against the free memory of the device."""
+        (taken as 3 N^2 float64) against the free memory of the device.  eigensolver="partial": instead of eigh's, the
+        solver's blocks (taken as 8 of N x 256 float64: Q, A Q, the Ritz vectors and their images, the QR's copies) and
+        dm_eig_apply's workspace; a fit that falls back to the full route allocates eigh's storage unchecked."""
         need_x = 0 if resident else 4 * N * F
         need_k = 8 * N * N
         need_ws = max(int(ops.L.load().dm_pca_rowgram_workspace_bytes(N, F)), 0)
-        need_eigh = 3 * 8 * N * N
+        if eigensolver == "partial":
+            need_eigh = 8 * 8 * N * ops.EIG_MAX_BLOCK + max(int(ops.L.load().dm_eig_apply_workspace_bytes(N, ops.EIG_MAX_BLOCK)), 0)
+        else:
+            need_eigh = 3 * 8 * N * N
         free, _ = torch.cuda.mem_get_info(dev)
         need = need_x + need_k + max(need_ws, need_eigh)
         if need > free:
@@ -472,7 +566,7 @@ class WidePCA(PCA):
         """The fit behind the row Gram matrix: K = (x - s)(x - s)^T is centred in place and decomposed (the caller holds the
         device and no_grad)."""
         N, F = x.shape
-        attrs = finalize_samples(K.cpu() if self.eigh_device == "cpu" else K, N, F, self.n_components)
+        attrs = finalize_samples(K.cpu() if self.eigh_device == "cpu" else K, N, F, self.n_components, self.eigensolver)
         W = attrs.pop("W").to(device=x.device, dtype=torch.float32)
         k = W.shape[0]
         V = torch.empty((k, F), dtype=torch.float64, device=x.device)

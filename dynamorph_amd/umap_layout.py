@@ -177,24 +177,28 @@ def init_layout(y, seed):
     return (t * 10.0 + u * 1e-4).contiguous()
 
 
-def wide_gram(x):
+def wide_gram(x, eigensolver="full"):
     """(mean, s, K) of a resident wide matrix, as WidePCA.gram forms it: what wide_knn_graph and WidePCA both start from.  The
-    free memory of the device is checked first, as for a WidePCA fit (K, and eigh's 3 N^2 float64, which exceed the graph's
-    fp32 panel)."""
+    free memory of the device is checked first, as for a WidePCA(eigensolver=eigensolver) fit (K, and eigh's 3 N^2 float64,
+    which exceed the graph's fp32 panel)."""
     from .pca import WidePCA
-    WidePCA._check_memory(x.device, x.shape[0], x.shape[1], resident=True)
+    WidePCA._check_memory(x.device, x.shape[0], x.shape[1], resident=True, eigensolver=eigensolver)
     return WidePCA().gram(x)
 
 
-def pca_coordinates(X, device=None, gram=None, consume_gram=False):
+def pca_coordinates(X, device=None, gram=None, consume_gram=False, eigensolver="full"):
     """The first two principal-component scores of X from this package's PCA(n_components=2): init="pca" before rescaling.
     More than knn.MAX_FEATURES columns: WidePCA(n_components=2), from gram=(mean, s, K) = wide_gram(x) when it is given (K is
-    left unchanged unless consume_gram)."""
+    left unchanged unless consume_gram).  eigensolver: "full" or "partial", handed to the PCA."""
     if _knn.is_wide(X):
         from .pca import WidePCA
-        return WidePCA(n_components=2, device=device).fit_transform(X, gram=gram, consume_gram=consume_gram)
+        return WidePCA(n_components=2, device=device, eigensolver=eigensolver).fit_transform(X, gram=gram,
+                                                                                             consume_gram=consume_gram)
     from .pca import PCA
-    return PCA(n_components=2, device=device).fit_transform(X)
+    return PCA(n_components=2, device=device, eigensolver=eigensolver).fit_transform(X)
+
+
+pca_init = pca_coordinates      # init="pca"
 
 
 # ---------------------------------------------------------------------------------------------------------- the device
@@ -226,7 +230,7 @@ class UMAPEmbedding:
     transform(Q); it pickles with its state on the host."""
 
     def __init__(self, n_neighbors=15, a=1.58, b=0.9, n_epochs=None, negative_sample_rate=5, gamma=1.0, init="pca", seed=0,
-                 n_components=2, device=None):
+                 n_components=2, device=None, init_eigensolver="full"):
         if int(n_components) != 2:
             raise ValueError(f"the layout has two output dimensions, got n_components={n_components}")
         if int(n_neighbors) < 2 or int(n_neighbors) > MAX_K:
@@ -245,6 +249,7 @@ class UMAPEmbedding:
         self.n_epochs = None if n_epochs is None else int(n_epochs)
         self.negative_sample_rate, self.gamma, self.init, self.seed = int(negative_sample_rate), float(gamma), init, int(seed)
         self.device = device
+        self.init_eigensolver = init_eigensolver    # the eigensolver of init="pca": "full" or "partial" (pca.PCA's)
         self.group = 0              # lanes per vertex of dm_umap_epoch (0: chosen by the library; no effect on the result)
         self.transform_group = 0    # the same for dm_umap_transform_layout
         self._X = None              # the training matrix (M, F) fp32: the resident device tensor of the fit, or host numpy
@@ -265,12 +270,12 @@ class UMAPEmbedding:
         if not wide:
             idx, dist = _knn.knn_graph(x, self.n_neighbors, include_self=True)
             if isinstance(init, str):
-                init = pca_coordinates(x)
+                init = pca_coordinates(x, eigensolver=self.init_eigensolver)
         elif isinstance(init, str):                 # one row Gram matrix: the graph's filter first, then the PCA uses it up
             with torch.no_grad(), torch.cuda.device(x.device):
-                g = wide_gram(x)
+                g = wide_gram(x, eigensolver=self.init_eigensolver)
             idx, dist = _knn.wide_knn_graph(x, self.n_neighbors, include_self=True, gram=g)
-            init = pca_coordinates(x, gram=g, consume_gram=True)
+            init = pca_coordinates(x, gram=g, consume_gram=True, eigensolver=self.init_eigensolver)
             del g
         else:
             idx, dist = _knn.wide_knn_graph(x, self.n_neighbors, include_self=True)
@@ -411,6 +416,7 @@ class UMAPEmbedding:
         self.__dict__.update(state)
         self.__dict__.setdefault("_X", None)
         self.__dict__.setdefault("transform_group", 0)
+        self.__dict__.setdefault("init_eigensolver", "full")
 
     def graph(self):
         """The fuzzy simplicial set W (N, N) as scipy.sparse.csr_matrix (float32)."""

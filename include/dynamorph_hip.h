@@ -945,6 +945,22 @@ int dm_kmeans_sums(const float *X, int64_t N, int F, int64_t ldx, const int32_t 
 int dm_kmeans_row_d2(const float *X, int64_t N, int F, int64_t ldx, const float *C, int K, const int32_t *labels, double *d2,
                      void *stream);
 
+/* ===== Y = A Q in float64: the heavy step of the partial eigensolver behind the PCA fits ==== */
+/* A: n x n float64 row-major (lda >= n; NOT assumed symmetric), Q and Y: n x b float64 row-major (ldq, ldy >= b), n >= 1, b a
+ * multiple of 16 in 16 .. DM_EIG_MAX_BLOCK.  v_mfma_f64_16x16x4_f64; a workgroup owns 64 rows of A, all b columns and one
+ * range of the inner dimension, so every element of A crosses HBM once per call.  The ranges depend on (n, b) only and are
+ * added in order: no atomics, repeated launches are equal in every bit, and the result does not depend on the leading
+ * dimensions.  Columns of Y beyond b and rows beyond n are never written.  Negative return + dm_last_error() text for NULL or
+ * bad arguments before any launch; asynchronous on `stream`, no read-back. */
+#define DM_EIG_MAX_BLOCK 256
+/* HOST: bytes of device workspace (256-byte aligned) for the shape; -1 for a bad shape. */
+int64_t dm_eig_apply_workspace_bytes(int64_t n, int64_t b);
+/* HOST: what a call of this shape launches: workgroups along the rows, ranges of the inner dimension (1: Y is written
+ * directly, no reduction), rows of A per workgroup, inner indices per LDS stage.  Any output may be NULL. */
+int dm_eig_apply_plan(int64_t n, int64_t b, int *row_tiles, int *splits, int *tile_rows, int *stage);
+int dm_eig_apply(const double *A, int64_t n, int64_t lda, const double *Q, int64_t b, int64_t ldq, double *Y, int64_t ldy,
+                 void *ws, size_t ws_bytes, void *stream);
+
 /* ===== UMAP behind the exact k-NN graph: smooth distances, membership strengths, one layout epoch ==== */
 /* dists / indices: the N x k graph dm_knn returns with include_self (column 0 the row itself at 0.0, rows sorted),
  * 2 <= k <= DM_UMAP_MAX_K, k <= N < 2^31.  Negative return + dm_last_error() text for NULL or bad arguments before any
