@@ -1,49 +1,11 @@
-// exact_form.h -- the exact-form distance of a pair of fp32 rows and the row loads it is built from: ONE definition for every
+// exact_form.h -- the exact-form distance of a pair of fp32 rows, on the row loads of gram_tile.h: ONE definition for every
 // kernel that evaluates it (knn.hip, kmeans.hip).  The files that include it are compiled with
 // -ffp-contract=off: the vector and the scalar load forms, and every kernel that calls knn_exact_d2, produce the same bits.
 #pragma once
-#include "dm_common.h"
+#include "gram_tile.h"
 #include <math.h>
 
 namespace {
-
-// The 16-byte form of every kernel: rows start on 16 bytes and are a whole number of float4s.
-bool vec4_ok(const float *p, long long ld, int F) { return ld % 4 == 0 && F % 4 == 0 && ((uintptr_t)p & 15) == 0; }
-
-// Four consecutive features f .. f + 3 of a row, f < F, zero past F (V4: F % 4 == 0, nothing lies past it).
-template <bool V4>
-__device__ __forceinline__ f32x4 row_load4(const float *__restrict__ row, int f, int F)
-{
-    if (V4) return *(const f32x4 *)(row + f);
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-        if (f + e < F) v[e] = row[f + e];
-    return v;
-}
-
-__device__ __forceinline__ f32x4 shift_load4(const float *__restrict__ shift, int f, int F)
-{
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    if (shift) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (f + e < F) s[e] = shift[f + e];
-    }
-    return s;
-}
-
-// The same four features without a branch, for loads that must not be waited for where they are issued: addresses past F
-// are clamped into the row and the caller discards those elements.
-template <bool V4>
-__device__ __forceinline__ f32x4 row_load4_clamped(const float *__restrict__ row, int f, int F)
-{
-    if (V4) return *(const f32x4 *)(row + (f < F ? f : F - 4));
-    f32x4 v;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = row[f + e < F ? f + e : F - 1];
-    return v;
-}
 
 // ------------------------------------------------------------------------------------------------ the exact form
 // d^2 of one pair by one wave: lane l takes features 4 l + 256 t .. + 3; differences and squares in fp32, the four squares of

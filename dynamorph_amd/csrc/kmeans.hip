@@ -4,7 +4,7 @@
 // X is N x F fp32 (row-major, leading dimension ldx), the centres C are K x F fp32 (contiguous).  The distance of a row and a
 // centre is the exact form of the k-NN graph (exact_form.h: knn_exact_d2, knn_dist_of), the label the centre of smallest
 // (fp32 distance, index) -- what dm_knn(C, X, k = 1) returns, to the bit.
-//   assign   km_cnorm_kernel + km_cmax_kernel: |c - s|^2 of every centre in float64, their maximum; clears the counter of rechecked rows.
+//   assign   row_norms_kernel + norms_max_kernel (gram_tile.h): |c - s|^2 of every centre in float64, their maximum; clears the counter of rechecked rows.
 //            km_filter_kernel: a workgroup takes 128 rows of X and walks all centres in column tiles of 32, 64 or 128:
 //            g = |x - s|^2 + |c - s|^2 - 2 (x - s).(c - s) on v_mfma_f32_32x32x2_f32, fp32 within a slab of 256 features, slabs
 //            added in float64 registers (the filter of knn_gram_kernel, the same error bound); the row norms are summed in
@@ -24,49 +24,10 @@
 
 namespace {
 
-constexpr int KM_TM = 128;              // rows of X per workgroup of the labelling pass (32 per wave)
-constexpr int KM_CH = 16;               // features per LDS stage (8 k-steps of the 32x32x2 instruction)
-constexpr int KM_LW = KM_TM + 32;       // LDS row stride of the X operand
-constexpr int KM_SLAB = 256;            // features accumulated in fp32 before the partial sum is added in float64
-static_assert(KM_SLAB % KM_CH == 0, "a slab is a whole number of LDS stages");
 constexpr int KM_BLK = 256;             // rows per block of the grouping kernels
 constexpr int KM_SEG = 128;             // rows per segment of a cluster's sum
 
-// --------------------------------------------------------------------------------------------------- centre norms
-// One wave per centre: sum_f fl(c_f - s_f)^2, the squares and the sum in float64, lanes added in a butterfly.
-template <bool V4>
-__global__ __launch_bounds__(256) void km_cnorm_kernel(const float *__restrict__ C, int K, int F,
-                                                       const float *__restrict__ shift, double *__restrict__ out)
-{
-    const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= K) return;
-    const float *__restrict__ row = C + (long long)r * F;
-    double acc = 0.0;
-    for (int f = 4 * lane; f < F; f += 256) {
-        const f32x4 v = row_load4<V4>(row, f, F) - shift_load4(shift, f, F);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc += (double)v[e] * (double)v[e];
-    }
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if (lane == 0) out[r] = acc;
-}
-
-// The largest of the K norms (one workgroup); thread 0 also clears the call's counter of rechecked rows.
-__global__ __launch_bounds__(256) void km_cmax_kernel(const double *__restrict__ v, int K, double *__restrict__ out,
-                                                      int *__restrict__ counter)
-{
-    __shared__ double s[256];
-    double m = 0.0;
-    for (int i = threadIdx.x; i < K; i += 256) m = fmax(m, v[i]);
-    s[threadIdx.x] = m;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) s[threadIdx.x] = fmax(s[threadIdx.x], s[threadIdx.x + o]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { *out = s[0]; *counter = 0; }
-}
+// The centre norms and their maximum: row_norms_kernel and norms_max_kernel of gram_tile.h.
 
 // ------------------------------------------------------------------------------------------------ labelling pass
 // 4 waves; wave w owns rows 32 w .. 32 w + 31 of the workgroup's 128 and all TN = 32 NT centres of the current tile as NT
@@ -86,16 +47,16 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void km_filter_kernel(const f
     constexpr int CR = TN < 64 ? TN : 64;       // centre rows one staging step of the workgroup covers
     constexpr int CQ = NT == 4 ? 2 : 1;         // centre rows per thread
     constexpr int CLW = TN + 32;                // LDS row stride of the centre operand
-    constexpr int BUF = KM_CH * KM_LW + KM_CH * CLW;
+    constexpr int BUF = GT_CH * GT_LW + GT_CH * CLW;
     __shared__ __attribute__((aligned(16))) float lds[2][BUF];
-    __shared__ double s_part[4][KM_TM];         // the row norms by feature quarter, then s_nq: their sum
-    __shared__ double s_nq[KM_TM];
+    __shared__ double s_part[4][GT];         // the row norms by feature quarter, then s_nq: their sum
+    __shared__ double s_nq[GT];
 
-    const int I = (int)blockIdx.x * KM_TM;
+    const int I = (int)blockIdx.x * GT;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int sr = tid & 63, sf = 4 * (tid >> 6);
     const int cr = tid % CR, csf = 4 * (tid / CR);
-    const bool cact = csf < KM_CH;              // (32 centres: waves 0 and 1 stage them)
+    const bool cact = csf < GT_CH;              // (32 centres: waves 0 and 1 stage them)
 
     const float *xrow[2];
 #pragma unroll
@@ -103,10 +64,9 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void km_filter_kernel(const f
         const int rx = I + sr + 64 * q;
         xrow[q] = X + (long long)(rx < N ? rx : N - 1) * ldx;
     }
-    const int nstages = (F + KM_CH - 1) / KM_CH;
-    constexpr int STAGES_PER_SLAB = KM_SLAB / KM_CH;
+    const int nstages = (F + GT_CH - 1) / GT_CH;
+    constexpr int STAGES_PER_SLAB = GT_SLAB / GT_CH;
 
-    typedef float f32x16 __attribute__((ext_vector_type(16)));
     float m1[16], m2[16];
     int i1[16];
 #pragma unroll
@@ -125,30 +85,30 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void km_filter_kernel(const f
         double nacc[2] = {0.0, 0.0};
         auto fetch = [&](int stage, int slot) {
             const int st = stage < nstages ? stage : nstages - 1;
-            rs[slot] = row_load4_clamped<V4>(shift, st * KM_CH + sf, F);
+            rs[slot] = row_load4_clamped<V4>(shift, st * GT_CH + sf, F);
 #pragma unroll
-            for (int q = 0; q < 2; ++q) ra[slot][q] = row_load4_clamped<V4>(xrow[q], st * KM_CH + sf, F);
+            for (int q = 0; q < 2; ++q) ra[slot][q] = row_load4_clamped<V4>(xrow[q], st * GT_CH + sf, F);
             if (cact) {
-                rcs[slot] = row_load4_clamped<V4>(shift, st * KM_CH + csf, F);
+                rcs[slot] = row_load4_clamped<V4>(shift, st * GT_CH + csf, F);
 #pragma unroll
-                for (int q = 0; q < CQ; ++q) rb[slot][q] = row_load4_clamped<V4>(crow[q], st * KM_CH + csf, F);
+                for (int q = 0; q < CQ; ++q) rb[slot][q] = row_load4_clamped<V4>(crow[q], st * GT_CH + csf, F);
             }
         };
         auto stash = [&](int stage, int slot, int buf) {
-            float *A = lds[buf], *B = lds[buf] + KM_CH * KM_LW;
-            const int f = stage * KM_CH + sf;
+            float *A = lds[buf], *B = lds[buf] + GT_CH * GT_LW;
+            const int f = stage * GT_CH + sf;
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 const f32x4 va = ra[slot][q] - rs[slot];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {       // features past F: zeros
                     const float v = f + e < F ? va[e] : 0.f;
-                    A[(sf + e) * KM_LW + sr + 64 * q] = v;
+                    A[(sf + e) * GT_LW + sr + 64 * q] = v;
                     if (ct == 0) nacc[q] += (double)v * (double)v;
                 }
             }
             if (cact) {
-                const int fc = stage * KM_CH + csf;
+                const int fc = stage * GT_CH + csf;
 #pragma unroll
                 for (int q = 0; q < CQ; ++q) {
                     const f32x4 vb = rb[slot][q] - rcs[slot];
@@ -178,12 +138,12 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void km_filter_kernel(const f
                 if (st >= nstages) break;
                 fetch(st + 2, u);                   // (slot u went to LDS one stage ago)
                 __builtin_amdgcn_sched_barrier(0);  // the loads are issued here, not after the products
-                const float *A = lds[u], *B = lds[u] + KM_CH * KM_LW;
-                const int oa = (lane >> 5) * KM_LW + (lane & 31) + 32 * w;
+                const float *A = lds[u], *B = lds[u] + GT_CH * GT_LW;
+                const int oa = (lane >> 5) * GT_LW + (lane & 31) + 32 * w;
                 const int ob = (lane >> 5) * CLW + (lane & 31);
 #pragma unroll
-                for (int kk = 0; kk < KM_CH / 2; ++kk) {
-                    const float a = A[2 * kk * KM_LW + oa];
+                for (int kk = 0; kk < GT_CH / 2; ++kk) {
+                    const float a = A[2 * kk * GT_LW + oa];
 #pragma unroll
                     for (int j = 0; j < NT; ++j)
                         acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, B[2 * kk * CLW + ob + 32 * j], acc[j], 0, 0, 0);
@@ -204,7 +164,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void km_filter_kernel(const f
 #pragma unroll
             for (int q = 0; q < 2; ++q) s_part[w][sr + 64 * q] = nacc[q];
             __syncthreads();
-            if (tid < KM_TM) {
+            if (tid < GT) {
                 const double n2 = ((s_part[0][tid] + s_part[1][tid]) + s_part[2][tid]) + s_part[3][tid];
                 s_nq[tid] = n2;
                 if (I + tid < N) nq[I + tid] = n2;
@@ -436,8 +396,6 @@ __global__ __launch_bounds__(256) void km_row_d2_kernel(const float *__restrict_
 }
 
 // ------------------------------------------------------------------------------------------------------- host
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct KmPlan {
     int nb, nseg, FP;
     size_t o_nc, o_max, o_zero, o_nq, o_cand, o_rej;            // the labelling pass
@@ -448,7 +406,7 @@ struct KmPlan {
 // 0, or the reason the shape is refused.
 const char *km_plan(long long N, int F, int K, KmPlan *p)
 {
-    if (N < 1 || N > 0x7fffffffLL - KM_TM) return "N outside 1 .. 2^31 - 129";
+    if (N < 1 || N > 0x7fffffffLL - GT) return "N outside 1 .. 2^31 - 129";
     if (F < 1 || F > DM_KNN_MAX_FEATURES) return "F outside 1 .. DM_KNN_MAX_FEATURES (reduce wider latents with the PCA first)";
     if (K < 1 || K > DM_KMEANS_MAX_CLUSTERS) return "K outside 1 .. DM_KMEANS_MAX_CLUSTERS";
     p->nb = (int)((N + KM_BLK - 1) / KM_BLK);
@@ -474,16 +432,15 @@ const char *km_plan(long long N, int F, int K, KmPlan *p)
 
 template <bool V4>
 void km_assign_launch(const KmPlan &p, const float *X, int N, int F, long long ldx, const float *C, int K, const float *shift,
-                      int *labels, float *dist, int *rechecked, char *ws, hipStream_t s)
+                      const float *gs, int *labels, float *dist, int *rechecked, char *ws, hipStream_t s)
 {
     double *nc = (double *)(ws + p.o_nc), *ncmax = (double *)(ws + p.o_max);
-    const float *gs = shift ? shift : (const float *)(ws + p.o_zero);      // (zeros: the caller cleared them)
-    hipLaunchKernelGGL(km_cnorm_kernel<V4>, dim3((K + 3) / 4), dim3(256), 0, s, C, K, F, shift, nc);
-    hipLaunchKernelGGL(km_cmax_kernel, dim3(1), dim3(256), 0, s, (const double *)nc, K, ncmax, rechecked);
+    hipLaunchKernelGGL(row_norms_kernel<V4>, dim3((K + 3) / 4), dim3(256), 0, s, C, (long long)K, F, (long long)F, shift, nc);
+    hipLaunchKernelGGL(norms_max_kernel<256>, dim3(1), dim3(256), 0, s, (const double *)nc, (long long)K, ncmax, rechecked);
     double *nq = (double *)(ws + p.o_nq);
     int *cand = (int *)(ws + p.o_cand);
     float *rej = (float *)(ws + p.o_rej);
-    const dim3 grid((unsigned)((N + KM_TM - 1) / KM_TM));
+    const dim3 grid((unsigned)((N + GT - 1) / GT));
     if (K <= 32)
         hipLaunchKernelGGL((km_filter_kernel<V4, 1>), grid, dim3(256), 0, s, X, N, ldx, C, K, F, gs, (const double *)nc, nq, cand, rej);
     else if (K <= 64)
@@ -492,7 +449,7 @@ void km_assign_launch(const KmPlan &p, const float *X, int N, int F, long long l
         hipLaunchKernelGGL((km_filter_kernel<V4, 4>), grid, dim3(256), 0, s, X, N, ldx, C, K, F, gs, (const double *)nc, nq, cand, rej);
     hipLaunchKernelGGL(km_certify_kernel<V4>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, X, N, ldx, C, K, F,
                        (const double *)nq, (const int *)cand, (const float *)rej, (const double *)ncmax,
-                       exact_form_filter_bound(KM_SLAB), labels, dist, rechecked);
+                       exact_form_filter_bound(GT_SLAB), labels, dist, rechecked);
 }
 
 template <bool V4>
@@ -536,17 +493,12 @@ extern "C" int dm_kmeans_assign(const float *X, int64_t N, int F, int64_t ldx, c
                (long long)workspace_bytes, (long long)p.total);
     DM_REQUIRE(((uintptr_t)workspace & 255) == 0, "dm_kmeans_assign: workspace is not 256-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    if (!shift) {                           // the filter's loads are unconditional: no shift = a vector of zeros
-        const hipError_t e = hipMemsetAsync((char *)workspace + p.o_zero, 0, (size_t)F * sizeof(float), s);
-        if (e != hipSuccess) {
-            dm_set_error("dm_kmeans_assign: hipMemsetAsync: %s", hipGetErrorString(e));
-            return (int)e;
-        }
-    }
+    const float *gs;
+    if (const int e = shift_or_zeros("dm_kmeans_assign", shift, (char *)workspace + p.o_zero, F, s, &gs)) return e;
     if (vec4_ok(X, ldx, F) && vec4_ok(C, F, F) && ((uintptr_t)shift & 15) == 0)
-        km_assign_launch<true>(p, X, (int)N, F, ldx, C, K, shift, labels, dist, rechecked, (char *)workspace, s);
+        km_assign_launch<true>(p, X, (int)N, F, ldx, C, K, shift, gs, labels, dist, rechecked, (char *)workspace, s);
     else
-        km_assign_launch<false>(p, X, (int)N, F, ldx, C, K, shift, labels, dist, rechecked, (char *)workspace, s);
+        km_assign_launch<false>(p, X, (int)N, F, ldx, C, K, shift, gs, labels, dist, rechecked, (char *)workspace, s);
     return dm_launch_status("dm_kmeans_assign");
 }
 

@@ -5,7 +5,7 @@
 // r0 .. r0 + R - 1 of X itself (the pair (i, i) is then excluded by index).  One call handles one panel of R queries:
 //   norms     |x - s|^2 of every row in float64 (the squares of fp32 numbers are exact there), and their maximum.
 //   gram      g = |q - s|^2 + |x - s|^2 - 2 (q - s).(x - s): 128 x 128 tiles on v_mfma_f32_32x32x2_f32, fp32 within a slab of
-//             KN_SLAB features, slabs added in float64 registers, the result rounded to the fp32 panel (R x M).  A FILTER.
+//             GT_SLAB features, slabs added in float64 registers, the result rounded to the fp32 panel (R x M).  A FILTER.
 //   select    per panel row: the K = k + slack smallest by radix select on the value's bits (ties: the lowest columns), and
 //             the smallest value left out.
 //   refine    per row: the candidates' distances in the exact form -- differences and squares in fp32, four squares added in
@@ -27,49 +27,10 @@
 
 namespace {
 
-constexpr int KN_T = 128;               // tile edge of the Gram panel kernel
-constexpr int KN_CH = 16;               // features per LDS stage (8 k-steps of the 32x32x2 instruction)
-constexpr int KN_LW = KN_T + 32;        // LDS row stride: the two lane halves of a read (features k, k + 1) land 32 banks apart
-constexpr int KN_SLAB = 256;            // features accumulated in fp32 before the partial sum is added in float64
-static_assert(KN_SLAB % KN_CH == 0, "a slab is a whole number of LDS stages");
 constexpr int KN_CAND = DM_KNN_MAX_K + DM_KNN_MAX_SLACK;        // 512 candidates at most: the sort's LDS
 constexpr int KN_FB_ROWS = 256;         // rows of the fallback panel
 
-// --------------------------------------------------------------------------------------------------------- norms
-// One wave per row: sum_f fl(x_f - s_f)^2, the squares and the sum in float64, lanes added in a butterfly.
-template <bool V4>
-__global__ __launch_bounds__(256) void knn_norms_kernel(const float *__restrict__ X, long long rows, int F, long long ld,
-                                                        const float *__restrict__ shift, double *__restrict__ out)
-{
-    const int lane = threadIdx.x & 63;
-    const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= rows) return;
-    const float *__restrict__ row = X + r * ld;
-    double acc = 0.0;
-    for (int f = 4 * lane; f < F; f += 256) {
-        const f32x4 v = row_load4<V4>(row, f, F) - shift_load4(shift, f, F);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc += (double)v[e] * (double)v[e];
-    }
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if (lane == 0) out[r] = acc;
-}
-
-// The largest of n norms (one workgroup); thread 0 also clears the call's fallback counter.
-__global__ __launch_bounds__(256) void knn_max_kernel(const double *__restrict__ v, long long n, double *__restrict__ out,
-                                                      int *__restrict__ counter)
-{
-    __shared__ double s[256];
-    double m = 0.0;
-    for (long long i = threadIdx.x; i < n; i += 256) m = fmax(m, v[i]);
-    s[threadIdx.x] = m;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) s[threadIdx.x] = fmax(s[threadIdx.x], s[threadIdx.x + o]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { *out = s[0]; *counter = 0; }
-}
+// The norms and their maximum: row_norms_kernel and norms_max_kernel of gram_tile.h.
 
 // ---------------------------------------------------------------------------------------------------- Gram panel
 // Workgroup id = column tile * row_tiles + row tile: the workgroups resident together share a few column tiles of X, which
@@ -87,8 +48,8 @@ __global__ __launch_bounds__(256) void knn_gram_kernel(const float *__restrict__
                                                        const double *__restrict__ nx, int self_r0,
                                                        float *__restrict__ panel, long long ldp, int row_tiles)
 {
-    __shared__ __attribute__((aligned(16))) float lds[2][2][KN_CH * KN_LW];
-    const int I = (int)(blockIdx.x % row_tiles) * KN_T, J = (int)(blockIdx.x / row_tiles) * KN_T;
+    __shared__ __attribute__((aligned(16))) float lds[2][2][GT_CH * GT_LW];
+    const int I = (int)(blockIdx.x % row_tiles) * GT, J = (int)(blockIdx.x / row_tiles) * GT;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int wm = w >> 1, wn = w & 1;
     const int sr = tid & 63, sf = 4 * (tid >> 6);
@@ -100,11 +61,11 @@ __global__ __launch_bounds__(256) void knn_gram_kernel(const float *__restrict__
         qrow[q] = Q + (long long)(rq < R ? rq : R - 1) * ldq;
         xrow[q] = X + (long long)(rx < M ? rx : M - 1) * ldx;
     }
-    const int nstages = (F + KN_CH - 1) / KN_CH;
+    const int nstages = (F + GT_CH - 1) / GT_CH;
 
     f32x4 ra[2][2], rb[2][2], rs[2];
     auto fetch = [&](int stage, int slot) {
-        const int f = (stage < nstages ? stage : nstages - 1) * KN_CH + sf;
+        const int f = (stage < nstages ? stage : nstages - 1) * GT_CH + sf;
         rs[slot] = row_load4_clamped<V4>(shift, f, F);
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
@@ -113,19 +74,18 @@ __global__ __launch_bounds__(256) void knn_gram_kernel(const float *__restrict__
         }
     };
     auto stash = [&](int stage, int slot, int buf) {
-        const int f = stage * KN_CH + sf;
+        const int f = stage * GT_CH + sf;
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const f32x4 va = ra[slot][q] - rs[slot], vb = rb[slot][q] - rs[slot];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {       // features past F: zeros
-                lds[buf][0][(sf + e) * KN_LW + sr + 64 * q] = f + e < F ? va[e] : 0.f;
-                lds[buf][1][(sf + e) * KN_LW + sr + 64 * q] = f + e < F ? vb[e] : 0.f;
+                lds[buf][0][(sf + e) * GT_LW + sr + 64 * q] = f + e < F ? va[e] : 0.f;
+                lds[buf][1][(sf + e) * GT_LW + sr + 64 * q] = f + e < F ? vb[e] : 0.f;
             }
         }
     };
 
-    typedef float f32x16 __attribute__((ext_vector_type(16)));
     f32x16 acc[2][2];
     double dacc[2][2][16];
 #pragma unroll
@@ -141,7 +101,7 @@ __global__ __launch_bounds__(256) void knn_gram_kernel(const float *__restrict__
     fetch(1, 1);
     stash(0, 0, 0);
     __syncthreads();
-    constexpr int STAGES_PER_SLAB = KN_SLAB / KN_CH;
+    constexpr int STAGES_PER_SLAB = GT_SLAB / GT_CH;
     for (int st0 = 0; st0 < nstages; st0 += 2) {
 #pragma unroll
         for (int u = 0; u < 2; ++u) {           // stage st lives in register slot u and LDS buffer u
@@ -150,10 +110,10 @@ __global__ __launch_bounds__(256) void knn_gram_kernel(const float *__restrict__
             fetch(st + 2, u);                   // (slot u went to LDS one stage ago)
             __builtin_amdgcn_sched_barrier(0);  // the loads are issued here, not after the products
             const float *A = lds[u][0], *B = lds[u][1];
-            const int koff = (lane >> 5) * KN_LW + (lane & 31);
+            const int koff = (lane >> 5) * GT_LW + (lane & 31);
 #pragma unroll
-            for (int kk = 0; kk < KN_CH / 2; ++kk) {
-                const int o = 2 * kk * KN_LW + koff;
+            for (int kk = 0; kk < GT_CH / 2; ++kk) {
+                const int o = 2 * kk * GT_LW + koff;
                 const float a0 = A[o + wm * 64], a1 = A[o + wm * 64 + 32];
                 const float b0 = B[o + wn * 64], b1 = B[o + wn * 64 + 32];
                 acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
@@ -175,17 +135,16 @@ __global__ __launch_bounds__(256) void knn_gram_kernel(const float *__restrict__
             }
         }
     }
-    // C/D map of the 32x32 instructions: column lane & 31, row (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        const int col = J + wn * 64 + j * 32 + (lane & 31);
+        const int col = gt_col(J + wn * 64 + j * 32, lane);
         if (col >= M) continue;
         const double ncol = nx[col];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int row = I + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
+                const int row = gt_row(I + wm * 64 + i * 32, e, lane);
                 if (row >= R) continue;
                 float g = (float)(nq[row] + ncol - 2.0 * dacc[i][j][e]);
                 if (self_r0 >= 0 && self_r0 + row == col) g = INFINITY;      // the pair (i, i): excluded by index
@@ -194,7 +153,7 @@ __global__ __launch_bounds__(256) void knn_gram_kernel(const float *__restrict__
     }
 }
 
-// The exact form of a pair (knn_exact_d2, knn_dist_of) and the row loads: exact_form.h, shared with kmeans.hip.
+// The exact form of a pair (knn_exact_d2, knn_dist_of): exact_form.h, shared with kmeans.hip.
 
 // The rows a workgroup serves: slot s is row s of the panel, or (fallback) entry base + s of the list of uncertified rows.
 struct RowList { const int *rows; const int *count; int base; };
@@ -539,10 +498,8 @@ __global__ __launch_bounds__(256) void knn_sort_certify_kernel(const int *__rest
 }
 
 // ------------------------------------------------------------------------------------------------------- host
-// The filter's error bound per unit of |q - s|^2 + |x - s|^2 (exact_form.h) for slabs of KN_SLAB.
-double filter_bound() { return exact_form_filter_bound(KN_SLAB); }
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+// The filter's error bound per unit of |q - s|^2 + |x - s|^2 (exact_form.h) for the loop's slabs.
+double filter_bound() { return exact_form_filter_bound(GT_SLAB); }
 
 struct KnnPlan {
     int kk, K, fb_rows, rounds;
@@ -555,7 +512,7 @@ const char *knn_plan(long long R, long long M, int F, int k, int slack, int self
 {
     if (R < 1 || M < 1) return "R and M must be >= 1";
     if (R > 0x7fffffffLL || M > 0x7fffffffLL) return "R and M must fit 31 bits";
-    if (((R + KN_T - 1) / KN_T) * ((M + KN_T - 1) / KN_T) > 0x7fffffffLL) return "more than 2^31 tiles in one panel: split R";
+    if (((R + GT - 1) / GT) * ((M + GT - 1) / GT) > 0x7fffffffLL) return "more than 2^31 tiles in one panel: split R";
     if (!wide && (F < 1 || F > DM_KNN_MAX_FEATURES)) return "F outside 1 .. DM_KNN_MAX_FEATURES";
     if (wide && (F < 1 || F > DM_KNN_WIDE_MAX_FEATURES)) return "F outside 1 .. DM_KNN_WIDE_MAX_FEATURES";
     if (wide && M > DM_PCA_WIDE_MAX_SAMPLES) return "more than DM_PCA_WIDE_MAX_SAMPLES rows of X";
@@ -610,22 +567,21 @@ void knn_fallback_rounds(const KnnPlan &p, const float *X, int M, int F, long lo
 
 template <bool V4>
 void knn_launch(const KnnPlan &p, const float *X, int M, int F, long long ldx, const float *Q, int R, long long ldq,
-                int self_r0, int include_self, const float *shift, int *idx, float *dist, int *n_fallback, char *ws,
-                hipStream_t s)
+                int self_r0, int include_self, const float *shift, const float *gram_shift, int *idx, float *dist,
+                int *n_fallback, char *ws, hipStream_t s)
 {
     float *panel = (float *)(ws + p.o_panel);
     double *nx = (double *)(ws + p.o_nx), *nq = (double *)(ws + p.o_nq), *nmax = (double *)(ws + p.o_max);
     int *cand = (int *)(ws + p.o_cand), *list = (int *)(ws + p.o_list);
     double *rej = (double *)(ws + p.o_rej);
-    const float *gram_shift = shift ? shift : (const float *)(ws + p.o_zero);   // (zeros: the caller cleared them)
     const RowList all = {nullptr, nullptr, 0};
 
-    hipLaunchKernelGGL(knn_norms_kernel<V4>, dim3((M + 3) / 4), dim3(256), 0, s, X, (long long)M, F, ldx, shift, nx);
+    hipLaunchKernelGGL(row_norms_kernel<V4>, dim3((M + 3) / 4), dim3(256), 0, s, X, (long long)M, F, ldx, shift, nx);
     if (self_r0 >= 0) nq = nx + self_r0;
-    else hipLaunchKernelGGL(knn_norms_kernel<V4>, dim3((R + 3) / 4), dim3(256), 0, s, Q, (long long)R, F, ldq, shift, nq);
-    hipLaunchKernelGGL(knn_max_kernel, dim3(1), dim3(256), 0, s, (const double *)nx, (long long)M, nmax, n_fallback);
-    const int row_tiles = (R + KN_T - 1) / KN_T;
-    hipLaunchKernelGGL(knn_gram_kernel<V4>, dim3((unsigned)((long long)row_tiles * ((M + KN_T - 1) / KN_T))), dim3(256), 0, s,
+    else hipLaunchKernelGGL(row_norms_kernel<V4>, dim3((R + 3) / 4), dim3(256), 0, s, Q, (long long)R, F, ldq, shift, nq);
+    hipLaunchKernelGGL(norms_max_kernel<256>, dim3(1), dim3(256), 0, s, (const double *)nx, (long long)M, nmax, n_fallback);
+    const int row_tiles = (R + GT - 1) / GT;
+    hipLaunchKernelGGL(knn_gram_kernel<V4>, dim3((unsigned)((long long)row_tiles * ((M + GT - 1) / GT))), dim3(256), 0, s,
                        Q, R, ldq, X, M, ldx, F, gram_shift, (const double *)nq, (const double *)nx, self_r0, panel, p.ldp, row_tiles);
     hipLaunchKernelGGL(knn_select_kernel, dim3(R), dim3(256), 0, s, (const float *)panel, p.ldp, M, p.K, cand, p.K, rej,
                        all);
@@ -637,9 +593,7 @@ void knn_launch(const KnnPlan &p, const float *X, int M, int F, long long ldx, c
 
 // The wide self form: the panel comes from the row Gram matrix, each candidate pair is evaluated
 // once (pair_once) or by knn_refine_kernel on the same lists; the norms, the selection, the certificate and the fallback are
-// dm_knn's.  The filter's operands are dm_pca_rowgram's: the same fl(x - s), the same slab of features.
-static_assert(KN_SLAB == DM_PCA_ROWGRAM_SLAB_FEATURES, "the certificate's slab is the row Gram's");
-
+// dm_knn's.  The filter's operands are dm_pca_rowgram's: the same fl(x - s), the same loop (gram_tile.h).
 template <bool V4>
 void knn_wide_self_launch(const KnnPlan &p, const float *X, int N, int F, long long ldx, const float *shift, const double *K,
                           int include_self, int pair_once, int *idx, float *dist, int *n_fallback, int *n_pairs, char *ws,
@@ -650,8 +604,8 @@ void knn_wide_self_launch(const KnnPlan &p, const float *X, int N, int F, long l
     int *cand = (int *)(ws + p.o_cand), *list = (int *)(ws + p.o_list);
     const RowList all = {nullptr, nullptr, 0};
 
-    hipLaunchKernelGGL(knn_norms_kernel<V4>, dim3((N + 3) / 4), dim3(256), 0, s, X, (long long)N, F, ldx, shift, nx);
-    hipLaunchKernelGGL(knn_max_kernel, dim3(1), dim3(256), 0, s, (const double *)nx, (long long)N, nmax, n_fallback);
+    hipLaunchKernelGGL(row_norms_kernel<V4>, dim3((N + 3) / 4), dim3(256), 0, s, X, (long long)N, F, ldx, shift, nx);
+    hipLaunchKernelGGL(norms_max_kernel<256>, dim3(1), dim3(256), 0, s, (const double *)nx, (long long)N, nmax, n_fallback);
     const dim3 pg((unsigned)((N + 1023) / 1024), (unsigned)N);
     if (N % 2 == 0 && ((uintptr_t)K & 15) == 0)
         hipLaunchKernelGGL(knn_wide_panel_kernel<true>, pg, dim3(256), 0, s, K, N, (const double *)nx, panel, p.ldp);
@@ -704,19 +658,14 @@ int knn_call(const char *who, bool wide, const float *X, int64_t M, int F, int64
                            indices, distances, n_fallback);
         return dm_launch_status(who);
     }
-    if (!shift) {                           // the Gram kernel's loads are unconditional: no shift = a vector of zeros
-        const hipError_t e = hipMemsetAsync((char *)workspace + p.o_zero, 0, (size_t)F * sizeof(float), s);
-        if (e != hipSuccess) {
-            dm_set_error("%s: hipMemsetAsync: %s", who, hipGetErrorString(e));
-            return (int)e;
-        }
-    }
+    const float *gram_shift;
+    if (const int e = shift_or_zeros(who, shift, (char *)workspace + p.o_zero, F, s, &gram_shift)) return e;
     if (vec4_ok(X, ldx, F) && vec4_ok(Q, ldq, F) && ((uintptr_t)shift & 15) == 0)
-        knn_launch<true>(p, X, (int)M, F, ldx, Q, (int)R, ldq, (int)self_r0, include_self ? 1 : 0, shift, indices, distances,
-                         n_fallback, (char *)workspace, s);
+        knn_launch<true>(p, X, (int)M, F, ldx, Q, (int)R, ldq, (int)self_r0, include_self ? 1 : 0, shift, gram_shift, indices,
+                         distances, n_fallback, (char *)workspace, s);
     else
-        knn_launch<false>(p, X, (int)M, F, ldx, Q, (int)R, ldq, (int)self_r0, include_self ? 1 : 0, shift, indices, distances,
-                          n_fallback, (char *)workspace, s);
+        knn_launch<false>(p, X, (int)M, F, ldx, Q, (int)R, ldq, (int)self_r0, include_self ? 1 : 0, shift, gram_shift, indices,
+                          distances, n_fallback, (char *)workspace, s);
     return dm_launch_status(who);
 }
 

@@ -18,6 +18,7 @@
 //   components V = W (X - s) (k x F float64) for W (k x N): the transform turned round, fp32 within slabs of
 //              DM_PCA_COMPONENTS_SLAB_ROWS rows, fp64 across them.
 #include "dm_common.h"
+#include "gram_tile.h"
 
 namespace {
 
@@ -72,44 +73,29 @@ __global__ __launch_bounds__(CS_BLOCK) void colsum_final_kernel(const double *__
 }
 
 // ----------------------------------------------------------------------------------------------- Gram matrix
-constexpr int GT = 128;                 // tile edge: a workgroup computes one 128 x 128 block of G
-constexpr int GCH = 16;                 // rows per LDS stage (8 k-steps of the 32x32x2 instruction)
-constexpr int GLW = GT + 32;            // LDS row stride: the two lane halves of a read (rows k, k+1) land 32 banks apart
-constexpr int GR = DM_PCA_GRAM_SLAB_ROWS;
-static_assert(GR % GCH == 0, "a slab is a whole number of LDS stages");
-constexpr int G_SLOTS = 256;            // workgroups resident at once on a 256-CU part (one per CU: 316 registers per lane)
+constexpr int GR = DM_PCA_GRAM_SLAB_ROWS;   // gram_kernel stages ROWS: its slab is its own (gram_tile.h: the tile, the stage)
+static_assert(GR % GT_CH == 0, "a slab is a whole number of LDS stages");
+constexpr long long RG_DIRECT_PAIRS = 4 * GT_SLOTS; // rowgram: from here on the tile pairs fill the part, no feature split
 
-struct GramPlan { int T; long long pairs; long long nslabs; int S; long long slabs_per; };
+// Tile pairs of an `extent`-wide symmetric matrix, the inner dimension `depth` in slabs of `slab` (gram_tile.h: split_plan).
+struct GramPlan { int T; long long pairs; int S; long long slabs_per; };
 
-// The row split depends on (N, F) only, never on the device, so the summation order -- and the result -- is a function of
-// the data alone.  S is the split whose last wave of workgroups is fullest (ties: the smaller S), capped by the slabs there
-// are and by a 2 GiB workspace.
-GramPlan gram_plan(long long N, int F)
+GramPlan tile_pair_plan(long long extent, long long depth, int slab, long long direct_pairs)
 {
     GramPlan p;
-    p.T = (F + GT - 1) / GT;
+    p.T = (int)((extent + GT - 1) / GT);
     p.pairs = (long long)p.T * (p.T + 1) / 2;
-    p.nslabs = (N + GR - 1) / GR;
-    const long long tile_bytes = (long long)GT * GT * 8;
-    int best = 1;
-    double best_eff = 0.0;
-    for (int s = 1; s <= 64 && s <= p.nslabs; ++s) {
-        if (s > 1 && (long long)s * p.pairs * tile_bytes > (2LL << 30)) break;
-        const long long blocks = (long long)s * p.pairs;
-        const double eff = (double)blocks / (double)(((blocks + G_SLOTS - 1) / G_SLOTS) * G_SLOTS);
-        if (eff > best_eff + 1e-9) { best_eff = eff; best = s; }
-    }
-    p.slabs_per = (p.nslabs + best - 1) / best;
-    p.S = (int)((p.nslabs + p.slabs_per - 1) / p.slabs_per);
+    const SplitPlan sp = split_plan(p.pairs, (depth + slab - 1) / slab, direct_pairs);
+    p.S = sp.S;
+    p.slabs_per = sp.slabs_per;
     return p;
 }
 
-__device__ __forceinline__ void pair_of(int p, int T, int &ti, int &tj)
-{
-    ti = 0;
-    while (p >= T - ti) { p -= T - ti; ++ti; }
-    tj = ti + p;
-}
+// G (F x F): the rows are split.
+GramPlan gram_plan(long long N, int F) { return tile_pair_plan(F, N, GR, 0); }
+// K (N x N): the features are split.  Few tile pairs (N = 2000: 136 for 256 CUs) need the split; RG_DIRECT_PAIRS or more:
+// S = 1, which needs no workspace: the kernel stores its tile into K and rowgram_mirror_kernel completes K.
+GramPlan rowgram_plan(long long N, long long F) { return tile_pair_plan(N, F, GT_SLAB, RG_DIRECT_PAIRS); }
 
 // Four consecutive columns c .. c+3 of row r, centred; zero outside the matrix (never -shift: padding adds nothing).
 template <bool V4>
@@ -150,7 +136,7 @@ __global__ __launch_bounds__(256) void gram_kernel(const float *__restrict__ X, 
                                                    const float *__restrict__ shift, int T, long long slabs_per,
                                                    double *__restrict__ ws)
 {
-    __shared__ __attribute__((aligned(16))) float lds[2][2][GCH * GLW];
+    __shared__ __attribute__((aligned(16))) float lds[2][2][GT_CH * GT_LW];
     int ti, tj;
     pair_of(blockIdx.x, T, ti, tj);
     const int I = ti * GT, J = tj * GT;
@@ -162,11 +148,11 @@ __global__ __launch_bounds__(256) void gram_kernel(const float *__restrict__ X, 
     const long long row_begin = (long long)blockIdx.y * slabs_per * GR;
     long long row_end = row_begin + slabs_per * GR;
     if (row_end > N) row_end = N;
-    const long long nstages = (row_end - row_begin + GCH - 1) / GCH;
+    const long long nstages = (row_end - row_begin + GT_CH - 1) / GT_CH;
 
     f32x4 ra[2], rb[2];
     auto fetch = [&](long long stage) {
-        const long long r = row_begin + stage * GCH + rr;
+        const long long r = row_begin + stage * GT_CH + rr;
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const long long rq = r + 8 * q;
@@ -177,12 +163,11 @@ __global__ __launch_bounds__(256) void gram_kernel(const float *__restrict__ X, 
     auto stash = [&](int buf) {
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
-            *(f32x4 *)&lds[buf][0][(rr + 8 * q) * GLW + c4] = ra[q];
-            *(f32x4 *)&lds[buf][1][(rr + 8 * q) * GLW + c4] = rb[q];
+            *(f32x4 *)&lds[buf][0][(rr + 8 * q) * GT_LW + c4] = ra[q];
+            *(f32x4 *)&lds[buf][1][(rr + 8 * q) * GT_LW + c4] = rb[q];
         }
     };
 
-    typedef float f32x16 __attribute__((ext_vector_type(16)));
     f32x16 acc[2][2];
     double dacc[2][2][16];
 #pragma unroll
@@ -197,15 +182,15 @@ __global__ __launch_bounds__(256) void gram_kernel(const float *__restrict__ X, 
     fetch(0);
     stash(0);
     __syncthreads();
-    constexpr int STAGES_PER_SLAB = GR / GCH;
+    constexpr int STAGES_PER_SLAB = GR / GT_CH;
     for (long long st = 0; st < nstages; ++st) {
         const int buf = (int)(st & 1);
         if (st + 1 < nstages) fetch(st + 1);
         const float *A = lds[buf][0], *B = lds[buf][1];
-        const int koff = (lane >> 5) * GLW + (lane & 31);
+        const int koff = (lane >> 5) * GT_LW + (lane & 31);
 #pragma unroll
-        for (int kk = 0; kk < GCH / 2; ++kk) {
-            const int o = 2 * kk * GLW + koff;
+        for (int kk = 0; kk < GT_CH / 2; ++kk) {
+            const int o = 2 * kk * GT_LW + koff;
             const float a0 = A[o + wm * 64], a1 = A[o + wm * 64 + 32];
             const float b0 = B[o + wn * 64], b1 = B[o + wn * 64 + 32];
             acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
@@ -226,7 +211,6 @@ __global__ __launch_bounds__(256) void gram_kernel(const float *__restrict__ X, 
                 }
         }
     }
-    // C/D map of the 32x32 instructions: column lane & 31, row (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
     double *out = ws + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * (GT * GT);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -234,8 +218,8 @@ __global__ __launch_bounds__(256) void gram_kernel(const float *__restrict__ X, 
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int row = wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-                const int col = wn * 64 + j * 32 + (lane & 31);
+                const int row = gt_row(wm * 64 + i * 32, e, lane);
+                const int col = gt_col(wn * 64 + j * 32, lane);
                 out[row * GT + col] = dacc[i][j][e];
             }
 }
@@ -250,8 +234,7 @@ __global__ __launch_bounds__(256) void gram_reduce_kernel(const double *__restri
     int a = i, b = j;
     if (a / GT > b / GT) { a = j; b = i; }
     const int ta = a / GT, tb = b / GT;
-    const long long p = (long long)ta * T - (long long)ta * (ta - 1) / 2 + (tb - ta);
-    const long long off = p * (GT * GT) + (a % GT) * GT + (b % GT);
+    const long long off = pair_index(ta, tb, T) * (GT * GT) + (a % GT) * GT + (b % GT);
     double v = 0.0;
     for (int s = 0; s < S; ++s) v += ws[(long long)s * pairs * (GT * GT) + off];
     double *g = G + (long long)i * F + j;
@@ -338,8 +321,6 @@ int check_x(const char *who, const float *X, long long N, int F, long long ld)
     return 0;
 }
 
-bool vec4_ok(const float *X, long long ld) { return ld % 4 == 0 && ((uintptr_t)X & 15) == 0; }
-
 template <int KT>
 void launch_transform(bool v4, unsigned gx, hipStream_t s, const float *X, long long N, int F, long long ld,
                       const float *shift, const float *V, int k, float *Y)
@@ -351,47 +332,6 @@ void launch_transform(bool v4, unsigned gx, hipStream_t s, const float *X, long 
 
 // ------------------------------------------------------------------------------- row Gram matrix (sample space)
 // K = (X - s)(X - s)^T for latents wider than DM_PCA_MAX_FEATURES: the N x N side of the matrix the covariance route squares.
-constexpr int RG_CH = 16;                           // features per LDS stage (8 k-steps of the 32x32x2 instruction)
-constexpr int RG_SLAB = DM_PCA_ROWGRAM_SLAB_FEATURES;
-static_assert(RG_SLAB % RG_CH == 0, "a slab is a whole number of LDS stages");
-constexpr long long RG_DIRECT_PAIRS = 4 * G_SLOTS;  // from here on the tile pairs fill the part: no feature split
-
-struct RowgramPlan { int T; long long pairs; long long nslabs; int S; long long slabs_per; };
-
-// The feature split depends on (N, F) only.  Few tile pairs (N = 2000: 136 for 256 CUs): S is the split whose last wave of
-// workgroups is fullest (ties: the smaller S), capped by the slabs there are and by a 2 GiB workspace.  RG_DIRECT_PAIRS tile
-// pairs or more: S = 1.  S = 1 needs no workspace: the kernel stores its tile into K and rowgram_mirror_kernel completes K.
-RowgramPlan rowgram_plan(long long N, long long F)
-{
-    RowgramPlan p;
-    p.T = (int)((N + GT - 1) / GT);
-    p.pairs = (long long)p.T * (p.T + 1) / 2;
-    p.nslabs = (F + RG_SLAB - 1) / RG_SLAB;
-    const long long tile_bytes = (long long)GT * GT * 8;
-    int best = 1;
-    double best_eff = 0.0;
-    for (int s = 1; p.pairs < RG_DIRECT_PAIRS && s <= 64 && s <= p.nslabs; ++s) {
-        if (s > 1 && (long long)s * p.pairs * tile_bytes > (2LL << 30)) break;
-        const long long blocks = (long long)s * p.pairs;
-        const double eff = (double)blocks / (double)(((blocks + G_SLOTS - 1) / G_SLOTS) * G_SLOTS);
-        if (eff > best_eff + 1e-9) { best_eff = eff; best = s; }
-    }
-    p.slabs_per = (p.nslabs + best - 1) / best;
-    p.S = (int)((p.nslabs + p.slabs_per - 1) / p.slabs_per);
-    return p;
-}
-
-// Features f .. f + 3 of a row without a branch, for loads that must not be waited for where they are issued: addresses
-// past F are clamped into the row and the caller discards those elements.  V4: the 16-byte form, F % 4 == 0 and F >= 4.
-template <bool V4>
-__device__ __forceinline__ f32x4 row_load4_clamped(const float *__restrict__ row, int f, int F)
-{
-    if (V4) return *(const f32x4 *)(row + (f < F ? f : F - 4));
-    f32x4 v;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = row[f + e < F ? f + e : F - 1];
-    return v;
-}
 
 // Workgroup (tile pair ti <= tj of the rows, feature range y): knn_gram_kernel's loop with both operands taken from X.
 // 4 waves, wave w owns the 64 x 64 quarter (w >> 1, w & 1) as 2 x 2 accumulators of the 32x32x2 instruction.  A thread stages
@@ -408,7 +348,7 @@ __global__ __launch_bounds__(256) void rowgram_kernel(const float *__restrict__ 
                                                       const float *__restrict__ shift, int T, long long slabs_per,
                                                       double *__restrict__ ws, double *__restrict__ K, int accumulate)
 {
-    __shared__ __attribute__((aligned(16))) float lds[2][2][RG_CH * GLW];
+    __shared__ __attribute__((aligned(16))) float lds[2][2][GT_CH * GT_LW];
     int ti, tj;
     pair_of(blockIdx.x, T, ti, tj);
     const int I = ti * GT, J = tj * GT;
@@ -416,10 +356,10 @@ __global__ __launch_bounds__(256) void rowgram_kernel(const float *__restrict__ 
     const int wm = w >> 1, wn = w & 1;
     const int sr = tid & 63, sf = 4 * (tid >> 6);
 
-    const long long fb = (long long)blockIdx.y * slabs_per * RG_SLAB;
+    const long long fb = (long long)blockIdx.y * slabs_per * GT_SLAB;
     const int f_begin = (int)fb;
-    const int f_end = (int)(fb + slabs_per * RG_SLAB < F ? fb + slabs_per * RG_SLAB : F);
-    const int nstages = (f_end - f_begin + RG_CH - 1) / RG_CH;
+    const int f_end = (int)(fb + slabs_per * GT_SLAB < F ? fb + slabs_per * GT_SLAB : F);
+    const int nstages = (f_end - f_begin + GT_CH - 1) / GT_CH;
 
     const float *arow[2], *brow[2];
 #pragma unroll
@@ -431,7 +371,7 @@ __global__ __launch_bounds__(256) void rowgram_kernel(const float *__restrict__ 
 
     f32x4 ra[2][2], rb[2][2], rs[2];
     auto fetch = [&](int stage, int slot) {
-        const int f = f_begin + (stage < nstages ? stage : nstages - 1) * RG_CH + sf;
+        const int f = f_begin + (stage < nstages ? stage : nstages - 1) * GT_CH + sf;
         rs[slot] = SHIFT ? row_load4_clamped<false>(shift, f, F) : (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
@@ -440,19 +380,18 @@ __global__ __launch_bounds__(256) void rowgram_kernel(const float *__restrict__ 
         }
     };
     auto stash = [&](int stage, int slot, int buf) {
-        const int f = f_begin + stage * RG_CH + sf;
+        const int f = f_begin + stage * GT_CH + sf;
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const f32x4 va = ra[slot][q] - rs[slot], vb = rb[slot][q] - rs[slot];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {       // features past the range: zeros
-                lds[buf][0][(sf + e) * GLW + sr + 64 * q] = f + e < f_end ? va[e] : 0.f;
-                lds[buf][1][(sf + e) * GLW + sr + 64 * q] = f + e < f_end ? vb[e] : 0.f;
+                lds[buf][0][(sf + e) * GT_LW + sr + 64 * q] = f + e < f_end ? va[e] : 0.f;
+                lds[buf][1][(sf + e) * GT_LW + sr + 64 * q] = f + e < f_end ? vb[e] : 0.f;
             }
         }
     };
 
-    typedef float f32x16 __attribute__((ext_vector_type(16)));
     f32x16 acc[2][2];
     double dacc[2][2][16];
 #pragma unroll
@@ -468,7 +407,7 @@ __global__ __launch_bounds__(256) void rowgram_kernel(const float *__restrict__ 
     fetch(1, 1);
     stash(0, 0, 0);
     __syncthreads();
-    constexpr int STAGES_PER_SLAB = RG_SLAB / RG_CH;
+    constexpr int STAGES_PER_SLAB = GT_SLAB / GT_CH;
     for (int st0 = 0; st0 < nstages; st0 += 2) {
 #pragma unroll
         for (int u = 0; u < 2; ++u) {           // stage st lives in register slot u and LDS buffer u
@@ -477,10 +416,10 @@ __global__ __launch_bounds__(256) void rowgram_kernel(const float *__restrict__ 
             fetch(st + 2, u);                   // (slot u went to LDS one stage ago)
             __builtin_amdgcn_sched_barrier(0);  // the loads are issued here, not after the products
             const float *A = lds[u][0], *B = lds[u][1];
-            const int koff = (lane >> 5) * GLW + (lane & 31);
+            const int koff = (lane >> 5) * GT_LW + (lane & 31);
 #pragma unroll
-            for (int kk = 0; kk < RG_CH / 2; ++kk) {
-                const int o = 2 * kk * GLW + koff;
+            for (int kk = 0; kk < GT_CH / 2; ++kk) {
+                const int o = 2 * kk * GT_LW + koff;
                 const float a0 = A[o + wm * 64], a1 = A[o + wm * 64 + 32];
                 const float b0 = B[o + wn * 64], b1 = B[o + wn * 64 + 32];
                 acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
@@ -502,7 +441,6 @@ __global__ __launch_bounds__(256) void rowgram_kernel(const float *__restrict__ 
             }
         }
     }
-    // C/D map of the 32x32 instructions: column lane & 31, row (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
     double *tile = ws ? ws + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * (GT * GT) : nullptr;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -510,8 +448,8 @@ __global__ __launch_bounds__(256) void rowgram_kernel(const float *__restrict__ 
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int row = wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-                const int col = wn * 64 + j * 32 + (lane & 31);
+                const int row = gt_row(wm * 64 + i * 32, e, lane);
+                const int col = gt_col(wn * 64 + j * 32, lane);
                 if (tile) {
                     tile[row * GT + col] = dacc[i][j][e];
                 } else if (I + row <= J + col && J + col < N) {
@@ -530,8 +468,7 @@ __global__ __launch_bounds__(256) void rowgram_reduce_kernel(const double *__res
     if (i >= N || j >= N) return;
     const int a = i < j ? i : j, b = i < j ? j : i;
     const int ta = a / GT, tb = b / GT;
-    const long long p = (long long)ta * T - (long long)ta * (ta - 1) / 2 + (tb - ta);
-    const long long off = p * (GT * GT) + (a % GT) * GT + (b % GT);
+    const long long off = pair_index(ta, tb, T) * (GT * GT) + (a % GT) * GT + (b % GT);
     double v = 0.0;
     for (int s = 0; s < S; ++s) v += ws[(long long)s * pairs * (GT * GT) + off];
     double *k = K + (long long)i * N + j;
@@ -659,7 +596,7 @@ template <bool V4>
 void launch_rowgram(hipStream_t s, const float *X, int N, int F, long long ld, const float *shift, double *K, int accumulate,
                     double *workspace)
 {
-    const RowgramPlan p = rowgram_plan(N, F);
+    const GramPlan p = rowgram_plan(N, F);
     double *ws = p.S > 1 ? workspace : nullptr;
     const dim3 grid((unsigned)p.pairs, p.S), red((unsigned)((N + 63) / 64), (unsigned)((N + 3) / 4));
     if (shift)
@@ -676,7 +613,7 @@ void launch_rowgram(hipStream_t s, const float *X, int N, int F, long long ld, c
 
 int64_t rowgram_ws_bytes(long long N, int F)
 {
-    const RowgramPlan p = rowgram_plan(N, F);
+    const GramPlan p = rowgram_plan(N, F);
     return p.S > 1 ? (int64_t)p.S * p.pairs * GT * GT * (int64_t)sizeof(double) : 0;
 }
 
