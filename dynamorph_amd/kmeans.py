@@ -14,16 +14,13 @@ import torch
 
 from . import knn as _knn
 from . import ops
+from .rows import chunk_size, device_chunks, device_of, shape_of
 from .umap_layout import counter_word
 
 MAX_FEATURES = _knn.MAX_FEATURES
 MAX_CLUSTERS = ops.KMEANS_MAX_CLUSTERS
 DEFAULT_CHUNK_ROWS = 65536
 _VAR_CHUNK_ROWS = 8192
-
-
-def _shape_of(X):
-    return tuple(X.shape) if hasattr(X, "shape") else np.shape(X)
 
 
 def _check_shape(shape, K=None):
@@ -156,7 +153,7 @@ class KMeans:
 
     def fit(self, X):
         K = self.n_clusters
-        N, F = _check_shape(_shape_of(X), K)
+        N, F = _check_shape(shape_of(X), K)
         given = not isinstance(self.init, str)
         if given and self.init.shape[1] != F:
             raise ValueError(f"init has shape {self.init.shape}, expected ({K}, {F})")
@@ -198,12 +195,11 @@ class KMeans:
         not depend on it."""
         self._fitted()
         F, K = self.n_features_in_, self.n_clusters
-        N, Fx = _check_shape(_shape_of(X))
+        N, Fx = _check_shape(shape_of(X))
         if Fx != F:
             raise ValueError(f"X has shape {(N, Fx)}, expected (n, {F})")
-        on_device = torch.is_tensor(X) and X.is_cuda
-        dev = X.device if on_device else _knn._device(X, self.device)
-        cr = max(1, min(int(chunk_rows), N))
+        dev = device_of(X, self.device)
+        cr = chunk_size(chunk_rows, N)
         with torch.no_grad(), torch.cuda.device(dev):
             C = torch.from_numpy(np.ascontiguousarray(self.cluster_centers_, dtype=np.float32)).to(dev)
             if isinstance(shift, str):
@@ -213,38 +209,8 @@ class KMeans:
             ws = ops.kmeans_workspace(cr, F, K, C)
             labels = torch.empty(N, dtype=torch.int32, device=dev)
             counts = []
-            if on_device:
-                x = _knn._resident(X, dev)
-                for lo in range(0, N, cr):
-                    m = min(cr, N - lo)
-                    counts.append(ops.kmeans_assign(x[lo:lo + m], C, s, labels=labels[lo:lo + m], want_dist=False,
-                                                    workspace=ws)[2])
-            else:
-                Xh = X if torch.is_tensor(X) else torch.from_numpy(np.asarray(X))
-                compute = torch.cuda.current_stream()
-                s_in = torch.cuda.Stream()
-                s_in.wait_stream(compute)
-                direct = Xh.dtype == torch.float32 and Xh.is_contiguous() and Xh.is_pinned()
-                stage = None if direct else [torch.empty((cr, F), dtype=torch.float32, pin_memory=True) for _ in range(2)]
-                x_dev = [torch.empty((cr, F), dtype=torch.float32, device=dev) for _ in range(2)]
-                ev_in = [torch.cuda.Event() for _ in range(2)]       # chunk has reached x_dev[b] (staging b is free again)
-                ev_done = [torch.cuda.Event() for _ in range(2)]     # kernels reading x_dev[b] are done
-                for it, lo in enumerate(range(0, N, cr)):
-                    b = it & 1
-                    m = min(cr, N - lo)
-                    src = Xh[lo:lo + m]
-                    if not direct:
-                        ev_in[b].synchronize()
-                        stage[b][:m].copy_(src)
-                        src = stage[b][:m]
-                    with torch.cuda.stream(s_in):
-                        s_in.wait_event(ev_done[b])
-                        x_dev[b][:m].copy_(src, non_blocking=True)
-                        ev_in[b].record(s_in)
-                    compute.wait_event(ev_in[b])
-                    counts.append(ops.kmeans_assign(x_dev[b][:m], C, s, labels=labels[lo:lo + m], want_dist=False,
-                                                    workspace=ws)[2])
-                    ev_done[b].record(compute)
+            for lo, x in device_chunks(X, cr, dev):
+                counts.append(ops.kmeans_assign(x, C, s, labels=labels[lo:lo + x.shape[0]], want_dist=False, workspace=ws)[2])
             out = labels.cpu().numpy()
             return (out, int(torch.cat(counts).sum().item())) if return_rechecked else out
 

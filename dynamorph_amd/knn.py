@@ -13,6 +13,8 @@ import numpy as np
 import torch
 
 from . import ops
+from .pca import column_mean
+from .rows import chunk_size, device_chunks, device_of, host_rows, shape_of
 
 MAX_FEATURES = 16384           # DM_KNN_MAX_FEATURES
 MAX_K = ops.KNN_MAX_K
@@ -22,40 +24,31 @@ WIDE_MAX_ROWS = ops.KNN_WIDE_MAX_ROWS              # DM_PCA_WIDE_MAX_SAMPLES
 WIDE_STAGE_BYTES = 1 << 28                         # a chunk of wide queries is at most this large
 
 
-def _device(X, device):
-    if torch.is_tensor(X) and X.is_cuda:
-        return X.device
-    return torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
-
-
 def _resident(X, device):
     """X as a 2-D fp32 device matrix with unit column stride: a CUDA tensor is used in place, host data move there once."""
-    if torch.is_tensor(X) and X.is_cuda:
-        x = X if X.dtype == torch.float32 else X.float()
-    else:
-        if not torch.is_tensor(X):
-            X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32))
-        x = X.to(_device(X, device), dtype=torch.float32)
-    if x.dim() != 2:
-        raise ValueError(f"knn expects a 2-D (samples, features) array, got shape {tuple(x.shape)}")
+    x = host_rows(X, "knn").to(device_of(X, device), dtype=torch.float32)
     if x.shape[1] > 1 and x.stride(1) != 1:
         x = x.contiguous()
     return x
 
 
-def _check(M, F, k, eligible):
-    if F < 1 or F > MAX_FEATURES:
-        raise ValueError(f"knn on the GPU supports 1 .. {MAX_FEATURES} features, got {F}")
+def _check_k(M, k, eligible):
     if k < 1 or k > MAX_K:
         raise ValueError(f"k = {k} is outside 1 .. {MAX_K}")
     if k > eligible:
         raise ValueError(f"k = {k} exceeds the {eligible} rows a query can have as neighbours (M = {M})")
 
 
+def _check(M, F, k, eligible):
+    if F < 1 or F > MAX_FEATURES:
+        raise ValueError(f"knn on the GPU supports 1 .. {MAX_FEATURES} features, got {F}")
+    _check_k(M, k, eligible)
+
+
 def is_wide(X):
     """More columns than knn_graph / knn_query / PCA take: the wide route, decided from the shape alone, before any device
     call."""
-    shape = tuple(X.shape) if hasattr(X, "shape") else np.shape(X)
+    shape = shape_of(X)
     return len(shape) == 2 and shape[1] > MAX_FEATURES
 
 
@@ -65,26 +58,18 @@ def _check_wide(M, F, k, eligible):
     if M > WIDE_MAX_ROWS:
         raise ValueError(f"wide knn of {M} rows of {F} features: more than {MAX_FEATURES} features need all rows resident "
                          f"(and, for the graph, their {M} x {M} float64 Gram matrix) and support up to {WIDE_MAX_ROWS} rows")
-    if k < 1 or k > MAX_K:
-        raise ValueError(f"k = {k} is outside 1 .. {MAX_K}")
-    if k > eligible:
-        raise ValueError(f"k = {k} exceeds the {eligible} rows a query can have as neighbours (M = {M})")
+    _check_k(M, k, eligible)
 
 
 def column_shift(x):
-    """fp32 column mean of a device matrix (dm_pca_colsum: float64 sums in a fixed order)."""
-    return (ops.pca_colsum(x) / x.shape[0]).float()
-
-
-def wide_column_shift(x):
-    """column_shift for any width: dm_pca_colsum per block of MAX_FEATURES columns, as WidePCA.gram forms its shift."""
-    from .pca import column_mean
+    """fp32 column mean of a device matrix of any width (dm_pca_colsum per block of pca.MAX_FEATURES columns: float64 sums
+    in a fixed order), as WidePCA.gram forms its shift."""
     return column_mean(x).float()
 
 
 def _panel_state(x, R, k, cr, slack, shift, wide=False):
     """What every panel of a call shares: the shift, the slack, one workspace for panels of cr rows, the outputs."""
-    s = (wide_column_shift if wide else column_shift)(x) if isinstance(shift, str) else shift
+    s = column_shift(x) if isinstance(shift, str) else shift
     sl = ops.KNN_DEFAULT_SLACK if slack is None else int(slack)
     if wide:
         nbytes = ops.L.load().dm_knn_wide_workspace_bytes(cr, x.shape[0], x.shape[1], k, sl)
@@ -143,52 +128,18 @@ def _query(X, Q, k, chunk_rows, device, slack, shift, return_fallback, wide):
     k = int(k)
     (_check_wide if wide else _check)(M, F, k, M)
     call = ops.knn_wide if wide else ops.knn
-    on_device = torch.is_tensor(Q) and Q.is_cuda
-    if not torch.is_tensor(Q):
-        Q = torch.from_numpy(np.asarray(Q))
-    if Q.dim() != 2 or Q.shape[1] != F:
-        raise ValueError(f"Q has shape {tuple(Q.shape)}, expected (n, {F})")
-    R = Q.shape[0]
+    shape = shape_of(Q)
+    if len(shape) != 2 or shape[1] != F:
+        raise ValueError(f"Q has shape {shape}, expected (n, {F})")
+    R = shape[0]
     if R < 1:
         raise ValueError("Q has no rows")
-    cr = max(1, min(int(chunk_rows), R))
-    if wide:
-        cr = max(1, min(cr, WIDE_STAGE_BYTES // (4 * F)))
+    cr = chunk_size(chunk_rows, R, F, WIDE_STAGE_BYTES if wide else None)
     with torch.no_grad(), torch.cuda.device(x.device):
         s, sl, ws, idx, dist, counts = _panel_state(x, R, k, cr, slack, shift, wide)
-        if on_device:
-            q = Q if Q.dtype == torch.float32 else Q.float()
-            if F > 1 and q.stride(1) != 1:
-                q = q.contiguous()
-            for lo in range(0, R, cr):
-                m = min(cr, R - lo)
-                counts.append(call(x, q[lo:lo + m], k=k, shift=s, slack=sl, out=(idx[lo:lo + m], dist[lo:lo + m]),
-                                   workspace=ws)[2])
-        else:
-            compute = torch.cuda.current_stream()
-            s_in = torch.cuda.Stream()
-            s_in.wait_stream(compute)
-            direct = Q.dtype == torch.float32 and Q.is_contiguous() and Q.is_pinned()
-            stage = None if direct else [torch.empty((cr, F), dtype=torch.float32, pin_memory=True) for _ in range(2)]
-            q_dev = [torch.empty((cr, F), dtype=torch.float32, device=x.device) for _ in range(2)]
-            ev_in = [torch.cuda.Event() for _ in range(2)]       # chunk has reached q_dev[b] (staging b is free again)
-            ev_done = [torch.cuda.Event() for _ in range(2)]     # kernels reading q_dev[b] are done
-            for it, lo in enumerate(range(0, R, cr)):
-                b = it & 1
-                m = min(cr, R - lo)
-                src = Q[lo:lo + m]
-                if not direct:
-                    ev_in[b].synchronize()
-                    stage[b][:m].copy_(src)
-                    src = stage[b][:m]
-                with torch.cuda.stream(s_in):
-                    s_in.wait_event(ev_done[b])
-                    q_dev[b][:m].copy_(src, non_blocking=True)
-                    ev_in[b].record(s_in)
-                compute.wait_event(ev_in[b])
-                counts.append(call(x, q_dev[b][:m], k=k, shift=s, slack=sl, out=(idx[lo:lo + m], dist[lo:lo + m]),
-                                   workspace=ws)[2])
-                ev_done[b].record(compute)
+        for lo, q in device_chunks(Q, cr, x.device):
+            m = q.shape[0]
+            counts.append(call(x, q, k=k, shift=s, slack=sl, out=(idx[lo:lo + m], dist[lo:lo + m]), workspace=ws)[2])
         return _result(idx, dist, counts, return_fallback)
 
 
@@ -233,7 +184,7 @@ def wide_knn_graph(X, k, include_self=True, device=None, slack=None, shift="mean
     with torch.no_grad(), torch.cuda.device(x.device):
         _check_wide_memory(x.device, N, F, k, sl, gram is not None)
         if gram is None:
-            s = wide_column_shift(x) if isinstance(shift, str) else shift
+            s = column_shift(x) if isinstance(shift, str) else shift
             K = ops.pca_rowgram(x, s)
         idx, dist, nfb, npairs = ops.knn_wide_self(x, K, k=k, shift=s, slack=sl, include_self=include_self,
                                                    pair_once=pair_once)

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .rows import device_chunks, device_of, host_rows
 
 MAX_FEATURES = 16384           # DM_PCA_MAX_FEATURES
 MAX_COMPONENTS = 512           # DM_PCA_MAX_COMPONENTS (one transform launch; more are done in blocks of this many)
@@ -54,17 +55,22 @@ def _check_shape(N, F):
                          f"covariance alone is 34 GB)")
 
 
+def _int_components(n_components, N, F):
+    """An integer n_components as it is: at most min(N, F)."""
+    m = min(N, F)
+    if n_components > m:
+        raise ValueError(f"n_components={n_components} must be between 0 and min(n_samples, n_features)={m}")
+    return int(n_components)
+
+
 def select_n_components(n_components, ratio, N, F):
     """_fit_full's rule: a fraction -> searchsorted(cumsum(ratio), frac, side='right') + 1; an int as it is (<= min(N, F));
     None -> min(N, F).  `ratio`: explained_variance_ratio_ of all components, float64 numpy."""
     _check_n_components(n_components)
-    m = min(N, F)
     if n_components is None:
-        return m
+        return min(N, F)
     if isinstance(n_components, (int, np.integer)):
-        if n_components > m:
-            raise ValueError(f"n_components={n_components} must be between 0 and min(n_samples, n_features)={m}")
-        return int(n_components)
+        return _int_components(n_components, N, F)
     cum = np.cumsum(np.asarray(ratio, dtype=np.float64))
     return int(np.searchsorted(cum, float(n_components), side="right") + 1)
 
@@ -97,11 +103,8 @@ def _leading_pairs(M, n_components, N, F, eigensolver):
     if eigensolver != "partial" or n_components is None or M.shape[0] <= 2 * EIG_BLOCK:
         return None
     from . import eig
-    m = min(N, F)
     if isinstance(n_components, (int, np.integer)):
-        if n_components > m:
-            raise ValueError(f"n_components={n_components} must be between 0 and min(n_samples, n_features)={m}")
-        want = {"k": int(n_components)}
+        want = {"k": _int_components(n_components, N, F)}
     else:
         want = {"fraction": float(n_components)}
     trace = float(torch.diagonal(M).sum(dtype=torch.float64))
@@ -112,26 +115,63 @@ def _leading_pairs(M, n_components, N, F, eigensolver):
     return theta.clamp_min(0.0), V, trace, info
 
 
-def _partial_attrs(theta, trace, N, F):
-    """The attributes the partial route fills from theta (numpy, clipped) and the trace."""
-    k, m = theta.shape[0], min(N, F)
-    ev = theta / (N - 1)
+def _eigenpairs(M, n_components, N, F, eigensolver):
+    """(lam descending clipped at 0, V (order, len(lam)), trace, info) of the symmetric float64 matrix M: the partial route's
+    leading pairs (_leading_pairs), or from eigh the top min(N, F) pairs -- the spectrum of the full SVD that _fit_full's
+    'full' solver computes -- with trace None."""
+    part = _leading_pairs(M, n_components, N, F, eigensolver)
+    if part is not None:
+        return part
+    evals, evecs = torch.linalg.eigh(M)
+    m = min(N, F)
+    return torch.flip(evals, (0,))[:m].clamp_min(0.0), torch.flip(evecs, (1,))[:, :m], None, None
+
+
+def _attrs(ev, ratio, singular, noise, N, F, route, info=None):
+    """The fitted attributes that need no eigenvector, of the ev.shape[0] components kept."""
     return {
-        "explained_variance_": ev.copy(),
-        "explained_variance_ratio_": theta / trace if trace > 0 else np.zeros_like(theta),
-        "singular_values_": np.sqrt(theta),
-        "noise_variance_": max(float(trace - theta.sum()), 0.0) / (N - 1) / (m - k) if k < m else 0.0,
-        "n_components_": int(k),
+        "explained_variance_": ev,
+        "explained_variance_ratio_": ratio,
+        "singular_values_": singular,
+        "noise_variance_": noise,
+        "n_components_": int(ev.shape[0]),
         "n_samples_": int(N),
         "n_features_in_": int(F),
+        "eigensolver_": route,
+        "eig_info_": info,
     }
+
+
+def _full_attrs(ev, n_components, N, F):
+    """The full route: from the explained variances of all min(N, F) components (numpy), by scikit-learn's expressions."""
+    ratio = ev / ev.sum() if ev.sum() > 0 else np.zeros_like(ev)
+    k = select_n_components(n_components, ratio, N, F)
+    noise = float(ev[k:].mean()) if k < min(N, F) else 0.0
+    return _attrs(ev[:k].copy(), ratio[:k].copy(), np.sqrt(ev[:k] * (N - 1)), noise, N, F, "full")
+
+
+def _partial_attrs(theta, trace, N, F, info):
+    """The partial route: from the leading eigenvalues theta (numpy, clipped) and the trace, which stands in for the rest."""
+    k, m = theta.shape[0], min(N, F)
+    noise = max(float(trace - theta.sum()), 0.0) / (N - 1) / (m - k) if k < m else 0.0
+    return _attrs(theta / (N - 1), theta / trace if trace > 0 else np.zeros_like(theta), np.sqrt(theta), noise, N, F,
+                  "partial", info)
+
+
+def _svd_flip(V):
+    """svd_flip(u_based_decision=False) on the rows of V: the entry of largest magnitude of each row becomes positive.  In
+    place; returns V."""
+    idx = V.abs().argmax(dim=1)
+    signs = torch.sign(V.gather(1, idx[:, None]))
+    signs[signs == 0] = 1.0
+    V *= signs
+    return V
 
 
 def finalize(C, mean, N, n_components=0.5, eigensolver="full"):
     """From the float64 scatter matrix C = sum (x - mean)(x - mean)^T (F x F, any device) to scikit-learn's fitted attributes
     (a dict of float64 numpy arrays and ints).  eigh in float64 on C's device; eigenvalues clipped at 0; the top min(N, F)
-    eigenpairs are kept (the spectrum of the full SVD _fit_full's 'full' solver computes); signs by
-    svd_flip(u_based_decision=False): the entry of largest magnitude of each component is positive.
+    eigenpairs are kept (_eigenpairs); signs by _svd_flip.
 
     eigensolver="partial": only the leading pairs, from eig.top_eigenpairs (_leading_pairs); ratios against the trace and
     the noise variance from the trace's remainder.  "eigensolver_" names the route taken, "eig_info_" the solver's record."""
@@ -141,39 +181,14 @@ def finalize(C, mean, N, n_components=0.5, eigensolver="full"):
     _check_eigensolver(eigensolver)
     C = C.to(torch.float64)
     mean = mean.to(torch.float64).cpu().numpy() if torch.is_tensor(mean) else np.asarray(mean, np.float64)
-    part = _leading_pairs(C, n_components, N, F, eigensolver)
-    if part is not None:
-        theta, V, trace, info = part
-        comps = V.T.contiguous()
+    lam, V, trace, info = _eigenpairs(C, n_components, N, F, eigensolver)
+    if trace is None:
+        attrs = _full_attrs((lam / (N - 1)).cpu().numpy(), n_components, N, F)
     else:
-        evals, evecs = torch.linalg.eigh(C)
-        m = min(N, F)
-        evals = torch.flip(evals, (0,))[:m].clamp_min(0.0)
-        comps = torch.flip(evecs, (1,))[:, :m].T.contiguous()             # (m, F): rows are components
-    idx = comps.abs().argmax(dim=1)
-    signs = torch.sign(comps.gather(1, idx[:, None]))
-    signs[signs == 0] = 1.0
-    comps *= signs
-    if part is not None:
-        attrs = _partial_attrs(theta.cpu().numpy(), trace, N, F)
-        attrs.update(mean_=mean, components_=comps.cpu().numpy(), eigensolver_="partial", eig_info_=info)
-        return attrs
-    ev = (evals / (N - 1)).cpu().numpy()
-    ratio = ev / ev.sum() if ev.sum() > 0 else np.zeros_like(ev)
-    k = select_n_components(n_components, ratio, N, F)
-    return {
-        "mean_": mean,
-        "components_": comps[:k].cpu().numpy(),
-        "explained_variance_": ev[:k].copy(),
-        "explained_variance_ratio_": ratio[:k].copy(),
-        "singular_values_": np.sqrt(ev[:k] * (N - 1)),
-        "noise_variance_": float(ev[k:].mean()) if k < m else 0.0,
-        "n_components_": int(k),
-        "n_samples_": int(N),
-        "n_features_in_": int(F),
-        "eigensolver_": "full",
-        "eig_info_": None,
-    }
+        attrs = _partial_attrs(lam.cpu().numpy(), trace, N, F, info)
+    comps = _svd_flip(V.T.contiguous())                                   # rows are components
+    attrs.update(mean_=mean, components_=comps[:attrs["n_components_"]].cpu().numpy())
+    return attrs
 
 
 def _check_wide_shape(N, F):
@@ -211,70 +226,30 @@ def finalize_samples(K, N, F, n_components=0.5, eigensolver="full"):
     K -= rm[:, None]
     K -= cm[None, :]
     K += gm
-    part = _leading_pairs(K, n_components, N, F, eigensolver)
-    if part is not None:
-        theta, V, trace, info = part
-        lam = theta.cpu().numpy()
-        k = lam.shape[0]
-        rank = int((lam > N * 2.0 ** -52 * lam[0]).sum())
-        if k > rank:
-            raise ValueError(f"n_components={n_components!r} asks for {k} components of {N} samples, but at most {rank} "
-                             f"components are defined (the others have zero variance: centred data have rank <= n_samples - 1)")
-        attrs = _partial_attrs(lam, trace, N, F)
-        attrs.update(W=(V / theta.sqrt()).T.contiguous(), eigensolver_="partial", eig_info_=info)
-        return attrs
-    evals, evecs = torch.linalg.eigh(K)
-    m = min(N, F)
-    evals = torch.flip(evals, (0,))[:m].clamp_min(0.0)
-    lam = evals.cpu().numpy()
-    ev = lam / (N - 1)
-    ratio = ev / ev.sum() if ev.sum() > 0 else np.zeros_like(ev)
-    k = select_n_components(n_components, ratio, N, F)
-    rank = int((lam > N * 2.0 ** -52 * lam[0]).sum())
+    lam, V, trace, info = _eigenpairs(K, n_components, N, F, eigensolver)
+    lam_h = lam.cpu().numpy()
+    attrs = _full_attrs(lam_h / (N - 1), n_components, N, F) if trace is None else _partial_attrs(lam_h, trace, N, F, info)
+    k = attrs["n_components_"]
+    rank = int((lam_h > N * 2.0 ** -52 * lam_h[0]).sum())
     if k > rank:
         raise ValueError(f"n_components={n_components!r} asks for {k} components of {N} samples, but at most {rank} "
                          f"components are defined (the others have zero variance: centred data have rank <= n_samples - 1)")
-    W = (torch.flip(evecs, (1,))[:, :k] / evals[:k].sqrt()).T.contiguous()
-    return {
-        "W": W,
-        "explained_variance_": ev[:k].copy(),
-        "explained_variance_ratio_": ratio[:k].copy(),
-        "singular_values_": np.sqrt(ev[:k] * (N - 1)),
-        "noise_variance_": float(ev[k:].mean()) if k < m else 0.0,
-        "n_components_": int(k),
-        "n_samples_": int(N),
-        "n_features_in_": int(F),
-        "eigensolver_": "full",
-        "eig_info_": None,
-    }
+    attrs["W"] = (V[:, :k] / lam[:k].sqrt()).T.contiguous()
+    return attrs
 
 
 def orient_components(V):
-    """Rows of V (k x F float64 tensor) scaled to unit length and signed by svd_flip(u_based_decision=False), as finalize
-    signs them: the entry of largest magnitude of each component is positive.  In place; returns V."""
+    """Rows of V (k x F float64 tensor) scaled to unit length and signed by _svd_flip, as finalize signs them.  In place;
+    returns V."""
     V /= torch.linalg.vector_norm(V, dim=1, keepdim=True)
-    idx = V.abs().argmax(dim=1)
-    signs = torch.sign(V.gather(1, idx[:, None]))
-    signs[signs == 0] = 1.0
-    V *= signs
-    return V
+    return _svd_flip(V)
 
 
 def column_mean(x):
     """float64 column mean (F,) of a resident fp32 matrix of any width: dm_pca_colsum per block of MAX_FEATURES columns."""
     N, F = x.shape
-    return torch.cat([ops.pca_colsum(x[:, lo:min(lo + MAX_FEATURES, F)]) for lo in range(0, F, MAX_FEATURES)]) / N
-
-
-def _host_rows(X):
-    """Host data as a 2-D torch tensor (a view when it can be)."""
-    if isinstance(X, np.ndarray):
-        X = torch.from_numpy(X if X.dtype in (np.float32, np.float64) else X.astype(np.float32))
-    elif not torch.is_tensor(X):
-        X = torch.as_tensor(np.asarray(X, dtype=np.float32))
-    if X.dim() != 2:
-        raise ValueError(f"PCA expects a 2-D (samples, features) array, got shape {tuple(X.shape)}")
-    return X
+    sums = [ops.pca_colsum(x[:, lo:min(lo + MAX_FEATURES, F)]) for lo in range(0, F, MAX_FEATURES)]
+    return (sums[0] if len(sums) == 1 else torch.cat(sums)) / N
 
 
 class PCA:
@@ -304,11 +279,6 @@ class PCA:
         self._dev = {}
 
     # ------------------------------------------------------------------------------------------------------ fitting
-    def _device_of(self, X):
-        if torch.is_tensor(X) and X.is_cuda:
-            return X.device
-        return torch.device(self.device if self.device is not None else "cuda:%d" % torch.cuda.current_device())
-
     def moments(self, X, chunk_rows=None):
         """(N, mean (F,) float64, C (F, F) float64 = sum (x - mean)(x - mean)^T) on the device."""
         if torch.is_tensor(X) and X.is_cuda:
@@ -318,7 +288,7 @@ class PCA:
             _check_shape(N, F)
             with torch.cuda.device(X.device):
                 return (N,) + self._chunk_moments(X)
-        X = _host_rows(X)
+        X = host_rows(X)
         N, F = X.shape
         _check_shape(N, F)
         return self._stream_moments(X, int(chunk_rows or self.chunk_rows))
@@ -337,43 +307,24 @@ class PCA:
 
     def _stream_moments(self, X, chunk_rows):
         N, F = X.shape
-        dev = self._device_of(X)
+        dev = device_of(X, self.device)
         cr = max(2, min(chunk_rows, N))
         with torch.no_grad(), torch.cuda.device(dev):
-            compute = torch.cuda.current_stream()
-            s_in = torch.cuda.Stream()
-            direct = X.dtype == torch.float32 and X.is_contiguous() and X.is_pinned()
-            stage = None if direct else [torch.empty((cr, F), dtype=torch.float32, pin_memory=True) for _ in range(2)]
-            x_dev = [torch.empty((cr, F), dtype=torch.float32, device=dev) for _ in range(2)]
-            ev_in = [torch.cuda.Event() for _ in range(2)]       # chunk has reached x_dev[k] (staging k is free again)
-            ev_done = [torch.cuda.Event() for _ in range(2)]     # kernels reading x_dev[k] are done
             ws = torch.empty(max(ops.L.load().dm_pca_gram_workspace_bytes(cr, F), 8) // 8, dtype=torch.float64, device=dev)
             C = torch.zeros((F, F), dtype=torch.float64, device=dev)
             n, mean = 0, None
-            for it, lo in enumerate(range(0, N, cr)):
-                k = it & 1
-                m = min(cr, N - lo)
-                src = X[lo:lo + m]
-                if not direct:
-                    ev_in[k].synchronize()
-                    stage[k][:m].copy_(src)
-                    src = stage[k][:m]
-                with torch.cuda.stream(s_in):
-                    s_in.wait_event(ev_done[k])
-                    x_dev[k][:m].copy_(src, non_blocking=True)
-                    ev_in[k].record(s_in)
-                compute.wait_event(ev_in[k])
-                mean_c, _ = self._chunk_moments(x_dev[k][:m], G=C, accumulate=True, ws=ws)
+            for _, x in device_chunks(X, cr, dev):
+                m = x.shape[0]
+                mean_c, _ = self._chunk_moments(x, G=C, accumulate=True, ws=ws)
                 n, mean = merge_moments(n, mean, C, m, mean_c) if mean is not None else (m, mean_c)
-                ev_done[k].record(compute)
-            compute.synchronize()
+            torch.cuda.current_stream().synchronize()
         return n, mean, C
 
     def fit(self, X, chunk_rows=None):
         N, mean, C = self.moments(X, chunk_rows)
         if self.eigh_device == "cpu":
             C = C.cpu()
-        self._set(finalize(C, mean, N, self.n_components, self.eigensolver), self._device_of(X))
+        self._set(finalize(C, mean, N, self.n_components, self.eigensolver), device_of(X, self.device))
         return self
 
     def fit_transform(self, X, chunk_rows=None):
@@ -406,8 +357,8 @@ class PCA:
         if torch.is_tensor(X) and X.is_cuda:
             x = X if X.dtype == torch.float32 else X.float()
         else:
-            x = _host_rows(X)
-            dev = self._home if getattr(self, "_home", None) is not None else self._device_of(x)
+            x = host_rows(X)
+            dev = self._home if getattr(self, "_home", None) is not None else device_of(x, self.device)
             x = x.to(dev, dtype=torch.float32)
         if x.dim() != 2 or x.shape[1] != self.n_features_in_:
             raise ValueError(f"X has shape {tuple(x.shape)}, expected (n, {self.n_features_in_})")
@@ -491,10 +442,10 @@ class WidePCA(PCA):
             _check_wide_shape(*X.shape)
             self._check_memory(X.device, X.shape[0], X.shape[1], resident=True, eigensolver=self.eigensolver)
             return X if X.dtype == torch.float32 else X.float()
-        X = _host_rows(X)
+        X = host_rows(X)
         N, F = X.shape
         _check_wide_shape(N, F)
-        dev = self._device_of(X)
+        dev = device_of(X, self.device)
         self._check_memory(dev, N, F, resident=False, eigensolver=self.eigensolver)
         with torch.no_grad(), torch.cuda.device(dev):
             x = torch.empty((N, F), dtype=torch.float32, device=dev)

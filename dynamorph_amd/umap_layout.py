@@ -19,6 +19,7 @@ import torch
 
 from . import knn as _knn
 from . import ops
+from .rows import device_of, shape_of
 
 MAX_K = ops.UMAP_MAX_K
 _M64 = (1 << 64) - 1
@@ -202,15 +203,11 @@ pca_init = pca_coordinates      # init="pca"
 
 
 # ---------------------------------------------------------------------------------------------------------- the device
-def _device(device):
-    return torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
-
-
 def fuzzy_graph(knn_indices, knn_dists, device=None):
     """The fuzzy simplicial set of a k-NN graph as fit_knn / knn_graph(include_self=True) return it: (indptr int64, indices
     int32, data float32, rho float32, sigma float32) on the device."""
     idx, dist = check_graph(knn_indices, knn_dists)
-    dev = knn_dists.device if torch.is_tensor(knn_dists) and knn_dists.is_cuda else _device(device)
+    dev = device_of(knn_dists, device)
     with torch.no_grad(), torch.cuda.device(dev):
         i32 = torch.from_numpy(idx.astype(np.int32)).to(dev)
         d = torch.from_numpy(dist).to(dev)
@@ -297,7 +294,7 @@ class UMAPEmbedding:
             raise ValueError("fit_graph has no data to compute init='pca' from: pass init=pca_coordinates(X) or use fit_transform")
         y0 = _check_init(init, N)
         n_epochs = default_n_epochs(N) if self.n_epochs is None else self.n_epochs
-        dev = _device(self.device)
+        dev = device_of(None, self.device)
         with torch.no_grad(), torch.cuda.device(dev):
             indptr, cols, w, rho, sigma = fuzzy_graph(idx, dist, device=dev)
             self._graph = (indptr.cpu().numpy(), cols.cpu().numpy(), w.cpu().numpy(), N)
@@ -352,7 +349,7 @@ class UMAPEmbedding:
         M = self._fitted(need_data=False)
         idx, dist = check_query_graph(knn_indices, knn_dists, M)
         n_epochs, seed, row_offset = self._transform_args(n_epochs, seed, row_offset)
-        dev = _device(self.device)
+        dev = device_of(None, self.device)
         with torch.no_grad(), torch.cuda.device(dev):
             y, sigma, y0 = self._place(idx, dist, torch.from_numpy(self.embedding_).to(dev), n_epochs, seed, row_offset)
             self.sigma_t_, self.init_t_ = sigma.cpu().numpy(), y0.cpu().numpy()
@@ -365,7 +362,7 @@ class UMAPEmbedding:
         model alone: not on chunk_rows and not on the other rows."""
         M = self._fitted(need_data=True)
         F = self._X.shape[1]
-        shape = tuple(Q.shape) if hasattr(Q, "shape") else np.shape(Q)
+        shape = shape_of(Q)
         if len(shape) != 2 or shape[1] != F:
             raise ValueError(f"Q has shape {shape}, expected (n, {F})")
         if shape[0] < 1:
@@ -381,7 +378,7 @@ class UMAPEmbedding:
         x = self._X = _knn._resident(self._X, self.device)
         wide = F > _knn.MAX_FEATURES
         with torch.no_grad(), torch.cuda.device(x.device):
-            shift = _knn.wide_column_shift(x) if wide else _knn.column_shift(x)
+            shift = _knn.column_shift(x)
             y_train = torch.from_numpy(self.embedding_).to(x.device)
             ys, sigmas, inits = [], [], []
             for lo in range(0, shape[0], cr):
