@@ -214,6 +214,8 @@ SIGNATURES = {
     "dm_knn_wide_self_workspace_bytes": (i64, [i64, C.c_int, C.c_int, C.c_int]),
     "dm_knn_wide_self": (C.c_int, [vp, i64, C.c_int, i64, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, i64,
                                    vp]),
+    "dm_knn_ranks_workspace_bytes": (i64, [i64, i64, C.c_int, C.c_int, i64]),
+    "dm_knn_ranks": (C.c_int, [vp, i64, C.c_int, i64, i64, i64, vp, C.c_int, vp, i64, vp, vp, vp, vp, i64, vp]),
     "dm_kmeans_workspace_bytes": (i64, [i64, C.c_int, C.c_int]),
     "dm_kmeans_assign": (C.c_int, [vp, i64, C.c_int, i64, vp, C.c_int, vp, vp, vp, vp, vp, i64, vp]),
     "dm_kmeans_sums": (C.c_int, [vp, i64, C.c_int, i64, vp, C.c_int, vp, vp, vp, i64, vp]),

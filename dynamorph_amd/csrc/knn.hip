@@ -748,3 +748,346 @@ extern "C" int dm_knn_wide_self(const float *X, int64_t N, int F, int64_t ldx, c
                                     n_fallback, n_pairs, (char *)workspace, s);
     return dm_launch_status("dm_knn_wide_self");
 }
+
+// ============================================================================== ranks of given targets
+// The rank of target j for row i of X: 1 + #{ l != i : (d(i, l), l) < (d(i, j), j) }, d the exact-form fp32 distance above
+// (0 for j == i).  Per panel of R rows: the norms, the Gram panel and the fallback panel are the graph's kernels; here
+//   thresholds  the exact-form sums D of the row's c targets (a wave per pair), sorted by (D, index) with the permutation;
+//   count       one workgroup per panel row, the row read ONCE: a panel value g is placed among the sorted D by binary search
+//               in LDS with the filter's bound A on BOTH sides.  Certain against every threshold: one of c + 1 integer LDS
+//               bins.  Ambiguous against any: its column goes onto the row's list (cap entries); a list that overflows
+//               sends the row onto the fallback list;
+//   resolve     the listed columns' exact-form distances, each once, compared by (distance, index) with every threshold;
+//               rank = 1 + prefix sum of the bins + those comparisons, written in the caller's target order;
+//   fallback    listed rows, KN_FB_ROWS at a time: knn_exact_panel_kernel, then the same count by plain comparison.
+// Integer atomics only (a sum of ones does not depend on the order); no value depends on the launch shape, cap or the path.
+namespace {
+
+constexpr int KR_MAX_C = DM_KNN_MAX_K;
+constexpr double KR_RHO = 0x1p-21, KR_STEP = 0x1p-20;
+
+template <bool V4>
+__global__ __launch_bounds__(256) void rank_thresholds_kernel(const float *__restrict__ X, int M, long long ldx, int F, int self_r0,
+                                                              const int *__restrict__ targets, int c, double *__restrict__ tD,
+                                                              float *__restrict__ td, int *__restrict__ tj, int *__restrict__ tp)
+{
+    __shared__ double s_D[KR_MAX_C];
+    __shared__ int s_j[KR_MAX_C], s_p[KR_MAX_C];
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int me = self_r0 + row;
+    const int P = knn_sort_size(c);
+    const float *__restrict__ q = X + (long long)me * ldx;
+    for (int t = w; t < P; t += 4) {
+        double D = INFINITY;                    // padding, the row itself (rank 0) and a target outside X: above everything
+        int j = 0x7fffffff;
+        if (t < c) {
+            j = targets[(long long)row * c + t];
+            if (j >= 0 && j < M && j != me) D = knn_exact_d2<V4>(q, X + (long long)j * ldx, F, lane);
+        }
+        if (lane == 0) { s_D[t] = D; s_j[t] = j; s_p[t] = t; }
+    }
+    __syncthreads();
+    // (D, index, position) is a total order: repeated targets stay apart, and the result does not depend on the sort's path
+    for (int size = 2; size <= P; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            const int pos = 2 * tid - (tid & (stride - 1));
+            if (pos + stride < P) {
+                const bool up = (pos & size) == 0;
+                const double Da = s_D[pos], Db = s_D[pos + stride];
+                const int ja = s_j[pos], jb = s_j[pos + stride], pa = s_p[pos], pb = s_p[pos + stride];
+                const bool b_less = Db < Da || (Db == Da && (jb < ja || (jb == ja && pb < pa)));
+                if (b_less == up) {
+                    s_D[pos] = Db; s_j[pos] = jb; s_p[pos] = pb;
+                    s_D[pos + stride] = Da; s_j[pos + stride] = ja; s_p[pos + stride] = pa;
+                }
+            }
+            __syncthreads();
+        }
+    for (int t = tid; t < c; t += 256) {
+        const long long o = (long long)row * c + t;
+        tD[o] = s_D[t];
+        td[o] = knn_dist_of(s_D[t]);
+        tj[o] = s_j[t];
+        tp[o] = s_p[t];
+    }
+}
+
+// One workgroup per panel row.  lo = (g + A)(1 + rho)(1 + 2^-20) and hi = (g - A)(1 - rho): D_l lies in [hi, lo / (1 + 2^-20)]
+// (DESIGN.md 3.5i), so l is certainly below threshold t when lo < D_t and certainly above it when hi > D_t (1 + 2^-20) = E_t.
+// p = #{t : D_t <= lo}: l is certainly below the thresholds p .. c - 1, and certain against all of them when E_{p-1} < hi.
+// Most of a row lies above every threshold: those are counted in a register and added once.  The next two 16-byte steps of
+// the row are requested before the current two are searched.
+__global__ __launch_bounds__(256) void rank_count_kernel(const float *__restrict__ panel, long long ldp, int M, int self_r0,
+                                                         const double *__restrict__ tD, int c, const double *__restrict__ nq,
+                                                         const double *__restrict__ nxmax, double cbound, int cap,
+                                                         int *__restrict__ hist, int *__restrict__ namb, int *__restrict__ amb,
+                                                         int *__restrict__ fail_list, int *__restrict__ n_fail)
+{
+    __shared__ double s_D[KR_MAX_C], s_E[KR_MAX_C];
+    __shared__ int s_hist[KR_MAX_C + 1];
+    __shared__ int s_namb;
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const int me = self_r0 + row;
+    for (int t = tid; t < c; t += 256) {
+        const double D = tD[(long long)row * c + t];
+        s_D[t] = D;
+        s_E[t] = D * (1.0 + KR_STEP);
+    }
+    for (int t = tid; t <= c; t += 256) s_hist[t] = 0;
+    if (tid == 0) s_namb = 0;
+    __syncthreads();
+    const double A = cbound * (nq[row] + *nxmax) + 1e-30;
+    const double Emax = s_E[c - 1];
+    const float *__restrict__ prow = panel + (long long)row * ldp;
+    int *__restrict__ arow = amb + (long long)row * cap;
+    int above = 0;
+
+    auto place = [&](int col, float gv) {
+        if (col >= M || col == me) return;
+        const double g = (double)gv;
+        const double hi = (g - A) * (1.0 - KR_RHO);
+        if (hi > Emax) { ++above; return; }
+        const double lo = (g + A) * ((1.0 + KR_RHO) * (1.0 + KR_STEP));
+        int p = 0, n = c;
+        while (n > 0) {
+            const int h = n >> 1;
+            if (s_D[p + h] <= lo) { p += h + 1; n -= h + 1; }
+            else n = h;
+        }
+        if (p == 0 || s_E[p - 1] < hi) atomicAdd(&s_hist[p], 1);
+        else {
+            const int pos = atomicAdd(&s_namb, 1);
+            if (pos < cap) arow[pos] = col;
+        }
+    };
+
+    // rows of the panel start on 128 bytes and ldp is a multiple of 32: every 16-byte step below M lies inside the row
+    const int nvec = (M + 3) >> 2;
+    auto fetch = [&](int v) { return *(const f32x4 *)(prow + 4 * (v < nvec ? v : nvec - 1)); };     // (unconditional, clamped)
+    f32x4 c0 = fetch(tid), c1 = fetch(tid + 256);
+    for (int v = tid; v < nvec; v += 512) {
+        const f32x4 n0 = fetch(v + 512), n1 = fetch(v + 768);
+        __builtin_amdgcn_sched_barrier(0);      // the requests go out before the searches
+#pragma unroll
+        for (int e = 0; e < 4; ++e) place(4 * v + e, c0[e]);
+        if (v + 256 < nvec) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) place(4 * (v + 256) + e, c1[e]);
+        }
+        c0 = n0;
+        c1 = n1;
+    }
+    if (above) atomicAdd(&s_hist[c], above);
+    __syncthreads();
+    for (int t = tid; t <= c; t += 256) hist[(long long)row * (c + 1) + t] = s_hist[t];
+    if (tid == 0) {
+        namb[row] = s_namb;
+        if (s_namb > cap) fail_list[atomicAdd(n_fail, 1)] = row;
+    }
+}
+
+// The tail of resolve and of the fallback count, by the whole workgroup after a barrier: s_hist holds the row's c + 1 bins,
+// s_cnt the comparisons decided one by one.  rank of the sorted threshold t = 1 + s_hist[0] + .. + s_hist[t] + s_cnt[t].
+__device__ __forceinline__ void rank_write(int *s_hist, const int *s_cnt, const int *s_j, const int *__restrict__ tp, int c,
+                                           int me, int *__restrict__ out)
+{
+    const int tid = threadIdx.x;
+    if (tid == 0)
+        for (int t = 1; t < c; ++t) s_hist[t] += s_hist[t - 1];
+    __syncthreads();
+    for (int t = tid; t < c; t += 256) out[tp[t]] = s_j[t] == me ? 0 : 1 + s_hist[t] + s_cnt[t];
+}
+
+template <bool V4>
+__global__ __launch_bounds__(256) void rank_resolve_kernel(const float *__restrict__ X, long long ldx, int F, int self_r0, int c,
+                                                           const float *__restrict__ td, const int *__restrict__ tj,
+                                                           const int *__restrict__ tp, const int *__restrict__ hist,
+                                                           const int *__restrict__ namb, const int *__restrict__ amb, int cap,
+                                                           int *__restrict__ ranks, int *__restrict__ n_ambiguous)
+{
+    __shared__ float s_d[KR_MAX_C];
+    __shared__ int s_j[KR_MAX_C], s_cnt[KR_MAX_C], s_hist[KR_MAX_C + 1];
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int n = namb[row];
+    if (n > cap) return;                        // the fallback's row
+    const int me = self_r0 + row;
+    const long long o = (long long)row * c;
+    for (int t = tid; t < c; t += 256) {
+        s_d[t] = td[o + t];
+        s_j[t] = tj[o + t];
+        s_cnt[t] = 0;
+        s_hist[t] = hist[(long long)row * (c + 1) + t];
+    }
+    __syncthreads();
+    const float *__restrict__ q = X + (long long)me * ldx;
+    const int *__restrict__ arow = amb + (long long)row * cap;
+    for (int a = w; a < n; a += 4) {
+        const int l = arow[a];
+        const float d = knn_dist_of(knn_exact_d2<V4>(q, X + (long long)l * ldx, F, lane));
+        for (int t = lane; t < c; t += 64)
+            if (pair_less(d, l, s_d[t], s_j[t])) atomicAdd(&s_cnt[t], 1);
+    }
+    if (tid == 0 && n) atomicAdd(n_ambiguous, n);
+    __syncthreads();
+    rank_write(s_hist, s_cnt, s_j, tp + o, c, me, ranks + o);
+}
+
+// Fallback: the slot's row of exact-form distances (knn_exact_panel_kernel) against the thresholds' fp32 distances, which
+// are non-decreasing in the sorted order.  p = #{t : d_t <= v}: l is below the thresholds p .. c - 1; those equal to v are
+// decided by the index.
+__global__ __launch_bounds__(256) void rank_exact_count_kernel(const float *__restrict__ D, long long ldd, int M, int self_r0,
+                                                               int c, const float *__restrict__ td, const int *__restrict__ tj,
+                                                               const int *__restrict__ tp, int *__restrict__ ranks, RowList rl)
+{
+    __shared__ float s_d[KR_MAX_C];
+    __shared__ int s_j[KR_MAX_C], s_cnt[KR_MAX_C], s_hist[KR_MAX_C + 1];
+    const int slot = blockIdx.x, tid = threadIdx.x;
+    const int row = row_of_slot(rl, slot);
+    if (row < 0) return;
+    const int me = self_r0 + row;
+    const long long o = (long long)row * c;
+    for (int t = tid; t < c; t += 256) {
+        s_d[t] = td[o + t];
+        s_j[t] = tj[o + t];
+        s_cnt[t] = 0;
+    }
+    for (int t = tid; t <= c; t += 256) s_hist[t] = 0;
+    __syncthreads();
+    const float dmax = s_d[c - 1];
+    const float *__restrict__ drow = D + (long long)slot * ldd;
+    int above = 0;
+    auto place = [&](int col, float v) {
+        if (col >= M || col == me) return;
+        if (v > dmax) { ++above; return; }
+        int p = 0, n = c;
+        while (n > 0) {
+            const int h = n >> 1;
+            if (s_d[p + h] <= v) { p += h + 1; n -= h + 1; }
+            else n = h;
+        }
+        atomicAdd(&s_hist[p], 1);
+        for (int t = p - 1; t >= 0 && s_d[t] == v; --t)
+            if (col < s_j[t]) atomicAdd(&s_cnt[t], 1);
+    };
+    const int nvec = (M + 3) >> 2;
+    for (int v = tid; v < nvec; v += 256) {
+        const f32x4 x = *(const f32x4 *)(drow + 4 * v);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) place(4 * v + e, x[e]);
+    }
+    if (above) atomicAdd(&s_hist[c], above);
+    __syncthreads();
+    rank_write(s_hist, s_cnt, s_j, tp + o, c, me, ranks + o);
+}
+
+struct RankPlan {
+    int fb_rows, rounds, cap;
+    long long ldp;
+    size_t o_panel, o_nx, o_max, o_zero, o_tD, o_td, o_tj, o_tp, o_hist, o_namb, o_amb, o_list, o_fb, total;
+};
+
+// 0, or the reason the shape is refused.
+const char *rank_plan(long long R, long long M, int F, int c, long long cap, RankPlan *p)
+{
+    if (R < 1 || M < 2) return "R must be >= 1 and M >= 2";
+    if (R > 0x7fffffffLL || M > 0x7fffffffLL) return "R and M must fit 31 bits";
+    if (((R + GT - 1) / GT) * ((M + GT - 1) / GT) > 0x7fffffffLL) return "more than 2^31 tiles in one panel: split R";
+    if (F < 1 || F > DM_KNN_MAX_FEATURES) return "F outside 1 .. DM_KNN_MAX_FEATURES";
+    if (c < 1 || c > KR_MAX_C) return "c outside 1 .. DM_KNN_MAX_K";
+    if (cap < 1) return "cap must be >= 1";
+    p->cap = (int)(cap < M ? cap : M);
+    p->fb_rows = (int)(R < KN_FB_ROWS ? R : KN_FB_ROWS);
+    p->rounds = (int)((R + p->fb_rows - 1) / p->fb_rows);
+    p->ldp = (M + 31) / 32 * 32;
+    size_t o = 0;
+    p->o_panel = o; o += align256((size_t)R * p->ldp * sizeof(float));
+    p->o_nx = o;    o += align256((size_t)M * sizeof(double));
+    p->o_max = o;   o += 256;
+    p->o_zero = o;  o += align256((size_t)F * sizeof(float));
+    p->o_tD = o;    o += align256((size_t)R * c * sizeof(double));
+    p->o_td = o;    o += align256((size_t)R * c * sizeof(float));
+    p->o_tj = o;    o += align256((size_t)R * c * sizeof(int));
+    p->o_tp = o;    o += align256((size_t)R * c * sizeof(int));
+    p->o_hist = o;  o += align256((size_t)R * (c + 1) * sizeof(int));
+    p->o_namb = o;  o += align256((size_t)R * sizeof(int));
+    p->o_amb = o;   o += align256((size_t)R * p->cap * sizeof(int));
+    p->o_list = o;  o += align256((size_t)R * sizeof(int));
+    p->o_fb = o;    o += align256((size_t)p->fb_rows * p->ldp * sizeof(float));
+    p->total = o;
+    return nullptr;
+}
+
+template <bool V4>
+void rank_launch(const RankPlan &p, const float *X, int M, int F, long long ldx, int r0, int R, const int *targets, int c,
+                 const float *shift, const float *gram_shift, int *ranks, int *n_ambiguous, int *n_redone, char *ws, hipStream_t s)
+{
+    float *panel = (float *)(ws + p.o_panel), *td = (float *)(ws + p.o_td), *fb = (float *)(ws + p.o_fb);
+    double *nx = (double *)(ws + p.o_nx), *nmax = (double *)(ws + p.o_max), *tD = (double *)(ws + p.o_tD);
+    int *tj = (int *)(ws + p.o_tj), *tp = (int *)(ws + p.o_tp), *hist = (int *)(ws + p.o_hist), *namb = (int *)(ws + p.o_namb);
+    int *amb = (int *)(ws + p.o_amb), *list = (int *)(ws + p.o_list);
+    const float *Q = X + (long long)r0 * ldx;
+    const double *nq = nx + r0;
+
+    hipLaunchKernelGGL(row_norms_kernel<V4>, dim3((M + 3) / 4), dim3(256), 0, s, X, (long long)M, F, ldx, shift, nx);
+    hipLaunchKernelGGL(norms_max_kernel<256>, dim3(1), dim3(256), 0, s, (const double *)nx, (long long)M, nmax, n_redone);
+    const int row_tiles = (R + GT - 1) / GT;
+    hipLaunchKernelGGL(knn_gram_kernel<V4>, dim3((unsigned)((long long)row_tiles * ((M + GT - 1) / GT))), dim3(256), 0, s,
+                       Q, R, ldx, X, M, ldx, F, gram_shift, nq, (const double *)nx, r0, panel, p.ldp, row_tiles);
+    hipLaunchKernelGGL(rank_thresholds_kernel<V4>, dim3(R), dim3(256), 0, s, X, M, ldx, F, r0, targets, c, tD, td, tj, tp);
+    hipLaunchKernelGGL(rank_count_kernel, dim3(R), dim3(256), 0, s, (const float *)panel, p.ldp, M, r0, (const double *)tD, c,
+                       nq, (const double *)nmax, filter_bound(), p.cap, hist, namb, amb, list, n_redone);
+    hipLaunchKernelGGL(rank_resolve_kernel<V4>, dim3(R), dim3(256), 0, s, X, ldx, F, r0, c, (const float *)td, (const int *)tj,
+                       (const int *)tp, (const int *)hist, (const int *)namb, (const int *)amb, p.cap, ranks, n_ambiguous);
+    const unsigned gx = (unsigned)(M / 4 + 1 < 64 ? M / 4 + 1 : 64);
+    for (int b = 0; b < p.rounds; ++b) {        // always launched: a round without listed rows leaves at once
+        const RowList rl = {list, n_redone, b * p.fb_rows};
+        hipLaunchKernelGGL(knn_exact_panel_kernel<V4>, dim3(gx, p.fb_rows), dim3(256), 0, s, Q, ldx, X, M, ldx, F, r0, fb, p.ldp,
+                           rl);
+        hipLaunchKernelGGL(rank_exact_count_kernel, dim3(p.fb_rows), dim3(256), 0, s, (const float *)fb, p.ldp, M, r0, c,
+                           (const float *)td, (const int *)tj, (const int *)tp, ranks, rl);
+    }
+}
+
+}  // namespace
+
+extern "C" int64_t dm_knn_ranks_workspace_bytes(int64_t R, int64_t M, int F, int c, int64_t cap)
+{
+    RankPlan p;
+    if (rank_plan(R, M, F, c, cap, &p)) return -1;
+    return (int64_t)p.total;
+}
+
+extern "C" int dm_knn_ranks(const float *X, int64_t M, int F, int64_t ldx, int64_t r0, int64_t R, const int32_t *targets, int c,
+                            const float *shift, int64_t cap, int32_t *ranks, int32_t *n_ambiguous, int32_t *n_redone,
+                            void *workspace, int64_t workspace_bytes, void *stream)
+{
+    DM_REQUIRE(X, "dm_knn_ranks: X is NULL");
+    DM_REQUIRE(targets && ranks, "dm_knn_ranks: targets / ranks is NULL");
+    DM_REQUIRE(n_ambiguous && n_redone, "dm_knn_ranks: n_ambiguous / n_redone is NULL");
+    DM_REQUIRE(workspace, "dm_knn_ranks: workspace is NULL");
+    RankPlan p;
+    const char *why = rank_plan(R, M, F, c, cap, &p);
+    DM_REQUIRE(!why, "dm_knn_ranks: R = %lld, M = %lld, F = %d, c = %d, cap = %lld: %s", (long long)R, (long long)M, F, c,
+               (long long)cap, why ? why : "");
+    DM_REQUIRE(ldx >= F, "dm_knn_ranks: leading dimension of X %lld < F = %d", (long long)ldx, F);
+    DM_REQUIRE(r0 >= 0 && r0 + R <= M, "dm_knn_ranks: rows %lld .. %lld lie outside X (M = %lld)", (long long)r0,
+               (long long)(r0 + R - 1), (long long)M);
+    DM_REQUIRE(workspace_bytes >= (int64_t)p.total, "dm_knn_ranks: workspace of %lld bytes, need %lld", (long long)workspace_bytes,
+               (long long)p.total);
+    DM_REQUIRE(((uintptr_t)workspace & 255) == 0, "dm_knn_ranks: workspace is not 256-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const hipError_t e = hipMemsetAsync(n_ambiguous, 0, sizeof(int32_t), s);
+    if (e != hipSuccess) {
+        dm_set_error("dm_knn_ranks: hipMemsetAsync: %s", hipGetErrorString(e));
+        return (int)e;
+    }
+    const float *gram_shift;
+    if (const int e2 = shift_or_zeros("dm_knn_ranks", shift, (char *)workspace + p.o_zero, F, s, &gram_shift)) return e2;
+    if (vec4_ok(X, ldx, F) && ((uintptr_t)shift & 15) == 0)
+        rank_launch<true>(p, X, (int)M, F, ldx, (int)r0, (int)R, targets, c, shift, gram_shift, ranks, n_ambiguous, n_redone,
+                          (char *)workspace, s);
+    else
+        rank_launch<false>(p, X, (int)M, F, ldx, (int)r0, (int)R, targets, c, shift, gram_shift, ranks, n_ambiguous, n_redone,
+                           (char *)workspace, s);
+    return dm_launch_status("dm_knn_ranks");
+}

@@ -214,6 +214,34 @@ def dim_reduction_umap_embedding(input_dirs, weights_dir, prefixes, n_nbrs=(15, 
     return fit_umap_embedding(vectors, weights_output, labels=labels, n_nbrs=n_nbrs, a_s=a_s, b_s=b_s, **kw)
 
 
+def score_umap_embeddings(train_data, weights_dir, n_neighbors=15, **kw):
+    """Which of fit_umap_embedding's embeddings is faithful to the latents: every <weights_dir>/embedding_umap_nbr*_a*_b*.pkl
+    scored against train_data (the matrix they were fitted on, rows in the same order) in ONE quality.embedding_quality
+    call.  Writes <weights_dir>/embedding_quality.pkl (protocol 4, a plain dict {file name without
+    .pkl: {"trustworthiness", "continuity", "neighbor_recall"}}) and returns it.  kw: embedding_quality's (chunk_rows,
+    device, shift, cap, x_graph)."""
+    import fnmatch
+    from .quality import embedding_quality
+    embeddings = {}
+    for fname in sorted(fnmatch.filter(os.listdir(weights_dir), 'embedding_umap_nbr*_a*_b*.pkl')):
+        with open(os.path.join(weights_dir, fname), 'rb') as f:
+            embeddings[os.path.splitext(fname)[0]] = np.asarray(pickle.load(f)[0], dtype=np.float32)
+    if not embeddings:
+        raise ValueError(f"no embedding_umap_nbr*_a*_b*.pkl in {weights_dir}: fit_umap_embedding writes them")
+    scores = embedding_quality(train_data, embeddings, n_neighbors=n_neighbors, **kw)
+    with open(os.path.join(weights_dir, 'embedding_quality.pkl'), 'wb') as f:
+        pickle.dump(scores, f, protocol=4)
+    return scores
+
+
+def dim_reduction_score_umap_embeddings(input_dirs, weights_dir, prefixes, n_neighbors=15, **kw):
+    """The pooling of dim_reduction_umap_embedding -- the same files in the same order, so row i of the pooled matrix is row
+    i of every embedding -- followed by score_umap_embeddings."""
+    weights_output = os.path.dirname(weights_dir) if os.path.isfile(weights_dir) else weights_dir
+    vectors, _ = pool_latents(input_dirs, prefixes)
+    return score_umap_embeddings(vectors, weights_output, n_neighbors=n_neighbors, **kw)
+
+
 def load_umap_models(weights_dir):
     """{model name: model} of every umap*.pkl in weights_dir, in sorted order (run_dim_reduction.py:108-117).  A file that does
     not unpickle to an object with a transform method raises the reference's ValueError."""

@@ -1627,6 +1627,48 @@ def knn_wide_self(X, K, k=15, shift=None, slack=None, include_self=False, pair_o
     return idx, dist, nfb, npairs
 
 
+def knn_ranks_default_cap(c, M):
+    """Entries of a row's list of undecided columns.  Unstructured Gaussian rows at M = 100 000, F = 4096 put
+    about 110 columns per target inside the filter's window, and the number grows with the density of rows, that is with M:
+    c M / 480 holds twice that.  Structured data need less than one column per target beside the target itself: 4 c + 64
+    at least.  At most 32768 (4 bytes each, per row of a panel); dm_knn_ranks clips it to M.  A row that needs more is
+    redone exactly, so the choice moves time, never a result."""
+    c, M = int(c), int(M)
+    return min(32768, max(4 * c + 64, c * M // 480))
+
+
+@_op
+def knn_ranks(X, targets, rows=None, shift=None, cap=None, out=None, workspace=None):
+    """Ranks of the given target rows among each row's neighbours in X (M, F) (dm_knn_ranks): targets (R, c) int32 on the
+    device for the rows rows=(r0, R) (default all) -> (ranks (R, c) int32, n_ambiguous (1,) int32, n_redone (1,) int32 on the
+    device).  rank = 1 + the number of other rows that are nearer by (exact-form fp32 distance, index); 0 for the row itself.
+    The targets must lie in 0 .. M - 1 (the caller checks: nothing is read back here)."""
+    lib = L.load()
+    px, M, F, ldx = _rows(X)
+    r0, R = (0, M) if rows is None else (int(rows[0]), int(rows[1]))
+    if r0 < 0 or R < 1 or r0 + R > M:
+        raise ValueError(f"dm_knn_ranks: rows=({r0}, {R}) lie outside X with {M} rows")
+    if targets.dim() != 2 or targets.shape[0] != R or targets.dtype != torch.int32 or not targets.is_contiguous():
+        raise ValueError(f"dm_knn_ranks: targets has shape {tuple(targets.shape)} and dtype {targets.dtype}, need a contiguous "
+                         f"int32 ({R}, c)")
+    c = int(targets.shape[1])
+    if c < 1 or c > KNN_MAX_K:
+        raise ValueError(f"dm_knn_ranks: c outside 1 .. {KNN_MAX_K}, got {c}")
+    if shift is not None and shift.numel() != F:
+        raise ValueError(f"dm_knn_ranks: shift has {shift.numel()} entries, F = {F}")
+    cap = knn_ranks_default_cap(c, M) if cap is None else int(cap)
+    if out is None:
+        out = _new((R, c), X, torch.int32)
+    elif tuple(out.shape) != (R, c) or out.dtype != torch.int32 or not out.is_contiguous():
+        raise ValueError(f"dm_knn_ranks: out has shape {tuple(out.shape)}, need a contiguous int32 ({R}, {c})")
+    namb, nredo = _new((1,), X, torch.int32), _new((1,), X, torch.int32)
+    workspace = _knn_ws(lib.dm_knn_ranks_workspace_bytes(R, M, F, c, cap), workspace, X)
+    L.check(lib.dm_knn_ranks(px, M, F, ldx, r0, R, _ptr(targets, torch.int32), c, _ptr(shift), cap, _ptr(out, torch.int32),
+                             _ptr(namb, torch.int32), _ptr(nredo, torch.int32), _ptr(workspace, workspace.dtype),
+                             workspace.numel() * workspace.element_size(), _stream()), "dm_knn_ranks")
+    return out, namb, nredo
+
+
 # ----------------------------------------------------------------------------- exact k-means of the latents (DESIGN.md 3.5g)
 KMEANS_MAX_CLUSTERS = 1024     # DM_KMEANS_MAX_CLUSTERS
 

@@ -918,6 +918,18 @@ int64_t dm_knn_wide_self_workspace_bytes(int64_t N, int F, int k, int slack);
 int dm_knn_wide_self(const float *X, int64_t N, int F, int64_t ldx, const float *shift, const double *K, int k, int slack,
                      int include_self, int pair_once, int32_t *indices, float *distances, int32_t *n_fallback,
                      int32_t *n_pairs, void *workspace, int64_t workspace_bytes, void *stream);
+/* RANKS of given targets among a row's neighbours (trustworthiness and continuity of an embedding).  For the
+ * rows r0 .. r0 + R - 1 of X (M x F, 1 <= F <= DM_KNN_MAX_FEATURES) and per row c target rows of X (targets: R x c int32 on
+ * the device, 1 <= c <= DM_KNN_MAX_K, each in 0 .. M - 1, repeats allowed):
+ *   ranks[r][t] = 1 + #{ l != i : (d(i, l), l) < (d(i, j), j) },  i = r0 + r, j = targets[r][t];  0 where j == i,
+ * d the fp32 exact-form distance dm_knn reports: the rank of dm_knn's column t (no self column) is t + 1.  The results depend
+ * on the inputs only, not on shift, cap or the chunking.  cap >= 1: entries of a row's list of columns the filter cannot
+ * decide; a row that needs more is redone from exact-form distances to all M rows.  *n_ambiguous, *n_redone (device ints,
+ * cleared by the call): the columns decided one by one, and the rows redone.  Asynchronous, no read-back. */
+int64_t dm_knn_ranks_workspace_bytes(int64_t R, int64_t M, int F, int c, int64_t cap);
+int dm_knn_ranks(const float *X, int64_t M, int F, int64_t ldx, int64_t r0, int64_t R, const int32_t *targets, int c,
+                 const float *shift, int64_t cap, int32_t *ranks, int32_t *n_ambiguous, int32_t *n_redone, void *workspace,
+                 int64_t workspace_bytes, void *stream);
 
 /* ===== exact Lloyd k-means of the latents (sklearn.cluster.KMeans of the reference's clustering scripts) ==== */
 /* X: N x F fp32 row-major, leading dimension ldx >= F, 1 <= F <= DM_KNN_MAX_FEATURES; C: K x F fp32 contiguous centres,
